@@ -1,7 +1,7 @@
 """Parity tests proper: the HIP path (through the C ABI) against the CPU oracle on the same inputs.
 Bit-exact: this is integer work.  Run with `pytest -m gpu` on an MI355X."""
 import ctypes as C
-
+import os
 import time
 
 import numpy as np
@@ -649,6 +649,13 @@ def test_bucketed_layout_on_arc_shards(monkeypatch):
     assert np.array_equal(full, a["state"][:m_s])
 
 
+def _resident_slots():
+    """Resident grids one process runs on a device at a time: GPU_MAX_HW_QUEUES as the engine reads it (resident_host.hip.h), 4 when unset.
+    A grid never leaves its hardware queue, so shard tests that keep every shard's grid running at once use at most this many shards."""
+    v = os.environ.get("GPU_MAX_HW_QUEUES", "")
+    return int(v) if v.isdigit() and 1 <= int(v) <= 64 else 4
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("layout", ["registers", "rc-lds", "rc-stream"])
 def test_arc_shards_keep_their_own_candidate_caches(layout, monkeypatch):
@@ -661,7 +668,7 @@ def test_arc_shards_keep_their_own_candidate_caches(layout, monkeypatch):
         if layout == "rc-stream":
             monkeypatch.setenv("MCF_HIP_RC_LDS", "0")
     rng = np.random.default_rng(77)
-    m_s, n, world = 180_007, 40_000, 3
+    m_s, n, world = 180_007, 40_000, min(3, _resident_slots())
     a = _random_soa(rng, m_s, n, 40, 300, extra=0)
     shards = []
     for r in range(world):
@@ -1040,7 +1047,7 @@ def test_resident_shard_engines_resolve_like_one_engine(rule, optimized, vw):
     """The shard test above with every shard served by its own RESIDENT grid (co-resident on this GPU: MCF_ENGINE_SHARE_DEVICE and a
     grid cap), searches posted to all shards first and collected afterwards (mcf_engine_search_begin / _search_end_local)."""
     rng = np.random.default_rng(199 + rule)
-    m_s, n, world = 150_011, 30_000, 3
+    m_s, n, world = 150_011, 30_000, min(3, _resident_slots())
     a = _random_soa(rng, m_s, n, 5, 12, extra=0)
     block = 173
     one = M.PivotEngine(n, m_s, m_s, rule=RULES[rule], optimized=optimized, block_size=block, flags=M.ENGINE_DISPATCH, vector_width=vw)

@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mincostflow_amd as M
 g = M.netgen_like(13502460, 100_000, 300_000, 1000, 1000)
 for k in range(2):
