@@ -54,7 +54,6 @@ inline void cand_note_arc(mcf_engine *e, int a)
 }
 // Long lists (a big subtree): nothing will be evaluated here -- the device searches next, and a list of its epoch or later makes the
 // touched nodes' stamps irrelevant (cand_decide) -- so the list is taken over as it is, without a look at its nodes.
-constexpr int kShiftRunsPerLine = 7;        // {first, length} pairs per shift line (the shift grid's range-encoded lines)
 constexpr int kShiftRunMax = 256;           // nodes per pair: a longer run comes as several (a thread of the grid sets one pair's bits)
 
 // a big list that came as runs, as node ids after all (for the paths that read ids): the first blind_count entries of pend_node
@@ -313,7 +312,7 @@ int cand_collect(mcf_engine *e, uint32_t at)
         while (!cand_records_ready(e, g)) {
             _mm_pause();
             if (e->resident_running && (spins & 0xFFF) == 0xFFF && ((const volatile uint32_t *)e->h_exit)[0] != 0) {
-                if (((const volatile uint32_t *)e->h_exit)[0] == 4u) {
+                if (((const volatile uint32_t *)e->h_exit)[0] == kExitPartial) {
                     (void)resident_join(e, false);
                     e->resident_running = false;
                     resident_slot_release(e);
@@ -362,7 +361,7 @@ int cand_collect(mcf_engine *e, uint32_t at)
 // (a shift that was not announced, too many entries), the grid is stopped and the values go through update_rc_kernel.
 int cand_post_rc(mcf_engine *e)
 {
-    // a reload of the bound potentials that the grid can carry out itself (cmd 3): the array is read when the request is served, so every
+    // a reload of the bound potentials that the grid can carry out itself (kCmdReload): the array is read when the request is served, so every
     // potential change noted up to now is part of it -- the lists are dropped, the state writes travel with the request
     const bool reload = e->reload_pi && e->d_ext_pi != nullptr && (int64_t)e->sync_arcs.size() <= e->mailbox_max_st;
     if (reload) {
@@ -396,7 +395,7 @@ int cand_post_rc(mcf_engine *e)
     if (e->seq == 0) e->seq = 1;
     int rc = resident_start(e, e->prev_seq);
     if (rc) return rc;
-    resident_post(e, e->seq, reload ? 3u : 0u, fast);
+    resident_post(e, e->seq, reload ? kCmdReload : kCmdScan, fast);
     if (reload) e->st.rc_reloads_in_grid += 1;
     if (fast && (!e->pend_node.empty() || !e->pend_arc.empty())) e->st.inline_updates += 1;
     e->pend_node.clear(); e->pend_val.clear(); e->pend_arc.clear(); e->pend_state.clear();
@@ -405,7 +404,7 @@ int cand_post_rc(mcf_engine *e)
     return MCF_OK;
 }
 
-// ---- the grid that is patched straight from the request (resident_cand_kernel; kernels.hip.h has the mailbox layout)
+// ---- the grid that is patched straight from the request (resident_cand_kernel; mailbox.hip.h has the layout of its requests)
 
 // After that grid has left: the arrays in device memory are as the LAST LAUNCH found them.  The host's mirrors are authoritative in candidate
 // mode (potentials: the bound array or e->pi; states: h_state), so they are simply written again -- and with that the device has heard
@@ -426,77 +425,61 @@ int device_sync_from_mirrors(mcf_engine *e)
     return MCF_OK;
 }
 
+// shift lines [from, to) of a list of n entries, with the tag seq: node ids out of pend_node, or (runs) {first, length} pairs out of blind_runs
+void shift_write_lines(mcf_engine *e, int from, int to, size_t n, bool runs, uint32_t seq)
+{
+    const int per_line = runs ? kShiftPairsPerLine : kShiftNodesPerLine;
+    MailboxLine line;
+    for (int l = from; l < to; ++l) {
+        memset(line.w, 0, sizeof(line.w));
+        for (int k = 0; k < per_line && (size_t)l * per_line + k < n; ++k) {
+            const size_t i = (size_t)l * per_line + k;
+            if (runs) { line.w[2 * k] = e->blind_runs[2 * i]; line.w[2 * k + 1] = e->blind_runs[2 * i + 1]; }
+            else line.w[k] = (uint32_t)e->pend_node[i];
+        }
+        line.w[15] = seq;
+        mailbox_write_line(e->mailbox + e->shift_base + 16 * (size_t)l, line.w);
+    }
+}
+
 // header (+ entry and shift lines when with_patches) of request `seq`; the value entries are pend_node / pend_val [val_lo, end), the shift
 // list pend_node [0, n_shift)
 void shift_post_request(mcf_engine *e, uint32_t seq, uint32_t cmd, size_t val_lo, size_t n_shift, int64_t sigma, bool with_patches, bool runs = false)
 {
-    alignas(16) uint32_t line[16], line1[16];
     const int n_val = with_patches ? (int)(e->pend_node.size() - val_lo) : 0, n_st = with_patches ? (int)e->pend_arc.size() : 0;
-    const int extra_val = n_val > 1 ? n_val - 1 : 0, extra_st = n_st > 2 ? n_st - 2 : 0, entries = extra_val + extra_st;
-    memset(line1, 0, sizeof(line1));
-    for (int l = 0, i = 0; i < entries; ++l) {
-        memset(line, 0, sizeof(line));
-        for (int k = 0; k < kMailboxPatchesPerLine && i < entries; ++k, ++i) {
-            if (i < extra_val) {
-                const uint64_t v = (uint64_t)e->pend_val[val_lo + i + 1];
-                line[3 * k] = (uint32_t)e->pend_node[val_lo + i + 1];
-                line[3 * k + 1] = (uint32_t)v;
-                line[3 * k + 2] = (uint32_t)(v >> 32);
-            } else {
-                const int j = i - extra_val + 2;
-                line[3 * k] = (uint32_t)e->pend_arc[j];
-                line[3 * k + 1] = (uint32_t)e->pend_state[j];
-            }
-        }
-        line[15] = seq;
-        if (l == 0) memcpy(line1, line, sizeof(line));
-        else mailbox_write_line(e->mailbox + kMailboxTail + 16 * (size_t)(l - 1), line);
-    }
+    const ValueEntries vals{e->pend_node.data(), e->pend_val.data(), val_lo + 1, n_val > 1 ? n_val - 1 : 0};
+    const StateEntries sts{e->pend_arc.data(), e->pend_state.data(), 2, n_st > 2 ? n_st - 2 : 0};
+    const MailboxLine line1 = mailbox_encode_entries(e->mailbox, vals, sts, seq);
     if (with_patches) {
         // the shift list: n_shift node ids, or (runs) n_shift {first, length} pairs out of blind_runs
-        const int per_line = runs ? kShiftRunsPerLine : kShiftNodesPerLine;
-        const int total = (int)((n_shift + per_line - 1) / per_line);
-        for (int l = e->shift_streamed; l < total; ++l) {
-            memset(line, 0, sizeof(line));
-            for (int k = 0; k < per_line && (size_t)l * per_line + k < n_shift; ++k) {
-                if (runs) { line[2 * k] = e->blind_runs[2 * ((size_t)l * per_line + k)]; line[2 * k + 1] = e->blind_runs[2 * ((size_t)l * per_line + k) + 1]; }
-                else line[k] = (uint32_t)e->pend_node[(size_t)l * kShiftNodesPerLine + k];
-            }
-            line[15] = seq;
-            mailbox_write_line(e->mailbox + e->shift_base + 16 * (size_t)l, line);
-        }
+        const int per_line = runs ? kShiftPairsPerLine : kShiftNodesPerLine;
+        shift_write_lines(e, e->shift_streamed, (int)((n_shift + per_line - 1) / per_line), n_shift, runs, seq);
         e->shift_streamed = 0;
     }
-    memset(line, 0, sizeof(line));
-    line[0] = seq;
-    line[1] = cmd;
-    line[2] = (uint32_t)n_val;
-    line[3] = with_patches ? (uint32_t)n_shift : 0u;
-    line[4] = with_patches && runs ? 1u : 0u;      // the shift list is {first, length} pairs
-    line[5] = (uint32_t)n_st;
-    for (int k = 0; k < n_st && k < 2; ++k) { line[6 + 2 * k] = (uint32_t)e->pend_arc[k]; line[7 + 2 * k] = (uint32_t)e->pend_state[k]; }
+    MailboxLine h{};
+    h.w[kHdrSeq] = seq;
+    h.w[kHdrCmd] = cmd;
+    h.w[kShHdrValues] = (uint32_t)n_val;
+    h.w[kShHdrShift] = with_patches ? (uint32_t)n_shift : 0u;
+    h.w[kShHdrRuns] = with_patches && runs ? 1u : 0u;
+    h.w[kHdrStates] = (uint32_t)n_st;
+    for (int k = 0; k < n_st && k < 2; ++k) { h.w[kHdrState0 + 2 * k] = (uint32_t)e->pend_arc[k]; h.w[kHdrState0 + 1 + 2 * k] = (uint32_t)e->pend_state[k]; }
     if (n_val > 0) {
         const uint64_t v = (uint64_t)e->pend_val[val_lo];
-        line[10] = (uint32_t)e->pend_node[val_lo];
-        line[11] = (uint32_t)v;
-        line[12] = (uint32_t)(v >> 32);
+        h.w[kHdrValue0] = (uint32_t)e->pend_node[val_lo];
+        h.w[kHdrValue0 + 1] = (uint32_t)v;
+        h.w[kHdrValue0 + 2] = (uint32_t)(v >> 32);
     }
-    line[13] = (uint32_t)(uint64_t)sigma;
-    line[14] = (uint32_t)((uint64_t)sigma >> 32);
-    line[15] = seq;
-    _mm_sfence();                                  // entry and shift lines leave the write-combining buffers before any header does
-    for (int r = 0; r < e->poll_replicas; ++r) {
-        uint32_t *unit = e->mailbox + (size_t)r * kReplicaStride;
-        if (entries > 0) mailbox_write_line(unit + 16, line1);
-        mailbox_write_line(unit, line);
-    }
-    _mm_sfence();
+    h.w[kShHdrSigma] = (uint32_t)(uint64_t)sigma;
+    h.w[kShHdrSigma + 1] = (uint32_t)((uint64_t)sigma >> 32);
+    h.w[kHdrTag] = seq;
+    mailbox_publish(e->mailbox, e->poll_replicas, h, vals.n + sts.n > 0 ? &line1 : nullptr);
 }
 // a request without patches: quit, or a scan request put there again for a grid that has just been started with current arrays
 void shift_post(mcf_engine *e, uint32_t seq, uint32_t cmd, bool) { shift_post_request(e, seq, cmd, 0, 0, 0, false); }
 
-// the complete shift lines of this pivot's big list start travelling while the host is still walking the subtree (cmd 2: "shift lines
-// 0 .. L-1 of the coming scan request are in place": the grid sets their bits and goes back to polling)
+// the complete shift lines of this pivot's big list start travelling while the host is still walking the subtree (kCmdApply / kCmdApplyRuns:
+// "shift lines 0 .. L-1 of the coming scan request are in place": the grid sets their bits and goes back to polling)
 int shift_stream_min_lines()
 {
     static const int v = [] { int x = 96; if (const char *u = getenv("MCF_HIP_SHIFT_STREAM_LINES")) { const int y = atoi(u); if (y >= 8 && y <= 65536) x = y; } return x; }();
@@ -507,28 +490,20 @@ void shift_stream(mcf_engine *e)
     if (e->async_posted || e->blind_epoch != e->cand_now || e->blind_sets > 1 || !e->pend_shift) return;
     if (!e->resident_running || e->in_flight != mcf_engine::kNoSearch) return;
     const bool runs = e->blind_lazy;
-    const int complete = runs ? (int)(e->blind_runs.size() / 2 / kShiftRunsPerLine) : (int)(e->blind_count / kShiftNodesPerLine);
+    const int complete = runs ? (int)(e->blind_runs.size() / 2 / kShiftPairsPerLine) : (int)(e->blind_count / kShiftNodesPerLine);
     if (complete - e->shift_streamed < shift_stream_min_lines() || complete > e->max_shift_lines) return;
     uint32_t next_seq = e->seq + 1;
     if (next_seq == 0) next_seq = 1;
-    alignas(16) uint32_t line[16];
-    for (int l = e->shift_streamed; l < complete; ++l) {
-        if (runs) { memcpy(line, e->blind_runs.data() + (size_t)l * 2 * kShiftRunsPerLine, sizeof(uint32_t) * 2 * kShiftRunsPerLine); line[14] = 0u; }
-        else for (int k = 0; k < kShiftNodesPerLine; ++k) line[k] = (uint32_t)e->pend_node[(size_t)l * kShiftNodesPerLine + k];
-        line[15] = next_seq;
-        mailbox_write_line(e->mailbox + e->shift_base + 16 * (size_t)l, line);
-    }
+    shift_write_lines(e, e->shift_streamed, complete, runs ? e->blind_runs.size() / 2 : e->blind_count, runs, next_seq);
     e->stream_sub += 1;
     if (e->stream_sub == 0) e->stream_sub = 1;
-    memset(line, 0, sizeof(line));
-    line[0] = next_seq;
-    line[1] = runs ? 4u : 2u;                      // "shift lines in place": node ids / {first, length} pairs
-    line[3] = (uint32_t)complete;
-    line[4] = e->stream_sub;
-    line[15] = next_seq;
-    _mm_sfence();
-    for (int r = 0; r < e->poll_replicas; ++r) mailbox_write_line(e->mailbox + (size_t)r * kReplicaStride, line);
-    _mm_sfence();
+    MailboxLine h{};
+    h.w[kHdrSeq] = next_seq;
+    h.w[kHdrCmd] = runs ? kCmdApplyRuns : kCmdApply;
+    h.w[kShHdrShift] = (uint32_t)complete;
+    h.w[kShHdrApplySub] = e->stream_sub;
+    h.w[kHdrTag] = next_seq;
+    mailbox_publish(e->mailbox, e->poll_replicas, h, nullptr);
     e->shift_streamed = complete;
     e->stream_lines = complete;                    // "a list is travelling": what the other paths test before they change their mind about it
 }
@@ -542,7 +517,7 @@ int cand_post_shift(mcf_engine *e)
         if (rc) return rc;
     }
     if (e->reload_pi) {
-        // mcf_engine_reload_potentials: the grid reads the bound array when it serves the request (cmd 3), so every potential change noted up to
+        // mcf_engine_reload_potentials: the grid reads the bound array when it serves the request (kCmdReload), so every potential change noted up to
         // now is part of it -- the lists are dropped, the state writes travel with the request.  (A grid that has just been started read the
         // arrays the host wrote from its mirrors: nothing to reload, resident_start cleared the flag.)
         if (!e->d_ext_pi || e->shift_streamed > 0 || (int64_t)e->sync_arcs.size() > (int64_t)e->mailbox_max_st) {
@@ -561,7 +536,7 @@ int cand_post_shift(mcf_engine *e)
         e->prev_seq = e->seq;
         e->seq += 1;
         if (e->seq == 0) e->seq = 1;
-        shift_post_request(e, e->seq, 3u, 0, 0, 0, true);
+        shift_post_request(e, e->seq, kCmdReload, 0, 0, 0, true);
         e->st.rc_reloads_in_grid += 1;
         e->pend_arc.clear(); e->pend_state.clear();
         e->sync_arcs.clear();
@@ -576,7 +551,7 @@ int cand_post_shift(mcf_engine *e)
         const bool blind_current = n_b == 0 || (e->blind_epoch == e->cand_now && e->blind_sets <= 1);
         const size_t n_pairs = e->blind_lazy ? e->blind_runs.size() / 2 : 0;
         const bool as_shift = n_b > 0 && blind_current && e->pend_shift &&
-                              (e->blind_lazy ? n_pairs <= (size_t)e->max_shift_lines * kShiftRunsPerLine : n_b <= (size_t)e->max_shift_lines * kShiftNodesPerLine);
+                              (e->blind_lazy ? n_pairs <= (size_t)e->max_shift_lines * kShiftPairsPerLine : n_b <= (size_t)e->max_shift_lines * kShiftNodesPerLine);
         const bool fits = (int64_t)(as_shift ? n_s : n_b + n_s) <= (int64_t)e->patch_capacity && (int64_t)e->sync_arcs.size() <= (int64_t)e->mailbox_max_st;
         if ((!as_shift && e->shift_streamed > 0) || !fits) {
             // lines of a list that is no shift list any more have travelled, or the request would not fit: bring the device up to date wholesale
@@ -599,7 +574,7 @@ int cand_post_shift(mcf_engine *e)
         e->prev_seq = e->seq;
         e->seq += 1;
         if (e->seq == 0) e->seq = 1;
-        shift_post_request(e, e->seq, 0u, val_lo, as_shift ? (runs ? n_pairs : n_b) : 0, e->pend_sigma, true, runs);
+        shift_post_request(e, e->seq, kCmdScan, val_lo, as_shift ? (runs ? n_pairs : n_b) : 0, e->pend_sigma, true, runs);
         if (!e->pend_node.empty() || !e->pend_arc.empty()) e->st.inline_updates += 1;
         if (as_shift) e->st.shift_lists += 1;
         e->pend_node.clear(); e->pend_val.clear(); e->pend_arc.clear(); e->pend_state.clear();
@@ -628,7 +603,7 @@ int cand_post(mcf_engine *e)
     if (e->seq == 0) e->seq = 1;
     int rc = resident_start(e, e->prev_seq);
     if (rc) return rc;
-    resident_post(e, e->seq, 0u, true);
+    resident_post(e, e->seq, kCmdScan, true);
     if (!e->pend_node.empty() || !e->pend_arc.empty()) e->st.inline_updates += 1;
     e->pend_node.clear(); e->pend_val.clear(); e->pend_arc.clear(); e->pend_state.clear();
     e->posted_at = e->cand_now;

@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "../../include/mcf_hip.h"
+#include "mailbox.hip.h"
 
 namespace {
 
@@ -562,12 +563,7 @@ __global__ __launch_bounds__(kResidentThreads) void scan_kernel_lds(const ScanPa
 // writes through the PCIe BAR: the host posts {seq, next_arc, patches}, every workgroup sees the new seq by polling device
 // memory, applies the patches, scans the tile(s) it owns and answers with its 16-byte record in pinned host memory.
 // Workgroups that own a single tile keep its arcs in registers (REG), so a request costs two potential gathers per arc and nothing else.
-//
-constexpr int kMailboxLines = 256;                // lines staged in LDS at a time: 16 KB = line 0 + a chunk of 255 patch lines (1275 patches)
-constexpr int kMailboxPatchesPerLine = 5;
-constexpr int kMaxReplicas = 16;                  // copies of the poll unit (lines 0 and 1), 4 KB apart, so that 256 pollers do not hammer one address
-constexpr int kReplicaStride = 1024;              // dwords
-constexpr int kMailboxTail = kMaxReplicas * kReplicaStride;   // dword offset of line 2
+// The mailbox and the helpers that read it: mailbox.hip.h.
 
 template <typename T>
 struct ResidentParams {
@@ -578,25 +574,10 @@ struct ResidentParams {
     T *pi;
     Slot *slots;
     const int32_t *orig;        // bucketed layout (see ScanParams), only read by the PERM variant
-    const uint32_t *mailbox;    // fine-grained VRAM, written by the host through the BAR
-    uint32_t *exit_word;        // pinned host memory: [0] exit code, [1] requests served, [2..3] scan ticks of workgroup 0
     int32_t base, count_padded, m_s;
-    uint32_t start_seq, idle_ticks;
     int32_t n_nodes;            // length of pi
-    int32_t max_pi;             // potential patches the mailbox can hold
-    int32_t max_st;             // state patches it can hold
-    int32_t poll_replicas, poll_sleep;
-    const int64_t *host_pi;     // resident_cand_kernel: the caller's bound potentials in mapped host memory (cmd 3 reloads from them), or null
-    uint32_t *barrier;          // ... and the arrival counter of its grid-wide barrier (zero at launch)
+    MailboxParams mb;           // host_pi / barrier: resident_cand_kernel's in-grid reload (kCmdReload), else null
 };
-
-__device__ __forceinline__ void resident_exit(uint32_t *exit_word, uint32_t code, uint32_t served, uint64_t scan_ticks)
-{
-    __hip_atomic_store(exit_word + 1, served, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(exit_word + 2, (uint32_t)scan_ticks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(exit_word + 3, (uint32_t)(scan_ticks >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(exit_word, code, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // (c, p) lexicographic; {0, kNone} = "none" and loses against every eligible arc
 struct Cand { int64_t c; uint32_t p; };
@@ -730,16 +711,6 @@ __device__ __forceinline__ void publish_candidates(int64_t c1, uint32_t p1, int6
     }
 }
 
-// Mailbox: lines of 64 bytes; dword 15 of EVERY line repeats seq, so a torn read of any line is detected and retried.
-//   line 0      [0] seq [1] cmd (0 scan, 1 quit, 2 apply) [2] next_arc [3] rstar [4] n_pi [5] n_st [6..9] state patches 0,1 {arc, value}
-//               [10..12] potential patch 0 {node, lo, hi} [13] scan: block size of THIS search (Block Search; the reference's adaptive
-//               rule changes it between searches, NS.cs:1400-1438) / apply: entry lines valid so far [14] apply: post counter
-// cmd 2 ("apply") streams a long potential list while the host is still walking the subtree: the entry lines 1..[13] of the NEXT scan
-// request are in place, every workgroup applies those it has not applied yet and goes back to polling (no answer).  The posts are
-// cumulative, so one that is overwritten before a workgroup saw it loses nothing; the scan request finishes the list.
-//   line 1..    five entries {a, b, c} each: potential patches 1..n_pi-1 {node, lo, hi}, then state patches 2..n_st-1 {arc, value, 0}
-// The poll reads line 0 only (one 64-byte read per workgroup per poll); the other lines are fetched when there are more entries.
-//
 // PIREG (register-resident arcs, potentials not in LDS, at most kPiRegThreads threads; with or without the candidate list): a thread also keeps the potentials of its arcs' end points in
 // registers and PATCHES them instead of gathering them again for every request -- the eight divergent gathers per thread cost
 // ~1.5 us per request on a CU (one lane per clock) while three out of four pivots move five nodes or fewer.  Lists of up to
@@ -778,99 +749,51 @@ __global__ __launch_bounds__(PIREG ? kPiRegThreads : kResidentThreads) void resi
         __syncthreads();
     }
     const T *const pi_view = LPI ? lpi : p.pi;
-    uint32_t last = p.start_seq, served = 0, last_sub = 0;
-    int applied = 0;                                          // entry lines of the coming scan request already applied (cmd 2)
+    uint32_t last = p.mb.start_seq, served = 0, last_sub = 0;
+    int applied = 0;                                          // entry lines of the coming scan request already applied (kCmdApply)
     uint64_t scan_ticks = 0;
     uint64_t idle_since = __builtin_amdgcn_s_memrealtime();
-    const uint32_t *const my_unit = p.mailbox + (size_t)(blockIdx.x % p.poll_replicas) * kReplicaStride;   // this workgroup's copy of lines 0, 1
+    const uint32_t *const my_unit = p.mb.mailbox + (size_t)(blockIdx.x % p.mb.poll_replicas) * kReplicaStride;   // this workgroup's copy of lines 0, 1
     for (;;) {
-        // ---- wait for a request: wave 0 polls lines 0 and 1 of the mailbox (128 bytes, system-scope reads of device memory) in a tight
-        // loop, the other waves sleep at the barrier
-        if (tid < 64) {
-            typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-            v4u x = v4u{0u, 0u, 0u, 0u};
-            uint32_t flag;
-            for (;;) {
-                if (tid < 8) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(x) : "v"(my_unit + tid * 4) : "memory");
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(x)::"memory");
-                const uint32_t seq0 = lane_u32(x[0], 0), tag0 = lane_u32(x[3], 3), cmd0 = lane_u32(x[1], 0), sub0 = lane_u32(x[2], 3);
-                if (seq0 != last && tag0 == seq0 && (cmd0 != 2u || sub0 != last_sub)) { flag = 1u; break; }
-                if (__builtin_amdgcn_s_memrealtime() - idle_since > p.idle_ticks) { flag = 2u; break; }
-                for (int z = 0; z < p.poll_sleep; ++z) __builtin_amdgcn_s_sleep(1);
-            }
-            if (tid < 8) *reinterpret_cast<v4u *>(lm + tid * 4) = x;
-            if (tid == 0) s_timeout = flag;
-        }
-        __syncthreads();
-        const uint32_t seq = lm[0];
-        int n_pi = (int)lm[4], n_st = (int)lm[5];
-        n_pi = n_pi < 0 ? 0 : (n_pi > p.max_pi ? p.max_pi : n_pi);
-        n_st = n_st < 0 ? 0 : (n_st > p.max_st ? p.max_st : n_st);
+        const bool timed_out = poll_request<kHdrApplySub>(my_unit, last, last_sub, [](uint32_t c) { return c == kCmdApply; }, idle_since, p.mb, lm, s_timeout);
+        const uint32_t seq = lm[kHdrSeq];
+        const int n_pi = clamp_count((int)lm[kHdrValues], p.mb.max_pi), n_st = clamp_count((int)lm[kHdrStates], p.mb.max_st);
         const int extra_pi = n_pi > 1 ? n_pi - 1 : 0, extra_st = n_st > 2 ? n_st - 2 : 0;
         const int entries = extra_pi + extra_st;
-        const uint32_t cmd = lm[1];
-        const bool apply_only = cmd == 2u;
-        const uint32_t sub = lm[14];
-        int upto = (int)lm[13];                              // apply: the last entry line in place
-        upto = upto < 0 ? 0 : (upto > (p.max_pi + p.max_st) / kMailboxPatchesPerLine ? (p.max_pi + p.max_st) / kMailboxPatchesPerLine : upto);
-        const int lines = apply_only ? 1 + upto : 1 + (entries + kMailboxPatchesPerLine - 1) / kMailboxPatchesPerLine;
-        const bool timed_out = s_timeout == 2u;
-        const bool line1_staged = lm[31] == seq;           // line 1 came along with the poll and is complete
-        const int next_arc = (int)lm[2], rstar = (int)lm[3];
-        const int block_size = (int)lm[13] > 0 ? (int)lm[13] : 1;      // scan requests only (an apply post keeps its line count there)
-        const int st_arc0 = (int)lm[6], st_arc1 = (int)lm[8];
-        const uint32_t st_val0 = lm[7], st_val1 = lm[9];
-        const uint32_t p0_node = lm[10], p0_lo = lm[11], p0_hi = lm[12];
-        if (lines > 1) __syncthreads();                    // everybody has read lines 0 and 1 before the patch lines land in lm (uniform condition)
-        if (timed_out) {
-            if (tid == 0 && blockIdx.x == 0) resident_exit(p.exit_word, 2u, served, scan_ticks);
+        const uint32_t cmd = lm[kHdrCmd];
+        const bool apply_only = cmd == kCmdApply;
+        const uint32_t sub = lm[kHdrApplySub];
+        const int upto = clamp_count((int)lm[kHdrApplyLines], (p.mb.max_pi + p.mb.max_st) / kMailboxPatchesPerLine);   // apply: entry lines in place
+        const int lines = apply_only ? upto : (entries + kMailboxPatchesPerLine - 1) / kMailboxPatchesPerLine;
+        const bool line1_staged = lm[16 + 15] == seq;      // entry line 0 came along with the poll and is complete
+        const int next_arc = (int)lm[kHdrNextArc], rstar = (int)lm[kHdrRstar];
+        const int block_size = (int)lm[kHdrBlockSize] > 0 ? (int)lm[kHdrBlockSize] : 1;      // scan requests only (an apply post keeps its line count there)
+        const int st_arc0 = (int)lm[kHdrState0], st_arc1 = (int)lm[kHdrState0 + 2];
+        const uint32_t st_val0 = lm[kHdrState0 + 1], st_val1 = lm[kHdrState0 + 3];
+        const uint32_t p0_node = lm[kHdrValue0], p0_lo = lm[kHdrValue0 + 1], p0_hi = lm[kHdrValue0 + 2];
+        if (lines > 0) __syncthreads();                    // everybody has read lines 0 and 1 before the entry lines land in lm (uniform condition)
+        if (timed_out || cmd == kCmdQuit) {
+            if (tid == 0 && blockIdx.x == 0) resident_exit(p.mb.exit_word, timed_out ? kExitIdle : kExitQuit, served, scan_ticks);
             return;
         }
         const uint64_t t_seen = blockIdx.x == 0 ? __builtin_amdgcn_s_memrealtime() : 0;     // only workgroup 0's clock is reported
-        if (cmd == 1u) {                                   // quit
-            if (tid == 0 && blockIdx.x == 0) resident_exit(p.exit_word, 1u, served, scan_ticks);
-            return;
-        }
         // ---- patches: final values, applied by EVERY workgroup before it reads (same argument as scan_kernel).
         // The entries beyond the header come in chunks of 255 lines (1275 entries), each line verified by its tag before use.
         // PIREG: 0 = nothing beyond the header, 1 = compare directly, 2 = bitmap + gather the hits, 3 = gather everything again
         // a streamed list (apply posts seen, or this is one) only stores; the scan request then gathers everything again (mode 3)
         const int pr_mode = !PIREG ? 0 : ((apply_only || applied > 0) ? 3 : (entries == 0 ? 0 : (entries <= kPiRegCompare ? 1 : (entries <= kPiRegBitmapMax ? 2 : 3))));
-        const int entries_here = apply_only ? upto * kMailboxPatchesPerLine : entries;      // entries that lines 1 .. lines-1 hold
+        const int entries_here = apply_only ? upto * kMailboxPatchesPerLine : entries;      // entries that entry lines 0 .. lines-1 hold
         const int pi_here = apply_only ? entries_here : extra_pi;                          // ... of which potential patches come first
         bool torn = false;
-        for (int first = applied + 1; first < lines; first += kChunk) {
+        for (int first = applied; first < lines; first += kChunk) {
             const int chunk = lines - first < kChunk ? lines - first : kChunk;
-            const bool staged = first == 1 && chunk == 1 && line1_staged;
-            for (int base = 0; base < chunk * 4 && !staged; base += nt * 4) {      // up to four 16-byte reads per thread in flight, one wait
-                typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-                v4u x[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    x[q] = v4u{0u, 0u, 0u, 0u};
-                    const int c = base + q * nt + tid;
-                    if (c < chunk * 4) {
-                        const int line = first + (c >> 2);      // line 1 sits in the poll unit, lines 2.. in the tail
-                        const uint32_t *src = line == 1 ? my_unit + 16 + (c & 3) * 4 : p.mailbox + (kMailboxTail + (size_t)(line - 2) * 16 + (c & 3) * 4);
-                        asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(x[q]) : "v"(src) : "memory");
-                    }
-                }
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3])::"memory");
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int c = base + q * nt + tid;
-                    if (c < chunk * 4) *reinterpret_cast<v4u *>(lm + 16 + c * 4) = x[q];
-                }
-            }
-            __syncthreads();
-            int bad = 0;
-            for (int l = tid; l < chunk; l += nt) bad |= (lm[(1 + l) * 16 + 15] != seq);
-            if (__syncthreads_or(bad)) { torn = true; break; }
-            const int i_lo = (first - 1) * kMailboxPatchesPerLine;                    // entry index of the chunk's first entry
+            const bool staged = first == 0 && chunk == 1 && line1_staged;                  // (then it is in place at lm + 16 already)
+            if (!stage_lines<4>(lm + 16, p.mb.mailbox, my_unit, 0, 0, 0, staged ? 0 : chunk, first, seq)) { torn = true; break; }
+            const int i_lo = first * kMailboxPatchesPerLine;                               // entry index of the chunk's first entry
             const int i_hi = entries_here < i_lo + chunk * kMailboxPatchesPerLine ? entries_here : i_lo + chunk * kMailboxPatchesPerLine;
             for (int i = i_lo + tid; i < i_hi; i += nt) {
                 const int rel = i - i_lo;
-                const uint32_t *q = lm + (1 + rel / kMailboxPatchesPerLine) * 16 + 3 * (rel % kMailboxPatchesPerLine);
+                const uint32_t *q = entry_at(lm + 16, rel);
                 if (i < pi_here) {
                     const int64_t v = (int64_t)(((uint64_t)q[2] << 32) | q[1]);
                     p.pi[q[0]] = (T)v;
@@ -885,7 +808,7 @@ __global__ __launch_bounds__(PIREG ? kPiRegThreads : kResidentThreads) void resi
                 const int hi_pi = i_hi < pi_here ? i_hi : pi_here;
                 for (int i = i_lo; i < hi_pi; ++i) {
                     const int rel = i - i_lo;
-                    const uint32_t *q = lm + (1 + rel / kMailboxPatchesPerLine) * 16 + 3 * (rel % kMailboxPatchesPerLine);
+                    const uint32_t *q = entry_at(lm + 16, rel);
                     const int node = (int)q[0];
                     const T v = (T)(int64_t)(((uint64_t)q[2] << 32) | q[1]);
 #pragma unroll
@@ -896,7 +819,7 @@ __global__ __launch_bounds__(PIREG ? kPiRegThreads : kResidentThreads) void resi
                 const int s_lo = i_lo > extra_pi ? i_lo : extra_pi;
                 for (int i = s_lo; i < i_hi; ++i) {
                     const int rel = i - i_lo;
-                    const uint32_t *q = lm + (1 + rel / kMailboxPatchesPerLine) * 16 + 3 * (rel % kMailboxPatchesPerLine);
+                    const uint32_t *q = entry_at(lm + 16, rel);
                     const int a = (int)q[0] - p.base - my_i0;
                     if ((unsigned)a < 4u) mine.st4 = (mine.st4 & ~(0xFFu << (8 * a))) | ((q[1] & 0xFFu) << (8 * a));
                 }
@@ -987,32 +910,25 @@ __global__ __launch_bounds__(PIREG ? kPiRegThreads : kResidentThreads) void resi
 //   * SHIFT LIST: the one big subtree a pivot moved, as bare node ids (15 per line) + the pivot's sigma (NS.cs:1187-1190: one sigma for
 //     the whole subtree).  Every workgroup sets the nodes' bits in an exact bitmap in LDS (one bit per node: node_count <= kShiftBits) and
 //     every thread adds sigma to those of its eight end points whose bit is set.  The lines travel while the host is still walking the
-//     subtree (cmd 2 posts: set bits, no answer); 4 bytes per node instead of 12, and the host never forms the values.
+//     subtree (kCmdApply posts: set bits, no answer); 4 bytes per node instead of 12, and the host never forms the values.
 //   * VALUE ENTRIES {node, value}: the nodes the host-side cache touched since the last request, with their final values (they override
 //     the shift: a value is read by the host when the request is built).  Few: compared directly; many: rounds of up to kCandRoundLines
 //     lines through a hash table in LDS (node -> value) that every thread probes for its eight end points.
 //   * STATE WRITES {arc, state}: compared against the thread's four arcs.
-//   * RELOAD (cmd 3): a walk so long that its node list would cost more than it is worth names no nodes: the host only moves its own
+//   * RELOAD (kCmdReload): a walk so long that its node list would cost more than it is worth names no nodes: the host only moves its own
 //     potentials, the workgroups copy the bound array (mapped host memory; each its slice, coalesced, over PCIe) into the device array, meet
 //     at a grid-wide barrier and every thread gathers its end points' potentials again.  The one place where this grid touches memory.
 // The arrays in memory are only read when the grid starts: the host, whose mirrors are authoritative in candidate mode, writes them again
 // before every launch (resident_start) -- so a grid that left on its idle timeout comes back with current values and the request it finds
 // waiting is re-posted without patches.
 constexpr int kShiftBits = 131072;                // nodes the exact bitmap covers (16 KB of LDS)
-constexpr int kShiftNodesPerLine = 15;
-constexpr int kShiftPairsPerLine = 7;             // ... or seven {first id, length} pairs: runs of consecutive ids (the host relabels the nodes in thread order)
 constexpr int kCandLines = 512;                   // staging: line 0 + 511 lines (32 KB)
 constexpr int kCandRoundLines = 480;              // value-entry lines per hash round: 2400 entries in ...
 constexpr int kCandHash = 4096;                   // ... this many slots
 constexpr uint32_t kHashEmpty = 0xFFFFFFFFu;
 constexpr int kCandCompare = 3;                   // value entries beyond the header's that are matched by direct comparison (~40 instructions each)
 
-// Mailbox of this grid.  Poll unit (replicated): line 0 = header, line 1 = first entry line.
-//   line 0   [0] seq [1] cmd (0 scan, 1 quit, 2 shift lines in place, 3 reload the potentials, then scan) [2] n_val [3] scan: n_shift nodes / cmd 2: shift lines in place so far
-//            [4] cmd 2: post counter [5] n_st [6..9] state writes 0, 1 {arc, state} [10..12] value entry 0 {node, lo, hi} [13..14] sigma [15] seq
-//   entry lines (tail, from kMailboxTail): five {a, b, c} each: value entries 1.., then state writes 2..; [15] = seq
-//   shift lines (from shift_base): fifteen node ids each, or (scan: line 0 [4] == 1; in-place posts: cmd 4 instead of 2) seven {first id,
-//            length} pairs; [15] = seq of the scan request they belong to
+// Its requests (mailbox.hip.h): a header with the kShHdr* words, entry lines, and the shift list in shift lines from shift_base.
 // TILES register tiles of four arcs per thread (tile t of a thread lies gridDim * blockDim * 4 arcs behind tile t - 1), at most kCandThreads
 // threads: four waves, one per SIMD of the CU.  A wave instruction takes four cycles and two waves on one SIMD take turns, so the reductions of
 // seven waves of 448 threads (one tile each) ran at half the rate of these four.
@@ -1054,134 +970,60 @@ __global__ __launch_bounds__(kCandThreads) void resident_cand_kernel(const Resid
         atomicOr(&sp_mask[t * kCandThreads + owner], 0xFFu << (8 * slot));
         atomicOr(&sp_val[t * kCandThreads + owner], (val & 0xFFu) << (8 * slot));
     };
-    uint32_t last = p.start_seq, served = 0, last_sub = 0, shifted_for = p.start_seq;
+    uint32_t last = p.mb.start_seq, served = 0, last_sub = 0, shifted_for = p.mb.start_seq;
     int shift_done = 0;                                   // shift lines of the coming scan request whose bits are set
     bool bits_set = false;
-    uint32_t reloaded_for = p.start_seq, barriers = 0;    // a request's reload happens once (a retry after a torn line must not meet the others at the barrier again)
-    // grid-wide barrier (all workgroups are resident: one per CU); false when it gave up -- every spin of this kernel is bounded
-    auto grid_barrier = [&]() -> bool {
-        __builtin_amdgcn_s_waitcnt(0);
-        __syncthreads();
-        barriers += 1;
-        if (tid == 0) {
-            __hip_atomic_fetch_add(p.barrier, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t want = barriers * gridDim.x;
-            const uint64_t t_bar = __builtin_amdgcn_s_memrealtime();
-            uint32_t gave_up = 0u;
-            while (__hip_atomic_load(p.barrier, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < want) {
-                __builtin_amdgcn_s_sleep(2);
-                if (__builtin_amdgcn_s_memrealtime() - t_bar > 8ull * p.idle_ticks) { gave_up = 1u; break; }
-            }
-            s_timeout = gave_up ? 3u : 0u;
-        }
-        __syncthreads();
-        if (s_timeout == 3u) return false;
-        // what the other XCDs wrote through to memory may still sit in this CU's L1 / this XCD's L2 in its old form: forget it
-        if (tid < 64) asm volatile("buffer_inv sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        return true;
-    };
+    uint32_t reloaded_for = p.mb.start_seq, barriers = 0; // a request's reload happens once (a retry after a torn line must not meet the others at the barrier again)
     uint64_t scan_ticks = 0;
     uint64_t ph_shift = 0, ph_values = 0, ph_scan = 0, n_shift_req = 0;       // workgroup 0's clock by phase (exit record words 4..11)
     const uint64_t born_rt = __builtin_amdgcn_s_memrealtime(), born_clk = __builtin_amdgcn_s_memtime();
     uint64_t idle_since = __builtin_amdgcn_s_memrealtime();
-    const uint32_t *const my_unit = p.mailbox + (size_t)(blockIdx.x % p.poll_replicas) * kReplicaStride;
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    const uint32_t *const my_unit = p.mb.mailbox + (size_t)(blockIdx.x % p.mb.poll_replicas) * kReplicaStride;
     constexpr int kStage = 32;                            // dword offset of the staging area in lm: lines 0 and 1 keep the poll unit
     constexpr int kChunk = kCandLines - 2;
-    // stages n_a shift lines (from shift line first_a) followed by n_v entry lines (from entry line first_v; entry line 0 sits in the poll
-    // unit, the others in the tail) into lm[kStage..] with ONE round of loads; true when every line carries the tag `seq`
+    // n_a shift lines (from shift line first_a), then n_v entry lines (from entry line first_v) into lm[kStage..] with ONE round of loads
     auto fetch = [&](int n_a, int first_a, int n_v, int first_v, uint32_t seq) -> bool {
-        const int count = n_a + n_v;
-        for (int base = 0; base < count * 4; base += nt * 4) {
-            v4u x[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                x[q] = v4u{0u, 0u, 0u, 0u};
-                const int c = base + q * nt + tid;
-                if (c < count * 4) {
-                    const int l = c >> 2;
-                    const uint32_t *src;
-                    if (l < n_a) src = p.mailbox + (shift_base + (size_t)(first_a + l) * 16 + (c & 3) * 4);
-                    else {
-                        const int v = first_v + l - n_a;
-                        src = v == 0 ? my_unit + 16 + (c & 3) * 4 : p.mailbox + (kMailboxTail + (size_t)(v - 1) * 16 + (c & 3) * 4);
-                    }
-                    asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(x[q]) : "v"(src) : "memory");
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3])::"memory");
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int c = base + q * nt + tid;
-                if (c < count * 4) *reinterpret_cast<v4u *>(lm + kStage + c * 4) = x[q];
-            }
-        }
-        __syncthreads();
-        int bad = 0;
-        for (int l = tid; l < count; l += nt) bad |= (lm[kStage + l * 16 + 15] != seq);
-        return __syncthreads_or(bad) == 0;
+        return stage_lines<4>(lm + kStage, p.mb.mailbox, my_unit, shift_base, n_a, first_a, n_v, first_v, seq);
     };
     for (;;) {
-        if (tid < 64) {
-            v4u x = v4u{0u, 0u, 0u, 0u};
-            uint32_t flag;
-            for (;;) {
-                if (tid < 8) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(x) : "v"(my_unit + tid * 4) : "memory");
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(x)::"memory");
-                const uint32_t seq0 = lane_u32(x[0], 0), tag0 = lane_u32(x[3], 3), cmd0 = lane_u32(x[1], 0), sub0 = lane_u32(x[0], 1);
-                if (seq0 != last && tag0 == seq0 && ((cmd0 != 2u && cmd0 != 4u) || sub0 != last_sub)) { flag = 1u; break; }
-                if (__builtin_amdgcn_s_memrealtime() - idle_since > p.idle_ticks) { flag = 2u; break; }
-                for (int z = 0; z < p.poll_sleep; ++z) __builtin_amdgcn_s_sleep(1);
-            }
-            if (tid < 8) *reinterpret_cast<v4u *>(lm + tid * 4) = x;
-            if (tid == 0) s_timeout = flag;
-        }
-        __syncthreads();
-        const uint32_t seq = lm[0], cmd = lm[1], sub = lm[4];
-        int n_val = (int)lm[2], n_st = (int)lm[5];
-        n_val = n_val < 0 ? 0 : (n_val > p.max_pi ? p.max_pi : n_val);
-        n_st = n_st < 0 ? 0 : (n_st > p.max_st ? p.max_st : n_st);
-        const bool apply_only = cmd == 2u || cmd == 4u;
+        const bool timed_out = poll_request<kShHdrApplySub>(my_unit, last, last_sub, [](uint32_t c) { return c == kCmdApply || c == kCmdApplyRuns; },
+                                                            idle_since, p.mb, lm, s_timeout);
+        const uint32_t seq = lm[kHdrSeq], cmd = lm[kHdrCmd], sub = lm[kShHdrApplySub];
+        const int n_val = clamp_count((int)lm[kShHdrValues], p.mb.max_pi), n_st = clamp_count((int)lm[kHdrStates], p.mb.max_st);
+        const bool apply_only = cmd == kCmdApply || cmd == kCmdApplyRuns;
         // the shift list comes as node ids (15 per line) or as {first, length} pairs (7 per line: runs of consecutive ids)
-        const bool ranges = apply_only ? cmd == 4u : lm[4] == 1u;
+        const bool ranges = apply_only ? cmd == kCmdApplyRuns : lm[kShHdrRuns] == 1u;
         const int per_line = ranges ? kShiftPairsPerLine : kShiftNodesPerLine;
-        int n_shift = apply_only ? 0 : (int)lm[3];                      // entries: nodes or pairs
-        n_shift = n_shift < 0 ? 0 : (n_shift > max_shift_lines * per_line ? max_shift_lines * per_line : n_shift);
-        int shift_lines = apply_only ? (int)lm[3] : (n_shift + per_line - 1) / per_line;
-        shift_lines = shift_lines < 0 ? 0 : (shift_lines > max_shift_lines ? max_shift_lines : shift_lines);
-        const int64_t sigma = (int64_t)(((uint64_t)lm[14] << 32) | lm[13]);
-        const bool timed_out = s_timeout == 2u;
-        const bool line1_staged = lm[31] == seq;
-        const int st_arc0 = (int)lm[6], st_arc1 = (int)lm[8];
-        const uint32_t st_val0 = lm[7], st_val1 = lm[9];
-        const uint32_t v0_node = lm[10];
-        const T v0 = (T)(int64_t)(((uint64_t)lm[12] << 32) | lm[11]);
-        if (timed_out || cmd == 1u) {
+        const int n_shift = apply_only ? 0 : clamp_count((int)lm[kShHdrShift], max_shift_lines * per_line);      // entries: nodes or pairs
+        const int shift_lines = clamp_count(apply_only ? (int)lm[kShHdrShift] : (n_shift + per_line - 1) / per_line, max_shift_lines);
+        const int64_t sigma = (int64_t)(((uint64_t)lm[kShHdrSigma + 1] << 32) | lm[kShHdrSigma]);
+        const bool line1_staged = lm[16 + 15] == seq;
+        const int st_arc0 = (int)lm[kHdrState0], st_arc1 = (int)lm[kHdrState0 + 2];
+        const uint32_t st_val0 = lm[kHdrState0 + 1], st_val1 = lm[kHdrState0 + 3];
+        const uint32_t v0_node = lm[kHdrValue0];
+        const T v0 = (T)(int64_t)(((uint64_t)lm[kHdrValue0 + 2] << 32) | lm[kHdrValue0 + 1]);
+        if (timed_out || cmd == kCmdQuit) {
             if (tid == 0 && blockIdx.x == 0) {
                 // shader clock over this launch in MHz (s_memtime counts shader cycles, s_memrealtime 100 MHz): word 10
                 const uint64_t d_rt = __builtin_amdgcn_s_memrealtime() - born_rt, d_clk = __builtin_amdgcn_s_memtime() - born_clk;
                 n_shift_req = d_rt ? d_clk * 100 / d_rt : 0;
                 const uint64_t ph[4] = {ph_shift, ph_values, ph_scan, n_shift_req};
                 for (int q = 0; q < 4; ++q) {
-                    __hip_atomic_store(p.exit_word + 4 + 2 * q, (uint32_t)ph[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    __hip_atomic_store(p.exit_word + 5 + 2 * q, (uint32_t)(ph[q] >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(p.mb.exit_word + 4 + 2 * q, (uint32_t)ph[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(p.mb.exit_word + 5 + 2 * q, (uint32_t)(ph[q] >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
-                resident_exit(p.exit_word, timed_out ? 2u : 1u, served, scan_ticks);
+                resident_exit(p.mb.exit_word, timed_out ? kExitIdle : kExitQuit, served, scan_ticks);
             }
             return;
         }
         const uint64_t t_seen = blockIdx.x == 0 ? __builtin_amdgcn_s_memrealtime() : 0;
         // ---- reload: every potential anew from the caller's array, my end points' potentials anew from them (NS.cs:1196-1208 moved so many
         // nodes that the host sends no list: it only moved its own potentials)
-        if (cmd == 3u && p.host_pi && reloaded_for != seq) {
-            const int per = (p.n_nodes + (int)gridDim.x - 1) / (int)gridDim.x;
-            const int lo = (int)blockIdx.x * per, hi = lo + per < p.n_nodes ? lo + per : p.n_nodes;
-            // agent scope: written through to memory, where the workgroups of the other XCDs (each with an L2 of its own) will find it
-            for (int i = lo + tid; i < hi; i += nt) __hip_atomic_store(p.pi + i, (T)p.host_pi[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (!grid_barrier()) {
-                // the grid leaves with code 3: the host writes the arrays from its mirrors, starts it again and posts the request as a plain scan
-                if (tid == 0) resident_exit(p.exit_word, 3u, served, scan_ticks);
+        if (cmd == kCmdReload && p.mb.host_pi && reloaded_for != seq) {
+            reload_slice(p.pi, sizeof(T) == 4, p.mb.host_pi, p.n_nodes);
+            if (!grid_barrier(p.mb, barriers, s_timeout)) {
+                // the grid leaves with kExitBarrier: the host writes the arrays from its mirrors, starts it again and posts the request as a plain scan
+                if (tid == 0) resident_exit(p.mb.exit_word, kExitBarrier, served, scan_ticks);
                 return;
             }
 #pragma unroll
@@ -1279,7 +1121,7 @@ __global__ __launch_bounds__(kCandThreads) void resident_cand_kernel(const Resid
             if (n_here <= kCandCompare) {
                 for (int i = i_lo; i < v_hi; ++i) {
                     const int rel = i - i_lo;
-                    const uint32_t *q = at + (rel / kMailboxPatchesPerLine) * 16 + 3 * (rel % kMailboxPatchesPerLine);
+                    const uint32_t *q = entry_at(at, rel);
                     const int node = (int)q[0];
                     const T v = (T)(int64_t)(((uint64_t)q[2] << 32) | q[1]);
 #pragma unroll
@@ -1297,7 +1139,7 @@ __global__ __launch_bounds__(kCandThreads) void resident_cand_kernel(const Resid
                 for (int x = tid; x < p2; x += nt) {
                     const int rel = (x * 37) & (p2 - 1);                                // neighbouring lanes: entries 37 apart (see set_bits)
                     if (rel >= n_here) continue;
-                    const uint32_t *q = at + (rel / kMailboxPatchesPerLine) * 16 + 3 * (rel % kMailboxPatchesPerLine);
+                    const uint32_t *q = entry_at(at, rel);
                     const uint32_t node = q[0];
                     atomicOr(&vmap[(node >> 5) & (kShiftBits / 32 - 1)], 1u << (node & 31));
                     uint32_t h = (node * 2654435761u) >> 20;                            // 12 bits
@@ -1339,7 +1181,7 @@ __global__ __launch_bounds__(kCandThreads) void resident_cand_kernel(const Resid
                 // wipe: the marks by walking the entries again (whole words: no atomics needed, everybody writes 0), the table wholesale
                 for (int i = i_lo + tid; i < v_hi; i += nt) {
                     const int rel = i - i_lo;
-                    const uint32_t node = at[(rel / kMailboxPatchesPerLine) * 16 + 3 * (rel % kMailboxPatchesPerLine)];
+                    const uint32_t node = *entry_at(at, rel);
                     vmap[(node >> 5) & (kShiftBits / 32 - 1)] = 0u;
                 }
                 for (int i = tid; i < kCandHash; i += nt) hkey[i] = kHashEmpty;
@@ -1348,7 +1190,7 @@ __global__ __launch_bounds__(kCandThreads) void resident_cand_kernel(const Resid
                 const int s_lo = i_lo > extra_val ? i_lo : extra_val;
                 for (int i = s_lo + tid; i < i_hi; i += nt) {
                     const int rel = i - i_lo;
-                    const uint32_t *q = at + (rel / kMailboxPatchesPerLine) * 16 + 3 * (rel % kMailboxPatchesPerLine);
+                    const uint32_t *q = entry_at(at, rel);
                     post_state((int)q[0], q[1]);
                 }
             }
@@ -1482,23 +1324,19 @@ struct ResidentRcParams {
     const int32_t *adj_start;
     const uint32_t *adj;
     Slot *slots;
-    const uint32_t *mailbox;
-    uint32_t *exit_word;
-    // in-grid reload (cmd 3): the arcs' end points and costs, the caller's bound potentials as the device sees them (mapped host memory; nullptr:
-    // the host never posts a reload), and a counter in device memory for the grid-wide barrier (zeroed by the host before every launch)
+    // in-grid reload (kCmdReload): the arcs' end points and costs (mb.host_pi null: the host never posts a reload; mb.barrier also serves the
+    // dealt-out long lists)
     const int32_t *src, *tgt;
     const void *cost;
-    const int64_t *host_pi;
-    uint32_t *barrier;
     int32_t base, count_padded, m_s, window;       // window: arcs per workgroup (LD), multiple of 4 * blockDim
-    uint32_t start_seq, idle_ticks;
-    int32_t narrow, max_pi, max_st, poll_replicas, poll_sleep, n_nodes;
+    int32_t narrow, n_nodes;
+    MailboxParams mb;
 };
 
 // A request of this grid: the State[] writes and the moved nodes WITH THEIR SHIFT ({node, delta}), any number of them: the entry lines are
 // staged and worked off in chunks of one staging area (255 lines).  Shifts are atomics -- applying a chunk twice would be wrong -- so the
 // grid remembers how far it got with the request it is working on (a torn line makes it poll again and resume there).
-//   cmd 3 (reload): "the bound potentials in host memory are current, every potential may have changed": the workgroups copy the array
+//   kCmdReload: "the bound potentials in host memory are current, every potential may have changed": the workgroups copy the array
 //   (each its share, over PCIe), meet at a grid-wide barrier, and every workgroup computes the reduced costs of ITS arcs again -- what
 //   mcf_engine_reload_potentials used to stop the grid for (memcpy + rc_init_kernel + a new launch).
 template <int RULE, bool OPT, bool LD, bool CAND = false>
@@ -1517,7 +1355,6 @@ __global__ __launch_bounds__(kResidentThreads) void resident_rc_kernel(const Res
     const int tid = threadIdx.x, nt = (int)blockDim.x;
     const int w_lo = LD ? (int)blockIdx.x * p.window : 0;                       // first position of my window
     typedef long v2l __attribute__((ext_vector_type(2)));
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
     auto load_window = [&]() {
         for (int i = tid * 4; i < p.window; i += nt * 4) {
             const int g = w_lo + i;
@@ -1533,12 +1370,12 @@ __global__ __launch_bounds__(kResidentThreads) void resident_rc_kernel(const Res
         __syncthreads();
     };
     if (LD) load_window();
-    uint32_t last = p.start_seq, served = 0, prog_seq = p.start_seq, barriers = 0;
+    uint32_t last = p.mb.start_seq, served = 0, prog_seq = p.mb.start_seq, barriers = 0;
     int prog_lines = 0;                                        // entry lines of request prog_seq already worked off
     bool prog_header = false;                                  // ... and its header entries
     uint64_t scan_ticks = 0;
     uint64_t idle_since = __builtin_amdgcn_s_memrealtime();
-    const uint32_t *const my_unit = p.mailbox + (size_t)(blockIdx.x % p.poll_replicas) * kReplicaStride;
+    const uint32_t *const my_unit = p.mb.mailbox + (size_t)(blockIdx.x % p.mb.poll_replicas) * kReplicaStride;
     // one moved node's arcs: shift those of MY window (LDS copy and memory), each arc exactly once, by its only reader
     auto shift_lists = [&](int n_here) {
         if (tid == 0) s_pre[0] = 0;
@@ -1584,83 +1421,31 @@ __global__ __launch_bounds__(kResidentThreads) void resident_rc_kernel(const Res
             if (LD && a >= w_lo && a < w_lo + p.window) ls[a - w_lo] = (int8_t)val;
         }
     };
-    // grid-wide barrier (all workgroups are resident: one per CU).  Returns false when it gave up: a workgroup that never got a CU
-    // (somebody else's grid holds them) must not hang the others -- every spin of this kernel is bounded.
-    auto grid_barrier = [&]() -> bool {
-        __builtin_amdgcn_s_waitcnt(0);
-        __syncthreads();
-        barriers += 1;
-        if (tid == 0) {
-            __hip_atomic_fetch_add(p.barrier, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t want = barriers * gridDim.x;
-            const uint64_t t_bar = __builtin_amdgcn_s_memrealtime();
-            uint32_t gave_up = 0u;
-            while (__hip_atomic_load(p.barrier, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < want) {
-                __builtin_amdgcn_s_sleep(2);
-                if (__builtin_amdgcn_s_memrealtime() - t_bar > 8ull * p.idle_ticks) { gave_up = 1u; break; }
-            }
-            s_timeout = gave_up ? 3u : 0u;
-        }
-        __syncthreads();
-        if (s_timeout == 3u) return false;
-        // what other XCDs wrote through to memory may still sit in this CU's L1 / this XCD's L2 in its old form: forget it (once per workgroup)
-        if (tid < 64) asm volatile("buffer_inv sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        return true;
-    };
     for (;;) {
-        if (tid < 64) {                                        // wave 0 polls lines 0 and 1 (see resident_kernel)
-            v4u x = v4u{0u, 0u, 0u, 0u};
-            uint32_t flag;
-            for (;;) {
-                if (tid < 8) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(x) : "v"(my_unit + tid * 4) : "memory");
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(x)::"memory");
-                const uint32_t seq0 = lane_u32(x[0], 0), tag0 = lane_u32(x[3], 3);
-                if (seq0 != last && tag0 == seq0) { flag = 1u; break; }
-                if (__builtin_amdgcn_s_memrealtime() - idle_since > p.idle_ticks) { flag = 2u; break; }
-                for (int z = 0; z < p.poll_sleep; ++z) __builtin_amdgcn_s_sleep(1);
-            }
-            if (tid < 8) *reinterpret_cast<v4u *>(lm + tid * 4) = x;
-            if (tid == 0) s_timeout = flag;
-        }
-        __syncthreads();
-        const uint32_t seq = lm[0], cmd = lm[1];
-        int n_pi = (int)lm[4], n_st = (int)lm[5];
-        n_pi = n_pi < 0 ? 0 : (n_pi > p.max_pi ? p.max_pi : n_pi);
-        n_st = n_st < 0 ? 0 : (n_st > p.max_st ? p.max_st : n_st);
+        const bool timed_out = poll_request<-1>(my_unit, last, 0u, [](uint32_t) { return false; }, idle_since, p.mb, lm, s_timeout);
+        const uint32_t seq = lm[kHdrSeq], cmd = lm[kHdrCmd];
+        const int n_pi = clamp_count((int)lm[kHdrValues], p.mb.max_pi), n_st = clamp_count((int)lm[kHdrStates], p.mb.max_st);
         const int extra_pi = n_pi > 1 ? n_pi - 1 : 0, extra_st = n_st > 2 ? n_st - 2 : 0, entries = extra_pi + extra_st;
         const int lines = (entries + kMailboxPatchesPerLine - 1) / kMailboxPatchesPerLine;
-        const bool timed_out = s_timeout == 2u;
-        const bool line1_staged = lm[31] == seq;
-        const int next_arc = (int)lm[2], rstar = (int)lm[3];
-        const int block_size = (int)lm[13] > 0 ? (int)lm[13] : 1;
-        const int st_arc0 = (int)lm[6], st_arc1 = (int)lm[8];
-        const uint32_t st_val0 = lm[7], st_val1 = lm[9];
-        const uint32_t p0_node = lm[10], p0_lo = lm[11], p0_hi = lm[12];
+        const bool line1_staged = lm[16 + 15] == seq;
+        const int next_arc = (int)lm[kHdrNextArc], rstar = (int)lm[kHdrRstar];
+        const int block_size = (int)lm[kHdrBlockSize] > 0 ? (int)lm[kHdrBlockSize] : 1;
+        const int st_arc0 = (int)lm[kHdrState0], st_arc1 = (int)lm[kHdrState0 + 2];
+        const uint32_t st_val0 = lm[kHdrState0 + 1], st_val1 = lm[kHdrState0 + 3];
+        const uint32_t p0_node = lm[kHdrValue0], p0_lo = lm[kHdrValue0 + 1], p0_hi = lm[kHdrValue0 + 2];
         __syncthreads();                                       // everybody has read lines 0 and 1 before entry lines land in lm
-        if (timed_out) {
-            if (tid == 0 && blockIdx.x == 0) resident_exit(p.exit_word, 2u, served, scan_ticks);
+        if (timed_out || cmd == kCmdQuit) {
+            if (tid == 0 && blockIdx.x == 0) resident_exit(p.mb.exit_word, timed_out ? kExitIdle : kExitQuit, served, scan_ticks);
             return;
         }
         const uint64_t t_seen = blockIdx.x == 0 ? __builtin_amdgcn_s_memrealtime() : 0;
-        if (cmd == 1u) {
-            if (tid == 0 && blockIdx.x == 0) resident_exit(p.exit_word, 1u, served, scan_ticks);
-            return;
-        }
         if (prog_seq != seq) { prog_seq = seq; prog_lines = 0; prog_header = false; }
         // ---- reload: every potential anew from the caller's array, every reduced cost of my arcs anew from them
-        if (cmd == 3u && !prog_header && p.host_pi) {
-            const int per = (p.n_nodes + (int)gridDim.x - 1) / (int)gridDim.x;
-            const int lo = (int)blockIdx.x * per, hi = lo + per < p.n_nodes ? lo + per : p.n_nodes;
-            for (int i = lo + tid; i < hi; i += nt) {
-                const int64_t v = p.host_pi[i];
-                // agent scope: written through to memory, where the workgroups of the other XCDs (each with an L2 of its own) will find it
-                if (p.narrow) __hip_atomic_store(reinterpret_cast<int32_t *>(p.pi) + i, (int32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else __hip_atomic_store(reinterpret_cast<int64_t *>(p.pi) + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (!grid_barrier()) {
-                // the grid leaves with code 3; the host starts it again and the reload, which overwrites everything, runs from the start
-                if (tid == 0) resident_exit(p.exit_word, 3u, served, scan_ticks);
+        if (cmd == kCmdReload && !prog_header && p.mb.host_pi) {
+            reload_slice(p.pi, p.narrow != 0, p.mb.host_pi, p.n_nodes);
+            if (!grid_barrier(p.mb, barriers, s_timeout)) {
+                // the grid leaves with kExitBarrier; the host starts it again and the reload, which overwrites everything, runs from the start
+                if (tid == 0) resident_exit(p.mb.exit_word, kExitBarrier, served, scan_ticks);
                 return;
             }
             const int step = LD ? nt * kArcsPerThread : (int)gridDim.x * nt * kArcsPerThread;
@@ -1696,7 +1481,7 @@ __global__ __launch_bounds__(kResidentThreads) void resident_rc_kernel(const Res
         // (every workgroup walks every list and shifts only what it reads itself); that scheme read the arc lists 256 times over, which for a
         // list of 50 000 nodes was 0.9 ms per request.  Not repeatable (shifts are not idempotent): nothing here is retried, a line that has
         // not arrived yet is waited for.
-        if (cmd != 3u && n_pi > kRcResidentNodes && p.barrier && !prog_header) {
+        if (cmd != kCmdReload && n_pi > kRcResidentNodes && p.mb.barrier && !prog_header) {
             const int wave = tid >> 6, lane = tid & 63, waves = nt >> 6;
             uint32_t failed = 0u;
             if (blockIdx.x == 0 && wave == 0) {                // the header's moved node
@@ -1712,16 +1497,8 @@ __global__ __launch_bounds__(kResidentThreads) void resident_rc_kernel(const Res
                 }
             }
             for (int l = (int)blockIdx.x + wave * (int)gridDim.x; l < lines; l += (int)gridDim.x * waves) {
-                const uint32_t *src = l == 0 ? my_unit + 16 : p.mailbox + (kMailboxTail + (size_t)(l - 1) * 16);
-                v4u x = v4u{0u, 0u, 0u, 0u};
-                const uint64_t t_line = __builtin_amdgcn_s_memrealtime();
-                for (;;) {
-                    if (lane < 4) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(x) : "v"(src + lane * 4) : "memory");
-                    asm volatile("s_waitcnt vmcnt(0)" : "+v"(x)::"memory");
-                    if (lane_u32(x[3], 3) == seq) break;
-                    if (__builtin_amdgcn_s_memrealtime() - t_line > p.idle_ticks) { failed = 1u; break; }
-                }
-                if (failed) break;
+                v4u x;
+                if (!wait_line(entry_line(p.mb.mailbox, my_unit, l), seq, p.mb.idle_ticks, x)) { failed = 1u; break; }
 #pragma unroll
                 for (int k = 0; k < kMailboxPatchesPerLine; ++k) {
                     const int e = l * kMailboxPatchesPerLine + k;
@@ -1745,16 +1522,8 @@ __global__ __launch_bounds__(kResidentThreads) void resident_rc_kernel(const Res
             // every XCD's L2 holds every write (one workgroup writing through to memory would leave the other XCDs' copies of the line stale).
             // They sit in the entry lines behind the moved nodes.
             for (int l = extra_pi / kMailboxPatchesPerLine + wave; l < lines && !failed; l += waves) {
-                const uint32_t *src = l == 0 ? my_unit + 16 : p.mailbox + (kMailboxTail + (size_t)(l - 1) * 16);
-                v4u x = v4u{0u, 0u, 0u, 0u};
-                const uint64_t t_line = __builtin_amdgcn_s_memrealtime();
-                for (;;) {
-                    if (lane < 4) asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(x) : "v"(src + lane * 4) : "memory");
-                    asm volatile("s_waitcnt vmcnt(0)" : "+v"(x)::"memory");
-                    if (lane_u32(x[3], 3) == seq) break;
-                    if (__builtin_amdgcn_s_memrealtime() - t_line > p.idle_ticks) { failed = 1u; break; }
-                }
-                if (failed) break;
+                v4u x;
+                if (!wait_line(entry_line(p.mb.mailbox, my_unit, l), seq, p.mb.idle_ticks, x)) { failed = 1u; break; }
 #pragma unroll
                 for (int k = 0; k < kMailboxPatchesPerLine; ++k) {
                     const int e = l * kMailboxPatchesPerLine + k;
@@ -1763,10 +1532,10 @@ __global__ __launch_bounds__(kResidentThreads) void resident_rc_kernel(const Res
             }
             if (tid == 0 && n_st > 0) state_write(st_arc0, st_val0);
             if (tid == 1 && n_st > 1) state_write(st_arc1, st_val1);
-            const bool met = grid_barrier();
+            const bool met = grid_barrier(p.mb, barriers, s_timeout);
             if (__syncthreads_or((int)failed) || !met) {
                 // part of the list is applied and part is not: there is no way back.  The host gets an error, not a wrong answer
-                if (tid == 0 && blockIdx.x == 0) resident_exit(p.exit_word, 4u, served, scan_ticks);
+                if (tid == 0 && blockIdx.x == 0) resident_exit(p.mb.exit_word, kExitPartial, served, scan_ticks);
                 return;
             }
             if (LD) load_window();
@@ -1775,7 +1544,7 @@ __global__ __launch_bounds__(kResidentThreads) void resident_rc_kernel(const Res
         }
         // ---- header entries: moved node 0 {node, delta}, state writes 0 and 1
         if (!prog_header) {
-            if (n_pi > 0 && cmd != 3u) {
+            if (n_pi > 0 && cmd != kCmdReload) {
                 if (tid == 0) {
                     s_node[0] = (int)p0_node;
                     s_delta[0] = (int64_t)(((uint64_t)p0_hi << 32) | p0_lo);
@@ -1793,30 +1562,14 @@ __global__ __launch_bounds__(kResidentThreads) void resident_rc_kernel(const Res
         bool torn = false;
         for (int first = prog_lines; first < lines; first += kChunk) {
             const int chunk = lines - first < kChunk ? lines - first : kChunk;
-            const bool staged = first == 0 && chunk == 1 && line1_staged;
-            if (!staged) {                                     // (a single line that came with the poll is in place already)
-                for (int base = 0; base < chunk * 4; base += nt) {
-                    const int c = base + tid;
-                    if (c < chunk * 4) {
-                        const int line = first + (c >> 2);          // entry line 0 sits in the poll unit, the others in the tail
-                        const uint32_t *src = line == 0 ? my_unit + 16 + (c & 3) * 4 : p.mailbox + (kMailboxTail + (size_t)(line - 1) * 16 + (c & 3) * 4);
-                        v4u x;
-                        asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(x) : "v"(src) : "memory");
-                        asm volatile("s_waitcnt vmcnt(0)" : "+v"(x)::"memory");
-                        *reinterpret_cast<v4u *>(lm + 16 + c * 4) = x;
-                    }
-                }
-            }
-            __syncthreads();
-            int bad = 0;
-            for (int l = tid; l < chunk; l += nt) bad |= (lm[(1 + l) * 16 + 15] != seq);
-            if (__syncthreads_or(bad)) { torn = true; break; }
+            const bool staged = first == 0 && chunk == 1 && line1_staged;     // (then it is in place at lm + 16 already)
+            if (!stage_lines<1>(lm + 16, p.mb.mailbox, my_unit, 0, 0, 0, staged ? 0 : chunk, first, seq)) { torn = true; break; }
             const int i_lo = first * kMailboxPatchesPerLine;
             const int i_hi = entries < i_lo + chunk * kMailboxPatchesPerLine ? entries : i_lo + chunk * kMailboxPatchesPerLine;
             const int pi_hi = i_hi < extra_pi ? i_hi : extra_pi;                     // moved nodes of this chunk: [i_lo, pi_hi)
             const int n_here = pi_hi > i_lo ? pi_hi - i_lo : 0;
             for (int i = tid; i < n_here; i += nt) {
-                const uint32_t *q = lm + (1 + i / kMailboxPatchesPerLine) * 16 + 3 * (i % kMailboxPatchesPerLine);
+                const uint32_t *q = entry_at(lm + 16, i);
                 const uint32_t node = q[0];
                 const int a0 = p.adj_start[node], a1 = p.adj_start[node + 1];
                 s_node[i] = (int)node;
@@ -1824,10 +1577,10 @@ __global__ __launch_bounds__(kResidentThreads) void resident_rc_kernel(const Res
                 s_lo[i] = a0;
                 s_pre[i + 1] = a1 - a0;
             }
-            if (n_here > 0 && cmd != 3u) shift_lists(n_here);
+            if (n_here > 0 && cmd != kCmdReload) shift_lists(n_here);
             for (int i = (i_lo > extra_pi ? i_lo : extra_pi) + tid; i < i_hi; i += nt) {
                 const int rel = i - i_lo;
-                const uint32_t *q = lm + (1 + rel / kMailboxPatchesPerLine) * 16 + 3 * (rel % kMailboxPatchesPerLine);
+                const uint32_t *q = entry_at(lm + 16, rel);
                 state_write((int)q[0], q[1]);
             }
             prog_lines = first + chunk;
@@ -1839,7 +1592,7 @@ __global__ __launch_bounds__(kResidentThreads) void resident_rc_kernel(const Res
         // The shifts above are atomics performed in this XCD's L2; a line of d that this CU's L1 still holds from an earlier request would be
         // stale.  Only the L1 has to forget it (buffer_inv sc0: the L1 alone -- an agent-scope invalidate also walks the L2 and cost 30 us
         // per request when every wave issued one).  The LDS variant never reads d from memory again.
-        if (!LD && (n_pi || cmd == 3u)) asm volatile("buffer_inv sc0\n\ts_waitcnt vmcnt(0)" ::: "memory");
+        if (!LD && (n_pi || cmd == kCmdReload)) asm volatile("buffer_inv sc0\n\ts_waitcnt vmcnt(0)" ::: "memory");
         // ---- scan
         Key best{0, kNone, kNone}, range{0, kNone, kNone};
         int64_t c1 = 0, c2 = 0;              // CAND: best and second best of this thread's arcs

@@ -117,16 +117,25 @@ void launch_resident_rc_r(mcf_engine *e, const ResidentRcParams &p)
     else hipExtLaunchKernelGGL((resident_rc_kernel<RULE, OPT, false>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
 }
 
+// the kernel arguments that every resident grid takes; host_pi: what a kCmdReload reads, or null
+MailboxParams mailbox_params(const mcf_engine *e, uint32_t start_seq, const int64_t *host_pi)
+{
+    MailboxParams m;
+    m.mailbox = e->mailbox; m.exit_word = e->d_exit;
+    m.start_seq = start_seq; m.idle_ticks = resident_idle_ticks();
+    m.max_pi = e->patch_capacity; m.max_st = e->mailbox_max_st; m.poll_replicas = e->poll_replicas; m.poll_sleep = e->poll_sleep;
+    m.host_pi = host_pi; m.barrier = e->d_barrier;
+    return m;
+}
+
 int launch_resident_rc(mcf_engine *e, uint32_t start_seq)
 {
     ResidentRcParams p;
     p.state = e->d_state; p.rc = e->d_rc; p.pi = e->d_pi; p.adj_start = e->d_adj_start; p.adj = e->d_adj; p.slots = e->d_slots;
-    p.mailbox = e->mailbox; p.exit_word = e->d_exit;
     p.base = e->begin; p.count_padded = e->count_padded; p.m_s = e->d.search_arc_num; p.window = e->rc_window;
-    p.start_seq = start_seq; p.idle_ticks = resident_idle_ticks(); p.narrow = e->d.int_width == 32 ? 1 : 0;
-    p.max_pi = e->patch_capacity; p.max_st = e->mailbox_max_st; p.poll_replicas = e->poll_replicas; p.poll_sleep = e->poll_sleep;
+    p.narrow = e->d.int_width == 32 ? 1 : 0;
     p.src = e->d_src; p.tgt = e->d_tgt; p.cost = e->d_cost; p.n_nodes = e->d.node_count;
-    p.host_pi = e->d_ext_pi; p.barrier = e->d_barrier;
+    p.mb = mailbox_params(e, start_seq, e->d_ext_pi);
     if (e->d_barrier) HIP_TRY(hipMemsetAsync(e->d_barrier, 0, 64, e->res_stream));
     switch (e->d.rule) {
     case MCF_RULE_BEST_ELIGIBLE: launch_resident_rc_r<MCF_RULE_BEST_ELIGIBLE, false>(e, p); break;
@@ -144,12 +153,10 @@ int launch_resident(mcf_engine *e, uint32_t start_seq)
 {
     ResidentParams<T> p;
     p.src = e->d_src; p.tgt = e->d_tgt; p.cost = (const T *)e->d_cost; p.state = e->d_state; p.pi = (T *)e->d_pi;
-    p.slots = e->d_slots; p.orig = e->bucket_nodes > 0 ? e->d_orig : nullptr; p.mailbox = e->mailbox; p.exit_word = e->d_exit;
-    p.base = e->begin; p.count_padded = e->count_padded; p.m_s = e->d.search_arc_num;
-    p.start_seq = start_seq; p.idle_ticks = resident_idle_ticks(); p.n_nodes = e->d.node_count; p.max_pi = e->patch_capacity; p.max_st = e->mailbox_max_st; p.poll_replicas = e->poll_replicas; p.poll_sleep = e->poll_sleep;
-    p.host_pi = e->shift_grid && e->d_barrier ? e->d_ext_pi : nullptr;
-    p.barrier = e->d_barrier;
-    if (p.host_pi) HIP_TRY(hipMemsetAsync(e->d_barrier, 0, 64, e->res_stream));
+    p.slots = e->d_slots; p.orig = e->bucket_nodes > 0 ? e->d_orig : nullptr;
+    p.base = e->begin; p.count_padded = e->count_padded; p.m_s = e->d.search_arc_num; p.n_nodes = e->d.node_count;
+    p.mb = mailbox_params(e, start_seq, e->shift_grid && e->d_barrier ? e->d_ext_pi : nullptr);
+    if (p.mb.host_pi) HIP_TRY(hipMemsetAsync(e->d_barrier, 0, 64, e->res_stream));
     const bool opt = e->d.semantics == MCF_SEM_OPTIMIZED;
     switch (e->d.rule) {
     case MCF_RULE_BEST_ELIGIBLE: launch_resident_r<T, MCF_RULE_BEST_ELIGIBLE, false>(e, p); break;
@@ -216,79 +223,43 @@ int resident_start(mcf_engine *e, uint32_t start_seq)
     return MCF_OK;
 }
 
-// one 64-byte line into the write-combining BAR mapping: four 16-byte stores, the tag goes out with the last one
-inline void mailbox_write_line(uint32_t *dst, const uint32_t *line16)
-{
-    const __m128i *src = (const __m128i *)line16;
-    __m128i *d = (__m128i *)dst;
-    _mm_store_si128(d + 0, _mm_loadu_si128(src + 0));
-    _mm_store_si128(d + 1, _mm_loadu_si128(src + 1));
-    _mm_store_si128(d + 2, _mm_loadu_si128(src + 2));
-    _mm_store_si128(d + 3, _mm_loadu_si128(src + 3));
-}
-
 void resident_post(mcf_engine *e, uint32_t seq, uint32_t cmd, bool with_patches)
 {
-    alignas(16) uint32_t line[16];
     const int n_pi = with_patches ? (int)e->pend_node.size() : 0, n_st = with_patches ? (int)e->pend_arc.size() : 0;
-    // entries beyond the header: potential patches 1.., then state patches 2..
-    const int extra_pi = n_pi > 1 ? n_pi - 1 : 0, extra_st = n_st > 2 ? n_st - 2 : 0, entries = extra_pi + extra_st;
-    alignas(16) uint32_t line1[16];
-    memset(line1, 0, sizeof(line1));
-    for (int l = 0, i = 0; i < entries; ++l) {
-        if (l > 0 && l + 1 <= e->stream_lines) { i += kMailboxPatchesPerLine; continue; }   // already in place (resident_stream); line 1 always goes out again
-        memset(line, 0, sizeof(line));
-        for (int k = 0; k < kMailboxPatchesPerLine && i < entries; ++k, ++i) {
-            if (i < extra_pi) {
-                const uint64_t v = (uint64_t)e->pend_val[i + 1];
-                line[3 * k] = (uint32_t)e->pend_node[i + 1];
-                line[3 * k + 1] = (uint32_t)v;
-                line[3 * k + 2] = (uint32_t)(v >> 32);
-            } else {
-                const int j = i - extra_pi + 2;
-                line[3 * k] = (uint32_t)e->pend_arc[j];
-                line[3 * k + 1] = (uint32_t)e->pend_state[j];
-            }
-        }
-        line[15] = seq;
-        if (l == 0) memcpy(line1, line, sizeof(line));                                  // line 1 goes out with every copy of the poll unit
-        else mailbox_write_line(e->mailbox + kMailboxTail + 16 * (size_t)(l - 1), line);  // lines 2.. : the tail
-    }
+    // entries beyond the header: value entries 1.., then state writes 2..; lines an apply post has put in place stay, line 1 always goes out again
+    const ValueEntries vals{e->pend_node.data(), e->pend_val.data(), 1, n_pi > 1 ? n_pi - 1 : 0};
+    const StateEntries sts{e->pend_arc.data(), e->pend_state.data(), 2, n_st > 2 ? n_st - 2 : 0};
+    const int entries = vals.n + sts.n;
+    const MailboxLine line1 = mailbox_encode_entries(e->mailbox, vals, sts, seq, e->stream_lines);
     if (with_patches) e->stream_lines = 0;
-    memset(line, 0, sizeof(line));
-    line[0] = seq;
-    line[1] = cmd;
+    MailboxLine h{};
+    h.w[kHdrSeq] = seq;
+    h.w[kHdrCmd] = cmd;
     const int na = e->next_arc >= e->d.search_arc_num ? 0 : e->next_arc;
-    line[2] = (uint32_t)na;
+    h.w[kHdrNextArc] = (uint32_t)na;
     int rstar = -1;
     if (e->d.rule == MCF_RULE_BLOCK_SEARCH && e->d.semantics == MCF_SEM_OPTIMIZED && e->next_arc < e->d.search_arc_num) {
         const int len1 = e->d.search_arc_num - e->next_arc;
         if (len1 % e->block_size != 0) rstar = len1 / e->block_size;
     }
-    line[3] = (uint32_t)rstar;
-    line[13] = (uint32_t)e->block_size;      // per request: the adaptive rule of the plain Block Search changes it between searches
-    line[4] = (uint32_t)n_pi;
-    line[5] = (uint32_t)n_st;
-    for (int k = 0; k < n_st && k < 2; ++k) { line[6 + 2 * k] = (uint32_t)e->pend_arc[k]; line[7 + 2 * k] = (uint32_t)e->pend_state[k]; }
+    h.w[kHdrRstar] = (uint32_t)rstar;
+    h.w[kHdrBlockSize] = (uint32_t)e->block_size;      // per request: the adaptive rule of the plain Block Search changes it between searches
+    h.w[kHdrValues] = (uint32_t)n_pi;
+    h.w[kHdrStates] = (uint32_t)n_st;
+    for (int k = 0; k < n_st && k < 2; ++k) { h.w[kHdrState0 + 2 * k] = (uint32_t)e->pend_arc[k]; h.w[kHdrState0 + 1 + 2 * k] = (uint32_t)e->pend_state[k]; }
     if (n_pi > 0) {
         const uint64_t v = (uint64_t)e->pend_val[0];
-        line[10] = (uint32_t)e->pend_node[0];
-        line[11] = (uint32_t)v;
-        line[12] = (uint32_t)(v >> 32);
+        h.w[kHdrValue0] = (uint32_t)e->pend_node[0];
+        h.w[kHdrValue0 + 1] = (uint32_t)v;
+        h.w[kHdrValue0 + 2] = (uint32_t)(v >> 32);
     }
-    line[15] = seq;
-    if (entries > kMailboxPatchesPerLine) _mm_sfence();   // tail lines leave the write-combining buffers before any header does
-    for (int r = 0; r < e->poll_replicas; ++r) {
-        uint32_t *unit = e->mailbox + (size_t)r * kReplicaStride;
-        if (entries > 0) mailbox_write_line(unit + 16, line1);
-        mailbox_write_line(unit, line);
-    }
-    _mm_sfence();
+    h.w[kHdrTag] = seq;
+    mailbox_publish(e->mailbox, e->poll_replicas, h, entries > 0 ? &line1 : nullptr, entries > kMailboxPatchesPerLine);
 }
 
 // Long potential lists start travelling while the host is still producing them (mcf_engine_append_potential): the complete entry lines
-// gathered so far go into the mailbox and an "apply" post (cmd 2) tells the grid how far the list of the COMING scan request reaches.
-// No answer is expected; the posts are cumulative and the scan request finishes the list (kernels.hip.h, mailbox layout).
+// gathered so far go into the mailbox and an apply post (kCmdApply) tells the grid how far the list of the COMING scan request reaches.
+// No answer is expected; the posts are cumulative and the scan request finishes the list (mailbox.hip.h).
 int stream_min_lines()                         // 1920 entries per post at least by default: one piece of the host driver's walk (2048 nodes)
 {
     static const int v = [] { int x = 384; if (const char *u = getenv("MCF_HIP_STREAM_LINES")) { const int y = atoi(u); if (y >= 16 && y <= 65536) x = y; } return x; }();
@@ -306,37 +277,19 @@ void resident_stream(mcf_engine *e)
     if (complete - e->stream_lines < stream_min_lines()) return;
     uint32_t next_seq = e->seq + 1;
     if (next_seq == 0) next_seq = 1;
-    alignas(16) uint32_t line[16], line1[16];
-    memset(line1, 0, sizeof(line1));
-    for (int l = e->stream_lines == 0 ? 0 : e->stream_lines; l < complete; ++l) {          // l = entry line l + 1
-        memset(line, 0, sizeof(line));
-        for (int k = 0; k < kMailboxPatchesPerLine; ++k) {
-            const int i = l * kMailboxPatchesPerLine + k;
-            const uint64_t v = (uint64_t)e->pend_val[i + 1];
-            line[3 * k] = (uint32_t)e->pend_node[i + 1];
-            line[3 * k + 1] = (uint32_t)v;
-            line[3 * k + 2] = (uint32_t)(v >> 32);
-        }
-        line[15] = next_seq;
-        if (l == 0) memcpy(line1, line, sizeof(line));
-        else mailbox_write_line(e->mailbox + kMailboxTail + 16 * (size_t)(l - 1), line);
-    }
+    // the complete entry lines not in place yet (entry line 0 goes out with the first post's header)
+    const MailboxLine line1 = mailbox_encode_entries(e->mailbox, ValueEntries{e->pend_node.data(), e->pend_val.data(), 1, complete * kMailboxPatchesPerLine},
+                                                     StateEntries{nullptr, nullptr, 0, 0}, next_seq, e->stream_lines);
     const bool first_post = e->stream_lines == 0;
     e->stream_sub += 1;
     if (e->stream_sub == 0) e->stream_sub = 1;
-    memset(line, 0, sizeof(line));
-    line[0] = next_seq;
-    line[1] = 2u;
-    line[13] = (uint32_t)complete;
-    line[14] = e->stream_sub;
-    line[15] = next_seq;
-    _mm_sfence();                                  // the entry lines leave the write-combining buffers before any header does
-    for (int r = 0; r < e->poll_replicas; ++r) {
-        uint32_t *unit = e->mailbox + (size_t)r * kReplicaStride;
-        if (first_post) mailbox_write_line(unit + 16, line1);
-        mailbox_write_line(unit, line);
-    }
-    _mm_sfence();
+    MailboxLine h{};
+    h.w[kHdrSeq] = next_seq;
+    h.w[kHdrCmd] = kCmdApply;
+    h.w[kHdrApplyLines] = (uint32_t)complete;
+    h.w[kHdrApplySub] = e->stream_sub;
+    h.w[kHdrTag] = next_seq;
+    mailbox_publish(e->mailbox, e->poll_replicas, h, first_post ? &line1 : nullptr);
     e->stream_lines = complete;
 }
 
@@ -398,8 +351,8 @@ int resident_stop(mcf_engine *e)
     e->prev_seq = e->seq;
     e->seq += 1;
     if (e->seq == 0) e->seq = 1;
-    if (e->shift_grid) shift_post(e, e->seq, 1u, false);
-    else resident_post(e, e->seq, 1u, false);
+    if (e->shift_grid) shift_post(e, e->seq, kCmdQuit, false);
+    else resident_post(e, e->seq, kCmdQuit, false);
     { const int rcj = resident_join(e); if (rcj) return rcj; }       // bounded: the grid leaves on quit, or by itself after kResidentIdleTicks; counts what the launch served
     e->resident_running = false;
     e->stream_lines = 0;
@@ -421,7 +374,7 @@ int resident_restart(mcf_engine *e)
         e->stream_lines = 0;
         const int rc = device_sync_from_mirrors(e);
         if (rc) return rc;
-        shift_post(e, e->seq, 0u, false);
+        shift_post(e, e->seq, kCmdScan, false);
     }
     return resident_start(e, e->prev_seq);
 }
@@ -452,7 +405,7 @@ int collect(mcf_engine *e, int grid, Key *out)
         while (!(pair_ready(slots + (size_t)g * stride) && (!dual || pair_ready(slots + (size_t)g * stride + 2)))) {
             _mm_pause();
             if (e->resident_running && (spins & 0xFFF) == 0xFFF && ((const volatile uint32_t *)e->h_exit)[0] != 0) {
-                if (((const volatile uint32_t *)e->h_exit)[0] == 4u) {
+                if (((const volatile uint32_t *)e->h_exit)[0] == kExitPartial) {
                     (void)resident_join(e, false);
                     e->resident_running = false;
                     resident_slot_release(e);
