@@ -12,6 +12,10 @@ TOP = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "h
        "roofline")
 ROOFLINE = ("bound", "achieved", "peak", "unit", "frac", "traffic")
 CPU = ("value", "unit", "cores", "kind", "sample")
+# blocks only --full adds: each is a run of its own beside the timed steps
+FULL_ONLY = ("cpu_baseline", "cpu_baseline_block_search", "cpu_baseline_block_search_without_hardware_vectors", "cpu_baseline_reference_default",
+             "solve_time_vs_cpu", "other_configs", "scan_microbench", "hbm_measured", "potential_update_microbench", "large_instance_sample",
+             "solution_validator", "every_search_on_the_device", "concurrent_solves_one_gpu", "sharded")
 
 
 def _check(line, with_cpu):
@@ -48,12 +52,30 @@ def test_committed_bench_line_keeps_the_contract(name):
 
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-microbench",
-                          "--no-validator", "--concurrent", "0"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    """A plain run (no --full) prints the contract line from the timed solves alone: none of the legs that take runs of their own."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
-    _check(json.loads(lines[0]), with_cpu=False)
+    line = json.loads(lines[0])
+    _check(line, with_cpu=False)
+    assert not set(FULL_ONLY) & set(line) and "scan_dispatch" not in line["roofline"], sorted(line)
+
+
+@pytest.mark.gpu
+def test_bench_full_adds_the_legs_of_their_own():
+    """--full runs the extra legs beside the timed steps; the --no-* options still choose among them (here: the two cheapest)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-microbench",
+                          "--no-validator", "--no-other-configs", "--concurrent", "0", "--sharded-pivots", "0"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    _check(line, with_cpu=False)
+    assert line["roofline"]["scan_dispatch"]["avg_kernel_us"] > 0
+    assert line["every_search_on_the_device"]["identical_pivot_sequence"] is True
+    assert not (set(FULL_ONLY) - {"every_search_on_the_device"}) & set(line), sorted(line)
 
 
 def test_bench_refuses_a_world_size_that_differs_from_gpus():

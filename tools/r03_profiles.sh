@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$R" || exit 1
 mkdir -p gpurun_out
-BENCH_MIN="--no-cpu-baseline --no-microbench --concurrent 0 --no-other-configs --no-validator --sharded-pivots 0"
+BENCH_MIN="--full --no-cpu-baseline --no-microbench --concurrent 0 --no-other-configs --no-validator --sharded-pivots 0"
 echo "== bench under rocprofv3 (config 3)"; rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_r03_c3 -- python3 bench.py --steps 2 --warmup 1 $BENCH_MIN > gpurun_out/r03_bench_under_rocprofv3.json 2> gpurun_out/prof_r03_c3.err || exit 2
 echo "== config 2"; rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_r03_c2 -- python3 bench.py --workload config2 --steps 2 --warmup 1 $BENCH_MIN > gpurun_out/r03_bench_config2_under_rocprofv3.json 2> gpurun_out/prof_r03_c2.err || exit 3
 echo "== config 4"; rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_r03_c4 -- python3 bench.py --workload config4 --steps 2 --warmup 1 $BENCH_MIN > gpurun_out/r03_bench_config4_under_rocprofv3.json 2> gpurun_out/prof_r03_c4.err || exit 4
