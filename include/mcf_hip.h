@@ -51,8 +51,11 @@ typedef enum mcf_status {
     MCF_ERR_COMM = -8         /* RCCL failure */
 } mcf_status;
 
-/* Types/PivotRule.cs:7-41 (values kept) */
-typedef enum mcf_pivot_rule { MCF_RULE_FIRST_ELIGIBLE = 0, MCF_RULE_BEST_ELIGIBLE = 1, MCF_RULE_BLOCK_SEARCH = 2 } mcf_pivot_rule;
+/* Types/PivotRule.cs:7-41 (values kept).  CANDIDATE_LIST and ALTERING_LIST are declared by the reference but not implemented there
+ * (NS.cs:879-885 throws); this library runs them as LEMON's rules (lemon/network_simplex.h:415-635) on the host driver, with the
+ * device doing the major scans only: mcf_ns_set_list_pivot_rule, mcf_engine_collect_eligible. */
+typedef enum mcf_pivot_rule { MCF_RULE_FIRST_ELIGIBLE = 0, MCF_RULE_BEST_ELIGIBLE = 1, MCF_RULE_BLOCK_SEARCH = 2,
+                              MCF_RULE_CANDIDATE_LIST = 3, MCF_RULE_ALTERING_LIST = 4 } mcf_pivot_rule;
 /* Which of the reference's two implementations of a rule is reproduced:
  * PLAIN = the nested classes of NS.cs:1292-1668; OPTIMIZED = BSPO.cs (EnableOptimizedPivot(true)). */
 typedef enum mcf_semantics { MCF_SEM_PLAIN = 1, MCF_SEM_OPTIMIZED = 2 } mcf_semantics;
@@ -243,6 +246,33 @@ MCF_API int mcf_engine_find_entering(mcf_engine *e, int32_t *found, int32_t *arc
 MCF_API int mcf_engine_search_begin(mcf_engine *e);
 MCF_API int mcf_engine_search_end(mcf_engine *e, int32_t *found, int32_t *arc, int64_t *reduced_cost);
 
+/* The device half of LEMON's list rules (engines created with MCF_RULE_CANDIDATE_LIST / MCF_RULE_ALTERING_LIST only; such engines run in
+ * dispatch mode -- no resident grid, no RC layout, no candidate cache, no arc shards -- and refuse find_entering / search_begin with
+ * MCF_ERR_STATE).  Scans the search range [0, search_arc_num) cyclically from rq->next_arc and returns the eligible arcs
+ * (state * (cost + pi[source] - pi[target]) < 0) IN SCAN ORDER with their reduced costs, up to where LEMON's loop stops:
+ *   MCF_COLLECT_FIRST_N (Candidate List, major iteration, ns.h:478-507): at the limit-th eligible arc (*end_arc = that arc); a cycle with
+ *     fewer returns all of them and *end_arc = next_arc.
+ *   MCF_COLLECT_BLOCKS (Altering List, extension of the list, ns.h:583-610): blocks of block_size arcs, the block counter running on across
+ *     the wrap; with c_j eligible arcs in block j (1-based) and `survivors` = the list length after the host re-checked its list, the scan stops
+ *     after block 1 if survivors + c_1 > head_length, else after block 2 if survivors + c_1 + c_2 > 0, else after the first block that holds an
+ *     eligible arc; *end_arc = the last arc of that block.  A stop that would fall behind the end of the cycle (a partial last block, no
+ *     eligible arc) does not happen: every eligible arc of the cycle is returned and *end_arc = next_arc.
+ * *arcs_scanned = the arcs LEMON's loop visits.  Patches queued since the last device call (any number of pivots' state writes and potential
+ * lists, a node repeated across pivots included) are applied first, in the order they were given.  At most `capacity` entries are written;
+ * *count is the full number, and a count above capacity fails with MCF_ERR_INVALID.  Blocking. */
+#define MCF_COLLECT_FIRST_N 0
+#define MCF_COLLECT_BLOCKS 1
+typedef struct mcf_collect_request {
+    int32_t next_arc;         /* start of the cyclic scan, [0, search_arc_num) */
+    int32_t mode;             /* MCF_COLLECT_FIRST_N | MCF_COLLECT_BLOCKS */
+    int32_t limit;            /* FIRST_N: eligible arcs to collect (>= 1) */
+    int32_t block_size;       /* BLOCKS: arcs per block (>= 1) */
+    int32_t head_length;      /* BLOCKS: LEMON's _head_length */
+    int32_t survivors;        /* BLOCKS: the list length before the extension */
+} mcf_collect_request;
+MCF_API int mcf_engine_collect_eligible(mcf_engine *e, const mcf_collect_request *rq, int32_t capacity, int32_t *count, int32_t *arcs,
+                                        int64_t *reduced_costs, int32_t *end_arc, int64_t *arcs_scanned);
+
 /* Sharded search: the local candidate of this engine's shard, as an exchangeable 32-byte record. */
 typedef struct mcf_candidate {
     int64_t reduced_cost;   /* 0 when none */
@@ -382,7 +412,13 @@ MCF_API int mcf_ns_set_node_supply(mcf_ns *s, int32_t node, int64_t supply);    
 /* bulk forms of the three setters (NULL = keep defaults: lower 0, upper INF, cost 0, supply 0: NS.cs:614-621) */
 MCF_API int mcf_ns_set_problem(mcf_ns *s, const int64_t *lower, const int64_t *upper, const int64_t *cost, const int64_t *supply);
 MCF_API int mcf_ns_set_supply_type(mcf_ns *s, int32_t type);                               /* NS.cs:197-201 */
-MCF_API int mcf_ns_set_pivot_rule(mcf_ns *s, int32_t rule);                                /* NS.cs:206-210 */
+MCF_API int mcf_ns_set_pivot_rule(mcf_ns *s, int32_t rule);                                /* NS.cs:206-210; refuses 3 and 4 like NS.cs:884 */
+/* LEMON's Candidate List (3) or Altering List (4) pivot rule (lemon/network_simplex.h:415-635 with LEMON's fixed parameters), run on this
+ * host driver: minor iterations, the re-check of the list and the partial sort happen here, the major scans on the device
+ * (mcf_engine_collect_eligible, one blocking device call each).  Any other value fails with MCF_ERR_INVALID; a later mcf_ns_set_pivot_rule replaces it.
+ * The list rules ignore mcf_ns_enable_optimized_pivot, the vector width, the OptimizationConfig and auto-configuration; sharding of any kind
+ * together with a list rule fails at mcf_ns_prepare with MCF_ERR_INVALID. */
+MCF_API int mcf_ns_set_list_pivot_rule(mcf_ns *s, int32_t rule);
 MCF_API int mcf_ns_enable_optimized_pivot(mcf_ns *s, int32_t enable);                      /* NS.cs:532-535 */
 /* Vector<long>.Count of the machine whose EnableOptimizedPivot(true) Block Search is reproduced (mcf_engine_desc.vector_width; the
  * reference has no setter, it reads the property: BSPO.cs:74, :115).  Default 4 = x64. */
@@ -450,6 +486,23 @@ typedef struct mcf_ns_metrics {
     int32_t reserved2;
 } mcf_ns_metrics;
 MCF_API int mcf_ns_get_metrics(mcf_ns *s, mcf_ns_metrics *out);                            /* NS.cs:584-587 */
+/* Counters of the last Solve() with a list rule (all zero after a solve with rules 0-2).  searches = major_scans + host_answered. */
+typedef struct mcf_list_rule_stats {
+    int32_t rule;                 /* MCF_RULE_CANDIDATE_LIST / MCF_RULE_ALTERING_LIST, 0 when the last solve ran another rule */
+    int32_t list_length;          /* Candidate List: _list_length; Altering List: _head_length + _block_size (the list's capacity) */
+    int32_t minor_limit;          /* Candidate List: _minor_limit */
+    int32_t block_size;           /* Altering List: _block_size */
+    int32_t head_length;          /* Altering List: _head_length */
+    int32_t reserved;
+    int64_t searches;             /* findEnteringArc calls */
+    int64_t major_scans;          /* searches that called the device (mcf_engine_collect_eligible) */
+    int64_t host_answered;        /* searches answered from the host's list without a device call */
+    int64_t device_arcs_read;     /* arcs the device's count passes read (the whole search range per major scan) */
+    int64_t lemon_arcs_scanned;   /* arcs LEMON's loops visit in those major scans */
+    int64_t collected;            /* eligible arcs the major scans returned */
+    double collect_us;            /* host wall time inside mcf_engine_collect_eligible */
+} mcf_list_rule_stats;
+MCF_API int mcf_ns_get_list_rule_stats(mcf_ns *s, mcf_list_rule_stats *out);
 /* measurement aid: Solve() stops after max_pivots pivots and reports MCF_NOT_SOLVED (0 = no limit) */
 MCF_API int mcf_ns_set_pivot_limit(mcf_ns *s, int64_t max_pivots);
 /* optional pivot trace: entering arc of every pivot of the next Solve() (for parity tests) */

@@ -14,7 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmcf_hip.so")
 
 # enums of include/mcf_hip.h
-RULE_FIRST_ELIGIBLE, RULE_BEST_ELIGIBLE, RULE_BLOCK_SEARCH = 0, 1, 2
+RULE_FIRST_ELIGIBLE, RULE_BEST_ELIGIBLE, RULE_BLOCK_SEARCH, RULE_CANDIDATE_LIST, RULE_ALTERING_LIST = 0, 1, 2, 3, 4
+COLLECT_FIRST_N, COLLECT_BLOCKS = 0, 1        # mcf_collect_request.mode
 SEM_PLAIN, SEM_OPTIMIZED = 1, 2
 VECTOR_DEFAULT, VECTOR_NONE = 0, -1          # mcf_engine_desc.vector_width: 0 = 4 (x64), -1 = Vector.IsHardwareAccelerated is false
 SUPPLY_GEQ, SUPPLY_LEQ = 0, 1
@@ -93,6 +94,19 @@ class NsMetrics(C.Structure):
 VALIDATION_KINDS = ("conservation", "lower", "upper", "slack_pos", "slack_neg", "node_dual", "node_slack", "objective", "dual_cost", "status")
 
 
+class CollectRequest(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("next_arc", "mode", "limit", "block_size", "head_length", "survivors")]
+
+
+class ListRuleStats(C.Structure):
+    _fields_ = [("rule", C.c_int32), ("list_length", C.c_int32), ("minor_limit", C.c_int32), ("block_size", C.c_int32), ("head_length", C.c_int32),
+                ("reserved", C.c_int32), ("searches", C.c_int64), ("major_scans", C.c_int64), ("host_answered", C.c_int64),
+                ("device_arcs_read", C.c_int64), ("lemon_arcs_scanned", C.c_int64), ("collected", C.c_int64), ("collect_us", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class Validation(C.Structure):
     _fields_ = [("valid", C.c_int32), ("supply_type", C.c_int32), ("objective", C.c_int64), ("dual_cost", C.c_int64),
                 ("errors", C.c_int64 * len(VALIDATION_KINDS)), ("first", C.c_int64 * len(VALIDATION_KINDS)),
@@ -152,6 +166,8 @@ SIGNATURES = {
     "mcf_engine_search_begin": (C.c_int, [C.c_void_p]),
     "mcf_engine_search_end": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_int32), _P(C.c_int64)]),
     "mcf_engine_find_entering_local": (C.c_int, [C.c_void_p, _P(Candidate)]),
+    "mcf_engine_collect_eligible": (C.c_int, [C.c_void_p, _P(CollectRequest), C.c_int32, _P(C.c_int32), C.c_void_p, C.c_void_p,
+                                              _P(C.c_int32), _P(C.c_int64)]),
     "mcf_engine_search_end_local": (C.c_int, [C.c_void_p, _P(Candidate)]),
     "mcf_exchange_open": (C.c_int, [_P(C.c_void_p), C.c_char_p, C.c_int32, C.c_int32]),
     "mcf_exchange_close": (None, [C.c_void_p]),
@@ -187,6 +203,7 @@ SIGNATURES = {
     "mcf_ns_set_problem": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcf_ns_set_supply_type": (C.c_int, [C.c_void_p, C.c_int32]),
     "mcf_ns_set_pivot_rule": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mcf_ns_set_list_pivot_rule": (C.c_int, [C.c_void_p, C.c_int32]),
     "mcf_ns_enable_optimized_pivot": (C.c_int, [C.c_void_p, C.c_int32]),
     "mcf_ns_set_vector_width": (C.c_int, [C.c_void_p, C.c_int32]),
     "mcf_ns_set_optimization_config": (C.c_int, [C.c_void_p, _P(BlockConfig)]),
@@ -207,6 +224,7 @@ SIGNATURES = {
     "mcf_ns_get_potentials": (C.c_int, [C.c_void_p, _i64p]),
     "mcf_ns_get_arc_upper_bound": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int64)]),
     "mcf_ns_get_metrics": (C.c_int, [C.c_void_p, _P(NsMetrics)]),
+    "mcf_ns_get_list_rule_stats": (C.c_int, [C.c_void_p, _P(ListRuleStats)]),
     "mcf_ns_set_pivot_limit": (C.c_int, [C.c_void_p, C.c_int64]),
     "mcf_ns_set_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "mcf_ns_get_trace_length": (C.c_int, [C.c_void_p, _P(C.c_int64)]),

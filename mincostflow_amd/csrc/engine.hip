@@ -35,6 +35,7 @@
 #include "common.h"
 
 #include "kernels.hip.h"
+#include "collect.hip.h"
 
 namespace {
 
@@ -265,6 +266,16 @@ struct mcf_engine {
     // flush buffer for cold micro-benchmarks
     void *d_flush = nullptr;
     size_t flush_bytes = 0;
+    // LEMON's list rules (MCF_RULE_CANDIDATE_LIST / MCF_RULE_ALTERING_LIST): dispatch mode only, searched by mcf_engine_collect_eligible alone.
+    // Between two device calls the host answers several searches itself, so several pivots' potential lists queue up: they are merged per
+    // node (the later value replaces the earlier one, as applying them in order would), pend_index[u] = where u's entry sits in pend_node
+    // (valid when pend_node[pend_index[u]] == u, so no clearing is needed when the list is shipped)
+    bool list_rule = false;
+    std::vector<int32_t> pend_index;
+    CollectTile *d_tiles = nullptr;
+    CollectHeader *h_collect_hdr = nullptr, *d_collect_hdr = nullptr;   // pinned host memory and its device alias
+    CollectEntry *h_collect = nullptr, *d_collect = nullptr;
+    int collect_cap = 0;
 };
 
 namespace {
@@ -586,6 +597,7 @@ int flush_pending(mcf_engine *e)
 // posts / launches the search; search_end collects it.  local_search = both.
 int search_begin(mcf_engine *e)
 {
+    if (e->list_rule) return mcf::fail(MCF_ERR_STATE, "engines of the list rules (3, 4) are searched with mcf_engine_collect_eligible only");
     if (!e->uploaded) return mcf::fail(MCF_ERR_STATE, "mcf_engine_upload has not been called");
     if (e->in_flight != mcf_engine::kNoSearch) return mcf::fail(MCF_ERR_STATE, "a search is already in flight");
     Key *const k = &e->answered;
@@ -883,7 +895,10 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
     if (desc->node_count < 1 || desc->search_arc_num < 0 || desc->arc_capacity < desc->search_arc_num)
         return mcf::fail(MCF_ERR_INVALID, "mcf_engine_create: bad sizes (nodes %d, arcs %d, search %d)", desc->node_count, desc->arc_capacity, desc->search_arc_num);
     if (desc->int_width != 32 && desc->int_width != 64) return mcf::fail(MCF_ERR_INVALID, "int_width must be 32 or 64");
-    if (desc->rule < 0 || desc->rule > 2) return mcf::fail(MCF_ERR_INVALID, "pivot rule %d not implemented (NS.cs:884)", desc->rule);
+    if (desc->rule < 0 || desc->rule > 4) return mcf::fail(MCF_ERR_INVALID, "pivot rule %d does not exist (Types/PivotRule.cs:7-41)", desc->rule);
+    const bool list_rule = desc->rule == MCF_RULE_CANDIDATE_LIST || desc->rule == MCF_RULE_ALTERING_LIST;
+    if (list_rule && !((desc->shard_begin == 0 && desc->shard_end == 0) || (desc->shard_begin == 0 && desc->shard_end == desc->search_arc_num)))
+        return mcf::fail(MCF_ERR_INVALID, "the list rules (3, 4) scan the whole search range: no arc shards");
     if (desc->semantics != MCF_SEM_PLAIN && desc->semantics != MCF_SEM_OPTIMIZED) return mcf::fail(MCF_ERR_INVALID, "bad semantics %d", desc->semantics);
     if (desc->vector_width != MCF_VECTOR_DEFAULT && desc->vector_width != MCF_VECTOR_NONE && desc->vector_width != 2 && desc->vector_width != 4 && desc->vector_width != 8)
         return mcf::fail(MCF_ERR_INVALID, "vector_width %d is not Vector<long>.Count of any machine (2, 4, 8, MCF_VECTOR_NONE, or 0 = 4)", desc->vector_width);
@@ -894,6 +909,7 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
     e->cal_ns = mcf::now_ns();
     e->cal_ticks = (double)__rdtsc();
     e->d = *desc;
+    e->list_rule = list_rule;
     e->vec = desc->vector_width == MCF_VECTOR_NONE ? 0 : (desc->vector_width == MCF_VECTOR_DEFAULT ? 4 : desc->vector_width);
     e->begin = desc->shard_begin;
     e->end = desc->shard_end;
@@ -947,6 +963,7 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
     {
         bool want = !e->resident_reg && !e->lds_pi;
         if (const char *u = getenv("MCF_HIP_RC")) want = u[0] == '1' ? true : (u[0] == '0' ? false : want);
+        if (list_rule) want = false;          // the list rules read the SoA arrays themselves (collect.hip.h)
         e->rc_mode = want;
         if (e->rc_mode) {
             // pure streaming: more bytes in flight per thread, the grid sized so that every workgroup gets the same number of trips
@@ -1001,6 +1018,12 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
         chk(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
     }
     for (int i = 0; i < mcf_engine::kEvRing && err == hipSuccess; ++i) { chk(hipEventCreate(&e->ev_start[i])); chk(hipEventCreate(&e->ev_stop[i])); }
+    if (list_rule && err == hipSuccess) {
+        e->pend_index.assign((size_t)desc->node_count, -1);
+        chk(hipMalloc((void **)&e->d_tiles, sizeof(CollectTile) * kCollectMaxTiles));
+        chk(hipHostMalloc((void **)&e->h_collect_hdr, sizeof(CollectHeader), hipHostMallocMapped | hipHostMallocCoherent));
+        if (err == hipSuccess) chk(hipHostGetDevicePointer((void **)&e->d_collect_hdr, e->h_collect_hdr, 0));
+    }
     if (err != hipSuccess) {
         const int rc = mcf::fail(MCF_ERR_HIP, "mcf_engine_create: %s", hipGetErrorString(err));
         mcf_engine_destroy(e);
@@ -1018,6 +1041,7 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
         if (e->rc_mode) want = rc_resident;
         if (env && env[0] == '1' && !e->rc_mode) want = true;
         if (env && env[0] == '0') want = false;
+        if (list_rule) want = false;          // dispatch mode only: no resident grid, hence no candidate cache either
         // an arc shard is served by a resident grid like a whole instance (every workgroup applies every potential patch, state patches
         // outside the shard are ignored); only the RCCL exchange needs the stream, and mcf_engine_comm_init switches to dispatch mode
         if (want && !(desc->flags & (MCF_ENGINE_TIME_EVERY_KERNEL | MCF_ENGINE_NO_INLINE_UPDATE))) {
@@ -1151,6 +1175,9 @@ void mcf_engine_destroy(mcf_engine *e)
     (void)hipFree(e->d_rc); (void)hipFree(e->d_adj_start); (void)hipFree(e->d_adj); (void)hipFree(e->d_barrier); (void)hipFree(e->d_node_map);
     (void)hipFree(e->d_src); (void)hipFree(e->d_tgt); (void)hipFree(e->d_cost); (void)hipFree(e->d_state); (void)hipFree(e->d_pi);
     (void)hipFree(e->d_cand_local); (void)hipFree(e->d_cand_all); (void)hipFree(e->d_flush); (void)hipFree(e->d_dev_slots);
+    (void)hipFree(e->d_tiles);
+    if (e->h_collect_hdr) (void)hipHostFree(e->h_collect_hdr);
+    if (e->h_collect) (void)hipHostFree(e->h_collect);
     if (e->h_cand_all) (void)hipHostFree(e->h_cand_all);
     if (e->comm_stream) { (void)hipStreamSynchronize(e->comm_stream); (void)hipStreamDestroy(e->comm_stream); }
     if (e->x_send) (void)hipHostFree(e->x_send);
@@ -1299,6 +1326,10 @@ int mcf_engine_patch_state(mcf_engine *e, int32_t count, const int32_t *arcs, co
     return MCF_OK;
 }
 
+}  // extern "C"
+namespace { int list_merge_potentials(mcf_engine *e, int32_t count, const int32_t *nodes, const int64_t *values); }
+extern "C" {
+
 int mcf_engine_update_potential(mcf_engine *e, int32_t count, const int32_t *nodes, int64_t sigma)
 {
     if (!e || count < 0 || (count && !nodes)) return mcf::fail(MCF_ERR_INVALID, "mcf_engine_update_potential: bad arguments");
@@ -1327,6 +1358,18 @@ int mcf_engine_update_potential(mcf_engine *e, int32_t count, const int32_t *nod
             for (int i = 0; i < count; ++i) { e->pi[nodes[i]] += sigma; cand_note_node(e, nodes[i], true, sigma); }
         }
         e->st.potential_nodes += count;
+        return MCF_OK;
+    }
+    if (e->list_rule) {                 // merged per node with what is queued already
+        std::vector<int64_t> vals((size_t)count);
+        for (int i = 0; i < count; ++i) {
+            if ((unsigned)nodes[i] >= (unsigned)e->d.node_count) return mcf::fail(MCF_ERR_INVALID, "node %d out of range", nodes[i]);
+            vals[i] = e->pi[nodes[i]] + sigma;
+        }
+        const int rc = list_merge_potentials(e, count, nodes, vals.data());
+        if (rc) return rc;
+        for (int i = 0; i < count; ++i) e->pi[nodes[i]] = vals[i];
+        e->mirror_valid = true;
         return MCF_OK;
     }
     // one list per dispatch: a second list may repeat nodes of the first
@@ -1375,6 +1418,25 @@ void pend_values_append(mcf_engine *e, int32_t count, const int32_t *nodes, cons
     for (int i = 0; i < count; ++i) e->pend_val[at + i] = e->ext_pi[nodes[i]];
 }
 
+// list rules: the entries join the pending list, one per node -- a node already in it takes the new value (the lists of several pivots, in order)
+int list_merge_potentials(mcf_engine *e, int32_t count, const int32_t *nodes, const int64_t *values)
+{
+    if (const int rcc = check_potential_list(e, count, nodes, values)) return rcc;
+    for (int i = 0; i < count; ++i) {
+        const int32_t u = nodes[i];
+        const int64_t v = values ? values[i] : e->ext_pi[u];
+        const uint32_t q = (uint32_t)e->pend_index[u];
+        if (q < e->pend_node.size() && e->pend_node[q] == u) { e->pend_val[q] = v; continue; }
+        e->pend_index[u] = (int32_t)e->pend_node.size();
+        e->pend_node.push_back(u);
+        e->pend_val.push_back(v);
+    }
+    e->pend_shift = false;
+    e->mirror_valid = false;
+    e->st.potential_nodes += count;
+    return MCF_OK;
+}
+
 int set_potential_impl(mcf_engine *e, int32_t count, const int32_t *nodes, const int64_t *values)
 {
     if (!e->uploaded) return mcf::fail(MCF_ERR_STATE, "mcf_engine_upload has not been called");
@@ -1395,6 +1457,7 @@ int set_potential_impl(mcf_engine *e, int32_t count, const int32_t *nodes, const
         e->st.potential_nodes += count;
         return MCF_OK;
     }
+    if (e->list_rule) return list_merge_potentials(e, count, nodes, values);
     if (!e->pend_node.empty()) { int rc = resident_stop(e); if (!rc) rc = flush_pending(e); if (rc) return rc; }
     e->pend_node.assign(nodes, nodes + count);
     e->pend_val.clear();
@@ -1416,7 +1479,7 @@ int append_potential_impl(mcf_engine *e, int32_t count, const int32_t *nodes, co
         e->cand_appending = false;
         return rc;
     }
-    if (e->pend_node.empty()) return set_potential_impl(e, count, nodes, values);     // nothing queued yet
+    if (e->list_rule || e->pend_node.empty()) return set_potential_impl(e, count, nodes, values);     // nothing queued yet / merged per node
     if ((int64_t)e->pend_node.size() + count > e->d.node_count) return mcf::fail(MCF_ERR_INVALID, "more nodes appended than the graph has: the lists of one pivot must not repeat nodes");
     if (const int rcc = check_potential_list(e, count, nodes, values)) return rcc;
     e->pend_node.insert(e->pend_node.end(), nodes, nodes + count);
@@ -1813,6 +1876,85 @@ int mcf_resolve_candidates(int32_t rule, int32_t semantics, int32_t vector_width
     return MCF_OK;
 }
 
+}  // extern "C"
+
+// ---- the device half of LEMON's list rules (collect.hip.h)
+namespace {
+template <typename T>
+int launch_collect(mcf_engine *e, const mcf_collect_request *rq, int capacity, int rounds, int n_tiles)
+{
+    CollectArgs<T> a;
+    a.src = e->d_src; a.tgt = e->d_tgt; a.cost = (const T *)e->d_cost; a.state = e->d_state; a.pi = (const T *)e->d_pi;
+    a.m_s = e->d.search_arc_num; a.next_arc = rq->next_arc; a.rounds = rounds; a.mode = rq->mode;
+    a.limit = rq->mode == MCF_COLLECT_FIRST_N ? rq->limit : 0;
+    a.block_size = rq->mode == MCF_COLLECT_BLOCKS ? rq->block_size : 0;
+    a.head_length = rq->head_length; a.survivors = rq->survivors;
+    hipLaunchKernelGGL(collect_count_kernel<T>, dim3(n_tiles), dim3(kCollectThreads), 0, e->stream, a, e->d_tiles);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(collect_emit_kernel<T>, dim3(n_tiles), dim3(kCollectThreads), 0, e->stream, a, (const CollectTile *)e->d_tiles, n_tiles,
+                       e->d_collect, capacity, e->d_collect_hdr);
+    HIP_TRY(hipGetLastError());
+    return MCF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mcf_engine_collect_eligible(mcf_engine *e, const mcf_collect_request *rq, int32_t capacity, int32_t *count, int32_t *arcs,
+                                int64_t *reduced_costs, int32_t *end_arc, int64_t *arcs_scanned)
+{
+    if (!e || !rq || capacity < 0 || !count || !end_arc || (capacity > 0 && (!arcs || !reduced_costs)))
+        return mcf::fail(MCF_ERR_INVALID, "mcf_engine_collect_eligible: bad arguments");
+    if (!e->list_rule) return mcf::fail(MCF_ERR_STATE, "mcf_engine_collect_eligible: the engine was not created with a list rule (3, 4)");
+    if (!e->uploaded) return mcf::fail(MCF_ERR_STATE, "mcf_engine_upload has not been called");
+    const int m_s = e->d.search_arc_num;
+    if (rq->mode == MCF_COLLECT_FIRST_N) {
+        if (rq->limit < 1) return mcf::fail(MCF_ERR_INVALID, "mcf_engine_collect_eligible: limit %d < 1", rq->limit);
+    } else if (rq->mode == MCF_COLLECT_BLOCKS) {
+        if (rq->block_size < 1 || rq->head_length < 0 || rq->survivors < 0)
+            return mcf::fail(MCF_ERR_INVALID, "mcf_engine_collect_eligible: block_size %d, head_length %d, survivors %d", rq->block_size, rq->head_length, rq->survivors);
+    } else {
+        return mcf::fail(MCF_ERR_INVALID, "mcf_engine_collect_eligible: mode %d", rq->mode);
+    }
+    if (m_s == 0 ? rq->next_arc != 0 : (rq->next_arc < 0 || rq->next_arc >= m_s))
+        return mcf::fail(MCF_ERR_INVALID, "mcf_engine_collect_eligible: next_arc %d outside [0, %d)", rq->next_arc, m_s);
+    const double t0 = (double)__rdtsc();
+    HIP_TRY(hipSetDevice(e->d.device));
+    int rc = flush_pending(e);                 // every queued state write and potential, in order, before the scan (same stream)
+    if (rc) return rc;
+    if (m_s == 0) { *count = 0; *end_arc = rq->next_arc; if (arcs_scanned) *arcs_scanned = 0; return MCF_OK; }
+    if (e->collect_cap < std::max(capacity, 1)) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        if (e->h_collect) { (void)hipHostFree(e->h_collect); e->h_collect = nullptr; e->d_collect = nullptr; e->collect_cap = 0; }
+        const int cap = std::max({capacity, 1024, 2 * e->collect_cap});
+        HIP_TRY(hipHostMalloc((void **)&e->h_collect, sizeof(CollectEntry) * (size_t)cap, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer((void **)&e->d_collect, e->h_collect, 0));
+        e->collect_cap = cap;
+    }
+    const int64_t per_round = (int64_t)kCollectThreads * kCollectMaxTiles;
+    const int rounds = (int)std::max<int64_t>(4, ((int64_t)m_s + per_round - 1) / per_round);
+    const int tile_len = rounds * kCollectThreads;
+    const int n_tiles = (m_s + tile_len - 1) / tile_len;     // <= kCollectMaxTiles
+    volatile CollectHeader *hdr = e->h_collect_hdr;
+    hdr->count = -1;
+    rc = e->d.int_width == 32 ? launch_collect<int32_t>(e, rq, capacity, rounds, n_tiles) : launch_collect<int64_t>(e, rq, capacity, rounds, n_tiles);
+    if (rc) return rc;
+    const double t1 = (double)__rdtsc();
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->launch_ticks += t1 - t0;
+    e->wait_ticks += (double)__rdtsc() - t1;
+    const int32_t got = hdr->count;
+    if (got < 0) return mcf::fail(MCF_ERR_HIP, "mcf_engine_collect_eligible: the scan left no answer");
+    *count = got;
+    *end_arc = hdr->end_arc;
+    if (arcs_scanned) *arcs_scanned = hdr->arcs_scanned;
+    e->st.scan_launches += 1;
+    e->st.arcs_scanned += m_s;
+    if (got > capacity) return mcf::fail(MCF_ERR_INVALID, "mcf_engine_collect_eligible: %d eligible arcs, capacity %d", got, capacity);
+    for (int i = 0; i < got; ++i) { arcs[i] = e->h_collect[i].arc; reduced_costs[i] = e->h_collect[i].c; }
+    return MCF_OK;
+}
+
 int mcf_engine_park(mcf_engine *e)
 {
     if (!e) return mcf::fail(MCF_ERR_INVALID, "null argument");
@@ -1924,6 +2066,7 @@ int mcf_engine_reset_stats(mcf_engine *e)
 int mcf_engine_bench_scan(mcf_engine *e, int32_t reps, int32_t cold, int64_t flush_bytes, double *avg_ns, double *min_ns)
 {
     if (!e || reps < 1 || !avg_ns || !min_ns) return mcf::fail(MCF_ERR_INVALID, "mcf_engine_bench_scan: bad arguments");
+    if (e->list_rule) return mcf::fail(MCF_ERR_STATE, "engines of the list rules (3, 4) are searched with mcf_engine_collect_eligible only");
     if (!e->uploaded) return mcf::fail(MCF_ERR_STATE, "mcf_engine_upload has not been called");
     HIP_TRY(hipSetDevice(e->d.device));
     int rc = resident_stop(e);
@@ -2075,6 +2218,7 @@ int mcf_comm_unique_id(uint8_t id_out[128])
 int mcf_engine_comm_init(mcf_engine *e, const uint8_t id[128], int32_t rank, int32_t world)
 {
     if (!e || !id || world < 1 || rank < 0 || rank >= world) return mcf::fail(MCF_ERR_INVALID, "mcf_engine_comm_init: bad arguments");
+    if (e->list_rule) return mcf::fail(MCF_ERR_STATE, "the list rules (3, 4) are not sharded");
     RcclApi *r = rccl();
     if (!r) return mcf::fail(MCF_ERR_COMM, "librccl.so could not be loaded");
     HIP_TRY(hipSetDevice(e->d.device));

@@ -119,6 +119,19 @@ struct mcf_ns {
     int64_t trace_cap = 0, trace_len = 0;
     int64_t pivot_limit = 0;          // 0 = none; otherwise Solve() stops after that many pivots with status NotSolved
     mcf_ns_metrics metrics{};
+    // LEMON's list rules (mcf_ns_set_list_pivot_rule): 0 = none, else MCF_RULE_CANDIDATE_LIST / MCF_RULE_ALTERING_LIST.  The rule's state is
+    // kept here (lemon/network_simplex.h:415-635, member for member); the engine only carries out the major scans (mcf_engine_collect_eligible)
+    int list_rule = 0;
+    struct ListRule {
+        int list_length = 0, minor_limit = 0, curr_length = 0, minor_count = 0;   // Candidate List (_curr_length also Altering List's)
+        int block_size = 0, head_length = 0;                                    // Altering List
+        int next_arc = 0;
+        std::vector<int32_t> candidates;
+        std::vector<int64_t> cand_cost;     // Altering List: _cand_cost, indexed by arc
+        std::vector<int64_t> got;           // reduced costs the device returned with the collected arcs
+        double collect_ticks = 0;
+    } lr;
+    mcf_list_rule_stats list_stats{};
 };
 
 namespace {
@@ -820,6 +833,141 @@ bool pivot(mcf_ns *s, int arc, double *t_tree, double *t_pot)
     return false;
 }
 
+// ---- LEMON's Candidate List and Altering List rules (lemon/network_simplex.h:415-635) on this driver's _state, _pi, _cost: minor iterations,
+// the re-check of the list and the partial sort here, the major scans on the device.  m_s = _searchArcNum of the C# driver (m + n).
+void list_rule_init(mcf_ns *s)
+{
+    auto &L = s->lr;
+    L = mcf_ns::ListRule{};
+    const int m_s = s->search_arcs;
+    s->list_stats = mcf_list_rule_stats{};
+    s->list_stats.rule = s->list_rule;
+    if (s->list_rule == MCF_RULE_CANDIDATE_LIST) {
+        // ns.h:444-455
+        const double LIST_LENGTH_FACTOR = 0.25;
+        const int MIN_LIST_LENGTH = 10;
+        const double MINOR_LIMIT_FACTOR = 0.1;
+        const int MIN_MINOR_LIMIT = 3;
+        L.list_length = std::max(int(LIST_LENGTH_FACTOR * std::sqrt(double(m_s))), MIN_LIST_LENGTH);
+        L.minor_limit = std::max(int(MINOR_LIMIT_FACTOR * L.list_length), MIN_MINOR_LIMIT);
+        L.curr_length = L.minor_count = 0;
+        L.candidates.resize(L.list_length);
+        L.got.resize(L.list_length);
+        s->list_stats.list_length = L.list_length;
+        s->list_stats.minor_limit = L.minor_limit;
+    } else {
+        // ns.h:552-569
+        const double BLOCK_SIZE_FACTOR = 1.0;
+        const int MIN_BLOCK_SIZE = 10;
+        const double HEAD_LENGTH_FACTOR = 0.01;
+        const int MIN_HEAD_LENGTH = 3;
+        L.block_size = std::max(int(BLOCK_SIZE_FACTOR * std::sqrt(double(m_s))), MIN_BLOCK_SIZE);
+        L.head_length = std::max(int(HEAD_LENGTH_FACTOR * L.block_size), MIN_HEAD_LENGTH);
+        L.candidates.resize(L.head_length + L.block_size);
+        L.got.resize(L.head_length + L.block_size);
+        L.cand_cost.assign((size_t)m_s, 0);
+        L.curr_length = 0;
+        s->list_stats.list_length = L.head_length + L.block_size;
+        s->list_stats.block_size = L.block_size;
+        s->list_stats.head_length = L.head_length;
+    }
+}
+
+inline int64_t host_reduced_cost(const mcf_ns *s, int e)     // ns.h:469 / :577
+{
+    return s->state[e] * (s->cost[e] + s->pi[s->tail[e]] - s->pi[s->head[e]]);
+}
+
+// the device scan of a major iteration: `capacity` entries at out / L.got
+int list_collect(mcf_ns *s, const mcf_collect_request &rq, int32_t capacity, int32_t *out, int32_t *count, int32_t *end)
+{
+    const double t0 = ticks();
+    int64_t scanned = 0;
+    const int rc = mcf_engine_collect_eligible(s->engine, &rq, capacity, count, out, s->lr.got.data(), end, &scanned);
+    s->lr.collect_ticks += ticks() - t0;
+    s->list_stats.major_scans += 1;
+    s->list_stats.device_arcs_read += s->search_arcs;
+    s->list_stats.lemon_arcs_scanned += scanned;
+    s->list_stats.collected += *count;
+    return rc;
+}
+
+int list_find_entering(mcf_ns *s, int32_t *found, int32_t *in_arc)
+{
+    auto &L = s->lr;
+    s->list_stats.searches += 1;
+    *found = 0;
+    if (s->list_rule == MCF_RULE_CANDIDATE_LIST) {
+        // ns.h:458-508
+        int64_t min, c;
+        int e;
+        if (L.curr_length > 0 && L.minor_count < L.minor_limit) {
+            // Minor iteration: select the best eligible arc from the current candidate list
+            ++L.minor_count;
+            min = 0;
+            for (int i = 0; i < L.curr_length; ++i) {
+                e = L.candidates[i];
+                c = host_reduced_cost(s, e);
+                if (c < min) {
+                    min = c;
+                    *in_arc = e;
+                } else if (c >= 0) {
+                    L.candidates[i--] = L.candidates[--L.curr_length];
+                }
+            }
+            if (min < 0) { s->list_stats.host_answered += 1; *found = 1; return MCF_OK; }
+        }
+        // Major iteration: build a new candidate list (the device collects the first _list_length eligible arcs from _next_arc on)
+        const mcf_collect_request rq{L.next_arc, MCF_COLLECT_FIRST_N, L.list_length, 0, 0, 0};
+        int32_t k = 0, end = L.next_arc;
+        const int rc = list_collect(s, rq, L.list_length, L.candidates.data(), &k, &end);
+        if (rc) return rc;
+        min = 0;
+        L.curr_length = k;
+        for (int i = 0; i < k; ++i) {
+            if (L.got[i] < min) {
+                min = L.got[i];
+                *in_arc = L.candidates[i];
+            }
+        }
+        if (L.curr_length == 0) return MCF_OK;
+        L.minor_count = 1;
+        L.next_arc = end;
+        *found = 1;
+        return MCF_OK;
+    }
+    // ns.h:573-631.  Check the current candidate list
+    for (int i = 0; i != L.curr_length; ++i) {
+        const int e = L.candidates[i];
+        const int64_t c = host_reduced_cost(s, e);
+        if (c < 0) {
+            L.cand_cost[e] = c;
+        } else {
+            L.candidates[i--] = L.candidates[--L.curr_length];
+        }
+    }
+    // Extend the list (the device scans the blocks from _next_arc on and returns the eligible arcs up to LEMON's stop)
+    const mcf_collect_request rq{L.next_arc, MCF_COLLECT_BLOCKS, 0, L.block_size, L.head_length, L.curr_length};
+    int32_t k = 0, end = L.next_arc;
+    const int rc = list_collect(s, rq, (int32_t)L.candidates.size() - L.curr_length, L.candidates.data() + L.curr_length, &k, &end);
+    if (rc) return rc;
+    for (int i = 0; i < k; ++i) L.cand_cost[L.candidates[L.curr_length + i]] = L.got[i];
+    L.curr_length += k;
+    if (L.curr_length == 0) return MCF_OK;
+    // Perform partial sort operation on the candidate list (libstdc++'s, as LEMON built with g++ runs it: ties resolve alike)
+    const int new_length = std::min(L.head_length + 1, L.curr_length);
+    const int64_t *const cc = L.cand_cost.data();
+    std::partial_sort(L.candidates.begin(), L.candidates.begin() + new_length, L.candidates.begin() + L.curr_length,
+                      [cc](int left, int right) { return cc[left] < cc[right]; });
+    // Select the entering arc and remove it from the list
+    *in_arc = L.candidates[0];
+    L.next_arc = end;
+    L.candidates[0] = L.candidates[new_length - 1];
+    L.curr_length = new_length - 1;
+    *found = 1;
+    return MCF_OK;
+}
+
 int begin(mcf_ns *s, int32_t *status)
 {
     s->status = MCF_NOT_SOLVED;
@@ -938,6 +1086,15 @@ int mcf_ns_set_pivot_rule(mcf_ns *s, int32_t rule)
     if (!s) return mcf::fail(MCF_ERR_INVALID, "null solver");
     if (rule < 0 || rule > 2) return mcf::fail(MCF_ERR_INVALID, "Pivot rule %d not implemented yet (NS.cs:884)", rule);
     s->rule = rule;
+    s->list_rule = 0;
+    return MCF_OK;
+}
+int mcf_ns_set_list_pivot_rule(mcf_ns *s, int32_t rule)
+{
+    if (!s) return mcf::fail(MCF_ERR_INVALID, "null solver");
+    if (rule != MCF_RULE_CANDIDATE_LIST && rule != MCF_RULE_ALTERING_LIST)
+        return mcf::fail(MCF_ERR_INVALID, "mcf_ns_set_list_pivot_rule: %d is not a list rule (3 = Candidate List, 4 = Altering List)", rule);
+    s->list_rule = rule;
     return MCF_OK;
 }
 int mcf_ns_enable_optimized_pivot(mcf_ns *s, int32_t enable)
@@ -1136,6 +1293,8 @@ int mcf_ns_last_pivot(mcf_ns *s, int32_t *n_state, int32_t arcs[2], int8_t state
 int mcf_ns_prepare(mcf_ns *s)
 {
     if (!s) return mcf::fail(MCF_ERR_INVALID, "null solver");
+    if (s->list_rule && s->shard_mode != mcf_ns::kWhole)
+        return mcf::fail(MCF_ERR_INVALID, "the list rules (3, 4) scan the whole search range on one engine: no sharding");
     if (s->prepared) return MCF_OK;
     if (mcf_device_count() <= s->device)
         return mcf::fail(MCF_ERR_NO_DEVICE, "HIP device %d not available (%d visible); the entering-arc search only exists on the device", s->device, mcf_device_count());
@@ -1159,6 +1318,7 @@ int mcf_ns_prepare(mcf_ns *s)
     d.block_size = s->block_size;
     d.device = s->device;
     d.flags = s->engine_flags;
+    if (s->list_rule) { d.rule = s->list_rule; d.semantics = MCF_SEM_PLAIN; d.vector_width = MCF_VECTOR_DEFAULT; d.flags |= MCF_ENGINE_DISPATCH; }
     // NS.cs:237-250: the solver configures itself from the problem's shape unless told otherwise.  (The reference analyses after
     // TransformToStandardForm; the analysis only reads the graph, which that step does not touch.)
     if (s->auto_config) { rc = mcf_block_config_auto(&s->config, s->n, s->m, s->tail.data(), s->head.data()); if (rc) return rc; }
@@ -1244,7 +1404,7 @@ int mcf_ns_prepare(mcf_ns *s)
     s->cands.assign((size_t)std::max(1, s->world), mcf_candidate{0, 0xFFFFFFFFu, -1, 0, 0xFFFFFFFFu, -1});
     if (s->shard_mode == mcf_ns::kHost) { rc = mcf_exchange_open(&s->exchange, s->exchange_name.c_str(), s->rank, s->world); if (rc) return rc; }
     s->metrics.config_flags = s->config.flags;
-    if (!s->optimized_pivot && (s->config.flags & MCF_OPT_REDUCED_COST_CACHING) && s->rule == MCF_RULE_BLOCK_SEARCH) {
+    if (!s->list_rule && !s->optimized_pivot && (s->config.flags & MCF_OPT_REDUCED_COST_CACHING) && s->rule == MCF_RULE_BLOCK_SEARCH) {
         // NS.cs:855-883: `_nodeCount * _nodeCount` is an int product (it wraps) before the conversion to double
         const int32_t nn = (int32_t)((uint32_t)s->n * (uint32_t)s->n);
         const double density = (double)s->search_arcs / (double)nn;
@@ -1253,6 +1413,7 @@ int mcf_ns_prepare(mcf_ns *s)
     s->metrics.search_arc_num = s->search_arcs;
     s->metrics.int_width = d.int_width;
     mcf_engine_get_block_size(s->engine, &s->metrics.block_size);
+    if (s->list_rule) s->metrics.block_size = 0;
     s->metrics.setup_us = (mcf::now_ns() - t_start) / 1e3;
     return MCF_OK;
 }
@@ -1285,14 +1446,17 @@ int mcf_ns_solve(mcf_ns *s, int32_t *status)
     s->dbg.on = getenv("MCF_NS_DEBUG") != nullptr;
     int dbg_class = -1;              // size class of the pivot whose search is being waited for
     double dbg_t_prev = 0;
+    // a list rule searches synchronously at the top of the loop (the host answers from its list or the device collects); nothing is posted
+    s->list_stats = mcf_list_rule_stats{};
+    if (s->list_rule) list_rule_init(s);
     // The search for pivot k+1 is posted as soon as the device has what it depends on (State[] writes, potentials); the rest of pivot k
     // (flows around the cycle, re-hanging the subtree) runs while the device is searching.  Engines sharded over RCCL search in one
     // blocking call (the all-gather runs on their stream), so for them the two halves simply follow each other.
-    rc = engines_search_begin(s);
+    rc = s->list_rule ? MCF_OK : engines_search_begin(s);
     while (!rc) {
         const double t0 = ticks();
         int32_t found = 0, arc = -1;
-        rc = engines_search_end(s, &found, &arc);
+        rc = s->list_rule ? list_find_entering(s, &found, &arc) : engines_search_end(s, &found, &arc);
         const double t_got = ticks();
         t_search += t_got - t0;
         if (s->dbg.on && dbg_class >= 0) { s->dbg.wait[dbg_class] += t_got - t0; s->dbg.rest[dbg_class] += (t0 - dbg_t_prev); }
@@ -1337,7 +1501,7 @@ int mcf_ns_solve(mcf_ns *s, int32_t *status)
         else if (!rc && s->moved_n > s->moved_sent)
             rc = engines_append_potential(s, (int32_t)(s->moved_n - s->moved_sent), s->moved.data() + s->moved_sent, s->moved_without_values ? nullptr : s->moved_val.data() + s->moved_sent);
         const double t2 = ticks();
-        if (!rc) rc = engines_search_begin(s);
+        if (!rc && !s->list_rule) rc = engines_search_begin(s);
         const double t3 = ticks();
         t_pot += t3 - t1;
         t_hand += t2 - t1;
@@ -1399,7 +1563,8 @@ int mcf_ns_solve(mcf_ns *s, int32_t *status)
     }
     mcf_engine_get_stats(s->engine, &s->metrics.engine);
     // the rest of SolverMetrics: NS.cs:262-270 (initial block size), :276 (expected iterations), :344-357
-    const bool plain_block = s->rule == MCF_RULE_BLOCK_SEARCH && !s->optimized_pivot;
+    const bool plain_block = !s->list_rule && s->rule == MCF_RULE_BLOCK_SEARCH && !s->optimized_pivot;
+    s->list_stats.collect_us = s->lr.collect_ticks * ns_per_tick / 1e3;
     s->metrics.initial_block_size = plain_block ? s->metrics.engine.initial_block_size : 0;
     s->metrics.final_block_size = plain_block ? s->metrics.engine.current_block_size : 0;
     s->metrics.total_arcs_checked = s->metrics.engine.arcs_checked;
@@ -1507,6 +1672,12 @@ int mcf_ns_get_metrics(mcf_ns *s, mcf_ns_metrics *out)
 {
     if (!s || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
     *out = s->metrics;
+    return MCF_OK;
+}
+int mcf_ns_get_list_rule_stats(mcf_ns *s, mcf_list_rule_stats *out)
+{
+    if (!s || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
+    *out = s->list_stats;
     return MCF_OK;
 }
 

@@ -164,6 +164,16 @@ class NetworkSimplex:
     def set_pivot_rule(self, rule: int):
         L.check(L.lib().mcf_ns_set_pivot_rule(self._h, rule)); return self
 
+    def set_list_pivot_rule(self, rule: int):
+        """LEMON's Candidate List (PivotRule.CandidateList) or Altering List (PivotRule.AlteringList) rule: the reference declares both and throws
+        (NetworkSimplex.cs:879-885); here minor iterations run on the host driver and the major scans on the device.  set_pivot_rule replaces it.
+        The list rules ignore enable_optimized_pivot, the vector width, the optimization config and auto-configuration; sharding is refused."""
+        L.check(L.lib().mcf_ns_set_list_pivot_rule(self._h, rule)); return self
+
+    def list_rule_stats(self) -> dict:
+        """mcf_ns_get_list_rule_stats: major scans (device calls), searches answered on the host, arcs the device read, of the last solve."""
+        st = L.ListRuleStats(); L.check(L.lib().mcf_ns_get_list_rule_stats(self._h, C.byref(st))); return st.as_dict()
+
     def enable_optimized_pivot(self, enable: bool = True):     # NetworkSimplex.cs:532-535
         L.check(L.lib().mcf_ns_enable_optimized_pivot(self._h, int(enable))); return self
 
@@ -473,6 +483,19 @@ class PivotEngine:
         f, a, c = C.c_int32(), C.c_int32(), C.c_int64()
         L.check(L.lib().mcf_engine_resolve(self._h, len(cands), arr, C.byref(f), C.byref(a), C.byref(c)))
         return bool(f.value), a.value, c.value
+
+    def collect_eligible(self, next_arc: int, *, limit: int = 0, block_size: int = 0, head_length: int = 0, survivors: int = 0, capacity: int = None):
+        """mcf_engine_collect_eligible (list-rule engines only): the eligible arcs of the cyclic scan from next_arc, in scan order, up to LEMON's
+        stop -- FIRST_N with limit > 0 (Candidate List), else BLOCKS (Altering List).  Returns (arcs, reduced_costs, end_arc, arcs_scanned)."""
+        mode = L.COLLECT_FIRST_N if limit > 0 else L.COLLECT_BLOCKS
+        if capacity is None:
+            capacity = limit if mode == L.COLLECT_FIRST_N else head_length + block_size
+        rq = L.CollectRequest(next_arc, mode, limit, block_size, head_length, survivors)
+        arcs, rcs = np.zeros(max(capacity, 1), np.int32), np.zeros(max(capacity, 1), np.int64)
+        k, end, scanned = C.c_int32(), C.c_int32(), C.c_int64()
+        L.check(L.lib().mcf_engine_collect_eligible(self._h, C.byref(rq), capacity, C.byref(k), arcs.ctypes.data, rcs.ctypes.data,
+                                                    C.byref(end), C.byref(scanned)))
+        return arcs[: k.value].copy(), rcs[: k.value].copy(), end.value, scanned.value
 
     @property
     def next_arc(self) -> int:
