@@ -9,14 +9,16 @@
 // with a smaller key is on it) as of the moment it was posted (its epoch).  The host keeps
 //   * the list, and for every node / arc the epoch of its last change: a list entry is CLEAN when nothing of it changed after the list's epoch;
 //   * a min-heap with the current keys of all arcs touched since (re-evaluated from the host mirrors when they are touched; at most
-//     cand_max_nodes nodes' adjacency per pivot -- a bigger subtree is not evaluated here, the device searches instead).
+//     kCandMaxNodes nodes' adjacency per pivot -- a bigger subtree is not evaluated here, the device searches instead).
 // Then, exactly:   min over untouched arcs = first clean list entry (all unlisted untouched arcs lie above the threshold)
 //                  min over touched arcs   = top of the heap
 // and the entering arc is the smaller of the two -- the reference's pivot, arc for arc (every parity test runs with the cache on and off).
 // The list is refreshed ASYNCHRONOUSLY: when it runs low the next device search is posted while the host keeps answering from the current
 // list; its answer is installed when it has arrived.  The host only waits for the device when it cannot decide: after a big subtree
 // moved, or when the list ran out above the threshold.
-constexpr int64_t kCandDegreePerNode = 8;       // adjacency entries re-evaluated per pivot at most: this many per node of cand_max_nodes (2048 by default)
+constexpr int kCandMaxNodes = 256;              // sweep on config 3 (profiles/r03_cand_nodes_sweep.txt): 192-384 nodes evaluated on the host beat a device round trip
+constexpr int kCandRefreshLow = 12;             // entries left on the list when the next one is asked for
+constexpr int64_t kCandDegreePerNode = 8;       // adjacency entries re-evaluated per pivot at most: this many per node of kCandMaxNodes
 constexpr int kCandMaxAvgDegree = 24;           // denser graphs: a single moved node already touches too many arcs
 
 inline const int64_t *cand_pi(const mcf_engine *e) { return e->ext_pi ? e->ext_pi : e->pi.data(); }
@@ -42,7 +44,7 @@ inline void cand_note_node(mcf_engine *e, int u, bool sigma_known = false, int64
         if (!e->pivot_overflow) {
             e->pivot_nodes.push_back(u);
             e->pivot_degree += e->adj_start[u + 1] - e->adj_start[u];
-            if ((int)e->pivot_nodes.size() > e->cand_max_nodes || e->pivot_degree > kCandDegreePerNode * e->cand_max_nodes) e->pivot_overflow = true;
+            if ((int)e->pivot_nodes.size() > kCandMaxNodes || e->pivot_degree > kCandDegreePerNode * kCandMaxNodes) e->pivot_overflow = true;
         }
     }
 }
@@ -473,25 +475,21 @@ void shift_post_request(mcf_engine *e, uint32_t seq, uint32_t cmd, size_t val_lo
     h.w[kShHdrSigma] = (uint32_t)(uint64_t)sigma;
     h.w[kShHdrSigma + 1] = (uint32_t)((uint64_t)sigma >> 32);
     h.w[kHdrTag] = seq;
-    mailbox_publish(e->mailbox, e->poll_replicas, h, vals.n + sts.n > 0 ? &line1 : nullptr);
+    mailbox_publish(e->mailbox, kPollReplicas, h, vals.n + sts.n > 0 ? &line1 : nullptr);
 }
 // a request without patches: quit, or a scan request put there again for a grid that has just been started with current arrays
 void shift_post(mcf_engine *e, uint32_t seq, uint32_t cmd, bool) { shift_post_request(e, seq, cmd, 0, 0, 0, false); }
 
 // the complete shift lines of this pivot's big list start travelling while the host is still walking the subtree (kCmdApply / kCmdApplyRuns:
 // "shift lines 0 .. L-1 of the coming scan request are in place": the grid sets their bits and goes back to polling)
-int shift_stream_min_lines()
-{
-    static const int v = [] { int x = 96; if (const char *u = getenv("MCF_HIP_SHIFT_STREAM_LINES")) { const int y = atoi(u); if (y >= 8 && y <= 65536) x = y; } return x; }();
-    return v;
-}
+constexpr int kShiftStreamMinLines = 96;
 void shift_stream(mcf_engine *e)
 {
     if (e->async_posted || e->blind_epoch != e->cand_now || e->blind_sets > 1 || !e->pend_shift) return;
     if (!e->resident_running || e->in_flight != mcf_engine::kNoSearch) return;
     const bool runs = e->blind_lazy;
     const int complete = runs ? (int)(e->blind_runs.size() / 2 / kShiftPairsPerLine) : (int)(e->blind_count / kShiftNodesPerLine);
-    if (complete - e->shift_streamed < shift_stream_min_lines() || complete > e->max_shift_lines) return;
+    if (complete - e->shift_streamed < kShiftStreamMinLines || complete > e->max_shift_lines) return;
     uint32_t next_seq = e->seq + 1;
     if (next_seq == 0) next_seq = 1;
     shift_write_lines(e, e->shift_streamed, complete, runs ? e->blind_runs.size() / 2 : e->blind_count, runs, next_seq);
@@ -503,7 +501,7 @@ void shift_stream(mcf_engine *e)
     h.w[kShHdrShift] = (uint32_t)complete;
     h.w[kShHdrApplySub] = e->stream_sub;
     h.w[kHdrTag] = next_seq;
-    mailbox_publish(e->mailbox, e->poll_replicas, h, nullptr);
+    mailbox_publish(e->mailbox, kPollReplicas, h, nullptr);
     e->shift_streamed = complete;
     e->stream_lines = complete;                    // "a list is travelling": what the other paths test before they change their mind about it
 }

@@ -58,8 +58,7 @@ inline void *huge_block(size_t bytes)
     const size_t len = (bytes + stagger + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
     void *base = aligned_alloc((size_t)2 << 20, len);
     if (!base) return nullptr;
-    static const bool off = getenv("MCF_HUGEPAGES") && getenv("MCF_HUGEPAGES")[0] == '0';      // measurement aid
-    if (!off) (void)madvise(base, len, MADV_HUGEPAGE);
+    (void)madvise(base, len, MADV_HUGEPAGE);
     void *p = (char *)base + stagger;
     ((void **)p)[-1] = base;
     return p;
@@ -83,6 +82,23 @@ struct HugeAlloc {
     template <class U> bool operator!=(const HugeAlloc<U> &) const { return false; }
 };
 template <class T> using hvec = std::vector<T, HugeAlloc<T>>;
+
+// The MCF_* variables that tests and the benchmark set are read once, where the engine or the solver that uses them is made.
+// env_int: the variable's integer value when it is set and lies in [lo, hi], else dflt
+inline long long env_int(const char *name, long long lo, long long hi, long long dflt)
+{
+    const char *u = getenv(name);
+    if (!u) return dflt;
+    char *end = nullptr;
+    const long long v = strtoll(u, &end, 10);
+    return end != u && v >= lo && v <= hi ? v : dflt;
+}
+// env_off: the variable is set to 0 (it switches off something that is on by default)
+inline bool env_off(const char *name)
+{
+    const char *u = getenv(name);
+    return u && u[0] == '0';
+}
 
 // default Block Search block size of the two reference implementations
 int default_block_size(int search_arc_num, int semantics);

@@ -82,6 +82,8 @@ RcclApi *rccl()
 }
 constexpr int kNcclChar = 0;   // ncclInt8 / ncclChar
 constexpr int kStageStates = 4096;   // state patches one staged update carries
+constexpr int kScanMaxGrid = 2048;   // workgroups of the dispatched gathering scan at most (desc.scan_workgroups overrides)
+constexpr int kRcMaxGrid = 512;      // ... and of the dispatched RC scan
 
 }  // namespace
 
@@ -111,7 +113,6 @@ struct mcf_engine {
     Slot *d_dev_slots = nullptr;                    // the same records in device memory (RCCL exchange: they are folded on the device)
     Slot *slots_target = nullptr;                   // where the next dispatch writes its records
     int grid = 0, unroll = 1;
-    bool nt = false;
     bool lds_pi = false;           // node_count <= kLdsPiMax: kernels keep the potentials in LDS
     // bucketed layout (Best Eligible, potentials neither in LDS nor next to register-resident arcs, large sparse instances): the arcs are
     // stored stably sorted by target-node range so that one range's potentials (1 MB) stay in every XCD's L2 while the grid sweeps it
@@ -122,7 +123,6 @@ struct mcf_engine {
     bool rc_mode = false;
     bool rc_lds = false;           // resident RC grid: every workgroup's window of arcs fits LDS
     int rc_window = 0;             // arcs per workgroup in that case
-    int rc_threads = kThreads;     // workgroup width of the dispatched RC scan
     int64_t *d_rc = nullptr;
     int32_t *d_adj_start = nullptr;
     uint32_t *d_adj = nullptr;     // the shard's arcs at each node: local position, bit 31 = the node is the arc's target
@@ -131,7 +131,7 @@ struct mcf_engine {
     int rc_list_max = 0;                  // resident RC grid: {node, shift} entries one request may carry (longer lists stop the grid)
     bool pend_shift = false;       // every pending potential is its node's previous value + pend_sigma (mcf_engine_shift_potential)
     int64_t pend_sigma = 0;
-    bool no_pireg = false;         // MCF_ENGINE_SHARE_DEVICE or MCF_HIP_PIREG=0: the resident grid gathers the potentials for every request
+    bool no_pireg = false;         // MCF_ENGINE_SHARE_DEVICE: the resident grid gathers the potentials for every request
     int lds_grid = 0;
     uint32_t seq = 0;
     bool uploaded = false;
@@ -199,7 +199,8 @@ struct mcf_engine {
     int stream_lines = 0;          // entry lines of the coming request that an "apply" post has already put in place
     uint32_t stream_sub = 0;       // counter of those posts
     uint32_t *mailbox = nullptr;
-    int mailbox_lines = 0, mailbox_max_st = 0, poll_replicas = 8, poll_sleep = 1;
+    int mailbox_lines = 0, mailbox_max_st = 0;
+    uint32_t idle_ticks = 0;       // a resident grid leaves after this long without a request (kResidentIdleTicks; MCF_HIP_IDLE_MS)
     uint32_t prev_seq = 0;
     // candidate cache (Best Eligible, resident, register-resident tiles, sparse graphs): see cand_* below
     bool cand_on = false, cand_valid = false;
@@ -255,9 +256,10 @@ struct mcf_engine {
     bool async_posted = false;                    // a refresh is on its way while the host keeps answering from the current list
     uint32_t async_at = 0, posted_at = 0;
     int patch_capacity = 0;                       // potential patches one request / one staged update can carry (2 * node_count + 256)
-    int cand_max_nodes = 256, cand_refresh_low = 12;      // sweep on config 3 (profiles/r03_cand_nodes_sweep.txt): 192-384 nodes evaluated on the host beat a device round trip
+    uint32_t cand_epoch0 = 1;                     // the epoch an upload starts from (MCF_HIP_CAND_EPOCH0: tests start close to the wrap)
     size_t heap_compact_above = 1u << 18;         // heap entries above which the stale ones are swept out (MCF_HIP_CAND_HEAP_COMPACT: tests)
-    // where the host's time goes in candidate mode (TSC ticks; printed by mcf_engine_destroy when MCF_HIP_CAND_DEBUG is set)
+    bool cand_debug = false;                      // MCF_HIP_CAND_DEBUG: host-side time breakdown of the candidate cache on stderr
+    // where the host's time goes in candidate mode (TSC ticks; printed by mcf_engine_destroy when cand_debug is set)
     double tk_absorb = 0, tk_decide = 0, tk_post = 0, tk_collect = 0, tk_probe = 0;
     int64_t n_sync_posts = 0, n_async_waits = 0, n_gap_pivots = 0, n_heap_push = 0, n_heap_pop = 0, n_list_skip = 0;
     uint32_t *h_exit = nullptr, *d_exit = nullptr;
@@ -339,19 +341,19 @@ void fill_params(mcf_engine *e, ScanParams<T> &p, bool with_patches)
     }
 }
 
-template <typename T, int RULE, bool OPT, int UNROLL, bool NT>
+template <typename T, int RULE, bool OPT, int UNROLL>
 void launch_scan_k(mcf_engine *e, const ScanParams<T> &p, hipEvent_t start, hipEvent_t stop)
 {
     const dim3 grid(e->grid), block(kThreads);
     if constexpr (RULE == MCF_RULE_BEST_ELIGIBLE) {
         if (e->bucket_nodes > 0) {
-            if (start) hipExtLaunchKernelGGL((scan_kernel<T, RULE, OPT, UNROLL, NT, true>), grid, block, 0, e->stream, start, stop, 0, p);
-            else hipLaunchKernelGGL((scan_kernel<T, RULE, OPT, UNROLL, NT, true>), grid, block, 0, e->stream, p);
+            if (start) hipExtLaunchKernelGGL((scan_kernel<T, RULE, OPT, UNROLL, true>), grid, block, 0, e->stream, start, stop, 0, p);
+            else hipLaunchKernelGGL((scan_kernel<T, RULE, OPT, UNROLL, true>), grid, block, 0, e->stream, p);
             return;
         }
     }
-    if (start) hipExtLaunchKernelGGL((scan_kernel<T, RULE, OPT, UNROLL, NT>), grid, block, 0, e->stream, start, stop, 0, p);
-    else hipLaunchKernelGGL((scan_kernel<T, RULE, OPT, UNROLL, NT>), grid, block, 0, e->stream, p);
+    if (start) hipExtLaunchKernelGGL((scan_kernel<T, RULE, OPT, UNROLL>), grid, block, 0, e->stream, start, stop, 0, p);
+    else hipLaunchKernelGGL((scan_kernel<T, RULE, OPT, UNROLL>), grid, block, 0, e->stream, p);
 }
 
 template <typename T, int RULE, bool OPT>
@@ -368,9 +370,8 @@ void launch_scan_u(mcf_engine *e, const ScanParams<T> &p, hipEvent_t start, hipE
         }
         return;
     }
-    if (e->unroll == 4) { if (e->nt) launch_scan_k<T, RULE, OPT, 4, true>(e, p, start, stop); else launch_scan_k<T, RULE, OPT, 4, false>(e, p, start, stop); }
-    else if (e->unroll == 2) { if (e->nt) launch_scan_k<T, RULE, OPT, 2, true>(e, p, start, stop); else launch_scan_k<T, RULE, OPT, 2, false>(e, p, start, stop); }
-    else launch_scan_k<T, RULE, OPT, 1, false>(e, p, start, stop);
+    if (e->unroll == 2) launch_scan_k<T, RULE, OPT, 2>(e, p, start, stop);
+    else launch_scan_k<T, RULE, OPT, 1>(e, p, start, stop);
 }
 
 template <typename T>
@@ -453,11 +454,8 @@ bool rc_inline_ok(const mcf_engine *e)
 template <int RULE, bool OPT>
 void launch_rc_u(mcf_engine *e, const RcParams &p, hipEvent_t start, hipEvent_t stop)
 {
-    const dim3 grid(e->grid), block(e->rc_threads);
-    if (e->unroll == 4) {
-        if (start) hipExtLaunchKernelGGL((scan_rc_kernel<RULE, OPT, 4>), grid, block, 0, e->stream, start, stop, 0, p);
-        else hipLaunchKernelGGL((scan_rc_kernel<RULE, OPT, 4>), grid, block, 0, e->stream, p);
-    } else if (e->unroll == 2) {
+    const dim3 grid(e->grid), block(kThreads);
+    if (e->unroll == 2) {
         if (start) hipExtLaunchKernelGGL((scan_rc_kernel<RULE, OPT, 2>), grid, block, 0, e->stream, start, stop, 0, p);
         else hipLaunchKernelGGL((scan_rc_kernel<RULE, OPT, 2>), grid, block, 0, e->stream, p);
     } else {
@@ -644,7 +642,7 @@ int search_begin(mcf_engine *e)
                 e->st.host_decided += 1;
                 e->in_flight = mcf_engine::kAnswered;
                 // running low: ask for the next list now and keep answering from this one until it is here
-                if (!e->async_posted && e->cand_thr.p != kNone && e->cand_list.size() - e->cand_ptr <= (size_t)e->cand_refresh_low) {
+                if (!e->async_posted && e->cand_thr.p != kNone && e->cand_list.size() - e->cand_ptr <= (size_t)kCandRefreshLow) {
                     int rc = cand_post(e);
                     if (rc) return rc;
                     e->async_posted = true;
@@ -942,15 +940,11 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
     }
     e->block_size = desc->block_size > 0 ? desc->block_size : mcf::default_block_size(desc->search_arc_num, desc->semantics);
     e->unroll = count > (1 << 20) ? 2 : 1;
-    if (const char *u = getenv("MCF_HIP_UNROLL")) { const int v = atoi(u); if (v == 1 || v == 2 || v == 4) e->unroll = v; }
-    if (const char *u = getenv("MCF_HIP_NT")) e->nt = u[0] == '1';
-    int max_wg = 2048;
-    if (const char *u = getenv("MCF_HIP_MAXWG")) { const int v = atoi(u); if (v >= 1 && v <= kMaxWorkgroups) max_wg = v; }
     const int groups = e->count_padded / (kTile * e->unroll);
-    e->grid = desc->scan_workgroups > 0 ? std::min(desc->scan_workgroups, kMaxWorkgroups) : std::min(groups, max_wg);
+    e->grid = desc->scan_workgroups > 0 ? std::min(desc->scan_workgroups, kMaxWorkgroups) : std::min(groups, kScanMaxGrid);
     e->grid = std::max(1, std::min(e->grid, groups));
-    e->lds_pi = desc->node_count <= kLdsPiMax && !(getenv("MCF_HIP_LDS_PI") && getenv("MCF_HIP_LDS_PI")[0] == '0');
-    e->no_pireg = (desc->flags & MCF_ENGINE_SHARE_DEVICE) || (getenv("MCF_HIP_PIREG") && getenv("MCF_HIP_PIREG")[0] == '0');
+    e->lds_pi = desc->node_count <= kLdsPiMax;
+    e->no_pireg = (desc->flags & MCF_ENGINE_SHARE_DEVICE) != 0;
     if (e->lds_pi) {
         // one 1024-thread workgroup per CU (the 128 KB potential copy allows no more); each loops over its 4096-arc tiles
         e->unroll = count > (2 << 20) ? 2 : 1;
@@ -962,7 +956,7 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
     // scan (and with it the bucketed layout).
     {
         bool want = !e->resident_reg && !e->lds_pi;
-        if (const char *u = getenv("MCF_HIP_RC")) want = u[0] == '1' ? true : (u[0] == '0' ? false : want);
+        want = mcf::env_int("MCF_HIP_RC", 0, 1, want) != 0;
         if (list_rule) want = false;          // the list rules read the SoA arrays themselves (collect.hip.h)
         e->rc_mode = want;
         if (e->rc_mode) {
@@ -972,13 +966,11 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
             // the best of them, more workgroups only add launch ramp and tail
             e->rc_recompute_above = std::max(1024, desc->node_count / 16);
             e->rc_list_max = kRcResidentNodes;
-            if (const char *u = getenv("MCF_HIP_RC_RECOMPUTE")) { const long long v = atoll(u); e->rc_recompute_above = v <= 0 || v > INT32_MAX ? INT32_MAX : (int)v; }    // 0: never
+            const int recompute = (int)mcf::env_int("MCF_HIP_RC_RECOMPUTE", 0, INT32_MAX, e->rc_recompute_above);
+            e->rc_recompute_above = recompute == 0 ? INT32_MAX : recompute;      // 0: never
             e->unroll = count > (1 << 20) ? 2 : 1;
-            if (const char *u = getenv("MCF_HIP_UNROLL")) { const int v = atoi(u); if (v == 1 || v == 2 || v == 4) e->unroll = v; }
-            if (const char *u = getenv("MCF_HIP_RC_THREADS")) { const int v = atoi(u); if (v == 256 || v == 512 || v == 1024) e->rc_threads = v; }
-            const int groups_rc = std::max(1, e->count_padded / (e->rc_threads * kArcsPerThread * e->unroll));
-            const int max_rc = getenv("MCF_HIP_MAXWG") ? max_wg : 512;
-            e->grid = desc->scan_workgroups > 0 ? std::min(desc->scan_workgroups, kMaxWorkgroups) : std::min(groups_rc, max_rc);
+            const int groups_rc = std::max(1, e->count_padded / (kThreads * kArcsPerThread * e->unroll));
+            e->grid = desc->scan_workgroups > 0 ? std::min(desc->scan_workgroups, kMaxWorkgroups) : std::min(groups_rc, kRcMaxGrid);
             e->grid = std::max(1, std::min(e->grid, groups_rc));
         }
     }
@@ -1031,16 +1023,15 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
     }
     // resident mode: the default (MCF_ENGINE_DISPATCH / MCF_HIP_RESIDENT=0 ask for one dispatch per search)
     {
-        const char *env = getenv("MCF_HIP_RESIDENT");
+        const int env = (int)mcf::env_int("MCF_HIP_RESIDENT", 0, 1, -1);
         bool want = (desc->flags & MCF_ENGINE_DISPATCH) == 0;      // resident unless dispatch mode is asked for
         // arcs that fit neither registers nor (with their potentials) LDS are streamed from memory for every search anyway: one dispatch
         // per search with 2048 workgroups is then faster than 256 resident ones (config 5: 71 vs 85 us per pivot)
         if (!e->resident_reg && !e->lds_pi) want = false;
         // the RC layout has its own resident grid (resident_rc_kernel): windows of arcs in LDS when they fit, streamed otherwise
-        bool rc_resident = e->rc_mode && (desc->flags & MCF_ENGINE_DISPATCH) == 0 && !(getenv("MCF_HIP_RC_RESIDENT") && getenv("MCF_HIP_RC_RESIDENT")[0] == '0');
-        if (e->rc_mode) want = rc_resident;
-        if (env && env[0] == '1' && !e->rc_mode) want = true;
-        if (env && env[0] == '0') want = false;
+        if (e->rc_mode) want = (desc->flags & MCF_ENGINE_DISPATCH) == 0;
+        if (env == 1 && !e->rc_mode) want = true;
+        if (env == 0) want = false;
         if (list_rule) want = false;          // dispatch mode only: no resident grid, hence no candidate cache either
         // an arc shard is served by a resident grid like a whole instance (every workgroup applies every potential patch, state patches
         // outside the shard are ignored); only the RCCL exchange needs the stream, and mcf_engine_comm_init switches to dispatch mode
@@ -1049,8 +1040,7 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
             e->mailbox_lines = 2 + (e->patch_capacity + e->mailbox_max_st + kMailboxPatchesPerLine - 1) / kMailboxPatchesPerLine;
             e->max_shift_lines = (desc->node_count + kShiftNodesPerLine - 1) / kShiftNodesPerLine + 1;
             e->shift_base = (uint32_t)kMailboxTail + 16u * (uint32_t)e->mailbox_lines;
-            if (const char *u = getenv("MCF_HIP_POLL_REPLICAS")) { const int v = atoi(u); if (v >= 1 && v <= kMaxReplicas) e->poll_replicas = v; }
-            if (const char *u = getenv("MCF_HIP_POLL_SLEEP")) { const int v = atoi(u); if (v >= 0 && v <= 64) e->poll_sleep = v; }
+            e->idle_ticks = (uint32_t)(mcf::env_int("MCF_HIP_IDLE_MS", 1, 10000, kResidentIdleTicks / 100000) * 100000);
             e->mailbox = alloc_bar_vram(desc->device, (size_t)kMailboxTail * 4 + ((size_t)e->mailbox_lines + e->max_shift_lines) * 64);
             if (e->mailbox && hipHostMalloc((void **)&e->h_exit, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
                 hipHostGetDevicePointer((void **)&e->d_exit, e->h_exit, 0) == hipSuccess &&
@@ -1066,19 +1056,18 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
                     e->res_grid = std::max(1, std::min(max_grid, e->count_padded / kResidentTile));
                     const int64_t per = ((int64_t)e->count_padded + e->res_grid - 1) / e->res_grid;
                     e->rc_window = (int)((per + kResidentTile - 1) / kResidentTile * kResidentTile);
-                    e->rc_lds = e->rc_window <= kRcWindow && !(getenv("MCF_HIP_RC_LDS") && getenv("MCF_HIP_RC_LDS")[0] == '0');
+                    e->rc_lds = e->rc_window <= kRcWindow && !mcf::env_off("MCF_HIP_RC_LDS");
                     if (!e->rc_lds) e->rc_window = 0;
                     e->resident_reg = false;
                     // the grid-wide barrier of that grid (long lists are dealt out, reloads are carried out in the grid): one counter in device memory
-                    if (!(getenv("MCF_HIP_RC_BARRIER") && getenv("MCF_HIP_RC_BARRIER")[0] == '0') && hipMalloc((void **)&e->d_barrier, 64) != hipSuccess) { e->d_barrier = nullptr; (void)hipGetLastError(); }
-                    const bool dealt = e->d_barrier && !(getenv("MCF_HIP_RC_DEALT") && getenv("MCF_HIP_RC_DEALT")[0] == '0');
-                    e->rc_list_max = dealt ? std::min(2 * desc->node_count, std::max(kRcResidentNodes, e->rc_recompute_above)) : kRcResidentNodes;
+                    if (hipMalloc((void **)&e->d_barrier, 64) != hipSuccess) { e->d_barrier = nullptr; (void)hipGetLastError(); }
+                    e->rc_list_max = e->d_barrier ? std::min(2 * desc->node_count, std::max(kRcResidentNodes, e->rc_recompute_above)) : kRcResidentNodes;
                 }
-                e->cand_on = !(desc->flags & MCF_ENGINE_NO_CANDIDATES) && !(getenv("MCF_HIP_CANDIDATES") && getenv("MCF_HIP_CANDIDATES")[0] == '0') &&
+                e->cand_on = !(desc->flags & MCF_ENGINE_NO_CANDIDATES) && !mcf::env_off("MCF_HIP_CANDIDATES") &&
                              (e->resident_reg || e->rc_mode) && desc->rule == MCF_RULE_BEST_ELIGIBLE && desc->node_count < (1 << 29) &&
                              2 * (int64_t)desc->search_arc_num <= (int64_t)kCandMaxAvgDegree * desc->node_count;
                 e->shift_grid = e->cand_on && e->resident_reg && !e->rc_mode && !e->lds_pi && !e->no_pireg && desc->int_width == 64 &&
-                                desc->node_count <= kShiftBits && !(getenv("MCF_HIP_SHIFT_GRID") && getenv("MCF_HIP_SHIFT_GRID")[0] == '0');
+                                desc->node_count <= kShiftBits;
                 if (e->shift_grid) {
                     // that grid keeps 2 or 4 tiles of four arcs per thread: at most 256 threads, one wave per SIMD
                     const int64_t groups4 = ((int64_t)count + kArcsPerThread - 1) / kArcsPerThread;
@@ -1093,8 +1082,7 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
                     // Measured on config 3 (tools/gpu_walk_variants.py): the reload costs 40 - 44 us in the grid (800 KB over PCIe, the barrier, the
                     // gather) against 13 - 15 for a list that travelled during the walk, and saves the walk its list only before the first
                     // relabelling -- from 32768 nodes on it wins (246 against 240 - 245 k pivots/s), from 8192 on it does not (243 k).
-                    e->shift_reload_min = 32768;
-                    if (const char *u = getenv("MCF_HIP_SHIFT_RELOAD")) { const int v = atoi(u); e->shift_reload_min = v > 0 ? v : 0; }
+                    e->shift_reload_min = (int)mcf::env_int("MCF_HIP_SHIFT_RELOAD", 0, INT32_MAX, 32768);
                     if (e->shift_reload_min > 0 && hipMalloc((void **)&e->d_barrier, 64) != hipSuccess) { e->d_barrier = nullptr; (void)hipGetLastError(); }
                 }
             }
@@ -1104,7 +1092,7 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
     {
         // bucketed layout: automatic for large sparse Best-Eligible instances; MCF_HIP_BUCKET_NODES=N forces N nodes per range (0 = off)
         int want = (count >= kBucketMinArcs && desc->node_count > 2 * kBucketNodes) ? kBucketNodes : 0;
-        if (const char *u = getenv("MCF_HIP_BUCKET_NODES")) want = std::max(0, atoi(u));
+        want = (int)mcf::env_int("MCF_HIP_BUCKET_NODES", 0, INT32_MAX, want);
         const bool tile_loop = !e->lds_pi && !(e->resident_ok && e->resident_reg) && !e->rc_mode;
         if (want > 0 && desc->rule == MCF_RULE_BEST_ELIGIBLE && tile_loop && !e->cand_on) {
             if (hipMalloc((void **)&e->d_orig, sizeof(int32_t) * e->count_padded) == hipSuccess) e->bucket_nodes = want;
@@ -1118,6 +1106,9 @@ int mcf_engine_create(mcf_engine **out, const mcf_engine_desc *desc)
     e->st.rc_layout = e->rc_mode ? 1 : 0;
     e->st.shift_grid = e->shift_grid ? 1 : 0;
     e->st.initial_block_size = e->st.current_block_size = e->block_size;
+    e->cand_epoch0 = (uint32_t)mcf::env_int("MCF_HIP_CAND_EPOCH0", 1, 0xFFFFFFFFll, 1);
+    e->heap_compact_above = (size_t)mcf::env_int("MCF_HIP_CAND_HEAP_COMPACT", 1, 1ll << 30, (long long)e->heap_compact_above);
+    e->cand_debug = getenv("MCF_HIP_CAND_DEBUG") != nullptr;
     *out = e;
     return MCF_OK;
 }
@@ -1153,7 +1144,7 @@ void host_unpin(const void *p)
 void mcf_engine_destroy(mcf_engine *e)
 {
     if (!e) return;
-    if (e->cand_on && getenv("MCF_HIP_CAND_DEBUG") && e->st.searches > 1000) {
+    if (e->cand_on && e->cand_debug && e->st.searches > 1000) {
         const double ns_per_tick = (mcf::now_ns() - e->cal_ns) / std::max(1.0, (double)__rdtsc() - e->cal_ticks);
         const double n = (double)e->st.searches;
         fprintf(stderr, "[cand] searches %lld host %lld async %lld sync_posts %lld async_waits %lld gap_pivots %lld | per search ns: absorb %.0f probe %.0f decide %.0f post %.0f collect %.0f wait %.0f | heap size %zu\n",
@@ -1279,10 +1270,7 @@ int mcf_engine_upload(mcf_engine *e, const int32_t *source, const int32_t *targe
         e->rc_sync.clear(); e->rc_shift_unknown = false;
         cand_reset(e);
         e->heap_gap = 0;
-        if (const char *u = getenv("MCF_HIP_CAND_EPOCH0")) { const unsigned long long v = strtoull(u, nullptr, 10); if (v >= 1 && v <= 0xFFFFFFFFull) e->cand_now = (uint32_t)v; }    // tests: start close to the wrap
-        if (const char *u = getenv("MCF_HIP_CAND_NODES")) { const int v = atoi(u); if (v >= 0 && v <= 4096) e->cand_max_nodes = v; }
-        if (const char *u = getenv("MCF_HIP_CAND_REFRESH")) { const int v = atoi(u); if (v >= 0 && v <= 4096) e->cand_refresh_low = v; }
-        if (const char *u = getenv("MCF_HIP_CAND_HEAP_COMPACT")) { const long long v = atoll(u); if (v >= 1 && v <= (1ll << 30)) e->heap_compact_above = (size_t)v; }
+        e->cand_now = e->cand_epoch0;
     }
     // the pending lists grow to a subtree's size: get (and touch) their memory now, not in the middle of a solve
     e->pend_node.assign((size_t)e->patch_capacity, 0); e->pend_val.assign((size_t)e->patch_capacity, 0);
@@ -1346,7 +1334,7 @@ int mcf_engine_update_potential(mcf_engine *e, int32_t count, const int32_t *nod
             if ((unsigned)nodes[i] >= (unsigned)e->d.node_count) return mcf::fail(MCF_ERR_INVALID, "node %d out of range", nodes[i]);
             if (e->d.int_width == 32 && !fits32(e->pi[nodes[i]] + sigma)) return mcf::fail(MCF_ERR_OVERFLOW, "potential of node %d leaves int32; create the engine with int_width 64", nodes[i]);
         }
-        if (count > e->cand_max_nodes || e->pivot_overflow) {
+        if (count > kCandMaxNodes || e->pivot_overflow) {
             std::vector<int64_t> vals((size_t)count);
             for (int i = 0; i < count; ++i) vals[i] = (e->pi[nodes[i]] += sigma);
             const bool first = e->blind_count == 0;
@@ -1445,7 +1433,7 @@ int set_potential_impl(mcf_engine *e, int32_t count, const int32_t *nodes, const
     if (const int rcc = check_potential_list(e, count, nodes, values)) return rcc;
     if (e->cand_on) {                 // the mirror stays authoritative in candidate mode
         if (!e->ext_pi) for (int i = 0; i < count; ++i) e->pi[nodes[i]] = values[i];      // bound potentials: the caller's array already holds them
-        if (count > e->cand_max_nodes || e->pivot_overflow) {
+        if (count > kCandMaxNodes || e->pivot_overflow) {
             const bool first = e->blind_count == 0;
             // the big list has ONE shift when every piece of it came with the same announced shift (decided before the piece starts travelling)
             e->pend_shift = e->call_shift_known && (first || (e->pend_shift && e->pend_sigma == e->call_shift));
@@ -1524,7 +1512,7 @@ int mcf_engine_bind_potentials(mcf_engine *e, const int64_t *pi)
     if (pi && (e->rc_mode || (e->shift_grid && e->shift_reload_min > 0)) && e->d.int_width == 64) {
         (void)hipSetDevice(e->d.device);
         e->ext_pi_pinned = host_pin(pi, sizeof(int64_t) * (size_t)e->d.node_count);
-        if (e->ext_pi_pinned && e->resident_ok && !(getenv("MCF_HIP_RC_INGRID_RELOAD") && getenv("MCF_HIP_RC_INGRID_RELOAD")[0] == '0')) {
+        if (e->ext_pi_pinned && e->resident_ok) {
             void *dp = nullptr;
             if (e->d_barrier && hipHostGetDevicePointer(&dp, const_cast<int64_t *>(pi), 0) == hipSuccess) e->d_ext_pi = (const int64_t *)dp;
             (void)hipGetLastError();
@@ -1594,7 +1582,7 @@ int mcf_engine_shift_potential_runs(mcf_engine *e, int32_t n_runs, const int32_t
     }
     if (total > e->d.node_count) return mcf::fail(MCF_ERR_INVALID, "%lld nodes in a graph of %d: the runs of one pivot must not overlap", (long long)total, e->d.node_count);
     if (total == 0) return MCF_OK;
-    if (e->cand_on && e->shift_grid && e->d.int_width == 64 && (total > e->cand_max_nodes || e->pivot_overflow)) {
+    if (e->cand_on && e->shift_grid && e->d.int_width == 64 && (total > kCandMaxNodes || e->pivot_overflow)) {
         // the register-resident candidate grid takes the pairs as they are (seven to a line instead of fifteen node ids)
         const bool first_list = e->blind_count == 0;
         e->pend_shift = first_list || (e->pend_shift && e->pend_sigma == sigma);
@@ -2230,8 +2218,7 @@ int mcf_engine_comm_init(mcf_engine *e, const uint8_t id[128], int32_t rank, int
     // would starve it, so such an engine falls back to one dispatch per search with the exchange on its own stream, as in rounds 1 and 2.
     int cus = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->d.device);
-    const bool room = e->resident_ok && e->res_grid + 8 <= std::max(cus, 16);
-    const bool keep = room && !(getenv("MCF_HIP_RCCL_RESIDENT") && getenv("MCF_HIP_RCCL_RESIDENT")[0] == '0');
+    const bool keep = e->resident_ok && e->res_grid + 8 <= std::max(cus, 16);      // room beside the resident grid
     if (!keep) {
         if (e->cand_on) {              // the candidate cache lives on the resident grid's answers: hand what it still holds to the device and switch it off
             if (int rcf = flush_pending(e)) return rcf;

@@ -151,24 +151,12 @@ template <typename T> struct Vec4;
 template <> struct Vec4<int32_t> {
     int32_t v[4];
     __device__ __forceinline__ void load(const int32_t *p) { const int4 a = *reinterpret_cast<const int4 *>(p); v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; }
-    __device__ __forceinline__ void load_nt(const int32_t *p)
-    {
-        typedef int v4i __attribute__((ext_vector_type(4)));
-        const v4i a = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(p));
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    }
 };
 template <> struct Vec4<int64_t> {
     int64_t v[4];
     __device__ __forceinline__ void load(const int64_t *p)
     {
         const longlong2 a = *reinterpret_cast<const longlong2 *>(p), b = *reinterpret_cast<const longlong2 *>(p + 2);
-        v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-    }
-    __device__ __forceinline__ void load_nt(const int64_t *p)
-    {
-        typedef long v2l __attribute__((ext_vector_type(2)));
-        const v2l a = __builtin_nontemporal_load(reinterpret_cast<const v2l *>(p)), b = __builtin_nontemporal_load(reinterpret_cast<const v2l *>(p + 2));
         v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
     }
 };
@@ -183,20 +171,13 @@ struct TileData {
     Vec4<T> c;
 };
 
-template <typename T, bool NT = false>
+template <typename T>
 __device__ __forceinline__ void load_tile(const int32_t *src, const int32_t *tgt, const T *cost, const int8_t *state, int i0, TileData<T> &d)
 {
-    if (NT) {   // streamed once per scan: non-temporal, do not displace the potentials from L2
-        d.st4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(state + i0));
-        d.s.load_nt(src + i0);
-        d.t.load_nt(tgt + i0);
-        d.c.load_nt(cost + i0);
-    } else {
-        d.st4 = *reinterpret_cast<const uint32_t *>(state + i0);
-        d.s.load(src + i0);
-        d.t.load(tgt + i0);
-        d.c.load(cost + i0);
-    }
+    d.st4 = *reinterpret_cast<const uint32_t *>(state + i0);
+    d.s.load(src + i0);
+    d.t.load(tgt + i0);
+    d.c.load(cost + i0);
 }
 
 // the eight potential gathers of a thread's four arcs
@@ -259,11 +240,11 @@ __device__ __forceinline__ void eval_tile(const TileData<T> &d, const T *pi, int
     fold_tile<T, RULE, OPT, PERM>(d, ps, pt, e0, m_s, next_arc, block_size, rstar, best, range, orig, base);
 }
 
-template <typename T, int RULE, bool OPT, bool NT = false, bool PERM = false>
+template <typename T, int RULE, bool OPT, bool PERM = false>
 __device__ __forceinline__ void scan_tile(const ScanParams<T> &p, int i0, Key &best, Key &range)
 {
     TileData<T> d;
-    load_tile<T, NT>(p.src, p.tgt, p.cost, p.state, i0, d);
+    load_tile<T>(p.src, p.tgt, p.cost, p.state, i0, d);
     eval_tile<T, RULE, OPT, PERM>(d, p.pi, p.base + i0, p.m_s, p.next_arc, p.block_size, p.rstar, best, range, -1, (T)0, p.orig, p.base);
 }
 
@@ -323,7 +304,7 @@ __device__ __forceinline__ void publish_best(Key best, Slot *slot, uint32_t tag,
     }
 }
 
-template <typename T, int RULE, bool OPT, int UNROLL, bool NT = false, bool PERM = false>
+template <typename T, int RULE, bool OPT, int UNROLL, bool PERM = false>
 __global__ __launch_bounds__(kThreads) void scan_kernel(const ScanParams<T> p)
 {
     static_assert(!PERM || RULE == MCF_RULE_BEST_ELIGIBLE, "the bucketed layout serves Best Eligible only");
@@ -344,7 +325,7 @@ __global__ __launch_bounds__(kThreads) void scan_kernel(const ScanParams<T> p)
     const int step = gridDim.x * kTile * UNROLL;
     for (int i0 = blockIdx.x * kTile * UNROLL + tid * kArcsPerThread; i0 < p.count_padded; i0 += step) {
 #pragma unroll
-        for (int u = 0; u < UNROLL; ++u) scan_tile<T, RULE, OPT, NT, PERM>(p, i0 + u * kTile, best, range);
+        for (int u = 0; u < UNROLL; ++u) scan_tile<T, RULE, OPT, PERM>(p, i0 + u * kTile, best, range);
     }
     if (PERM && best.p != kNone) best.p = (uint32_t)p.orig[(int)best.p - p.base];     // position -> arc id; from here on everything is as without PERM
     publish_best<RULE, false, kThreads, kDual<RULE, OPT>>(best, p.slots + (size_t)blockIdx.x * kSlotStride, p.seq, true, range);

@@ -52,9 +52,7 @@ struct mcf_ns {
     std::vector<int32_t> new_of, orig_of;
     int64_t walked_since_renumber = 0, jumps_since_renumber = 0, renumbers = 0;
     bool allow_renumber = false;
-    bool fused_cycle_search = true;   // find_join + find_leaving in one climb (MCF_NS_FUSED_CYCLE=0: two climbs, as the reference does it)
-    bool use_runs = true;             // ... and hand the big ones over as runs of consecutive ids (MCF_NS_RUNS=0: as nodes)
-    bool seq_walk = true;             // after the first relabelling the big walks go in runs of consecutive ids (MCF_NS_SEQWALK=0: keep the hinted walk)
+    bool use_runs = true;             // after a relabelling, big walks go to the shift grid as runs of consecutive ids (it takes them as they are)
     double renumber_every = 128.0;    // relabel when the walks since the last relabelling covered this many times the node count
     double renumber_ticks = 0, renumber_last_ticks = 0, renumber_last_at = 0, renumber_jump_budget = 0;
     int64_t renumber_at_pivot = 0;
@@ -67,7 +65,7 @@ struct mcf_ns {
     int64_t delta = 0;
     int8_t in_state_before = 0;       // State[in_arc] when the pivot started
     bool out_on_tail_path = false;    // the leaving arc lies on the cycle half that starts at the entering arc's tail
-    bool change = false;              // the pivot changes the basis (find_leaving found a blocking arc)
+    bool change = false;              // the pivot changes the basis (find_join_and_leaving found a blocking arc)
     // what the last pivot changed (the engine calls of a host)
     int n_state = 0;
     int32_t st_arc[2] = {0, 0};
@@ -282,44 +280,6 @@ void start_basis(mcf_ns *s)
     s->all_arcs = extra;
 }
 
-// ---- NS.cs:925-941
-void find_join(mcf_ns *s)
-{
-    int a = s->tail[s->in_arc], b = s->head[s->in_arc];
-    while (a != b) {
-        if (s->sub[a] < s->sub[b]) a = s->par[a];
-        else b = s->par[b];
-    }
-    s->join = a;
-}
-
-// ---- NS.cs:943-1010.  Ties: strict '<' on the first path, '<=' on the second, so the last blocking arc in
-// cycle direction leaves (keeps the basis strongly feasible).
-bool find_leaving(mcf_ns *s)
-{
-    int first, second;
-    if (s->state[s->in_arc] == MCF_STATE_LOWER) { first = s->tail[s->in_arc]; second = s->head[s->in_arc]; }
-    else { first = s->head[s->in_arc]; second = s->tail[s->in_arc]; }
-    s->delta = s->upper[s->in_arc];
-    int side = 0;
-    for (int u = first; u != s->join; u = s->par[u]) {
-        const int e = s->par_arc[u];
-        int64_t room = s->flow[e];
-        if (s->par_dir[u] == kDown) room = s->upper[e] >= kMax ? kInf : s->upper[e] - room;
-        if (room < s->delta) { s->delta = room; s->u_out = u; side = 1; }
-    }
-    for (int u = second; u != s->join; u = s->par[u]) {
-        const int e = s->par_arc[u];
-        int64_t room = s->flow[e];
-        if (s->par_dir[u] == kUp) room = s->upper[e] >= kMax ? kInf : s->upper[e] - room;
-        if (room <= s->delta) { s->delta = room; s->u_out = u; side = 2; }
-    }
-    if (side == 1) { s->u_in = first; s->v_in = second; }
-    else { s->u_in = second; s->v_in = first; }
-    s->out_on_tail_path = side != 0 && ((side == 1) == (first == s->tail[s->in_arc]));
-    return side != 0;
-}
-
 // ---- NS.cs:1030-1039, before the flows are touched: the State[] writes of the pivot.  The leaving arc's new state depends on its
 // flow after ChangeFlow (0 -> LOWER, else UPPER), which is its flow now -/+ delta along its half of the cycle (same sums as push_flow).
 void decide_states(mcf_ns *s, bool change)
@@ -438,11 +398,7 @@ void rehang_subtree(mcf_ns *s)
 constexpr int kWalkAhead = 8, kWalkHintMin = 48;
 constexpr double kJumpNs = 24.0;   // what a step of a walk that leaves the id order costs (a mispredicted branch and a miss; measured 23 - 25 ns)
 constexpr int kRunsMin = 512;      // walks of this many nodes and more hand over runs of consecutive ids (after a relabelling)
-int walk_piece()                   // a big walk hands its nodes to the engine in pieces of this size (2048; mcf_engine_append_potential);
-{
-    static const int v = [] { int x = 2048; if (const char *u = getenv("MCF_NS_WALK_PIECE")) { const int y = atoi(u); if (y >= 64 && y <= (1 << 20)) x = y; } return x; }();
-    return v;
-}
+constexpr int kWalkPiece = 2048;   // a big walk hands its nodes to the engine in pieces of this size (mcf_engine_append_potential);
                                    // 1024 .. 8192 measure alike on config 3, no hand-over at all costs 0.9 us per pivot
 
 // ---- runs of consecutive ids (after a relabelling in thread order the successor of node a is a + 1 almost everywhere).  Inside a run the
@@ -519,7 +475,7 @@ void shift_potentials(mcf_ns *s)
         // the walk only moves the potentials.  The hints need the node kWalkAhead steps back: a ring of that many.
         int64_t *const pi = s->pi.data();
         const int32_t *const nxt = s->nxt.data();
-        if (s->renumbers > 0 && s->seq_walk) {
+        if (s->renumbers > 0) {
             int behind = 0;
             s->jumps_since_renumber += walk_runs(s, first, count, sigma, nullptr, &behind);
             s->moved_as_reload = true;
@@ -559,8 +515,7 @@ void shift_potentials(mcf_ns *s)
         if (lo == hi) { nodes[lo] = a; vals[lo] = (pi[a] += sigma); }
         return;
     }
-    const int piece = walk_piece();
-    if (s->renumbers > 0 && s->seq_walk) {
+    if (s->renumbers > 0) {
         // After a relabelling in thread order the successor of node a is a + 1 almost everywhere: walk in RUNS.  Inside a run the next
         // address does not depend on the loaded successor (the exit test is a predicted branch, not a data dependency), so the loads of
         // consecutive nodes overlap and the hardware prefetcher sees a linear stream; a jump costs one unpredicted miss.
@@ -573,7 +528,7 @@ void shift_potentials(mcf_ns *s)
             s->moved_as_runs = true;
             s->runs_sent = 0;
             while (i < count) {
-                const int stop = s->hand_over && count - (s->moved_sent + piece) >= piece / 2 ? std::max(i, s->moved_sent + piece) : count;
+                const int stop = s->hand_over && count - (s->moved_sent + kWalkPiece) >= kWalkPiece / 2 ? std::max(i, s->moved_sent + kWalkPiece) : count;
                 while (i < stop) {
                     const int start = a;
                     int len = 0;
@@ -604,7 +559,7 @@ void shift_potentials(mcf_ns *s)
         int64_t jumps = 0;
         s->moved_without_values = true;
         while (i < count) {
-            const int stop = s->hand_over && count - (s->moved_sent + piece) >= piece / 2 ? std::max(i, s->moved_sent + piece) : count;
+            const int stop = s->hand_over && count - (s->moved_sent + kWalkPiece) >= kWalkPiece / 2 ? std::max(i, s->moved_sent + kWalkPiece) : count;
             if (stop > i) { jumps += walk_runs(s, a, stop - i, sigma, nodes + i, &a); i = stop; }
             if (i < count) {
                 const double tp = ticks();
@@ -631,7 +586,7 @@ void shift_potentials(mcf_ns *s)
     }
     while (i < count) {
         // up to the next point where a piece may be handed over (a piece's worth of nodes since the last one, at least half a piece still to come)
-        const int stop = s->hand_over && count - (s->moved_sent + piece) >= piece / 2 ? std::max(i, s->moved_sent + piece) : count;
+        const int stop = s->hand_over && count - (s->moved_sent + kWalkPiece) >= kWalkPiece / 2 ? std::max(i, s->moved_sent + kWalkPiece) : count;
         for (; i < stop; ++i) {
             const int h = follow[a];
             __builtin_prefetch(&nxt[h]);
@@ -802,7 +757,7 @@ bool pivot_front(mcf_ns *s, int arc, double *t_pot)
     s->moved_n = 0;
     s->moved_sent = 0;
     s->sigma = 0;
-    const bool change = s->change = s->fused_cycle_search ? find_join_and_leaving(s) : (find_join(s), find_leaving(s));
+    const bool change = s->change = find_join_and_leaving(s);
     if (!change && s->delta == 0) return true;
     decide_states(s, change);
     // the engine hears about the state writes before any piece of the potential list (the pieces may start travelling at once)
@@ -1311,7 +1266,7 @@ int mcf_ns_prepare(mcf_ns *s)
     d.search_arc_num = s->search_arcs;
     d.int_width = pick_int_width(s);
     // 32-bit engines check that every potential fits: the common offset of shift_potentials' smaller-side walk could break that, so they walk the subtree
-    s->allow_smaller_side = d.int_width == 64 && !(getenv("MCF_NS_SMALLER_SIDE") && getenv("MCF_NS_SMALLER_SIDE")[0] == '0');
+    s->allow_smaller_side = d.int_width == 64;
     d.rule = s->rule;
     d.semantics = s->optimized_pivot ? MCF_SEM_OPTIMIZED : MCF_SEM_PLAIN;
     d.vector_width = s->vector_width;
@@ -1333,16 +1288,11 @@ int mcf_ns_prepare(mcf_ns *s)
         // mcf_ns_set_device_share: several independent solvers of one process on one device, each with a grid of that many workgroups
         // (256 / K: every grid gets CUs of its own; an instance whose arcs no longer fit the registers of so few workgroups keeps reduced
         // costs per arc instead, section 3.8 of DESIGN.md)
-        if (s->shard_mode == mcf_ns::kWhole && dr.resident_workgroups == 0) {
-            dr.resident_workgroups = s->resident_workgroups;
-            if (const char *u = getenv("MCF_NS_RESIDENT_WORKGROUPS")) { const int v = atoi(u); if (v >= 8 && v <= 256) dr.resident_workgroups = v; }      // (measurement aid)
-        }
+        if (s->shard_mode == mcf_ns::kWhole && dr.resident_workgroups == 0) dr.resident_workgroups = s->resident_workgroups;
         if (s->shard_mode == mcf_ns::kRccl && dr.resident_workgroups == 0) {
             // the collective's kernel needs room beside the resident grid: leave one CU per XCD alone (mcf_engine_comm_init checks)
             const int cus = mcf_device_compute_units(dr.device);
-            int leave = 8;
-            if (const char *u = getenv("MCF_NS_RCCL_FREE_CUS")) { const int v = atoi(u); if (v >= 0 && v < cus) leave = v; }
-            if (cus >= 64) dr.resident_workgroups = cus - leave;
+            if (cus >= 64) dr.resident_workgroups = cus - 8;
         }
         if (s->shard_mode == mcf_ns::kGroup) {
             dr.device = s->group_devices[r];
@@ -1370,7 +1320,7 @@ int mcf_ns_prepare(mcf_ns *s)
     {
         // every engine of the solver has to agree to reloads (they all follow the same potentials): the largest of their thresholds, or none
         int32_t lo = 0;
-        bool all = !(getenv("MCF_NS_RELOAD") && getenv("MCF_NS_RELOAD")[0] == '0');
+        bool all = true;
         for (int r = 0; r < shards && all; ++r) {
             int32_t v = 0;
             rc = mcf_engine_reload_threshold(r == 0 ? s->engine : s->peers[r - 1], &v);
@@ -1383,7 +1333,8 @@ int mcf_ns_prepare(mcf_ns *s)
     {
         // node relabelling in thread order (renumber_nodes) needs every engine's consent; MCF_NS_RENUMBER=0 switches it off, =x sets the
         // interval in walked nodes per node of the graph
-        bool all = !(getenv("MCF_NS_RENUMBER") && getenv("MCF_NS_RENUMBER")[0] == '0' && getenv("MCF_NS_RENUMBER")[1] == 0);
+        const char *env = getenv("MCF_NS_RENUMBER");
+        bool all = !(env && strcmp(env, "0") == 0);
         for (int r = 0; r < shards && all; ++r) {
             int32_t yes = 0;
             rc = mcf_engine_can_renumber(r == 0 ? s->engine : s->peers[r - 1], &yes);
@@ -1392,14 +1343,12 @@ int mcf_ns_prepare(mcf_ns *s)
         }
         s->allow_renumber = all;
         s->renumber_every = 128.0;
-        if (const char *u = getenv("MCF_NS_RENUMBER")) { const double v = atof(u); if (v > 0) { s->renumber_every = v; s->renumber_forced = true; } }
-        s->seq_walk = !(getenv("MCF_NS_SEQWALK") && getenv("MCF_NS_SEQWALK")[0] == '0');
+        if (env && atof(env) > 0) { s->renumber_every = atof(env); s->renumber_forced = true; }
         // runs of consecutive ids instead of node lists: for the grid that takes them as they are (every other engine would expand them again)
         {
             mcf_engine_stats es;
-            s->use_runs = mcf_engine_get_stats(s->engine, &es) == MCF_OK && es.shift_grid != 0 && s->peers.empty() && !(getenv("MCF_NS_RUNS") && getenv("MCF_NS_RUNS")[0] == '0');
+            s->use_runs = mcf_engine_get_stats(s->engine, &es) == MCF_OK && es.shift_grid != 0 && s->peers.empty();
         }
-        s->fused_cycle_search = !(getenv("MCF_NS_FUSED_CYCLE") && getenv("MCF_NS_FUSED_CYCLE")[0] == '0');
     }
     s->cands.assign((size_t)std::max(1, s->world), mcf_candidate{0, 0xFFFFFFFFu, -1, 0, 0xFFFFFFFFu, -1});
     if (s->shard_mode == mcf_ns::kHost) { rc = mcf_exchange_open(&s->exchange, s->exchange_name.c_str(), s->rank, s->world); if (rc) return rc; }

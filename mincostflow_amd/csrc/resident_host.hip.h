@@ -61,13 +61,9 @@ uint32_t *alloc_bar_vram(int hip_device, size_t bytes)
 constexpr int kBucketNodes = 131072;        // 1 MB of int64 potentials per range: measured best on config 5 (profiles/r01_bucketed_layout_feasibility.txt)
 constexpr int kBucketMinArcs = 2 << 20;
 constexpr int kResidentMaxGrid = 256;       // one workgroup (64..1024 threads) per CU: always co-resident, every CU gathers
-constexpr uint32_t kResidentIdleTicks = 25000000u;   // 0.25 s of s_memrealtime
-uint32_t resident_idle_ticks()                       // MCF_HIP_IDLE_MS: tests shorten it so that grids leave between two searches
-{
-    uint32_t x = kResidentIdleTicks;
-    if (const char *u = getenv("MCF_HIP_IDLE_MS")) { const long long ms = atoll(u); if (ms >= 1 && ms <= 10000) x = (uint32_t)(ms * 100000); }
-    return x;
-}
+constexpr int kPollReplicas = 8;             // copies of the poll unit the host writes (of kMaxReplicas)
+constexpr int kPollSleep = 1;                // s_sleep(1) between two polls of an idle grid
+constexpr uint32_t kResidentIdleTicks = 25000000u;   // 0.25 s of s_memrealtime (MCF_HIP_IDLE_MS: tests shorten it so that grids leave between two searches)
 
 template <typename T, int RULE, bool OPT>
 void launch_resident_r(mcf_engine *e, const ResidentParams<T> &p)
@@ -122,8 +118,8 @@ MailboxParams mailbox_params(const mcf_engine *e, uint32_t start_seq, const int6
 {
     MailboxParams m;
     m.mailbox = e->mailbox; m.exit_word = e->d_exit;
-    m.start_seq = start_seq; m.idle_ticks = resident_idle_ticks();
-    m.max_pi = e->patch_capacity; m.max_st = e->mailbox_max_st; m.poll_replicas = e->poll_replicas; m.poll_sleep = e->poll_sleep;
+    m.start_seq = start_seq; m.idle_ticks = e->idle_ticks;
+    m.max_pi = e->patch_capacity; m.max_st = e->mailbox_max_st; m.poll_replicas = kPollReplicas; m.poll_sleep = kPollSleep;
     m.host_pi = host_pi; m.barrier = e->d_barrier;
     return m;
 }
@@ -254,17 +250,13 @@ void resident_post(mcf_engine *e, uint32_t seq, uint32_t cmd, bool with_patches)
         h.w[kHdrValue0 + 2] = (uint32_t)(v >> 32);
     }
     h.w[kHdrTag] = seq;
-    mailbox_publish(e->mailbox, e->poll_replicas, h, entries > 0 ? &line1 : nullptr, entries > kMailboxPatchesPerLine);
+    mailbox_publish(e->mailbox, kPollReplicas, h, entries > 0 ? &line1 : nullptr, entries > kMailboxPatchesPerLine);
 }
 
 // Long potential lists start travelling while the host is still producing them (mcf_engine_append_potential): the complete entry lines
 // gathered so far go into the mailbox and an apply post (kCmdApply) tells the grid how far the list of the COMING scan request reaches.
 // No answer is expected; the posts are cumulative and the scan request finishes the list (mailbox.hip.h).
-int stream_min_lines()                         // 1920 entries per post at least by default: one piece of the host driver's walk (2048 nodes)
-{
-    static const int v = [] { int x = 384; if (const char *u = getenv("MCF_HIP_STREAM_LINES")) { const int y = atoi(u); if (y >= 16 && y <= 65536) x = y; } return x; }();
-    return v;
-}
+constexpr int kStreamMinLines = 384;           // 1920 entries per post at least: one piece of the host driver's walk (2048 nodes)
 
 void resident_stream(mcf_engine *e)
 {
@@ -274,7 +266,7 @@ void resident_stream(mcf_engine *e)
     if (!e->resident_running || e->rc_mode || e->in_flight != mcf_engine::kNoSearch) return;
     const int n_pi = (int)e->pend_node.size();
     const int complete = (n_pi > 1 ? n_pi - 1 : 0) / kMailboxPatchesPerLine;
-    if (complete - e->stream_lines < stream_min_lines()) return;
+    if (complete - e->stream_lines < kStreamMinLines) return;
     uint32_t next_seq = e->seq + 1;
     if (next_seq == 0) next_seq = 1;
     // the complete entry lines not in place yet (entry line 0 goes out with the first post's header)
@@ -289,7 +281,7 @@ void resident_stream(mcf_engine *e)
     h.w[kHdrApplyLines] = (uint32_t)complete;
     h.w[kHdrApplySub] = e->stream_sub;
     h.w[kHdrTag] = next_seq;
-    mailbox_publish(e->mailbox, e->poll_replicas, h, first_post ? &line1 : nullptr);
+    mailbox_publish(e->mailbox, kPollReplicas, h, first_post ? &line1 : nullptr);
     e->stream_lines = complete;
 }
 
@@ -325,7 +317,7 @@ void resident_harvest(mcf_engine *e)
     if (e->shift_grid) {
         auto u64 = [&](int i) { return (double)(((uint64_t)x[i + 1] << 32) | x[i]); };
         e->st.phase_shift_ns += 10.0 * u64(4); e->st.phase_values_ns += 10.0 * u64(6); e->st.phase_scan_ns += 10.0 * u64(8);
-        if (getenv("MCF_HIP_CAND_DEBUG")) fprintf(stderr, "[grid] shader clock over the launch: %.0f MHz\n", u64(10));
+        if (e->cand_debug) fprintf(stderr, "[grid] shader clock over the launch: %.0f MHz\n", u64(10));
     }
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, e->res_start, e->res_stop) == hipSuccess) e->st.resident_kernel_ns += (double)ms * 1e6;

@@ -1,4 +1,4 @@
-"""Candidate-cache timing on config 3: solves under a few settings of the knobs; MCF_HIP_CAND_DEBUG prints the host-side breakdown."""
+"""Candidate-cache timing on config 3: every search on the device against the cache; MCF_HIP_CAND_DEBUG prints the host-side breakdown."""
 import os, sys, time, subprocess
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -29,9 +29,3 @@ def run(flags, label, env=None):
 
 run(128, "every search on the device")
 run(0, "candidates default", {"MCF_HIP_CAND_DEBUG": 1})
-for piece, lines in ((1024, 192), (2048, 384), (512, 96)):
-    run(0, f"walk piece {piece} stream lines {lines}", {"MCF_NS_WALK_PIECE": piece, "MCF_HIP_STREAM_LINES": lines})
-for nodes in (48, 200):
-    run(0, f"nodes={nodes}", {"MCF_HIP_CAND_NODES": nodes})
-for low in (2, 12):
-    run(0, f"refresh_low={low}", {"MCF_HIP_CAND_REFRESH": low})

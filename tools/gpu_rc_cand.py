@@ -30,9 +30,6 @@ def solve(label, env, pivots):
 for pivots in [int(x) for x in sys.argv[1:]] or [100000]:
     b = solve("candidate", {}, pivots)
     if os.environ.get("RC_CAND_ONLY") != "1":
-        plain = {"MCF_HIP_CANDIDATES": 0}
-        if os.environ.get("RC_PLAINEST") == "1":      # ... and none of the host driver's short cuts either: every walk is the subtree's, every list is named and shifted arc by arc
-            plain.update({"MCF_NS_RELOAD": 0, "MCF_NS_SMALLER_SIDE": 0, "MCF_HIP_RC_RECOMPUTE": 0})
-        a = solve("device   ", plain, pivots)
+        a = solve("device   ", {"MCF_HIP_CANDIDATES": 0}, pivots)
         assert np.array_equal(a, b)
         print(f"entering arcs compared: {len(a)} of each run, identical", flush=True)

@@ -1,12 +1,11 @@
-"""Config 3 with the big walks handed to the register-resident candidate grid in its three ways: node ids (MCF_NS_RUNS=0), runs of consecutive
-ids (default), a reload of the bound potentials inside the grid from N nodes on (MCF_HIP_SHIFT_RELOAD=N).  Best of three solves each."""
+"""Config 3 with the big walks handed to the register-resident candidate grid as runs of consecutive ids, or as a reload of the bound
+potentials inside the grid from N nodes on (MCF_HIP_SHIFT_RELOAD=N, 0 = never).  Best of three solves each."""
 import os, sys
 sys.path.insert(0, ".")
 import mincostflow_amd as M
 g = M.netgen_like(13502460, 100_000, 300_000, 316, 316)
-cases = [("node ids", {"MCF_NS_RUNS": "0", "MCF_HIP_SHIFT_RELOAD": "0"}), ("runs", {"MCF_HIP_SHIFT_RELOAD": "0"}),
-         ("runs, reload from 32768 nodes", {"MCF_HIP_SHIFT_RELOAD": "32768"}), ("runs, reload from 8192 nodes", {"MCF_HIP_SHIFT_RELOAD": "8192"}),
-         ("node ids", {"MCF_NS_RUNS": "0", "MCF_HIP_SHIFT_RELOAD": "0"}), ("runs", {"MCF_HIP_SHIFT_RELOAD": "0"})]
+cases = [("runs", {"MCF_HIP_SHIFT_RELOAD": "0"}), ("runs, reload from 32768 nodes", {"MCF_HIP_SHIFT_RELOAD": "32768"}),
+         ("runs, reload from 8192 nodes", {"MCF_HIP_SHIFT_RELOAD": "8192"}), ("runs", {"MCF_HIP_SHIFT_RELOAD": "0"})]
 for label, env in cases:
     os.environ.update(env)
     best = None
