@@ -18,10 +18,14 @@
  *      Solve() / getters of NS.cs:153-527 and the tree maintenance NS.cs:925-1183) that drives
  *      the engine, so the path can be exercised end to end without a .NET toolchain.  Names and
  *      argument meaning mirror the reference class.  There is NO CPU entering-arc search in this
- *      library: mcf_ns_solve() fails with MCF_ERR_NO_DEVICE when no HIP device is usable.
+ *      library: mcf_ns_solve() fails with MCF_ERR_NO_DEVICE when no HIP device is usable.  (The one
+ *      exception is a test hook, mcf_batch_run_on_host, not a solver.)
  *
  *  (3) mcf_validator_* / mcf_ns_validate -- the reference's SolutionValidator (Validation/SolutionValidator.cs)
  *      as two device reductions; like the search it has no CPU path in this library.
+ *
+ *  (4) mcf_batch_*   -- many small independent instances, each solved entirely on the device by one
+ *      workgroup (no counterpart in the reference, whose callers loop over Solve()).
  *
  * Conventions: every function returns 0 (MCF_OK) or a negative mcf_status; the message is available
  * from mcf_last_error() (thread-local).  Nothing throws across the ABI.  Host arrays are borrowed
@@ -608,6 +612,71 @@ MCF_API int mcf_dimacs_write(const mcf_problem *p, const char *path);
  * increasing cost.  pi may be NULL in both. */
 MCF_API int mcf_solution_write(const char *path, int64_t cost, int32_t arc_count, const int64_t *flow, int32_t node_count, const int64_t *pi);
 MCF_API int mcf_solution_read(const char *path, const mcf_problem *p, int64_t *cost, int32_t *has_cost, int64_t *flow, int64_t *pi, int32_t *has_pi);
+
+/* ------------------------------------------------------------------------------------------------
+ * (4) Batch: many small independent instances, each one solved ENTIRELY on the device
+ * ----------------------------------------------------------------------------------------------
+ * One workgroup (one wave) per instance carries out whole pivots -- search, cycle, flows, tree surgery, potentials -- with no host
+ * involvement between them.  An instance's state lives in a workspace in global memory; instances whose workspace fits
+ * the LDS a workgroup may have run their pivots there.  The host sets every instance up (bounds check, standard form, start basis) and
+ * finishes it (feasibility, lower bounds) with the code mcf_ns uses.  Results are bit-identical to mcf_ns_solve with the same rule and
+ * EnableOptimizedPivot(false): same entering arc at every pivot.
+ * Limits: at most MCF_BATCH_MAX_ARCS arcs and MCF_BATCH_MAX_NODES nodes per instance (bigger problems are what mcf_ns_solve is for),
+ * at most MCF_BATCH_MAX_INSTANCES instances; rules First Eligible, Best Eligible, Block Search in MCF_SEM_PLAIN (Block Search as
+ * `new NetworkSimplex(g).Solve()` runs it: auto-configured, adaptive block size).  mcf_batch_create refuses MCF_SEM_OPTIMIZED, the list
+ * rules and sharding with MCF_ERR_INVALID. */
+#define MCF_BATCH_MAX_ARCS 65536
+#define MCF_BATCH_MAX_NODES 32768
+#define MCF_BATCH_MAX_INSTANCES 65536
+#define MCF_BATCH_SHARDED 1              /* mcf_batch_desc.flags: refused (a batch runs on one device) */
+
+typedef struct mcf_batch mcf_batch;
+typedef struct mcf_batch_desc {
+    int32_t device;               /* HIP device ordinal */
+    int32_t pivot_rule;           /* MCF_RULE_FIRST_ELIGIBLE / _BEST_ELIGIBLE / _BLOCK_SEARCH */
+    int32_t semantics;            /* MCF_SEM_PLAIN (0 = the same) */
+    int32_t reserved;
+    int64_t pivot_limit;          /* per instance, always on: 0 = 64 * (arc_count + 2 * node_count) + 1024.  An instance that reaches it
+                                     reports MCF_NOT_SOLVED; the batch call itself returns MCF_OK */
+    int32_t pivots_per_launch;    /* a launch runs every unfinished instance for at most this many pivots, writes the state back and
+                                     returns; the host relaunches.  0 = default */
+    int32_t trace_capacity;       /* entering arcs recorded per instance, 0 = none */
+    int32_t flags;                /* MCF_BATCH_* */
+} mcf_batch_desc;
+typedef struct mcf_batch_stats {
+    int64_t instances;            /* added */
+    int64_t lds_instances;        /* ran their pivots in LDS */
+    int64_t global_instances;     /* ran them in place on the workspace */
+    int64_t launches;             /* kernel launches of the last mcf_batch_solve */
+    int64_t total_pivots;
+    int64_t workspace_bytes;      /* the slab in device memory */
+    int64_t lds_bytes_max;        /* the largest dynamic LDS a launch asked for */
+    double kernel_ns;             /* host clock round the launches, each ended by a device synchronise */
+    double host_ns;               /* the rest of the call: packing, copies, finishing */
+} mcf_batch_stats;
+
+MCF_API int mcf_batch_create(mcf_batch **out, const mcf_batch_desc *desc);
+MCF_API void mcf_batch_destroy(mcf_batch *b);
+/* Adds one instance (everything is copied); *index = its number in the batch (may be NULL).  Validates like mcf_ns_create +
+ * mcf_ns_set_problem (lower / upper / cost / supply may be NULL: 0 / unbounded / 0 / 0); supply_type per instance. */
+MCF_API int mcf_batch_add(mcf_batch *b, int32_t node_count, int32_t arc_count, const int32_t *source, const int32_t *target,
+                          const int64_t *lower, const int64_t *upper, const int64_t *cost, const int64_t *supply, int32_t supply_type,
+                          int32_t *index);
+/* Solves every instance on the device.  Single-shot like Solve().  MCF_ERR_NO_DEVICE without a GPU. */
+MCF_API int mcf_batch_solve(mcf_batch *b);
+/* TEST HOOK, not a supported solver: the same step functions (csrc/batch_step.hip.h) run on the host with one lane, so that the tree
+ * surgery can be put under a host sanitizer or debugger.  Takes the place of mcf_batch_solve for this batch. */
+MCF_API int mcf_batch_run_on_host(mcf_batch *b);
+/* Per instance, in the caller's numbering and the C# sign convention -- what mcf_ns_status / mcf_ns_get_* return.  MCF_ERR_STATE before
+ * a solve; total cost, flows and potentials also unless the instance is optimal (NS.cs:418-421). */
+MCF_API int mcf_batch_get_status(mcf_batch *b, int32_t index, int32_t *status);
+MCF_API int mcf_batch_get_total_cost(mcf_batch *b, int32_t index, int64_t *cost);
+MCF_API int mcf_batch_get_flows(mcf_batch *b, int32_t index, int64_t *out);          /* [arc_count] */
+MCF_API int mcf_batch_get_potentials(mcf_batch *b, int32_t index, int64_t *out);     /* [node_count] */
+MCF_API int mcf_batch_get_pivots(mcf_batch *b, int32_t index, int64_t *pivots);
+/* copies min(capacity, recorded) entering arcs, *length = recorded (out may be NULL with capacity 0) */
+MCF_API int mcf_batch_get_trace(mcf_batch *b, int32_t index, int32_t *out, int64_t capacity, int64_t *length);
+MCF_API int mcf_batch_get_stats(mcf_batch *b, mcf_batch_stats *out);
 
 #ifdef __cplusplus
 }

@@ -118,6 +118,24 @@ class Validation(C.Structure):
                 "kernel_us": float(self.kernel_us), "algorithmic_bytes": int(self.algorithmic_bytes)}
 
 
+class BatchDesc(C.Structure):
+    """mcf_batch_desc"""
+    _fields_ = [("device", C.c_int32), ("pivot_rule", C.c_int32), ("semantics", C.c_int32), ("reserved", C.c_int32), ("pivot_limit", C.c_int64),
+                ("pivots_per_launch", C.c_int32), ("trace_capacity", C.c_int32), ("flags", C.c_int32)]
+
+
+class BatchStats(C.Structure):
+    """mcf_batch_stats"""
+    _fields_ = [("instances", C.c_int64), ("lds_instances", C.c_int64), ("global_instances", C.c_int64), ("launches", C.c_int64),
+                ("total_pivots", C.c_int64), ("workspace_bytes", C.c_int64), ("lds_bytes_max", C.c_int64), ("kernel_ns", C.c_double), ("host_ns", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+BATCH_MAX_ARCS, BATCH_MAX_NODES, BATCH_MAX_INSTANCES, BATCH_SHARDED = 65536, 32768, 65536, 1
+
+
 class ProblemStruct(C.Structure):
     _fields_ = [("node_count", C.c_int32), ("arc_count", C.c_int32), ("source", C.POINTER(C.c_int32)),
                 ("target", C.POINTER(C.c_int32)), ("lower", C.POINTER(C.c_int64)), ("upper", C.POINTER(C.c_int64)),
@@ -242,6 +260,18 @@ SIGNATURES = {
     "mcf_validator_upload": (C.c_int, [C.c_void_p] + [C.c_void_p] * 8),
     "mcf_validator_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _P(Validation)]),
     "mcf_ns_validate": (C.c_int, [C.c_void_p, _P(Validation)]),
+    "mcf_batch_create": (C.c_int, [_P(C.c_void_p), _P(BatchDesc)]),
+    "mcf_batch_destroy": (None, [C.c_void_p]),
+    "mcf_batch_add": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(C.c_int32)]),
+    "mcf_batch_solve": (C.c_int, [C.c_void_p]),
+    "mcf_batch_run_on_host": (C.c_int, [C.c_void_p]),
+    "mcf_batch_get_status": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int32)]),
+    "mcf_batch_get_total_cost": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int64)]),
+    "mcf_batch_get_flows": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "mcf_batch_get_potentials": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "mcf_batch_get_pivots": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int64)]),
+    "mcf_batch_get_trace": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, _P(C.c_int64)]),
+    "mcf_batch_get_stats": (C.c_int, [C.c_void_p, _P(BatchStats)]),
     "mcf_problem_free": (None, [_P(ProblemStruct)]),
     "mcf_gen_netgen_like": (C.c_int, [_P(ProblemStruct), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64]),

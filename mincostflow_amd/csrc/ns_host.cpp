@@ -17,35 +17,23 @@
 #include <x86intrin.h>
 
 #include "common.h"
+#include "ns_core.h"
 
 namespace {
 
 inline double ticks() { return (double)__rdtsc(); }     // invariant TSC; scaled to ns once per solve
 
-constexpr int8_t kUp = 1, kDown = -1;   // SpanningTree.cs:67-71 DIR_UP / DIR_DOWN
-constexpr int64_t kMax = INT64_MAX;     // NS.cs:126
-constexpr int64_t kInf = INT64_MAX / 2; // NS.cs:127
+using mcf::kUp; using mcf::kDown; using mcf::kMax; using mcf::kInf;     // ns_core.h
 
 }  // namespace
 
-struct mcf_ns {
-    int n = 0, m = 0, root = 0;
-    int search_arcs = 0, all_arcs = 0;
-    int supply_type = MCF_SUPPLY_GEQ, rule = MCF_RULE_BLOCK_SEARCH;   // NS.cs:38, :77
+struct mcf_ns : mcf::NsCore {                                         // the problem, the flows and the tree: ns_core.h
+    int rule = MCF_RULE_BLOCK_SEARCH;                                  // NS.cs:77
     bool optimized_pivot = false;                                      // NS.cs:34
     int vector_width = MCF_VECTOR_DEFAULT;                             // Vector<long>.Count of the reference's host (BSPO.cs:74): mcf_ns_set_vector_width
     int device = 0, int_width = 0, block_size = 0, engine_flags = 0;
     bool auto_config = true;                                           // NS.cs:90
     mcf_block_config config{};                                         // _optimizationConfig, NS.cs:89
-    // arcs: m + 2n entries (NS.cs:130)
-    mcf::hvec<int32_t> tail, head;
-    mcf::hvec<int64_t> lower, upper, cost, flow, orig_lower;
-    mcf::hvec<int8_t> state;
-    // nodes: n + 1 entries, the last one is the artificial root (NS.cs:137,144)
-    mcf::hvec<int64_t> supply, pi;
-    mcf::hvec<int32_t> par, par_arc, nxt, prv, sub, fin;   // Parent, Pred, Thread, RevThread, SuccNum, LastSucc
-    mcf::hvec<int8_t> par_dir;
-    std::vector<int32_t> scratch;
     // Node ids in use inside a solve may differ from the caller's: renumber_nodes() relabels the nodes in thread (preorder) order so that the
     // subtree walks, the cycle searches and the engines' per-node tables run through memory front to back instead of chasing pointers.
     // new_of[caller's id] = id in use, orig_of = the inverse; empty = identity.  Arc ids never change, so no pivot rule can tell.
@@ -57,9 +45,7 @@ struct mcf_ns {
     double renumber_ticks = 0, renumber_last_ticks = 0, renumber_last_at = 0, renumber_jump_budget = 0;
     int64_t renumber_at_pivot = 0;
     bool renumber_forced = false;     // MCF_NS_RENUMBER set: relabel at that interval whatever it costs (tests)
-    int64_t sum_supply = 0, art_cost = 0;
-    int status = MCF_NOT_SOLVED;
-    bool begun = false, transformed = false, prepared = false, solved = false;
+    bool begun = false, prepared = false, solved = false;
     // the pivot being carried out
     int in_arc = -1, join = -1, u_in = -1, v_in = -1, u_out = -1, v_out = -1;
     int64_t delta = 0;
@@ -211,14 +197,14 @@ void engines_destroy(mcf_ns *s)
 }
 
 // ---- NS.cs:624-669
-bool bounds_ok(const mcf_ns *s)
+bool bounds_ok(const mcf::NsCore *s)
 {
     for (int e = 0; e < s->m; ++e)
         if (s->upper[e] < s->lower[e]) return false;
     return true;
 }
 
-void to_standard_form(mcf_ns *s)
+void to_standard_form(mcf::NsCore *s)
 {
     for (int e = 0; e < s->m; ++e) {
         const int64_t lo = s->lower[e];
@@ -238,7 +224,7 @@ void to_standard_form(mcf_ns *s)
 
 // ---- NS.cs:671-845: star basis on the artificial root.  GEQ: nodes with supply <= 0 hang on a zero-cost
 // root->v arc, the others on an ART_COST v->root arc and get a zero-cost root->v arc at its lower bound; LEQ mirrored.
-void start_basis(mcf_ns *s)
+void start_basis(mcf::NsCore *s)
 {
     const int n = s->n, m = s->m, root = s->root = n;
     s->par[root] = -1; s->par_arc[root] = -1; s->nxt[root] = 0; s->prv[0] = root;
@@ -930,14 +916,25 @@ int begin(mcf_ns *s, int32_t *status)
     s->trace_len = 0;
     if (s->begun) return mcf::fail(MCF_ERR_STATE, "Solve() is single-shot: the reference mutates bounds and supplies in place (NS.cs:649, D11); create a new solver");
     s->begun = true;
-    if (!bounds_ok(s)) { s->status = MCF_INFEASIBLE; if (status) *status = s->status; return MCF_OK; }   // NS.cs:227-231
-    to_standard_form(s);
-    start_basis(s);
+    mcf::core_begin(s);                                  // Infeasible on an inverted bound pair (NS.cs:227-231), else the start basis
     if (status) *status = s->status;
     return MCF_OK;
 }
 
-void finish(mcf_ns *s)
+}  // namespace
+
+namespace mcf {
+
+bool core_begin(NsCore *s)
+{
+    s->status = MCF_NOT_SOLVED;
+    if (!bounds_ok(s)) { s->status = MCF_INFEASIBLE; return false; }   // NS.cs:227-231
+    to_standard_form(s);
+    start_basis(s);
+    return true;
+}
+
+void core_finish(NsCore *s)
 {
     // NS.cs:1272-1283 with _allArcNum overwritten by _searchArcNum at NS.cs:689 (difference D9): only the n root links
     for (int e = s->m; e < s->search_arcs; ++e)
@@ -951,6 +948,48 @@ void finish(mcf_ns *s)
         s->supply[s->head[e]] -= lo;
     }
 }
+
+int64_t core_total_cost(const NsCore *s)
+{
+    int64_t total = 0;
+    for (int e = 0; e < s->m; ++e) total += s->flow[e] * s->cost[e];   // NS.cs:459-464
+    return total;
+}
+
+int core_create(NsCore *s, int32_t node_count, int32_t arc_count, const int32_t *source, const int32_t *target)
+{
+    if (node_count < 0 || arc_count < 0 || (arc_count && (!source || !target))) return fail(MCF_ERR_INVALID, "graph must not be null (NS.cs:121)");
+    if ((int64_t)arc_count + 2 * (int64_t)node_count > INT32_MAX - 4096) return fail(MCF_ERR_INVALID, "graph too large for 32-bit arc ids");
+    for (int e = 0; e < arc_count; ++e)
+        if ((unsigned)source[e] >= (unsigned)node_count || (unsigned)target[e] >= (unsigned)node_count)
+            return fail(MCF_ERR_INVALID, "arc %d: end point out of range", e);
+    s->n = node_count; s->m = arc_count;
+    const size_t A = (size_t)arc_count + 2 * (size_t)node_count, N = (size_t)node_count + 1;
+    s->tail.assign(A, 0); s->head.assign(A, 0);
+    std::copy(source, source + arc_count, s->tail.begin());
+    std::copy(target, target + arc_count, s->head.begin());
+    s->lower.assign(A, 0); s->upper.assign(A, kInf); s->cost.assign(A, 0); s->flow.assign(A, 0);   // NS.cs:614-617
+    s->orig_lower.assign(arc_count, 0);
+    s->state.assign(A, 0);
+    s->supply.assign(N, 0); s->pi.assign(N, 0);
+    s->par.assign(N, -1); s->par_arc.assign(N, -1); s->nxt.assign(N, 0); s->prv.assign(N, 0);
+    s->sub.assign(N, 0); s->fin.assign(N, 0); s->par_dir.assign(N, 0); s->scratch.assign(N + 1, 0);
+    return MCF_OK;
+}
+
+void core_set_problem(NsCore *s, const int64_t *lower, const int64_t *upper, const int64_t *cost, const int64_t *supply)
+{
+    for (int e = 0; e < s->m; ++e) {
+        if (lower) { s->lower[e] = lower[e]; s->orig_lower[e] = lower[e]; }
+        if (upper) s->upper[e] = upper[e] == MCF_INF_CAP ? kInf : upper[e];
+        if (cost) s->cost[e] = cost[e];
+    }
+    if (supply) std::copy(supply, supply + s->n, s->supply.begin());
+}
+
+}  // namespace mcf
+
+namespace {
 
 int pick_int_width(const mcf_ns *s)
 {
@@ -969,25 +1008,12 @@ int mcf_ns_create(mcf_ns **out, int32_t node_count, int32_t arc_count, const int
 {
     if (!out) return mcf::fail(MCF_ERR_INVALID, "mcf_ns_create: null argument");
     *out = nullptr;
-    if (node_count < 0 || arc_count < 0 || (arc_count && (!source || !target))) return mcf::fail(MCF_ERR_INVALID, "graph must not be null (NS.cs:121)");
-    if ((int64_t)arc_count + 2 * (int64_t)node_count > INT32_MAX - 4096) return mcf::fail(MCF_ERR_INVALID, "graph too large for 32-bit arc ids");
-    for (int e = 0; e < arc_count; ++e)
-        if ((unsigned)source[e] >= (unsigned)node_count || (unsigned)target[e] >= (unsigned)node_count)
-            return mcf::fail(MCF_ERR_INVALID, "arc %d: end point out of range", e);
     mcf_ns *s = new mcf_ns();
-    s->n = node_count; s->m = arc_count;
+    if (const int rc = mcf::core_create(s, node_count, arc_count, source, target)) { delete s; return rc; }
     mcf_block_config_default(&s->config);
-    const size_t A = (size_t)arc_count + 2 * (size_t)node_count, N = (size_t)node_count + 1;
-    s->tail.assign(A, 0); s->head.assign(A, 0);
-    std::copy(source, source + arc_count, s->tail.begin());
-    std::copy(target, target + arc_count, s->head.begin());
-    s->lower.assign(A, 0); s->upper.assign(A, kInf); s->cost.assign(A, 0); s->flow.assign(A, 0);   // NS.cs:614-617
-    s->orig_lower.assign(arc_count, 0);
-    s->state.assign(A, 0);
-    s->supply.assign(N, 0); s->pi.assign(N, 0);
-    s->par.assign(N, -1); s->par_arc.assign(N, -1); s->nxt.assign(N, 0); s->prv.assign(N, 0); s->moved.assign(N, 0); s->moved_val.assign(N, 0); s->follow.assign(N, 0);
+    const size_t N = (size_t)node_count + 1;
+    s->moved.assign(N, 0); s->moved_val.assign(N, 0); s->follow.assign(N, 0);
     s->run_first.assign(N, 0); s->run_len.assign(N, 0);
-    s->sub.assign(N, 0); s->fin.assign(N, 0); s->par_dir.assign(N, 0); s->scratch.assign(N + 1, 0);
     *out = s;
     return MCF_OK;
 }
@@ -1022,12 +1048,7 @@ int mcf_ns_set_node_supply(mcf_ns *s, int32_t node, int64_t supply)
 int mcf_ns_set_problem(mcf_ns *s, const int64_t *lower, const int64_t *upper, const int64_t *cost, const int64_t *supply)
 {
     if (!s) return mcf::fail(MCF_ERR_INVALID, "null solver");
-    for (int e = 0; e < s->m; ++e) {
-        if (lower) { s->lower[e] = lower[e]; s->orig_lower[e] = lower[e]; }
-        if (upper) s->upper[e] = upper[e] == MCF_INF_CAP ? kInf : upper[e];
-        if (cost) s->cost[e] = cost[e];
-    }
-    if (supply) std::copy(supply, supply + s->n, s->supply.begin());
+    mcf::core_set_problem(s, lower, upper, cost, supply);
     return MCF_OK;
 }
 int mcf_ns_set_supply_type(mcf_ns *s, int32_t type)
@@ -1200,7 +1221,7 @@ int mcf_ns_finish(mcf_ns *s, int32_t *status)
 {
     if (!s) return mcf::fail(MCF_ERR_INVALID, "null solver");
     if (!s->transformed) return mcf::fail(MCF_ERR_STATE, "mcf_ns_begin has not been called");
-    if (s->status != MCF_UNBOUNDED) finish(s);
+    if (s->status != MCF_UNBOUNDED) mcf::core_finish(s);
     if (status) *status = s->status;
     return MCF_OK;
 }
@@ -1484,7 +1505,7 @@ int mcf_ns_solve(mcf_ns *s, int32_t *status)
     engines_park(s);                 // a resident scan grid must not outlive Solve()
     s->trace_len = std::min(it, s->trace_cap);
     s->metrics.iterations = it;
-    if (!rc && s->status == MCF_NOT_SOLVED && !limited) finish(s);
+    if (!rc && s->status == MCF_NOT_SOLVED && !limited) mcf::core_finish(s);
     // the phase buckets were counted in time-stamp-counter ticks (a clock call per phase costs 20+ ns, seven of them per pivot): scale them
     const double ns_per_tick = (mcf::now_ns() - t_start) / std::max(1.0, ticks() - tick_start);
     s->metrics.pivot_search_us = t_search * ns_per_tick / 1e3;
@@ -1557,9 +1578,7 @@ int mcf_ns_get_total_cost(mcf_ns *s, int64_t *cost)
 {
     if (!s || !cost) return mcf::fail(MCF_ERR_INVALID, "null argument");
     if (int rc = need_optimal(s)) return rc;
-    int64_t total = 0;
-    for (int e = 0; e < s->m; ++e) total += s->flow[e] * s->cost[e];   // NS.cs:459-464
-    *cost = total;
+    *cost = mcf::core_total_cost(s);
     return MCF_OK;
 }
 int mcf_ns_get_flows(mcf_ns *s, int64_t *out)

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.h"
+#include "batch_step.hip.h"
 
 namespace mcf {
 
@@ -129,25 +130,7 @@ int mcf_block_initial_size(const mcf_block_config *c, int32_t m_s, int32_t graph
 int mcf_block_adapt(const mcf_block_config *c, int32_t dynamic_min, int64_t arcs_checked, int32_t *block_size, int32_t counters[2])
 {
     if (!c || !block_size || !counters) return mcf::fail(MCF_ERR_INVALID, "mcf_block_adapt: bad arguments");
-    if (!(c->flags & MCF_OPT_ADAPTIVE_BLOCK_SIZE)) return MCF_OK;
-    const double hit_rate = arcs_checked > 0 ? 1.0 / (double)arcs_checked : 0;
-    if (hit_rate < c->low_hit_rate_threshold) {
-        counters[1] = 0;
-        if (++counters[0] >= c->consecutive_hits_before_adapt) {
-            const int smaller = (int)(*block_size * c->block_size_shrink_factor);
-            *block_size = std::max(dynamic_min, smaller);
-            counters[0] = 0;
-        }
-    } else if (hit_rate > c->high_hit_rate_threshold) {
-        counters[0] = 0;
-        if (++counters[1] >= c->consecutive_hits_before_adapt) {
-            const int larger = (int)(*block_size * c->block_size_growth_factor);
-            *block_size = std::min(c->max_block_size, larger);
-            counters[1] = 0;
-        }
-    } else {
-        counters[0] = counters[1] = 0;
-    }
+    mcf::block_adapt_step(c, dynamic_min, arcs_checked, block_size, counters);      // batch_step.hip.h: one statement for host and device
     return MCF_OK;
 }
 

@@ -314,6 +314,81 @@ class NetworkSimplex:
                     nodes=nd, sigma=sigma.value)
 
 
+class BatchSolver:
+    """Many small independent instances, each solved entirely on the device by one workgroup (mcf_batch_*).
+
+    add() copies an instance and returns its index; solve() runs the whole batch on the MI355X; the getters answer per index what
+    NetworkSimplex answers for a single solve with the same rule and enable_optimized_pivot(False).  run_on_host() is a test hook
+    (the same pivot code with one lane on the CPU), not a supported solver."""
+
+    def __init__(self, rule=PivotRule.BlockSearch, pivot_limit=0, record_trace=0, device=0, pivots_per_launch=0, semantics=L.SEM_PLAIN, flags=0):
+        self._h = C.c_void_p()
+        self._problems = []           # (node_count, arc_count) per index
+        d = L.BatchDesc(int(device), int(rule), int(semantics), 0, int(pivot_limit), int(pivots_per_launch), int(record_trace), int(flags))
+        L.check(L.lib().mcf_batch_create(C.byref(self._h), C.byref(d)))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            L.lib().mcf_batch_destroy(h)
+            self._h = None
+
+    def __len__(self):
+        return len(self._problems)
+
+    def add(self, problem, supply_type=SupplyType.Geq) -> int:
+        """problem: anything with the fields of Problem (node_count / arc_count / source / ...) or of the oracle's (n / m / src / tgt / ...)."""
+        g = lambda a, b: getattr(problem, a) if hasattr(problem, a) else getattr(problem, b)
+        n, m = int(g("node_count", "n")), int(g("arc_count", "m"))
+        src, tgt = _i32(g("source", "src")), _i32(g("target", "tgt"))
+        lo, up, co, su = _i64(problem.lower), _i64(problem.upper), _i64(problem.cost), _i64(problem.supply)
+        if src.shape != (m,) or tgt.shape != (m,) or lo.shape != (m,) or up.shape != (m,) or co.shape != (m,) or su.shape != (n,):
+            raise ValueError("array lengths do not match node_count / arc_count")
+        idx = C.c_int32(-1)
+        L.check(L.lib().mcf_batch_add(self._h, n, m, src.ctypes.data, tgt.ctypes.data, lo.ctypes.data, up.ctypes.data, co.ctypes.data,
+                                      su.ctypes.data, int(supply_type), C.byref(idx)))
+        self._problems.append((n, m))
+        return idx.value
+
+    def solve(self):
+        L.check(L.lib().mcf_batch_solve(self._h)); return self
+
+    def run_on_host(self):
+        L.check(L.lib().mcf_batch_run_on_host(self._h)); return self
+
+    def status(self, i: int) -> int:
+        v = C.c_int32(); L.check(L.lib().mcf_batch_get_status(self._h, i, C.byref(v))); return v.value
+
+    def total_cost(self, i: int) -> int:
+        v = C.c_int64(); L.check(L.lib().mcf_batch_get_total_cost(self._h, i, C.byref(v))); return v.value
+
+    def _dims(self, i: int):
+        if not 0 <= i < len(self._problems):
+            L.check(L.lib().mcf_batch_get_status(self._h, i, C.byref(C.c_int32())))      # raises the library's own error
+        return self._problems[i]
+
+    def flows(self, i: int) -> np.ndarray:
+        m = self._dims(i)[1]
+        out = np.empty(max(m, 1), np.int64); L.check(L.lib().mcf_batch_get_flows(self._h, i, out.ctypes.data)); return out[:m]
+
+    def potentials(self, i: int) -> np.ndarray:
+        n = self._dims(i)[0]
+        out = np.empty(max(n, 1), np.int64); L.check(L.lib().mcf_batch_get_potentials(self._h, i, out.ctypes.data)); return out[:n]
+
+    def pivots(self, i: int) -> int:
+        v = C.c_int64(); L.check(L.lib().mcf_batch_get_pivots(self._h, i, C.byref(v))); return v.value
+
+    def trace(self, i: int) -> np.ndarray:
+        n = C.c_int64()
+        L.check(L.lib().mcf_batch_get_trace(self._h, i, None, 0, C.byref(n)))
+        out = np.empty(max(n.value, 1), np.int32)
+        L.check(L.lib().mcf_batch_get_trace(self._h, i, out.ctypes.data, n.value, C.byref(n)))
+        return out[: n.value]
+
+    def stats(self) -> dict:
+        st = L.BatchStats(); L.check(L.lib().mcf_batch_get_stats(self._h, C.byref(st))); return st.as_dict()
+
+
 def block_config(**kw) -> "L.BlockConfig":
     """new OptimizationConfig { ... } (OptimizationTypes.cs:24-38): the defaults, with the given fields replaced."""
     c = L.BlockConfig()
