@@ -70,7 +70,6 @@ __host__ __device__ inline void bind(mcf::BatchWork &w, unsigned char *base, con
     w.par = (int32_t *)(base + l.par); w.par_arc = (int32_t *)(base + l.par_arc); w.nxt = (int32_t *)(base + l.nxt);
     w.prv = (int32_t *)(base + l.prv); w.sub = (int32_t *)(base + l.sub); w.fin = (int32_t *)(base + l.fin);
     w.scratch = (int32_t *)(base + l.scratch); w.state = (int8_t *)(base + l.state); w.par_dir = (int8_t *)(base + l.par_dir);
-    w.supply = nullptr;
 }
 
 // what a launch needs to know of an instance and what it leaves behind; one per instance, in device memory
@@ -312,10 +311,8 @@ int mcf_batch_run_on_host(mcf_batch *b)
             mcf::NsCore &c = in->core;
             mcf::BatchWork w{};
             load_slot(w, in->slot, in->trace.data());
-            w.tail = c.tail.data(); w.head = c.head.data(); w.cost = c.cost.data(); w.upper = c.upper.data();
-            w.flow = c.flow.data(); w.state = c.state.data(); w.pi = c.pi.data(); w.supply = c.supply.data();
-            w.par = c.par.data(); w.par_arc = c.par_arc.data(); w.nxt = c.nxt.data(); w.prv = c.prv.data();
-            w.sub = c.sub.data(); w.fin = c.fin.data(); w.par_dir = c.par_dir.data(); w.scratch = c.scratch.data();
+            static_cast<mcf::TreeView &>(w) = c.tree();
+            w.cost = c.cost.data(); w.state = c.state.data(); w.pi = c.pi.data();
             mcf::batch_run(w, 0, 1, INT64_MAX);
             store_slot(in->slot, w);
             total += in->slot.pivots;

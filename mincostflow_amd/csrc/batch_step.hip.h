@@ -1,6 +1,6 @@
-// batch_step.hip.h -- ONE network-simplex pivot, stated once for host and device (the batch solver, batch.hip).
+// batch_step.hip.h -- ONE network-simplex pivot of the batch solver (batch.hip), stated once for host and device.
 //
-// The functions work on a BatchWork: plain pointers to the arrays mcf_ns keeps (ns_core.h) plus the pivot rule's state.  They never learn
+// The functions work on a BatchWork: the TreeView of tree_pivot.h, the other arrays mcf_ns keeps (ns_core.h) and the pivot rule's state.  They never learn
 // where the pointers point: the kernel binds them to LDS or to the instance's workspace in global memory, mcf_batch_run_on_host binds
 // them to host vectors.  Two halves per pivot:
 //   * the entering-arc search is written over (lane, lanes): 64 lanes of one wave share it on the device, one "lane" runs it on the host.
@@ -9,21 +9,15 @@
 //     NS.cs:1292-1668 (find_first / find_best / find_block_plain of oracle/ns_oracle.c), ties broken as there: the first arc in scan
 //     order among equals.
 //   * join node, leaving arc, State[] writes, potentials of the subtree, flows round the cycle and the tree surgery are sequential:
-//     batch_pivot restates find_join_and_leaving, decide_states, the plain walk of shift_potentials, push_flow and rehang_subtree of
-//     ns_host.cpp.  Lane 0 runs it while the others wait.
+//     batch_pivot calls the steps of tree_pivot.h (the ones mcf_ns calls) in the reference's order, with the plain walk over the subtree's
+//     potentials between them.  Lane 0 runs it while the others wait.
 // block_adapt_step is the arithmetic of mcf_block_adapt (NS.cs:1400-1438); util.cpp calls it, so there is one statement of it.
 #pragma once
 
 #include <stdint.h>
 
 #include "../../include/mcf_hip.h"
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define MCF_HD __host__ __device__
-#else
-#define MCF_HD
-#endif
+#include "tree_pivot.h"
 
 namespace mcf {
 
@@ -36,18 +30,12 @@ enum BatchRun : int32_t {
     kBatchMaxIter = 4      // the reference's own iteration guard (NS.cs:280, :311-317): Infeasible
 };
 
-struct BatchWork {
+struct BatchWork : TreeView {
     // arcs [0, all_arcs); the rules scan [0, search_arcs)
-    const int32_t *tail, *head;
-    const int64_t *cost, *upper;
-    int64_t *flow;
+    const int64_t *cost;
     int8_t *state;
     // nodes [0, n], n = the artificial root
     int64_t *pi;
-    const int64_t *supply;             // host only: no pivot reads it, so a workspace does not carry it
-    int32_t *par, *par_arc, *nxt, *prv, *sub, *fin;
-    int8_t *par_dir;
-    int32_t *scratch;                  // n + 2 entries
     int32_t *trace;                    // entering arc of every pivot, up to trace_cap (may be null)
     int32_t n, search_arcs, rule;
     // the rule's state
@@ -202,133 +190,25 @@ MCF_HD inline bool batch_find_entering(BatchWork &w, int lane, int lanes, int32_
 // ---- the sequential half.  Returns true when the problem is found unbounded (NS.cs:321-325: no blocking arc and delta == 0).
 MCF_HD inline bool batch_pivot(BatchWork &w, int in_arc)
 {
-    constexpr int8_t kUp = 1, kDown = -1;
-    constexpr int64_t kMax = INT64_MAX, kInf = INT64_MAX / 2;
-    int32_t *const par = w.par, *const parc = w.par_arc, *const nxt = w.nxt, *const prv = w.prv, *const sub = w.sub, *const fin = w.fin;
-    int8_t *const pdir = w.par_dir;
-    int64_t *const flow = w.flow;
-    const int64_t *const upper = w.upper;
-
-    // -- find_join_and_leaving (NS.cs:925-1010 in one climb; the tie rules are explained in ns_host.cpp)
-    const int8_t in_state = w.state[in_arc];
-    const bool lower = in_state == MCF_STATE_LOWER;
-    const int tail = w.tail[in_arc], head = w.head[in_arc];
-    int a = tail, b = head;
-    int64_t d_first = kMax, d_second = kMax;
-    int u_first = -1, u_second = -1;
-    const int8_t gain_a = lower ? kDown : kUp, gain_b = lower ? kUp : kDown;
-    while (a != b) {
-        if (sub[a] < sub[b]) {
-            const int e = parc[a];
-            int64_t room = flow[e];
-            if (pdir[a] == gain_a) room = upper[e] >= kMax ? kInf : upper[e] - room;
-            if (lower) { if (room < d_first) { d_first = room; u_first = a; } }
-            else { if (room <= d_second) { d_second = room; u_second = a; } }
-            a = par[a];
-        } else {
-            const int e = parc[b];
-            int64_t room = flow[e];
-            if (pdir[b] == gain_b) room = upper[e] >= kMax ? kInf : upper[e] - room;
-            if (lower) { if (room <= d_second) { d_second = room; u_second = b; } }
-            else { if (room < d_first) { d_first = room; u_first = b; } }
-            b = par[b];
-        }
-    }
-    const int join = a;
-    const int first = lower ? tail : head, second = lower ? head : tail;
-    int64_t delta = upper[in_arc];
-    int side = 0, u_out = -1;
-    if (u_first >= 0 && d_first < delta) { delta = d_first; u_out = u_first; side = 1; }
-    if (u_second >= 0 && d_second <= delta) { delta = d_second; u_out = u_second; side = 2; }
-    const int u_in = side == 1 ? first : second, v_in = side == 1 ? second : first;
-    const bool out_on_tail_path = side != 0 && ((side == 1) == (first == tail));
-    const bool change = side != 0;
-    if (!change && delta == 0) return true;
-
-    // -- decide_states (NS.cs:1030-1039), from the flows as they are
-    if (change) {
-        const int out = parc[u_out];
-        const int64_t val = in_state * delta;
-        const int64_t after = out_on_tail_path ? flow[out] - pdir[u_out] * val : flow[out] + pdir[u_out] * val;
+    const Pivot p = find_cycle(w, in_arc, w.state[in_arc]);
+    if (!p.change && p.delta == 0) return true;
+    // NS.cs:1030-1039, from the flows as they are
+    if (p.change) {
+        const int out = w.par_arc[p.u_out];
+        const int8_t out_state = leaving_state(w, p);
         w.state[in_arc] = MCF_STATE_TREE;
-        w.state[out] = after == 0 ? MCF_STATE_LOWER : MCF_STATE_UPPER;
+        w.state[out] = out_state;
     } else {
-        w.state[in_arc] = (int8_t)-in_state;
+        w.state[in_arc] = (int8_t)-p.in_state;
     }
-    const int8_t dir_in = u_in == tail ? kUp : kDown;
-
-    // -- shift_potentials, the plain walk (NS.cs:1185-1209): the subtree of u_out as it hangs now
-    if (change) {
-        const int64_t sigma = w.pi[v_in] - w.pi[u_in] - dir_in * w.cost[in_arc];
-        int u = u_out;
-        for (int i = sub[u_out]; i > 0; --i) { w.pi[u] += sigma; u = nxt[u]; }
+    // the plain walk (NS.cs:1185-1209): the subtree of u_out as it hangs now
+    if (p.change) {
+        const int64_t sigma = pivot_sigma(p, w.pi, w.cost);
+        int u = p.u_out;
+        for (int i = w.sub[p.u_out]; i > 0; --i) { w.pi[u] += sigma; u = w.nxt[u]; }
     }
-
-    // -- push_flow (NS.cs:1012-1029)
-    if (delta > 0) {
-        const int64_t val = in_state * delta;
-        flow[in_arc] += val;
-        for (int u = tail; u != join; u = par[u]) flow[parc[u]] -= pdir[u] * val;
-        for (int u = head; u != join; u = par[u]) flow[parc[u]] += pdir[u] * val;
-    }
-    if (!change) return false;
-
-    // -- rehang_subtree (NS.cs:1042-1183)
-    const int before_out = prv[u_out], size_out = sub[u_out], fin_out_old = fin[u_out];
-    const int v_out = par[u_out];
-    if (u_in == u_out) {
-        par[u_in] = v_in; parc[u_in] = in_arc; pdir[u_in] = dir_in;
-        if (nxt[v_in] != u_out) {
-            int after = nxt[fin_out_old];
-            nxt[before_out] = after; prv[after] = before_out;
-            after = nxt[v_in];
-            nxt[v_in] = u_out; prv[u_out] = v_in;
-            nxt[fin_out_old] = after; prv[after] = fin_out_old;
-        }
-    } else {
-        const int resume = before_out == v_in ? nxt[fin_out_old] : nxt[v_in];
-        int stem = u_in, new_par = v_in, last = fin[u_in], after = nxt[last];
-        nxt[v_in] = u_in;
-        int n_dirty = 0;
-        w.scratch[n_dirty++] = v_in;
-        while (stem != u_out) {
-            const int up = par[stem];
-            nxt[last] = up;
-            w.scratch[n_dirty++] = last;
-            const int before = prv[stem];
-            nxt[before] = after; prv[after] = before;
-            par[stem] = new_par;
-            new_par = stem;
-            stem = up;
-            last = fin[stem] == fin[new_par] ? prv[new_par] : fin[stem];
-            after = nxt[last];
-        }
-        par[u_out] = new_par;
-        nxt[last] = resume; prv[resume] = last;
-        fin[u_out] = last;
-        if (before_out != v_in) { nxt[before_out] = after; prv[after] = before_out; }
-        for (int i = 0; i < n_dirty; ++i) { const int u = w.scratch[i]; prv[nxt[u]] = u; }
-        int acc = 0;
-        const int fin_new = fin[u_out];
-        for (int u = u_out, p = par[u]; u != u_in; u = p, p = par[u]) {
-            parc[u] = parc[p];
-            pdir[u] = (int8_t)-pdir[p];
-            acc += sub[u] - sub[p];
-            sub[u] = acc;
-            fin[p] = fin_new;
-        }
-        parc[u_in] = in_arc; pdir[u_in] = dir_in; sub[u_in] = size_out;
-    }
-    const int stop_out = fin[join] == v_in ? join : -1;
-    const int fin_moved = fin[u_out];
-    for (int u = v_in; u != -1 && fin[u] == v_in; u = par[u]) fin[u] = fin_moved;
-    if (join != before_out && v_in != before_out) {
-        for (int u = v_out; u != stop_out && fin[u] == fin_out_old; u = par[u]) fin[u] = before_out;
-    } else if (fin_moved != fin_out_old) {
-        for (int u = v_out; u != stop_out && fin[u] == fin_out_old; u = par[u]) fin[u] = fin_moved;
-    }
-    for (int u = v_in; u != join; u = par[u]) sub[u] += size_out;
-    for (int u = v_out; u != join; u = par[u]) sub[u] -= size_out;
+    push_flow(w, p);
+    if (p.change) rehang_subtree(w, p);
     return false;
 }
 

@@ -2,16 +2,13 @@
 //
 // NsCore is what mcf_ns keeps of a problem and its spanning tree (NS.cs:126-151), without anything that drives a device.  mcf_ns derives
 // from it; the batch solver (batch.hip) keeps one per instance.  The functions are the set-up and the end of Solve() (NS.cs:215-393),
-// defined once in ns_host.cpp and used by both.
+// defined once in ns_core.cpp and used by both.  The pivot between them is tree_pivot.h, on the view that tree() gives.
 #pragma once
 
 #include "common.h"
+#include "tree_pivot.h"
 
 namespace mcf {
-
-constexpr int8_t kUp = 1, kDown = -1;   // SpanningTree.cs:67-71 DIR_UP / DIR_DOWN
-constexpr int64_t kMax = INT64_MAX;     // NS.cs:126
-constexpr int64_t kInf = INT64_MAX / 2; // NS.cs:127
 
 struct NsCore {
     int n = 0, m = 0, root = 0;
@@ -29,6 +26,13 @@ struct NsCore {
     int64_t sum_supply = 0, art_cost = 0;
     int status = MCF_NOT_SOLVED;
     bool transformed = false;
+
+    // the arrays a pivot touches; valid as long as the vectors are not resized (core_create sizes them, nothing does after it)
+    TreeView tree()
+    {
+        return TreeView{tail.data(), head.data(), upper.data(), flow.data(), par.data(), par_arc.data(), nxt.data(), prv.data(),
+                        sub.data(), fin.data(), par_dir.data(), scratch.data()};
+    }
 };
 
 // the checks and allocations of mcf_ns_create (NS.cs:113-151, :605-617); source / target are validated here, before anything can reach a device

@@ -1,11 +1,12 @@
 // ns_host.cpp -- the sequential half of the primal network simplex, kept on the CPU.
 //
-// Restates the host side of the reference solver (NS.cs = src/MinCostFlow.Core/Lemon/Algorithms/
-// NetworkSimplex.cs): problem set-up, transformation to standard form, the artificial-root start
-// basis, and per pivot the cycle search, flow augmentation and spanning-tree surgery on the
-// thread-index representation.  The two data-parallel pieces -- FindEnteringArc and the potential
-// update -- are NOT here: they are calls into the device engine (engine.hip).  There is no CPU
-// entering-arc search in this file or anywhere else in the library.
+// Drives the host side of the reference solver (NS.cs = src/MinCostFlow.Core/Lemon/Algorithms/
+// NetworkSimplex.cs): problem set-up, standard form and the artificial-root start basis are
+// ns_core.cpp; per pivot the cycle search, flow augmentation and spanning-tree surgery on the
+// thread-index representation are tree_pivot.h, and what is here is their order, the walk over
+// the subtree's potentials and what the engines are told.  The two data-parallel pieces --
+// FindEnteringArc and the potential update -- are NOT here: they are calls into the device engine
+// (engine.hip).  There is no CPU entering-arc search in this file or anywhere else in the library.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -18,14 +19,6 @@
 
 #include "common.h"
 #include "ns_core.h"
-
-namespace {
-
-inline double ticks() { return (double)__rdtsc(); }     // invariant TSC; scaled to ns once per solve
-
-using mcf::kUp; using mcf::kDown; using mcf::kMax; using mcf::kInf;     // ns_core.h
-
-}  // namespace
 
 struct mcf_ns : mcf::NsCore {                                         // the problem, the flows and the tree: ns_core.h
     int rule = MCF_RULE_BLOCK_SEARCH;                                  // NS.cs:77
@@ -46,12 +39,8 @@ struct mcf_ns : mcf::NsCore {                                         // the pro
     int64_t renumber_at_pivot = 0;
     bool renumber_forced = false;     // MCF_NS_RENUMBER set: relabel at that interval whatever it costs (tests)
     bool begun = false, prepared = false, solved = false;
-    // the pivot being carried out
-    int in_arc = -1, join = -1, u_in = -1, v_in = -1, u_out = -1, v_out = -1;
-    int64_t delta = 0;
-    int8_t in_state_before = 0;       // State[in_arc] when the pivot started
-    bool out_on_tail_path = false;    // the leaving arc lies on the cycle half that starts at the entering arc's tail
-    bool change = false;              // the pivot changes the basis (find_join_and_leaving found a blocking arc)
+    mcf::TreeView tv{};               // the arrays the steps of tree_pivot.h work on: bound by begin()
+    mcf::Pivot pv;                    // the pivot being carried out
     // what the last pivot changed (the engine calls of a host)
     int n_state = 0;
     int32_t st_arc[2] = {0, 0};
@@ -119,6 +108,10 @@ struct mcf_ns : mcf::NsCore {                                         // the pro
 };
 
 namespace {
+
+inline double ticks() { return (double)__rdtsc(); }     // invariant TSC; scaled to ns once per solve
+
+using mcf::kInf;     // tree_pivot.h
 
 // ---- the engine calls of a pivot, fanned out to every shard this process drives
 int engines_patch_state(mcf_ns *s, int32_t count, const int32_t *arcs, const int8_t *states)
@@ -196,79 +189,8 @@ void engines_destroy(mcf_ns *s)
     if (s->exchange) { mcf_exchange_close(s->exchange); s->exchange = nullptr; }
 }
 
-// ---- NS.cs:624-669
-bool bounds_ok(const mcf::NsCore *s)
-{
-    for (int e = 0; e < s->m; ++e)
-        if (s->upper[e] < s->lower[e]) return false;
-    return true;
-}
-
-void to_standard_form(mcf::NsCore *s)
-{
-    for (int e = 0; e < s->m; ++e) {
-        const int64_t lo = s->lower[e];
-        if (lo == 0) continue;
-        s->supply[s->tail[e]] -= lo;
-        s->supply[s->head[e]] += lo;
-        s->upper[e] -= lo;
-        s->lower[e] = 0;
-    }
-    s->sum_supply = 0;
-    for (int v = 0; v < s->n; ++v) s->sum_supply += s->supply[v];
-    int64_t biggest = 0;
-    for (int e = 0; e < s->m; ++e) biggest = std::max<int64_t>(biggest, s->cost[e] < 0 ? -s->cost[e] : s->cost[e]);
-    s->art_cost = (biggest + 1) * (int64_t)s->n;
-    s->transformed = true;
-}
-
-// ---- NS.cs:671-845: star basis on the artificial root.  GEQ: nodes with supply <= 0 hang on a zero-cost
-// root->v arc, the others on an ART_COST v->root arc and get a zero-cost root->v arc at its lower bound; LEQ mirrored.
-void start_basis(mcf::NsCore *s)
-{
-    const int n = s->n, m = s->m, root = s->root = n;
-    s->par[root] = -1; s->par_arc[root] = -1; s->nxt[root] = 0; s->prv[0] = root;
-    s->sub[root] = n + 1; s->fin[root] = n - 1; s->par_dir[root] = 0; s->pi[root] = 0;
-    for (int e = 0; e < m; ++e) { s->state[e] = MCF_STATE_LOWER; s->flow[e] = 0; }
-    s->search_arcs = m + n;
-    int extra = m + n;
-    for (int v = 0; v < n; ++v) { s->nxt[v] = v + 1 < n ? v + 1 : root; }
-    for (int v = 0; v < n; ++v) s->prv[s->nxt[v]] = v;
-    const bool geq = s->supply_type == MCF_SUPPLY_GEQ;
-    for (int v = 0; v < n; ++v) {
-        const int link = m + v;
-        s->par[v] = root; s->sub[v] = 1; s->fin[v] = v;
-        const bool plain = geq ? s->supply[v] <= 0 : s->supply[v] >= 0;
-        // direction of the zero-cost link: GEQ root->v, LEQ v->root
-        const int lt = geq ? root : v, lh = geq ? v : root;
-        s->tail[link] = lt; s->head[link] = lh; s->upper[link] = kInf; s->cost[link] = 0;
-        if (plain) {
-            s->par_dir[v] = geq ? kDown : kUp;
-            s->pi[v] = 0;
-            s->par_arc[v] = link;
-            s->flow[link] = geq ? -s->supply[v] : s->supply[v];
-            s->state[link] = MCF_STATE_TREE;
-        } else {
-            s->par_dir[v] = geq ? kUp : kDown;
-            s->pi[v] = geq ? -s->art_cost : s->art_cost;
-            s->par_arc[v] = extra;
-            s->tail[extra] = lh; s->head[extra] = lt;   // the opposite direction
-            s->upper[extra] = kInf;
-            s->flow[extra] = geq ? s->supply[v] : -s->supply[v];
-            s->cost[extra] = s->art_cost;
-            s->state[extra] = MCF_STATE_TREE;
-            s->flow[link] = 0;
-            s->state[link] = MCF_STATE_LOWER;
-            ++extra;
-        }
-    }
-    if (n > 0) s->prv[root] = n - 1;
-    s->all_arcs = extra;
-}
-
-// ---- NS.cs:1030-1039, before the flows are touched: the State[] writes of the pivot.  The leaving arc's new state depends on its
-// flow after ChangeFlow (0 -> LOWER, else UPPER), which is its flow now -/+ delta along its half of the cycle (same sums as push_flow).
-void decide_states(mcf_ns *s, bool change)
+// ---- NS.cs:1030-1039, before the flows are touched: the State[] writes of the pivot, kept for the engines
+void decide_states(mcf_ns *s)
 {
     s->n_state = 0;
     auto set_state = [&](int arc, int8_t v) {
@@ -277,98 +199,13 @@ void decide_states(mcf_ns *s, bool change)
         s->st_val[s->n_state] = v;
         s->n_state++;
     };
-    const int8_t in_state = s->state[s->in_arc];
-    s->in_state_before = in_state;
-    if (change) {
-        const int out = s->par_arc[s->u_out];
-        const int64_t val = in_state * s->delta;
-        const int64_t after = s->out_on_tail_path ? s->flow[out] - s->par_dir[s->u_out] * val : s->flow[out] + s->par_dir[s->u_out] * val;
-        set_state(s->in_arc, MCF_STATE_TREE);
-        set_state(out, after == 0 ? MCF_STATE_LOWER : MCF_STATE_UPPER);
+    const mcf::Pivot &p = s->pv;
+    if (p.change) {
+        set_state(p.in_arc, MCF_STATE_TREE);
+        set_state(s->par_arc[p.u_out], mcf::leaving_state(s->tv, p));
     } else {
-        set_state(s->in_arc, (int8_t)-in_state);
+        set_state(p.in_arc, (int8_t)-p.in_state);
     }
-}
-
-// ---- NS.cs:1012-1029: the flow change around the cycle (old tree; nothing the device needs)
-void push_flow(mcf_ns *s)
-{
-    if (s->delta > 0) {
-        const int64_t val = s->in_state_before * s->delta;
-        s->flow[s->in_arc] += val;
-        for (int u = s->tail[s->in_arc]; u != s->join; u = s->par[u]) s->flow[s->par_arc[u]] -= s->par_dir[u] * val;
-        for (int u = s->head[s->in_arc]; u != s->join; u = s->par[u]) s->flow[s->par_arc[u]] += s->par_dir[u] * val;
-    }
-}
-
-// ---- NS.cs:1042-1183.  The subtree of u_out is cut off v_out, re-rooted at u_in and hung below v_in; the preorder
-// (thread) list is spliced accordingly and SuccNum / LastSucc are repaired along the two root paths.
-void rehang_subtree(mcf_ns *s)
-{
-    auto &par = s->par; auto &parc = s->par_arc; auto &nxt = s->nxt; auto &prv = s->prv;
-    auto &sub = s->sub; auto &fin = s->fin; auto &pdir = s->par_dir;
-    const int u_in = s->u_in, v_in = s->v_in, u_out = s->u_out, in_arc = s->in_arc, join = s->join;
-    const int before_out = prv[u_out], size_out = sub[u_out], fin_out_old = fin[u_out];
-    const int v_out = s->v_out = par[u_out];
-    const int8_t dir_in = u_in == s->tail[in_arc] ? kUp : kDown;
-
-    if (u_in == u_out) {
-        // the whole subtree moves as it is
-        par[u_in] = v_in; parc[u_in] = in_arc; pdir[u_in] = dir_in;
-        if (nxt[v_in] != u_out) {
-            int after = nxt[fin_out_old];
-            nxt[before_out] = after; prv[after] = before_out;          // unlink [u_out .. fin_out_old]
-            after = nxt[v_in];
-            nxt[v_in] = u_out; prv[u_out] = v_in;                       // relink right behind v_in
-            nxt[fin_out_old] = after; prv[after] = fin_out_old;
-        }
-    } else {
-        // before_out == v_in also means join == v_out
-        const int resume = before_out == v_in ? nxt[fin_out_old] : nxt[v_in];
-        int stem = u_in, new_par = v_in, last = fin[u_in], after = nxt[last];
-        nxt[v_in] = u_in;
-        int n_dirty = 0;
-        s->scratch[n_dirty++] = v_in;
-        while (stem != u_out) {
-            const int up = par[stem];
-            nxt[last] = up;                       // the next stem node follows this stem's subtree
-            s->scratch[n_dirty++] = last;
-            const int before = prv[stem];         // drop the stem's subtree from its old place
-            nxt[before] = after; prv[after] = before;
-            par[stem] = new_par;
-            new_par = stem;
-            stem = up;
-            last = fin[stem] == fin[new_par] ? prv[new_par] : fin[stem];
-            after = nxt[last];
-        }
-        par[u_out] = new_par;
-        nxt[last] = resume; prv[resume] = last;
-        fin[u_out] = last;
-        if (before_out != v_in) { nxt[before_out] = after; prv[after] = before_out; }
-        for (int i = 0; i < n_dirty; ++i) { const int u = s->scratch[i]; prv[nxt[u]] = u; }
-        // reverse the parent arcs along the stem, rebuild sizes
-        int acc = 0;
-        const int fin_new = fin[u_out];
-        for (int u = u_out, p = par[u]; u != u_in; u = p, p = par[u]) {
-            parc[u] = parc[p];
-            pdir[u] = (int8_t)-pdir[p];
-            acc += sub[u] - sub[p];
-            sub[u] = acc;
-            fin[p] = fin_new;
-        }
-        parc[u_in] = in_arc; pdir[u_in] = dir_in; sub[u_in] = size_out;
-    }
-
-    const int stop_out = fin[join] == v_in ? join : -1;
-    const int fin_moved = fin[u_out];
-    for (int u = v_in; u != -1 && fin[u] == v_in; u = par[u]) fin[u] = fin_moved;
-    if (join != before_out && v_in != before_out) {
-        for (int u = v_out; u != stop_out && fin[u] == fin_out_old; u = par[u]) fin[u] = before_out;
-    } else if (fin_moved != fin_out_old) {
-        for (int u = v_out; u != stop_out && fin[u] == fin_out_old; u = par[u]) fin[u] = fin_moved;
-    }
-    for (int u = v_in; u != join; u = par[u]) sub[u] += size_out;
-    for (int u = v_out; u != join; u = par[u]) sub[u] -= size_out;
 }
 
 // ---- NS.cs:1185-1209: host copy of pi is kept current (sigma needs pi[v_in], pi[u_in]); the node list is what
@@ -434,10 +271,10 @@ int64_t walk_runs(mcf_ns *s, int first, int count, int64_t sigma, int32_t *nodes
 void shift_potentials(mcf_ns *s)
 {
     // runs BEFORE the re-hanging: the nodes that move are the subtree of u_out as it hangs now, and u_in's new parent direction is known
-    const int8_t dir_in = s->u_in == s->tail[s->in_arc] ? kUp : kDown;
-    s->sigma = s->pi[s->v_in] - s->pi[s->u_in] - dir_in * s->cost[s->in_arc];
-    int count = s->sub[s->u_out];
-    int first = s->u_out, last = s->fin[s->u_out];
+    const int u_out = s->pv.u_out;
+    s->sigma = mcf::pivot_sigma(s->pv, s->pi.data(), s->cost.data());
+    int count = s->sub[u_out];
+    int first = u_out, last = s->fin[u_out];
     // (the common offset pi[root] that this builds up is bounded: past 2^60 the complement is never walked again, so it stops growing and every
     // potential stays representable -- the reference's values differ from ours by exactly that offset until normalise_potentials takes it out)
     if (s->shift_smaller_side && (s->pi[s->root] > (1ll << 60) || s->pi[s->root] < -(1ll << 60))) s->shift_smaller_side = false;
@@ -448,7 +285,7 @@ void shift_potentials(mcf_ns *s)
         // reference keeps at 0) is taken out again before the solve returns (normalise_potentials).
         s->sigma = -s->sigma;
         first = s->nxt[last];
-        last = s->prv[s->u_out];
+        last = s->prv[u_out];
         count = s->n + 1 - count;
     }
     const int64_t sigma = s->sigma;
@@ -593,21 +430,28 @@ void shift_potentials(mcf_ns *s)
     }
 }
 
-// pi[root] back to 0 (where the reference keeps it): every potential moves by -pi[root], the engines hear of it as one list of all nodes
-int normalise_potentials(mcf_ns *s)
+// pi[root] back to 0 (where the reference keeps it; the smaller-side walks let it drift) without telling an engine: every potential moves
+// by -pi[root].  Returns what pi[root] was.
+int64_t zero_root_potential(mcf::NsCore *s)
 {
     const int64_t off = s->pi[s->root];
+    if (off != 0) for (int u = 0; u <= s->n; ++u) s->pi[u] -= off;
+    return off;
+}
+
+// the same at the end of a solve, where the engines hear of it: as one list of all nodes, or as a reload of _pi
+int normalise_potentials(mcf_ns *s)
+{
+    const int64_t off = zero_root_potential(s);
     if (off == 0) return MCF_OK;
     const int total = s->n + 1;
+    s->sigma = -off;
     if (s->reload_min > 0) {
-        for (int u = 0; u < total; ++u) s->pi[u] -= off;
-        s->sigma = -off;
         s->moved_n = total;
         s->moved_sent = total;
         return engines_reload_potentials(s, total);
     }
-    for (int u = 0; u < total; ++u) { s->moved[u] = u; s->moved_val[u] = (s->pi[u] -= off); }
-    s->sigma = -off;
+    for (int u = 0; u < total; ++u) { s->moved[u] = u; s->moved_val[u] = s->pi[u]; }
     s->moved_n = total;
     s->moved_sent = 0;
     const int rc = engines_append_potential(s, total, s->moved.data(), s->moved_val.data());
@@ -646,8 +490,8 @@ void renumber_nodes(mcf_ns *s, std::vector<int32_t> *perm_out)
     s->orig_of.assign(N, 0);
     for (int v = 0; v < N; ++v) s->orig_of[s->new_of[v]] = v;
     // the pivot in progress (none between pivots, but keep the fields meaningful)
-    auto tr1 = [&](int &x) { if (x >= 0) x = to[x]; };
-    tr1(s->join); tr1(s->u_in); tr1(s->v_in); tr1(s->u_out); tr1(s->v_out);
+    auto tr1 = [&](int32_t &x) { if (x >= 0) x = to[x]; };
+    tr1(s->pv.join); tr1(s->pv.u_in); tr1(s->pv.v_in); tr1(s->pv.u_out); tr1(s->pv.v_out);
     s->walked_since_renumber = 0; s->jumps_since_renumber = 0; s->renumbers += 1;
     if (perm_out) perm_out->swap(to);
 }
@@ -673,83 +517,23 @@ void restore_node_ids(mcf_ns *s)
     s->new_of.clear(); s->orig_of.clear();
 }
 
-// find_join + find_leaving in ONE climb.  The reference climbs twice: first to the join node (NS.cs:925-941: whichever side has the smaller
-// SuccNum steps up), then from both end points of the entering arc to the join again, taking the minimum residual of each path (NS.cs:943-1010).
-// Both climbs visit the same nodes in the same bottom-up order per side, and the second one only needs to know where each side stops -- which
-// the first one discovers as it goes.  So the residuals are folded into the first climb: a step on the FIRST path (the side the entering arc's
-// state makes "first") compares with '<', a step on the second with '<=', exactly as NS.cs:957-997 -- with one difference in ORDER: the
-// reference finishes the first path before it starts the second, here the two interleave.  That matters for ties between the paths: the
-// reference lets a second-path arc with residual EQUAL to the first path's minimum win (d <= delta), whenever it comes.  Interleaved, each
-// side keeps its own minimum and the two are combined at the end with the same rule (second path wins ties), which is the same arc:
-//   first-path winner  = the lowest node u on it with residual < everything below it      (strict: the first among equals, bottom-up)
-//   second-path winner = the highest node u on it with residual <= everything below it and <= the first path's minimum (the last among equals)
-// and the second path's own '<=' chain must be evaluated against min(first-path minimum, running): since min is associative the result
-// is: delta = min(d1, d2); leaving = second-path's LAST node with d == d2 if d2 <= d1, else first-path's FIRST node with d == d1.
-bool find_join_and_leaving(mcf_ns *s)
-{
-    const int in_arc = s->in_arc;
-    const bool lower = s->state[in_arc] == MCF_STATE_LOWER;
-    const int tail = s->tail[in_arc], head = s->head[in_arc];
-    // side A climbs from the tail, side B from the head; the FIRST path starts at the tail when the arc is at its lower bound
-    int a = tail, b = head;
-    const int32_t *const par = s->par.data(), *const sub = s->sub.data(), *const parc = s->par_arc.data();
-    const int8_t *const pdir = s->par_dir.data();
-    const int64_t *const flow = s->flow.data(), *const upper = s->upper.data();
-    const int64_t cap_in = s->upper[in_arc];
-    // residual of the tree arc above u when flow is pushed along the cycle: on the first path arcs pointing DOWN gain flow, on the second arcs pointing UP
-    int64_t d_first = kMax, d_second = kMax;
-    int u_first = -1, u_second = -1;
-    const int8_t gain_a = lower ? kDown : kUp;            // the direction whose arcs GAIN flow (residual = upper - flow) on side A ...
-    const int8_t gain_b = lower ? kUp : kDown;            // ... and on side B
-    while (a != b) {
-        if (sub[a] < sub[b]) {
-            const int e = parc[a];
-            int64_t room = flow[e];
-            if (pdir[a] == gain_a) room = upper[e] >= kMax ? kInf : upper[e] - room;
-            if (lower) { if (room < d_first) { d_first = room; u_first = a; } }
-            else { if (room <= d_second) { d_second = room; u_second = a; } }
-            a = par[a];
-        } else {
-            const int e = parc[b];
-            int64_t room = flow[e];
-            if (pdir[b] == gain_b) room = upper[e] >= kMax ? kInf : upper[e] - room;
-            if (lower) { if (room <= d_second) { d_second = room; u_second = b; } }
-            else { if (room < d_first) { d_first = room; u_first = b; } }
-            b = par[b];
-        }
-    }
-    s->join = a;
-    const int first = lower ? tail : head, second = lower ? head : tail;
-    // NS.cs:952: delta starts at the entering arc's capacity; the first path replaces it only with something strictly smaller, the second
-    // with anything not larger
-    int64_t delta = cap_in;
-    int side = 0;
-    if (u_first >= 0 && d_first < delta) { delta = d_first; s->u_out = u_first; side = 1; }
-    if (u_second >= 0 && d_second <= delta) { delta = d_second; s->u_out = u_second; side = 2; }
-    s->delta = delta;
-    if (side == 1) { s->u_in = first; s->v_in = second; }
-    else { s->u_in = second; s->v_in = first; }
-    s->out_on_tail_path = side != 0 && ((side == 1) == (first == tail));
-    return side != 0;
-}
-
 // One pivot with a given entering arc, in two halves.  pivot_front does what the next search depends on -- the cycle, the State[] writes and
 // the potentials of the subtree that is about to move (handed to the engine as they arise) -- and returns true when the problem is
 // found unbounded (NS.cs:321-325).  pivot_back does the rest (flows around the cycle, re-hanging the subtree): the solve loop runs it
 // while the device is already searching.
 bool pivot_front(mcf_ns *s, int arc, double *t_pot)
 {
-    s->in_arc = arc;
     s->moved_n = 0;
     s->moved_sent = 0;
     s->sigma = 0;
-    const bool change = s->change = find_join_and_leaving(s);
-    if (!change && s->delta == 0) return true;
-    decide_states(s, change);
+    s->pv = mcf::find_cycle(s->tv, arc, s->state[arc]);
+    const mcf::Pivot &p = s->pv;
+    if (!p.change && p.delta == 0) return true;
+    decide_states(s);
     // the engine hears about the state writes before any piece of the potential list (the pieces may start travelling at once)
     if (s->hand_over && !s->engine_rc) s->engine_rc = engines_patch_state(s, s->n_state, s->st_arc, s->st_val);
-    if (s->delta == 0) s->metrics.degenerate_pivots++;
-    if (change) {
+    if (p.delta == 0) s->metrics.degenerate_pivots++;
+    if (p.change) {
         const double t1 = ticks();
         shift_potentials(s);
         if (t_pot) *t_pot += ticks() - t1;
@@ -759,10 +543,10 @@ bool pivot_front(mcf_ns *s, int arc, double *t_pot)
 
 void pivot_back(mcf_ns *s, double *t_tree)
 {
-    push_flow(s);
-    if (s->change) {
+    mcf::push_flow(s->tv, s->pv);
+    if (s->pv.change) {
         const double t0 = ticks();
-        rehang_subtree(s);
+        mcf::rehang_subtree(s->tv, s->pv);
         if (t_tree) *t_tree += ticks() - t0;
     }
 }
@@ -916,80 +700,13 @@ int begin(mcf_ns *s, int32_t *status)
     s->trace_len = 0;
     if (s->begun) return mcf::fail(MCF_ERR_STATE, "Solve() is single-shot: the reference mutates bounds and supplies in place (NS.cs:649, D11); create a new solver");
     s->begun = true;
+    // the vectors were sized by core_create and are never resized; renumber_nodes and restore_node_ids permute them in place, so the view
+    // stays valid across a relabelling
+    s->tv = s->tree();
     mcf::core_begin(s);                                  // Infeasible on an inverted bound pair (NS.cs:227-231), else the start basis
     if (status) *status = s->status;
     return MCF_OK;
 }
-
-}  // namespace
-
-namespace mcf {
-
-bool core_begin(NsCore *s)
-{
-    s->status = MCF_NOT_SOLVED;
-    if (!bounds_ok(s)) { s->status = MCF_INFEASIBLE; return false; }   // NS.cs:227-231
-    to_standard_form(s);
-    start_basis(s);
-    return true;
-}
-
-void core_finish(NsCore *s)
-{
-    // NS.cs:1272-1283 with _allArcNum overwritten by _searchArcNum at NS.cs:689 (difference D9): only the n root links
-    for (int e = s->m; e < s->search_arcs; ++e)
-        if (s->flow[e] != 0) { s->status = MCF_INFEASIBLE; return; }
-    s->status = MCF_OPTIMAL;
-    for (int e = 0; e < s->m; ++e) {                      // NS.cs:364-388
-        const int64_t lo = s->orig_lower[e];
-        if (lo == 0) continue;
-        s->flow[e] += lo;
-        s->supply[s->tail[e]] += lo;
-        s->supply[s->head[e]] -= lo;
-    }
-}
-
-int64_t core_total_cost(const NsCore *s)
-{
-    int64_t total = 0;
-    for (int e = 0; e < s->m; ++e) total += s->flow[e] * s->cost[e];   // NS.cs:459-464
-    return total;
-}
-
-int core_create(NsCore *s, int32_t node_count, int32_t arc_count, const int32_t *source, const int32_t *target)
-{
-    if (node_count < 0 || arc_count < 0 || (arc_count && (!source || !target))) return fail(MCF_ERR_INVALID, "graph must not be null (NS.cs:121)");
-    if ((int64_t)arc_count + 2 * (int64_t)node_count > INT32_MAX - 4096) return fail(MCF_ERR_INVALID, "graph too large for 32-bit arc ids");
-    for (int e = 0; e < arc_count; ++e)
-        if ((unsigned)source[e] >= (unsigned)node_count || (unsigned)target[e] >= (unsigned)node_count)
-            return fail(MCF_ERR_INVALID, "arc %d: end point out of range", e);
-    s->n = node_count; s->m = arc_count;
-    const size_t A = (size_t)arc_count + 2 * (size_t)node_count, N = (size_t)node_count + 1;
-    s->tail.assign(A, 0); s->head.assign(A, 0);
-    std::copy(source, source + arc_count, s->tail.begin());
-    std::copy(target, target + arc_count, s->head.begin());
-    s->lower.assign(A, 0); s->upper.assign(A, kInf); s->cost.assign(A, 0); s->flow.assign(A, 0);   // NS.cs:614-617
-    s->orig_lower.assign(arc_count, 0);
-    s->state.assign(A, 0);
-    s->supply.assign(N, 0); s->pi.assign(N, 0);
-    s->par.assign(N, -1); s->par_arc.assign(N, -1); s->nxt.assign(N, 0); s->prv.assign(N, 0);
-    s->sub.assign(N, 0); s->fin.assign(N, 0); s->par_dir.assign(N, 0); s->scratch.assign(N + 1, 0);
-    return MCF_OK;
-}
-
-void core_set_problem(NsCore *s, const int64_t *lower, const int64_t *upper, const int64_t *cost, const int64_t *supply)
-{
-    for (int e = 0; e < s->m; ++e) {
-        if (lower) { s->lower[e] = lower[e]; s->orig_lower[e] = lower[e]; }
-        if (upper) s->upper[e] = upper[e] == MCF_INF_CAP ? kInf : upper[e];
-        if (cost) s->cost[e] = cost[e];
-    }
-    if (supply) std::copy(supply, supply + s->n, s->supply.begin());
-}
-
-}  // namespace mcf
-
-namespace {
 
 int pick_int_width(const mcf_ns *s)
 {
@@ -1201,10 +918,7 @@ int mcf_ns_replay(mcf_ns *s, const int32_t *arcs, int64_t count, int32_t smaller
     s->shift_smaller_side = false;
     const double t0 = ticks();
     restore_node_ids(s);
-    {   // pi[root] back to 0 (the smaller-side walks let it drift)
-        const int64_t off = s->pi[s->root];
-        if (off != 0) for (int u = 0; u <= s->n; ++u) s->pi[u] -= off;
-    }
+    zero_root_potential(s);
     t_renum += ticks() - t0;
     const double ns_per_tick = (mcf::now_ns() - t_start) / std::max(1.0, ticks() - tick_start);
     s->metrics.iterations += it;
@@ -1493,11 +1207,7 @@ int mcf_ns_solve(mcf_ns *s, int32_t *status)
     s->hand_over = false;
     s->shift_smaller_side = false;
     if (!rc) rc = normalise_potentials(s);
-    else {
-        // after an engine error the engines are not told any more, but the caller's view of _pi is the reference's: pi[root] = 0
-        const int64_t off = s->pi[s->root];
-        if (off != 0) for (int u = 0; u <= s->n; ++u) s->pi[u] -= off;
-    }
+    else zero_root_potential(s);     // after an engine error the engines are not told any more, but the caller's view of _pi is the reference's
     s->reload_min = 0;
     restore_node_ids(s);             // the caller's node ids again (the parked engines keep the relabelled ones: Solve() is single-shot)
     const char *first_error = rc ? mcf_last_error() : nullptr;
