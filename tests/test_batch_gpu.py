@@ -10,7 +10,9 @@ import mincostflow_amd as M
 from oracle import ns_oracle as O
 
 from helpers import fixtures, load
-from test_batch_host import RULES, assert_equals_oracle, check_mixed_batch, generated, mixed_cases, oracle_of
+from test_batch_host import (LDS_LIMITS, RULES, assert_equals_oracle, assert_fuzz_equals_oracle, bound_infeasible, check_mixed_batch,
+                             check_nothing_to_run, check_padded_fuzz, check_short_and_absent_traces, footprint_of, fuzz_cases,
+                             fuzz_reference, fuzz_solver, generated, ladder, mixed_cases, oracle_of, padded_fuzz)
 
 pytestmark = pytest.mark.gpu
 
@@ -148,3 +150,88 @@ def test_pivot_limit_on_the_device():
             assert b.pivots(i) == want and np.array_equal(b.trace(i), full.trace(i)[:want])
             assert b.status(i) == (M.SolverStatus.NotSolved if k < full.pivots(i) else M.SolverStatus.Optimal)
         assert b.status(2) == (M.SolverStatus.Optimal if k >= 4 else M.SolverStatus.NotSolved)
+
+
+# ---- 17
+@pytest.mark.parametrize("rule", [O.RULE_BLOCK, O.RULE_BEST, O.RULE_FIRST])
+def test_adversarial_batch_on_the_device(rule):
+    """The fuzz of test_adversarial_batch_on_the_host with 64 lanes: Infeasible and Unbounded endings, LEQ, lower bounds, infinite and zero
+    capacities, ties and costs above 2^32 where the lanes' minima are combined over up to 16 strides, search ranges of 63 / 64 / 65 ...
+    257 arcs, instances that never reach the device between ones that do.  Slices of 3 pivots end solves of every kind in the middle of a
+    sequence of launches.  Every workspace here fits LDS; the global tier's share is test_adversarial_instances_in_the_global_tier."""
+    count = len(fuzz_cases())
+    dev = fuzz_solver(rule).solve()
+    assert_fuzz_equals_oracle(dev, rule)
+    host = fuzz_solver(rule).run_on_host()
+    assert_same_results(dev, host, count)
+    st = dev.stats()
+    print(f"rule {rule}: {st}")
+    by_bounds = sum(bound_infeasible(p) for p, _ in fuzz_cases())
+    assert st["lds_instances"] + st["global_instances"] == count - by_bounds and st["total_pivots"] == host.stats()["total_pivots"]
+    assert st["workspace_bytes"] == sum(footprint_of(p, stype) for p, stype in fuzz_cases())
+    by3 = fuzz_solver(rule, pivots_per_launch=3).solve()
+    assert by3.stats()["launches"] >= max(o.n_pivots for o, _, _ in fuzz_reference(rule)) // 3
+    assert_same_results(dev, by3, count)
+    assert_fuzz_equals_oracle(by3, rule)
+
+
+# ---- 18
+@pytest.mark.parametrize("rule", [O.RULE_BLOCK, O.RULE_BEST, O.RULE_FIRST])
+def test_adversarial_instances_in_the_global_tier(rule):
+    """The fuzz batch above fits LDS on every device (its largest workspace is 37 KB), so batch_kernel<false> sees none of it.  Here the
+    largest instances of every outcome, padded with isolated nodes until no LDS limit holds them, run in place: whole, and in slices of 7."""
+    count = len(padded_fuzz(rule))
+    whole = check_padded_fuzz(lambda b: b.solve(), rule)
+    st = whole.stats()
+    print(f"rule {rule}: {st}")
+    assert st["global_instances"] == count and st["lds_instances"] == 0 and st["lds_bytes_max"] == 0
+    assert st["workspace_bytes"] == sum(footprint_of(q, stype) for q, stype, _ in padded_fuzz(rule))
+    by7 = check_padded_fuzz(lambda b: b.solve(), rule, pivots_per_launch=7)
+    assert by7.stats()["launches"] >= max(r[0].n_pivots for _, _, r in padded_fuzz(rule)) // 7
+    assert_same_results(whole, by7, count)
+
+
+# ---- 19
+def test_footprint_ladder_across_the_classes_and_the_tier_edge():
+    """One batch with, for every class limit L / d (L = 160 KiB and 64 KiB, d = 16, 8, 4, 3, 2, 1), the last workspace that fits and the
+    first that does not: the classes hold mixed footprints, and whatever L this device gives, its two neighbours are here."""
+    steps = ladder()
+    count = len(steps)
+    dev = M.BatchSolver(record_trace=1 << 14)
+    host = M.BatchSolver(record_trace=1 << 14)
+    for p, *_ in steps:
+        dev.add(p)
+        host.add(p)
+    dev.solve()
+    host.run_on_host()
+    st = dev.stats()
+    sizes = sorted(size for _, size, _, _ in steps)
+    assert st["workspace_bytes"] == sum(sizes)                       # Layout (batch.hip) against the restatement of DESIGN.md 3.14
+    j = st["lds_instances"]
+    assert j + st["global_instances"] == count and 0 < j < count
+    fitting = [L for L in LDS_LIMITS if st["lds_bytes_max"] <= L]
+    assert fitting
+    L = min(fitting)
+    print(f"LDS limit found: {L} bytes; {st}")
+    assert all(size <= st["lds_bytes_max"] for size in sizes[:j]) and sizes[j] > L
+    assert sizes[j - 1] == st["lds_bytes_max"] and sizes[j - 1] <= L
+    assert all(dev.status(i) == M.SolverStatus.Optimal and dev.pivots(i) < 1 << 14 for i in range(count))
+    assert_same_results(dev, host, count)
+    edge = [i for i, (_, size, _, _) in enumerate(steps) if size in (sizes[j - 1], sizes[j])]
+    assert len(edge) == 2
+    for i in edge:
+        o, st_o, tr = oracle_of(steps[i][0], O.RULE_BLOCK)
+        assert_equals_oracle(dev, i, o, st_o, tr, f"ladder step {i}")
+
+
+# ---- 20
+@pytest.mark.parametrize("pivots_per_launch", [0, 5])
+def test_short_and_absent_traces_on_the_device(pivots_per_launch):
+    """All traces of a batch share one device buffer: with a capacity below every pivot count each instance's entries are its own first
+    pivots.  Capacity 0: the kernel gets no trace pointer."""
+    check_short_and_absent_traces(lambda b: b.solve(), pivots_per_launch=pivots_per_launch)
+
+
+# ---- 21
+def test_nothing_to_run_on_the_device():
+    check_nothing_to_run(lambda b: b.solve())

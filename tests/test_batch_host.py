@@ -5,6 +5,7 @@ The reference is the CPU oracle in SEM_CSHARP.  For Block Search the batch runs 
 auto-configured, adaptive rule -- so the oracle is built with auto_config=True (the oracle's own default is the bare `new
 OptimizationConfig()`); the configuration does not touch the other two rules."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -15,6 +16,7 @@ import mincostflow_amd as M
 from mincostflow_amd import _lib as L
 from oracle import ns_oracle as O
 
+from adversarial import adversarial_batch
 from helpers import fixtures, load, problem_from_dict
 from kat_data import CSHARP_KATS, LEMON_TABLE
 
@@ -84,6 +86,167 @@ def check_mixed_batch(b, cases, rule):
 def generated(seed, nodes=200, arcs=600):
     g = M.netgen_like(seed, nodes, arcs, max(2, nodes // 50), max(2, nodes // 50))
     return O.Problem(g.node_count, g.arc_count, g.source, g.target, g.lower, g.upper, g.cost, g.supply)
+
+
+# ---- the adversarial fuzz (tests/adversarial.py): the batch, and per rule the oracle's answers, computed once and left unchanged
+FUZZ_TRACE = 2048        # above the longest solve of the batch (asserted in fuzz_reference)
+
+
+@functools.lru_cache(maxsize=None)
+def fuzz_cases():
+    return tuple(adversarial_batch())
+
+
+def bound_infeasible(p):
+    return bool(np.any(p.upper < p.lower))
+
+
+@functools.lru_cache(maxsize=None)
+def fuzz_reference(rule):
+    """((oracle, status, trace) per instance of fuzz_cases()).  Everything the fuzz needs of its reference is asserted here, on the oracle's
+    answers alone: its numbers did not overflow, the traces are whole, and the batch holds what it was built for -- above one stride of
+    the wave (m + n > 64) at least 10 Optimal, 10 Infeasible and 10 Unbounded, 5 of each with costs above 2^32, and at least 3 instances
+    infeasible by their bounds between neighbours that run on the device."""
+    cases = fuzz_cases()
+    refs = tuple(oracle_of(p, rule, stype, trace_cap=FUZZ_TRACE) for p, stype in cases)
+    count = {st: [0, 0] for st in (O.OPTIMAL, O.INFEASIBLE, O.UNBOUNDED)}          # status -> [above one stride, of these with 64-bit costs]
+    by_bounds = []
+    for k, ((p, _), (o, st, tr)) in enumerate(zip(cases, refs)):
+        assert st in count and o.n_pivots < FUZZ_TRACE and len(tr) == o.n_pivots, k
+        if st == O.OPTIMAL:
+            assert o.total_cost == sum(int(f) * int(c) for f, c in zip(o.flow(), p.cost)), k
+            assert max((abs(int(v)) for v in o.potential()), default=0) < 1 << 62, k
+        if bound_infeasible(p):
+            assert st == O.INFEASIBLE and o.n_pivots == 0, k
+            by_bounds.append(k)
+        if p.m + p.n > 64:
+            count[st][0] += 1
+            count[st][1] += int(np.abs(p.cost).max() > 1 << 32)
+    print(f"fuzz, rule {rule}: {len(cases)} instances, longest solve {max(o.n_pivots for o, _, _ in refs)} pivots; above 64 search arcs (of these with 64-bit costs): "
+          f"Optimal {count[O.OPTIMAL]}, Infeasible {count[O.INFEASIBLE]}, Unbounded {count[O.UNBOUNDED]}; infeasible by bounds: {by_bounds}")
+    assert len(cases) < 500 and max(p.m for p, _ in cases) <= 1000
+    for st, (above, wide) in count.items():
+        assert above >= 10 and wide >= 5, (st, above, wide)
+    assert len(by_bounds) >= 3
+    for k in by_bounds:
+        assert 0 < k < len(cases) - 1 and not bound_infeasible(cases[k - 1][0]) and not bound_infeasible(cases[k + 1][0]), k
+    return refs
+
+
+def fuzz_solver(rule, **kw):
+    b = M.BatchSolver(rule=RULES[rule], record_trace=FUZZ_TRACE, **kw)
+    for k, (p, stype) in enumerate(fuzz_cases()):
+        assert b.add(p, supply_type=stype) == k
+    return b
+
+
+def assert_fuzz_equals_oracle(b, rule):
+    """Every instance, none left out."""
+    refs = fuzz_reference(rule)
+    compared = 0
+    for k, (o, st, tr) in enumerate(refs):
+        assert_equals_oracle(b, k, o, st, tr, f"fuzz instance {k}")
+        compared += 1
+    assert compared == len(fuzz_cases()) == len(b)
+
+
+# ---- the workspace of DESIGN.md 3.14, restated: 15 arrays in the documented order, each rounded up to 16 bytes
+LDS_LIMITS = (160 << 10, 64 << 10)       # the MI355X's figure; the default limit that holds where the opt-in above it is refused
+LDS_DIVISORS = (16, 8, 4, 3, 2, 1)
+
+
+def footprint(A, N):
+    up16 = lambda b: (b + 15) // 16 * 16
+    constant = [4 * A, 4 * A, 8 * A, 8 * A]                                        # tail, head i32 | cost, upper i64
+    changing = [8 * A, 8 * N] + 6 * [4 * N] + [4 * (N + 1), A, N]                  # flow, pi i64 | par, par_arc, nxt, prv, sub, fin i32 | scratch[N + 1] i32 | state, par_dir i8
+    assert len(constant + changing) == 15
+    total = sum(up16(b) for b in constant + changing)
+    assert 0 <= total - (33 * A + 37 * N + 4) <= 15 * 15
+    return total
+
+
+def footprint_of(p, supply_type=O.GEQ):
+    """A = the m arcs, the n root links and one artificial arc per node that cannot hang on its root link: supply (after the lower bounds
+    have been moved into it) > 0 under GEQ, < 0 under LEQ (start_basis)."""
+    if bound_infeasible(p):
+        return 0                                                                   # never set up: no workspace
+    s = p.supply.copy()
+    np.subtract.at(s, p.src, p.lower)
+    np.add.at(s, p.tgt, p.lower)
+    hung = int(np.sum(s > 0) if supply_type == O.GEQ else np.sum(s < 0))
+    return footprint(p.m + p.n + hung, p.n + 1)
+
+
+@functools.lru_cache(maxsize=None)
+def ladder():
+    """((problem, footprint, limit, fits) ...): for every class limit L / d the generated() instance with the last arc count whose workspace
+    fits and the one with the first that does not.  400 nodes where such an arc count exists (generated() needs nodes - sources arcs
+    for its skeleton: 41 344 bytes at 400 nodes), 30 nodes for the limits below that."""
+    out = []
+    for L in LDS_LIMITS:
+        for d in LDS_DIVISORS:
+            limit = L // d
+            for n in (400, 30):
+                sources = max(2, n // 50)                                          # generated(): each with a positive supply, so each on an artificial arc
+                size = lambda m: footprint(m + n + sources, n + 1)
+                m = n - sources
+                if size(m) <= limit:
+                    break
+            assert size(m) <= limit, (limit, "below the smallest workspace of both families")
+            while size(m + 1) <= limit:
+                m += 1
+            for arcs, fits in ((m, True), (m + 1, False)):
+                p = generated(5000 + len(out), n, arcs)
+                assert footprint_of(p) == size(arcs) and (size(arcs) <= limit) == fits
+                out.append((p, size(arcs), limit, fits))
+    assert len(out) == 24 and sum(p.n == 400 for p, *_ in out) >= 8 and max(p.m for p, *_ in out) < 5000
+    return tuple(out)
+
+
+PADDED_NODES = 4500      # 37 bytes per node: above the larger of LDS_LIMITS whatever the arcs
+
+
+@functools.lru_cache(maxsize=None)
+def padded_fuzz(rule):
+    """((problem, supply type, (oracle, status, trace)) ...): fuzz instances above one stride with isolated zero-supply nodes appended up
+    to PADDED_NODES, so that the workspace fits no LDS limit and the solve runs in place in global memory.  Still valid input with a
+    defined answer; the root links of the added nodes join the search range.  The six largest instances per status of the unpadded reference, half
+    of them with 64-bit costs; what is asserted is what the oracle answers on the padded ones: every status at least twice, once with
+    costs above 2^32, and a LEQ instance among them."""
+    picked = {st: [[], []] for st in (O.OPTIMAL, O.INFEASIBLE, O.UNBOUNDED)}
+    for (p, stype), (o, st, _) in reversed(list(zip(fuzz_cases(), fuzz_reference(rule)))):          # the largest first
+        if p.m + p.n <= 64 or bound_infeasible(p):
+            continue
+        wide = int(np.abs(p.cost).max() > 1 << 32)
+        if len(picked[st][wide]) < 3:
+            picked[st][wide].append((p, stype))
+    out = []
+    seen = {st: [0, 0] for st in picked}
+    for p, stype in (c for st in picked for half in picked[st] for c in half):
+        q = O.Problem(PADDED_NODES, p.m, p.src, p.tgt, p.lower, p.upper, p.cost, np.concatenate([p.supply, np.zeros(PADDED_NODES - p.n, np.int64)]))
+        assert footprint_of(q, stype) > max(LDS_LIMITS)
+        o, st, tr = oracle_of(q, rule, stype, trace_cap=1 << 14)
+        assert o.n_pivots < 1 << 14
+        if st == O.OPTIMAL:
+            assert o.total_cost == sum(int(f) * int(c) for f, c in zip(o.flow(), q.cost))
+            assert max(abs(int(v)) for v in o.potential()) < 1 << 62
+        seen[st][0] += 1
+        seen[st][1] += int(np.abs(q.cost).max() > 1 << 32)
+        out.append((q, stype, (o, st, tr)))
+    print(f"padded fuzz, rule {rule}: {len(out)} instances, status -> [count, with 64-bit costs] {seen}, longest solve {max(r[0].n_pivots for _, _, r in out)} pivots")
+    assert len(out) == 18 and all(n >= 2 and wide >= 1 for n, wide in seen.values()), seen
+    assert any(stype == O.LEQ for _, stype, _ in out)
+    return tuple(out)
+
+
+def check_padded_fuzz(run, rule, **kw):
+    b = M.BatchSolver(rule=RULES[rule], record_trace=1 << 14, **kw)
+    for q, stype, _ in padded_fuzz(rule):
+        b.add(q, supply_type=stype)
+    run(b)
+    for i, (_, _, (o, st, tr)) in enumerate(padded_fuzz(rule)):
+        assert_equals_oracle(b, i, o, st, tr, f"padded fuzz instance {i}")
+    return b
 
 
 # ---- 1
@@ -280,3 +443,99 @@ def test_batch_structs_have_the_layout_of_the_header(tmp_path):
     header = open(os.path.join(ROOT, "include", "mcf_hip.h")).read()
     for name, value in (("MCF_BATCH_MAX_ARCS", L.BATCH_MAX_ARCS), ("MCF_BATCH_MAX_NODES", L.BATCH_MAX_NODES), ("MCF_BATCH_MAX_INSTANCES", L.BATCH_MAX_INSTANCES)):
         assert f"#define {name} {value}" in header
+
+
+# ---- 13
+@pytest.mark.parametrize("rule", [O.RULE_BLOCK, O.RULE_BEST, O.RULE_FIRST])
+def test_adversarial_batch_on_the_host(rule):
+    """All outcomes at every search-range size round the wave's strides, 64-bit costs, ties, LEQ, lower bounds, infinite and zero
+    capacities (tests/adversarial.py): the pivot code with one lane equals the oracle on every instance."""
+    b = fuzz_solver(rule).run_on_host()
+    assert_fuzz_equals_oracle(b, rule)
+    assert b.stats()["total_pivots"] == sum(o.n_pivots for o, _, _ in fuzz_reference(rule))
+    check_padded_fuzz(lambda q: q.run_on_host(), rule)
+
+
+# ---- 14
+def test_the_ladder_straddles_every_class_limit():
+    steps = ladder()
+    assert {limit for _, _, limit, _ in steps} == {L // d for L in LDS_LIMITS for d in LDS_DIVISORS}
+    for (p, size, limit, fits), (q, size_q, limit_q, fits_q) in zip(steps[::2], steps[1::2]):
+        assert limit == limit_q and fits and not fits_q and q.m == p.m + 1 and q.n == p.n
+        assert size <= limit < size_q
+    for L in LDS_LIMITS:                                   # the tier edge itself is made of the 400-node family
+        assert [p.n for p, _, limit, _ in steps if limit == L] == [400, 400]
+
+
+def short_trace_problems():
+    return [generated(21), generated(22, 120, 500), generated(23, 260, 700)]
+
+
+def check_short_and_absent_traces(run, **kw):
+    """run: BatchSolver -> solved BatchSolver.  Half of the smallest pivot count as the capacity: every trace is the prefix of its own full
+    trace (nobody's pivots are recorded in a neighbour's), the pivot counts are the full ones; capacity 0: no trace, the same solve."""
+    problems = short_trace_problems()
+    full = M.BatchSolver(record_trace=1 << 13)
+    for p in problems:
+        full.add(p)
+    full.run_on_host()
+    counts = [full.pivots(i) for i in range(3)]
+    assert all(full.status(i) == M.SolverStatus.Optimal and 100 < counts[i] < 1 << 13 for i in range(3)) and len(set(counts)) == 3
+    for cap in (min(counts) // 2, 0):
+        b = M.BatchSolver(record_trace=cap, **kw)
+        for p in problems:
+            b.add(p)
+        run(b)
+        for i in range(3):
+            assert b.status(i) == M.SolverStatus.Optimal and b.pivots(i) == counts[i], (cap, i)
+            assert len(b.trace(i)) == cap and np.array_equal(b.trace(i), full.trace(i)[:cap]), (cap, i)
+            assert b.total_cost(i) == full.total_cost(i), (cap, i)
+            assert np.array_equal(b.flows(i), full.flows(i)) and np.array_equal(b.potentials(i), full.potentials(i)), (cap, i)
+        assert b.stats()["total_pivots"] == sum(counts)
+    return full
+
+
+# ---- 15
+def test_short_and_absent_traces_on_the_host():
+    check_short_and_absent_traces(lambda b: b.run_on_host())
+
+
+def only_bound_infeasible():
+    """Valid input with a defined answer: Infeasible by an arc whose upper bound is below its lower bound (NS.cs:227-231)."""
+    p = load("transport_2x3")
+    q = generated(31, 60, 200)
+    out = []
+    for base, arc in ((p, 0), (q, 17), (p, p.m - 1)):
+        upper = base.upper.copy()
+        upper[arc] = base.lower[arc] - 1
+        out.append(O.Problem(base.n, base.m, base.src, base.tgt, base.lower, upper, base.cost, base.supply))
+    return out
+
+
+def check_nothing_to_run(run):
+    b = M.BatchSolver(record_trace=64)
+    run(b)
+    st = b.stats()
+    assert len(b) == 0 and st["instances"] == 0 and st["launches"] == 0 and st["workspace_bytes"] == 0 and st["total_pivots"] == 0
+    assert st["lds_instances"] == 0 and st["global_instances"] == 0
+    with pytest.raises(M.McfError) as ei:
+        b.status(0)
+    assert ei.value.code == L.ERR_INVALID
+    b = M.BatchSolver(record_trace=64)
+    problems = only_bound_infeasible()
+    for p in problems:
+        b.add(p)
+    run(b)
+    st = b.stats()
+    assert st["instances"] == 3 and st["launches"] == 0 and st["workspace_bytes"] == 0 and st["total_pivots"] == 0
+    assert st["lds_instances"] == 0 and st["global_instances"] == 0
+    for i, p in enumerate(problems):
+        o, st_o, tr = oracle_of(p, O.RULE_BLOCK)
+        assert st_o == O.INFEASIBLE and o.n_pivots == 0
+        assert_equals_oracle(b, i, o, st_o, tr)
+
+
+# ---- 16
+def test_nothing_to_run_on_the_host():
+    check_nothing_to_run(lambda b: b.run_on_host())
+

@@ -9,6 +9,7 @@ import pytest
 
 import kat_data as K
 import mincostflow_amd as M
+from adversarial import random_problem as _random_problem
 from helpers import fixtures, load, problem_from_dict, validate_solution
 from mincostflow_amd import _lib as L
 from oracle import ns_oracle as O
@@ -533,23 +534,6 @@ def test_bench_scan_reports_sane_durations():
     assert 500 < mn <= avg < 5e6
     f, e, c = eng.find_entering()
     assert (f, e, c) == O.scan_best(m_s, a["state"], a["cost"], a["src"], a["tgt"], a["pi"])
-
-
-def _random_problem(rng, n, m, supply_kind):
-    src = rng.integers(0, n, m).astype(np.int32)
-    tgt = rng.integers(0, n, m).astype(np.int32)
-    lower = np.where(rng.random(m) < 0.15, rng.integers(0, 4, m), 0).astype(np.int64)
-    upper = (lower + rng.integers(0, 12, m)).astype(np.int64)
-    upper[rng.random(m) < 0.1] = O.INF_CAP
-    cost = rng.integers(-6 if supply_kind == "negative" else 0, 20, m).astype(np.int64)
-    supply = np.zeros(n, np.int64)
-    k = max(1, n // 4)
-    s = rng.integers(1, 9, k)
-    supply[rng.choice(n, k, replace=False)] += s
-    supply[rng.choice(n, k, replace=False)] -= rng.permutation(s)
-    if supply_kind == "excess":
-        supply[rng.integers(0, n)] += 3          # unbalanced: whatever the C# solver makes of it, both sides must agree
-    return O.Problem(n, m, src, tgt, lower, upper, cost, supply)
 
 
 @pytest.mark.parametrize("seed", range(12))
