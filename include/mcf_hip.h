@@ -662,7 +662,7 @@ MCF_API void mcf_batch_destroy(mcf_batch *b);
 MCF_API int mcf_batch_add(mcf_batch *b, int32_t node_count, int32_t arc_count, const int32_t *source, const int32_t *target,
                           const int64_t *lower, const int64_t *upper, const int64_t *cost, const int64_t *supply, int32_t supply_type,
                           int32_t *index);
-/* Solves every instance on the device.  Single-shot like Solve().  MCF_ERR_NO_DEVICE without a GPU. */
+/* Solves every instance on the device.  Single-shot like Solve() (new costs: mcf_batch_resolve below).  MCF_ERR_NO_DEVICE without a GPU. */
 MCF_API int mcf_batch_solve(mcf_batch *b);
 /* TEST HOOK, not a supported solver: the same step functions (csrc/batch_step.hip.h) run on the host with one lane, so that the tree
  * surgery can be put under a host sanitizer or debugger.  Takes the place of mcf_batch_solve for this batch. */
@@ -677,6 +677,52 @@ MCF_API int mcf_batch_get_pivots(mcf_batch *b, int32_t index, int64_t *pivots);
 /* copies min(capacity, recorded) entering arcs, *length = recorded (out may be NULL with capacity 0) */
 MCF_API int mcf_batch_get_trace(mcf_batch *b, int32_t index, int32_t *out, int64_t capacity, int64_t *length);
 MCF_API int mcf_batch_get_stats(mcf_batch *b, mcf_batch_stats *out);
+
+/* ---- Re-solving a solved batch with new arc costs ("Re-solve").
+ * After a cost change the basis a solve ended with is still primal feasible: only the potentials and the optimality test change.  The
+ * batch keeps every instance's state in device memory until mcf_batch_destroy, so a re-solve moves the new costs, not the instances.
+ * Supplies, bounds and topology cannot be changed: those need a new basis, that is a new batch.  mcf_batch_solve, mcf_batch_run_on_host
+ * and mcf_batch_add on a solved batch stay MCF_ERR_STATE.
+ *
+ * Per instance whose costs were set since the last solve:
+ *   - infeasible by its bounds (it never reached the device): stays MCF_INFEASIBLE with 0 pivots;
+ *   - last status MCF_OPTIMAL and no flow left on an artificial arc: WARM.  Tree, State[] and flows stay; the artificial arcs get the cost `(max |cost| + 1) * node_count` of
+ *     the new costs; the potentials are recomputed from the basis; the rule starts as at a cold start (_nextArc 0, the initial block size,
+ *     adaptation counters 0); pivot count and trace restart and describe this re-solve; the pivot limit applies to it;
+ *   - any other last status (Infeasible after pivots, Unbounded, Not Solved at the pivot limit): COLD, from the start basis: pivot for
+ *     pivot what a fresh batch gives with these costs.  Also cold: Optimal WITH flow on an artificial arc.  That is the reference's answer
+ *     to supplies that do not sum to zero the wrong way (a surplus under GEQ, a deficit under LEQ): it checks the root links only, the
+ *     answer does not conserve flow, and since artificial arcs never enter the basis again, which node keeps the surplus -- and with it
+ *     the total cost -- depends on the pivot path.
+ * Every other instance keeps status, cost, flows, potentials, pivot count and trace exactly.
+ * LIMIT.  The reference answers an uncapacitated negative cycle Optimal with a wrapped cost, and an eligible arc of capacity zero
+ * Unbounded; both depend on the path the pivots take, so a warm re-solve of such an instance may answer differently from a cold solve.
+ * For instances whose arcs all have finite, positive capacity after the lower-bound shift (upper - lower in [1, MCF_INF_CAP)), status and
+ * total cost are those of a cold solve with the new costs; flows and potentials are an optimal pair, not necessarily the cold solve's. */
+typedef struct mcf_batch_resolve_stats {
+    int64_t warm_instances;       /* changed, last status Optimal (no artificial flow): re-solved from the kept basis */
+    int64_t cold_instances;       /* changed, anything else: from the start basis (incl. the ones infeasible by their bounds) */
+    int64_t untouched_instances;  /* no new costs: left exactly as they were */
+    int64_t launches;             /* batch_kernel launches of this re-solve */
+    int64_t total_pivots;         /* of the instances that ran */
+    int64_t bytes_uploaded;       /* slots, cost arrays (warm) and whole workspaces (cold, or stale on the device); the 4-byte instance
+                                     ids that go with every round of launches are not counted */
+    int64_t bytes_downloaded;     /* slots after every round, the changing part of the instances that ran, their traces */
+    double kernel_ns;             /* host clock round the launches, each round ended by a synchronising copy */
+    double host_ns;               /* the rest of the call */
+} mcf_batch_resolve_stats;
+/* New costs for instance `index` (copied; [arc_count]).  Only after a solve of any kind: before one, costs come with mcf_batch_add
+ * (MCF_ERR_STATE).  May be called several times before a re-solve: the last call wins.  The instance's results are the old ones until
+ * the re-solve. */
+MCF_API int mcf_batch_set_costs(mcf_batch *b, int32_t index, const int64_t *cost);
+/* Re-solves every instance with new costs on the device.  MCF_ERR_STATE before the first solve (of either kind).  With no changed
+ * instance: MCF_OK, nothing is launched.  MCF_ERR_NO_DEVICE without a GPU; the batch is left as it was.  May be repeated, and mixed with
+ * mcf_batch_rerun_on_host in any order: the results are the same. */
+MCF_API int mcf_batch_resolve(mcf_batch *b);
+/* TEST HOOK like mcf_batch_run_on_host, not a supported solver: the same re-solve with one lane on the CPU. */
+MCF_API int mcf_batch_rerun_on_host(mcf_batch *b);
+/* what the last mcf_batch_resolve / mcf_batch_rerun_on_host did (all zero before one) */
+MCF_API int mcf_batch_get_resolve_stats(mcf_batch *b, mcf_batch_resolve_stats *out);
 
 #ifdef __cplusplus
 }

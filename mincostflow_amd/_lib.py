@@ -133,6 +133,15 @@ class BatchStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class BatchResolveStats(C.Structure):
+    """mcf_batch_resolve_stats"""
+    _fields_ = [("warm_instances", C.c_int64), ("cold_instances", C.c_int64), ("untouched_instances", C.c_int64), ("launches", C.c_int64),
+                ("total_pivots", C.c_int64), ("bytes_uploaded", C.c_int64), ("bytes_downloaded", C.c_int64), ("kernel_ns", C.c_double), ("host_ns", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 BATCH_MAX_ARCS, BATCH_MAX_NODES, BATCH_MAX_INSTANCES, BATCH_SHARDED = 65536, 32768, 65536, 1
 
 
@@ -272,6 +281,10 @@ SIGNATURES = {
     "mcf_batch_get_pivots": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int64)]),
     "mcf_batch_get_trace": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, _P(C.c_int64)]),
     "mcf_batch_get_stats": (C.c_int, [C.c_void_p, _P(BatchStats)]),
+    "mcf_batch_set_costs": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "mcf_batch_resolve": (C.c_int, [C.c_void_p]),
+    "mcf_batch_rerun_on_host": (C.c_int, [C.c_void_p]),
+    "mcf_batch_get_resolve_stats": (C.c_int, [C.c_void_p, _P(BatchResolveStats)]),
     "mcf_problem_free": (None, [_P(ProblemStruct)]),
     "mcf_gen_netgen_like": (C.c_int, [_P(ProblemStruct), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64]),

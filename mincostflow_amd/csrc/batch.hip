@@ -7,6 +7,9 @@
 //     there, the part that changes is copied back at exit.  Global tier: the pivots run in place on the workspace.  Same step functions;
 //   * bounded launches: a launch runs every unfinished instance for at most pivots_per_launch pivots and returns; the host relaunches
 //     until every instance is done.  The rule's state and the pivot count travel in the instance's BatchSlot.
+//   * re-solves: the slab, the slots and the trace buffer live as long as the batch.  mcf_batch_set_costs + mcf_batch_resolve run the changed
+//     instances again: from the basis they ended with where that ended Optimal (new cost[] up, batch_reprice on the device, changing part
+//     down), from the start basis otherwise.
 // Device code does no bounds checks: mcf_batch_add validates every end point (core_create), and every index the kernel follows after
 // that was written by start_basis or by the pivot itself.
 #include <hip/hip_runtime.h>
@@ -81,9 +84,13 @@ struct BatchSlot {
     int32_t next_arc, block_size, dyn_min, counters[2];
     int32_t trace_cap;
     int32_t run;                // mcf::BatchRun
-    int32_t pad;
+    int32_t reprice;            // a warm re-solve: the potentials are recomputed from the basis before the first pivot; the launch that did it clears this
+    uint64_t staged_cost;       // a re-solve's staging buffer: where this instance's new cost[] waits (stage_kernel<true>) ...
+    uint64_t staged_out;        // ... and where its changing part goes for the download (stage_kernel<false>)
     mcf_block_config cfg;
 };
+
+static_assert(sizeof(BatchSlot) == 104 + sizeof(mcf_block_config), "BatchSlot has no padding: a re-solve counts the bytes it uploads by it");
 
 __host__ __device__ inline void load_slot(mcf::BatchWork &w, const BatchSlot &s, int32_t *trace_base)
 {
@@ -102,6 +109,7 @@ __host__ __device__ inline void store_slot(BatchSlot &s, const mcf::BatchWork &w
     s.counters[0] = w.counters[0]; s.counters[1] = w.counters[1];
     s.pivots = w.pivots;
     s.run = w.run;
+    s.reprice = 0;
 }
 
 // One workgroup = one wave = one instance: ids[blockIdx.x].  kLds: dynamic LDS holds the workspace (the host launches with at least
@@ -112,6 +120,7 @@ __global__ __launch_bounds__(kBatchThreads) void batch_kernel(BatchSlot *slots, 
     extern __shared__ __align__(16) unsigned char lds[];
     const int lane = (int)threadIdx.x;
     BatchSlot &slot = slots[ids[blockIdx.x]];
+    const bool reprice = slot.reprice != 0;
     const Layout l = layout_of((uint32_t)slot.all_arcs, (uint32_t)slot.n + 1u);
     unsigned char *const home = slab + slot.workspace;
     mcf::BatchWork w;
@@ -125,6 +134,7 @@ __global__ __launch_bounds__(kBatchThreads) void batch_kernel(BatchSlot *slots, 
         bind(w, home, l);
     }
     __syncthreads();
+    if (reprice) mcf::batch_reprice(w, lane, kBatchThreads);        // on LDS in the LDS tier: the new cost[] came in with the copy above
     mcf::batch_run(w, lane, kBatchThreads, (int64_t)budget);
     __syncthreads();
     if (kLds) {
@@ -135,6 +145,22 @@ __global__ __launch_bounds__(kBatchThreads) void batch_kernel(BatchSlot *slots, 
     if (lane == 0) store_slot(slot, w);
 }
 
+// A re-solve moves only what changed.  Block k serves instance ids[k].  kIn: its new cost[0, all_arcs) (rounded up to 16 bytes, as the
+// layout is) from the staging buffer into its workspace; else: the changing part of its workspace into the staging buffer, from where
+// one copy takes every instance's home.  Both offsets are in the slot; the host sizes the staging buffer for the larger of the two sums.
+constexpr int kStageThreads = 256;
+template <bool kIn>
+__global__ __launch_bounds__(kStageThreads) void stage_kernel(const BatchSlot *slots, const int32_t *ids, unsigned char *slab, unsigned char *stage)
+{
+    const BatchSlot &slot = slots[ids[blockIdx.x]];
+    const Layout l = layout_of((uint32_t)slot.all_arcs, (uint32_t)slot.n + 1u);
+    unsigned char *const home = slab + slot.workspace;
+    const uint4 *const src = (const uint4 *)(kIn ? stage + slot.staged_cost : home + l.changing);
+    uint4 *const dst = (uint4 *)(kIn ? home + l.cost : stage + slot.staged_out);
+    const uint32_t count = (kIn ? l.upper - l.cost : l.bytes - l.changing) / 16;
+    for (uint32_t i = threadIdx.x; i < count; i += kStageThreads) dst[i] = src[i];
+}
+
 struct Instance {
     mcf::NsCore core;
     Layout layout{};
@@ -142,6 +168,24 @@ struct Instance {
     std::vector<int32_t> trace;
     int64_t trace_len = 0;
     bool on_device = false;     // false: infeasible by its bounds, nothing to run
+    bool on_slab = false;       // the workspace in device memory holds this instance's state as its last solve left it
+    bool changed = false;       // mcf_batch_set_costs since the last solve
+    std::vector<int64_t> new_cost;
+};
+
+struct DeviceBuffers {
+    unsigned char *slab = nullptr, *stage = nullptr;
+    BatchSlot *slots = nullptr;
+    int32_t *ids = nullptr, *traces = nullptr;
+    size_t stage_bytes = 0;
+    ~DeviceBuffers()
+    {
+        if (slab) (void)hipFree(slab);
+        if (stage) (void)hipFree(stage);
+        if (slots) (void)hipFree(slots);
+        if (ids) (void)hipFree(ids);
+        if (traces) (void)hipFree(traces);
+    }
 };
 
 }  // namespace
@@ -151,35 +195,79 @@ struct mcf_batch {
     std::vector<Instance *> inst;
     bool solved = false;
     mcf_batch_stats stats{};
+    mcf_batch_resolve_stats resolve_stats{};
+    // device memory lives until mcf_batch_destroy: a re-solve starts from the state the last solve left in the slab
+    DeviceBuffers dev;
+    uint64_t slab_bytes = 0, trace_entries = 0;
+    int lds_max = 0;
     ~mcf_batch() { for (Instance *i : inst) delete i; }
 };
 
 namespace {
 
-// NS.cs:237-270 per instance: the configuration `new NetworkSimplex(g).Solve()` chooses, the constructor's block size, the limits
+// the rule's state at a cold start (NS.cs:237-270: the constructor's block size), the counts and the limits
+int reset_run_state(const mcf_batch *b, Instance *in)
+{
+    const mcf::NsCore &c = in->core;
+    BatchSlot &s = in->slot;
+    s.next_arc = 0; s.block_size = 0; s.dyn_min = 0; s.counters[0] = s.counters[1] = 0;
+    if (s.rule == MCF_RULE_BLOCK_SEARCH) {
+        int32_t block = 0, dyn_min = 0;
+        if (const int rc = mcf_block_initial_size(&s.cfg, c.search_arcs, c.n, &block, &dyn_min)) return rc;
+        s.block_size = std::max(1, block);
+        s.dyn_min = dyn_min;
+    }
+    s.pivots = 0;
+    s.pivot_limit = b->d.pivot_limit > 0 ? b->d.pivot_limit : 64 * ((int64_t)c.m + 2 * (int64_t)c.n) + 1024;
+    s.max_iter = std::max<int64_t>(1000000, (int64_t)c.n * (int64_t)c.m);      // NS.cs:280
+    s.trace_cap = b->d.trace_capacity;
+    s.run = mcf::kBatchRunning;
+    s.reprice = 0;
+    in->trace_len = 0;
+    return MCF_OK;
+}
+
+// NS.cs:237-270 per instance: the configuration `new NetworkSimplex(g).Solve()` chooses, the constructor's block size, the limits.
+// Where the instance's workspace and trace lie does not depend on its costs: a second call (a cold re-solve) keeps them.
 int prepare_instance(const mcf_batch *b, Instance *in)
 {
     mcf::NsCore &c = in->core;
     BatchSlot &s = in->slot;
+    const uint64_t workspace = s.workspace, trace = s.trace;
     s = BatchSlot{};
+    s.workspace = workspace; s.trace = trace;
+    in->trace_len = 0;
     in->on_device = mcf::core_begin(&c);
     if (!in->on_device) return MCF_OK;
     int rc = mcf_block_config_auto(&s.cfg, c.n, c.m, c.tail.data(), c.head.data());
     if (rc) return rc;
     s.n = c.n; s.all_arcs = c.all_arcs; s.search_arcs = c.search_arcs; s.rule = b->d.pivot_rule;
-    if (s.rule == MCF_RULE_BLOCK_SEARCH) {
-        int32_t block = 0, dyn_min = 0;
-        rc = mcf_block_initial_size(&s.cfg, c.search_arcs, c.n, &block, &dyn_min);
-        if (rc) return rc;
-        s.block_size = std::max(1, block);
-        s.dyn_min = dyn_min;
-    }
-    s.pivot_limit = b->d.pivot_limit > 0 ? b->d.pivot_limit : 64 * ((int64_t)c.m + 2 * (int64_t)c.n) + 1024;
-    s.max_iter = std::max<int64_t>(1000000, (int64_t)c.n * (int64_t)c.m);      // NS.cs:280
-    s.trace_cap = b->d.trace_capacity;
-    s.run = mcf::kBatchRunning;
+    if ((rc = reset_run_state(b, in))) return rc;
     in->layout = layout_of((uint32_t)c.all_arcs, (uint32_t)c.n + 1u);
     in->trace.assign((size_t)std::max(0, b->d.trace_capacity), 0);
+    return MCF_OK;
+}
+
+// A changed instance before its re-solve.  Warm (its last solve ended Optimal with no flow on an artificial arc): tree, State[] and the standard-form flows stay, the new
+// costs go in, the rule's state, the pivot count and the trace start again; the potentials are the kernel's (or the hook's) to recompute.
+// Cold (any other ending): everything from the start basis, as in a fresh batch.
+int prepare_resolve(const mcf_batch *b, Instance *in, bool *warm)
+{
+    mcf::NsCore &c = in->core;
+    *warm = in->on_device && c.status == MCF_OPTIMAL;
+    // Optimal with flow left on an artificial arc is the reference's answer to a surplus it cannot place (core_finish looks at the root
+    // links only): the artificial arcs are never searched, so which node keeps the surplus depends on the pivot path.  Cold, like a fresh batch.
+    for (int e = c.m + c.n; *warm && e < c.all_arcs; ++e)
+        if (c.flow[e] != 0) *warm = false;
+    in->changed = false;
+    mcf::core_reopen(&c);           // supplies (and flows) in standard form again, whichever way the solve starts
+    if (!*warm) {
+        mcf::core_recost(&c, in->new_cost.data());
+        return prepare_instance(b, in);
+    }
+    mcf::core_recost(&c, in->new_cost.data());
+    if (const int rc = reset_run_state(b, in)) return rc;
+    in->slot.reprice = 1;
     return MCF_OK;
 }
 
@@ -210,30 +298,33 @@ void pack(const Instance *in, unsigned char *base)
     memcpy(base + l.sub, c.sub.data(), 4 * N); memcpy(base + l.fin, c.fin.data(), 4 * N);
     memcpy(base + l.state, c.state.data(), A); memcpy(base + l.par_dir, c.par_dir.data(), N);
 }
-void unpack(Instance *in, const unsigned char *base)
+// part: the changing part of the instance's workspace (Layout::changing onwards)
+void unpack(Instance *in, const unsigned char *part)
 {
     mcf::NsCore &c = in->core;
     const Layout &l = in->layout;
     const size_t A = (size_t)c.all_arcs, N = (size_t)c.n + 1;
-    memcpy(c.flow.data(), base + l.flow, 8 * A); memcpy(c.pi.data(), base + l.pi, 8 * N);
-    memcpy(c.par.data(), base + l.par, 4 * N); memcpy(c.par_arc.data(), base + l.par_arc, 4 * N);
-    memcpy(c.nxt.data(), base + l.nxt, 4 * N); memcpy(c.prv.data(), base + l.prv, 4 * N);
-    memcpy(c.sub.data(), base + l.sub, 4 * N); memcpy(c.fin.data(), base + l.fin, 4 * N);
-    memcpy(c.state.data(), base + l.state, A); memcpy(c.par_dir.data(), base + l.par_dir, N);
+    const auto at = [&](uint32_t offset) { return part + (offset - l.changing); };
+    memcpy(c.flow.data(), at(l.flow), 8 * A); memcpy(c.pi.data(), at(l.pi), 8 * N);
+    memcpy(c.par.data(), at(l.par), 4 * N); memcpy(c.par_arc.data(), at(l.par_arc), 4 * N);
+    memcpy(c.nxt.data(), at(l.nxt), 4 * N); memcpy(c.prv.data(), at(l.prv), 4 * N);
+    memcpy(c.sub.data(), at(l.sub), 4 * N); memcpy(c.fin.data(), at(l.fin), 4 * N);
+    memcpy(c.state.data(), at(l.state), A); memcpy(c.par_dir.data(), at(l.par_dir), N);
 }
 
-struct DeviceBuffers {
-    unsigned char *slab = nullptr;
-    BatchSlot *slots = nullptr;
-    int32_t *ids = nullptr, *traces = nullptr;
-    ~DeviceBuffers()
-    {
-        if (slab) (void)hipFree(slab);
-        if (slots) (void)hipFree(slots);
-        if (ids) (void)hipFree(ids);
-        if (traces) (void)hipFree(traces);
-    }
-};
+// the pivots of one instance with one lane on the host (the test hooks)
+void run_instance_on_host(Instance *in)
+{
+    mcf::NsCore &c = in->core;
+    mcf::BatchWork w{};
+    load_slot(w, in->slot, in->trace.data());
+    w.trace = in->slot.trace_cap > 0 ? in->trace.data() : nullptr;      // the host keeps a trace per instance, not one buffer
+    static_cast<mcf::TreeView &>(w) = c.tree();
+    w.cost = c.cost.data(); w.state = c.state.data(); w.pi = c.pi.data();
+    if (in->slot.reprice) mcf::batch_reprice(w, 0, 1);
+    mcf::batch_run(w, 0, 1, INT64_MAX);
+    store_slot(in->slot, w);
+}
 
 int at(mcf_batch *b, int32_t index, Instance **out)
 {
@@ -247,7 +338,136 @@ int at(mcf_batch *b, int32_t index, Instance **out)
 int begin_solve(mcf_batch *b)
 {
     if (!b) return mcf::fail(MCF_ERR_INVALID, "null batch");
-    if (b->solved) return mcf::fail(MCF_ERR_STATE, "a batch is solved once (Solve() is single-shot, NS.cs:649); create a new batch");
+    if (b->solved) return mcf::fail(MCF_ERR_STATE, "a batch is solved once (Solve() is single-shot, NS.cs:649); create a new batch, or give it new costs (mcf_batch_set_costs) and re-solve");
+    return MCF_OK;
+}
+
+int begin_resolve(mcf_batch *b, const char *what)
+{
+    if (!b) return mcf::fail(MCF_ERR_INVALID, "null batch");
+    if (!b->solved) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
+    return MCF_OK;
+}
+
+int have_device(const mcf_batch *b, const char *what)
+{
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices < 1) { (void)hipGetLastError(); return mcf::fail(MCF_ERR_NO_DEVICE, "%s: no HIP device (the host hooks are test hooks, not solvers)", what); }
+    if (b->d.device >= devices) return mcf::fail(MCF_ERR_NO_DEVICE, "%s: device %d of %d", what, b->d.device, devices);
+    return MCF_OK;
+}
+
+int open_device(mcf_batch *b)
+{
+    HIP_TRY(hipSetDevice(b->d.device));
+    // the LDS one workgroup may have: the device's figure, never a constant of ours
+    int lds_max = 0, lds_optin = 0;
+    HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, b->d.device));
+    if (hipDeviceGetAttribute(&lds_optin, hipDeviceAttributeSharedMemPerBlockOptin, b->d.device) != hipSuccess) { (void)hipGetLastError(); lds_optin = 0; }
+    if (lds_optin > lds_max) lds_max = lds_optin;
+    // the opt-in for dynamic LDS above the default limit; where the runtime refuses it, the default limit of 64 KiB holds
+    if (hipFuncSetAttribute((const void *)batch_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) {
+        (void)hipGetLastError();
+        lds_max = std::min(lds_max, 64 << 10);
+    }
+    b->lds_max = lds_max;
+    return MCF_OK;
+}
+
+// Groups: the LDS tier in classes of the footprint (lds_max / 16, / 8, / 4, / 3, / 2, / 1: the steps at which one more workgroup fits a CU),
+// each launched with the largest footprint it holds, so that no launch sizes every workgroup for the batch's largest; the global tier last.
+constexpr int kClasses = 7;
+int class_of(const mcf_batch *b, const Instance *in)
+{
+    const int divisor[kClasses - 1] = {16, 8, 4, 3, 2, 1};
+    for (int k = 0; k < kClasses - 1; ++k)
+        if ((int64_t)in->layout.bytes <= (int64_t)b->lds_max / divisor[k]) return k;
+    return kClasses - 1;
+}
+
+// places the workspaces and the traces of the instances that run on the device and allocates the device's buffers
+int allocate(mcf_batch *b)
+{
+    const size_t count = b->inst.size();
+    b->slab_bytes = b->trace_entries = 0;
+    for (Instance *in : b->inst) {
+        if (!in->on_device) continue;
+        in->slot.workspace = b->slab_bytes; b->slab_bytes += in->layout.bytes;
+        in->slot.trace = b->trace_entries; b->trace_entries += (uint64_t)in->slot.trace_cap;
+    }
+    if (!b->slab_bytes) return MCF_OK;
+    HIP_TRY(hipMalloc((void **)&b->dev.slab, (size_t)b->slab_bytes));
+    HIP_TRY(hipMalloc((void **)&b->dev.slots, count * sizeof(BatchSlot)));
+    HIP_TRY(hipMalloc((void **)&b->dev.ids, count * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void **)&b->dev.traces, (size_t)std::max<uint64_t>(b->trace_entries, 1) * sizeof(int32_t)));
+    return MCF_OK;
+}
+
+struct LaunchTotals {
+    int64_t launches = 0, lds_bytes_max = 0, bytes_down = 0;
+    double kernel_ns = 0;
+};
+
+// Relaunches the instances `run` (ascending; their slots are on the device) until none is left running; every round ends in a
+// synchronising copy of the slots between the first and the last of them.  slots: the host's copy of every slot.
+int run_launches(mcf_batch *b, std::vector<BatchSlot> &slots, const std::vector<int32_t> &run, LaunchTotals *t)
+{
+    if (run.empty()) return MCF_OK;
+    std::vector<int32_t> group[kClasses];
+    for (int32_t i : run) group[class_of(b, b->inst[(size_t)i])].push_back(i);
+    const size_t lo = (size_t)run.front(), span = (size_t)run.back() - lo + 1;
+    const int32_t budget = b->d.pivots_per_launch > 0 ? b->d.pivots_per_launch : kDefaultPivotsPerLaunch;
+    DeviceBuffers &dev = b->dev;
+    std::vector<int32_t> ids;
+    for (;;) {
+        ids.clear();
+        struct Launch { int first, n; uint32_t lds; bool in_lds; };
+        std::vector<Launch> launches;
+        for (int g = 0; g < kClasses; ++g) {
+            Launch L{(int)ids.size(), 0, 0, g != kClasses - 1};
+            for (int32_t i : group[g]) {
+                if (slots[(size_t)i].run != mcf::kBatchRunning) continue;
+                ids.push_back(i);
+                L.n++;
+                L.lds = std::max(L.lds, b->inst[(size_t)i]->layout.bytes);
+            }
+            if (L.n) launches.push_back(L);
+        }
+        if (launches.empty()) break;
+        const double tk = mcf::now_ns();
+        HIP_TRY(hipMemcpy(dev.ids, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        for (const Launch &L : launches) {
+            if (L.in_lds) {
+                hipLaunchKernelGGL(batch_kernel<true>, dim3((unsigned)L.n), dim3(kBatchThreads), L.lds, 0, dev.slots, dev.ids + L.first, dev.slab, dev.traces, budget);
+                t->lds_bytes_max = std::max<int64_t>(t->lds_bytes_max, L.lds);
+            } else {
+                hipLaunchKernelGGL(batch_kernel<false>, dim3((unsigned)L.n), dim3(kBatchThreads), 0, 0, dev.slots, dev.ids + L.first, dev.slab, dev.traces, budget);
+            }
+            HIP_TRY(hipGetLastError());
+            t->launches++;
+        }
+        HIP_TRY(hipMemcpy(slots.data() + lo, dev.slots + lo, span * sizeof(BatchSlot), hipMemcpyDeviceToHost));     // waits for the launches
+        t->bytes_down += (int64_t)(span * sizeof(BatchSlot));
+        t->kernel_ns += mcf::now_ns() - tk;
+    }
+    return MCF_OK;
+}
+
+// the recorded entering arcs of the instances `run`, from one copy of the trace buffer between the first and the last of them
+int fetch_traces(mcf_batch *b, const std::vector<int32_t> &run, int64_t *bytes_down)
+{
+    if (run.empty() || !b->trace_entries) return MCF_OK;
+    const Instance *first = b->inst[(size_t)run.front()], *last = b->inst[(size_t)run.back()];
+    const uint64_t lo = first->slot.trace, hi = last->slot.trace + (uint64_t)last->slot.trace_cap;
+    std::vector<int32_t> traces((size_t)(hi - lo));
+    if (hi > lo) HIP_TRY(hipMemcpy(traces.data(), b->dev.traces + lo, (size_t)(hi - lo) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    *bytes_down += (int64_t)((hi - lo) * sizeof(int32_t));
+    for (int32_t i : run) {
+        Instance *in = b->inst[(size_t)i];
+        const int64_t len = std::min<int64_t>(in->slot.pivots, in->slot.trace_cap);
+        const ptrdiff_t from = (ptrdiff_t)(in->slot.trace - lo);
+        if (len > 0) std::copy(traces.begin() + from, traces.begin() + from + (ptrdiff_t)len, in->trace.begin());
+    }
     return MCF_OK;
 }
 
@@ -308,13 +528,7 @@ int mcf_batch_run_on_host(mcf_batch *b)
     for (Instance *in : b->inst) {
         if (const int rc = prepare_instance(b, in)) return rc;
         if (in->on_device) {
-            mcf::NsCore &c = in->core;
-            mcf::BatchWork w{};
-            load_slot(w, in->slot, in->trace.data());
-            static_cast<mcf::TreeView &>(w) = c.tree();
-            w.cost = c.cost.data(); w.state = c.state.data(); w.pi = c.pi.data();
-            mcf::batch_run(w, 0, 1, INT64_MAX);
-            store_slot(in->slot, w);
+            run_instance_on_host(in);
             total += in->slot.pivots;
         }
         finish_instance(in);
@@ -327,118 +541,206 @@ int mcf_batch_run_on_host(mcf_batch *b)
 int mcf_batch_solve(mcf_batch *b)
 {
     if (const int rc = begin_solve(b)) return rc;
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices < 1) { (void)hipGetLastError(); return mcf::fail(MCF_ERR_NO_DEVICE, "mcf_batch_solve: no HIP device (mcf_batch_run_on_host is a test hook, not a solver)"); }
-    if (b->d.device >= devices) return mcf::fail(MCF_ERR_NO_DEVICE, "mcf_batch_solve: device %d of %d", b->d.device, devices);
+    if (const int rc = have_device(b, "mcf_batch_solve")) return rc;
     const double t_start = mcf::now_ns();
-    double kernel_ns = 0;
     b->solved = true;
-    HIP_TRY(hipSetDevice(b->d.device));
-    // the LDS one workgroup may have: the device's figure, never a constant of ours
-    int lds_max = 0, lds_optin = 0;
-    HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, b->d.device));
-    if (hipDeviceGetAttribute(&lds_optin, hipDeviceAttributeSharedMemPerBlockOptin, b->d.device) != hipSuccess) { (void)hipGetLastError(); lds_optin = 0; }
-    if (lds_optin > lds_max) lds_max = lds_optin;
-    // the opt-in for dynamic LDS above the default limit; where the runtime refuses it, the default limit of 64 KiB holds
-    if (hipFuncSetAttribute((const void *)batch_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) {
-        (void)hipGetLastError();
-        lds_max = std::min(lds_max, 64 << 10);
-    }
+    if (const int rc = open_device(b)) return rc;
 
     // set every instance up; place the workspaces
     const size_t count = b->inst.size();
-    std::vector<BatchSlot> slots(count);
-    uint64_t slab_bytes = 0, trace_entries = 0;
-    for (size_t i = 0; i < count; ++i) {
-        Instance *in = b->inst[i];
+    for (Instance *in : b->inst)
         if (const int rc = prepare_instance(b, in)) return rc;
-        if (in->on_device) {
-            in->slot.workspace = slab_bytes; slab_bytes += in->layout.bytes;
-            in->slot.trace = trace_entries; trace_entries += (uint64_t)in->slot.trace_cap;
-        }
-        slots[i] = in->slot;
-    }
-    // Groups: the LDS tier in classes of the footprint (lds_max / 16, / 8, / 4, / 3, / 2, / 1: the steps at which one more workgroup fits a CU),
-    // each launched with the largest footprint it holds, so that no launch sizes every workgroup for the batch's largest; the global tier last.
-    const int kClasses = 7;
-    const int divisor[kClasses - 1] = {16, 8, 4, 3, 2, 1};
-    std::vector<int32_t> group[kClasses];
+    if (const int rc = allocate(b)) return rc;
+    std::vector<BatchSlot> slots(count);
+    std::vector<int32_t> run;
     for (size_t i = 0; i < count; ++i) {
         const Instance *in = b->inst[i];
+        slots[i] = in->slot;
         if (!in->on_device) continue;
-        int g = kClasses - 1;
-        for (int k = 0; k < kClasses - 1; ++k)
-            if ((int64_t)in->layout.bytes <= (int64_t)lds_max / divisor[k]) { g = k; break; }
-        group[g].push_back((int32_t)i);
-        if (g == kClasses - 1) b->stats.global_instances++; else b->stats.lds_instances++;
+        run.push_back((int32_t)i);
+        if (class_of(b, in) == kClasses - 1) b->stats.global_instances++; else b->stats.lds_instances++;
     }
-    b->stats.workspace_bytes = (int64_t)slab_bytes;
+    b->stats.workspace_bytes = (int64_t)b->slab_bytes;
 
-    DeviceBuffers dev;
-    std::vector<unsigned char> host_slab((size_t)slab_bytes);
-    if (slab_bytes) {
-        for (const Instance *in : b->inst) if (in->on_device) pack(in, host_slab.data() + in->slot.workspace);
-        HIP_TRY(hipMalloc((void **)&dev.slab, (size_t)slab_bytes));
-        HIP_TRY(hipMalloc((void **)&dev.slots, count * sizeof(BatchSlot)));
-        HIP_TRY(hipMalloc((void **)&dev.ids, count * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&dev.traces, (size_t)std::max<uint64_t>(trace_entries, 1) * sizeof(int32_t)));
-        HIP_TRY(hipMemcpy(dev.slab, host_slab.data(), (size_t)slab_bytes, hipMemcpyHostToDevice));
+    DeviceBuffers &dev = b->dev;
+    std::vector<unsigned char> host_slab((size_t)b->slab_bytes);
+    if (b->slab_bytes) {
+        for (Instance *in : b->inst) if (in->on_device) { pack(in, host_slab.data() + in->slot.workspace); in->on_slab = true; }
+        HIP_TRY(hipMemcpy(dev.slab, host_slab.data(), (size_t)b->slab_bytes, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dev.slots, slots.data(), count * sizeof(BatchSlot), hipMemcpyHostToDevice));
     }
-    const int32_t budget = b->d.pivots_per_launch > 0 ? b->d.pivots_per_launch : kDefaultPivotsPerLaunch;
-    // relaunch until nobody is left running; every round ends in a synchronising copy of the slots
-    std::vector<int32_t> ids;
-    for (;;) {
-        ids.clear();
-        struct Launch { int first, n; uint32_t lds; bool in_lds; };
-        std::vector<Launch> launches;
-        for (int g = 0; g < kClasses; ++g) {
-            Launch L{(int)ids.size(), 0, 0, g != kClasses - 1};
-            for (int32_t i : group[g]) {
-                if (slots[(size_t)i].run != mcf::kBatchRunning) continue;
-                ids.push_back(i);
-                L.n++;
-                L.lds = std::max(L.lds, b->inst[(size_t)i]->layout.bytes);
-            }
-            if (L.n) launches.push_back(L);
-        }
-        if (launches.empty()) break;
-        const double tk = mcf::now_ns();
-        HIP_TRY(hipMemcpy(dev.ids, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        for (const Launch &L : launches) {
-            if (L.in_lds) {
-                hipLaunchKernelGGL(batch_kernel<true>, dim3((unsigned)L.n), dim3(kBatchThreads), L.lds, 0, dev.slots, dev.ids + L.first, dev.slab, dev.traces, budget);
-                b->stats.lds_bytes_max = std::max<int64_t>(b->stats.lds_bytes_max, L.lds);
-            } else {
-                hipLaunchKernelGGL(batch_kernel<false>, dim3((unsigned)L.n), dim3(kBatchThreads), 0, 0, dev.slots, dev.ids + L.first, dev.slab, dev.traces, budget);
-            }
-            HIP_TRY(hipGetLastError());
-            b->stats.launches++;
-        }
-        HIP_TRY(hipMemcpy(slots.data(), dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));     // waits for the launches
-        kernel_ns += mcf::now_ns() - tk;
-    }
+    LaunchTotals t;
+    if (const int rc = run_launches(b, slots, run, &t)) return rc;
+    b->stats.launches = t.launches;
+    b->stats.lds_bytes_max = t.lds_bytes_max;
     // the state comes home; the host finishes every instance
-    std::vector<int32_t> traces((size_t)trace_entries);
-    if (slab_bytes) {
-        HIP_TRY(hipMemcpy(host_slab.data(), dev.slab, (size_t)slab_bytes, hipMemcpyDeviceToHost));
-        if (trace_entries) HIP_TRY(hipMemcpy(traces.data(), dev.traces, (size_t)trace_entries * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (b->slab_bytes) HIP_TRY(hipMemcpy(host_slab.data(), dev.slab, (size_t)b->slab_bytes, hipMemcpyDeviceToHost));
+    for (int32_t i : run) {
+        Instance *in = b->inst[(size_t)i];
+        in->slot = slots[(size_t)i];
+        unpack(in, host_slab.data() + in->slot.workspace + in->layout.changing);
     }
+    int64_t unused = 0;
+    if (const int rc = fetch_traces(b, run, &unused)) return rc;
     int64_t total = 0;
-    for (size_t i = 0; i < count; ++i) {
-        Instance *in = b->inst[i];
-        if (in->on_device) {
-            in->slot = slots[i];
-            unpack(in, host_slab.data() + in->slot.workspace);
-            const int64_t len = std::min<int64_t>(in->slot.pivots, in->slot.trace_cap);
-            if (len > 0) std::copy(traces.begin() + (ptrdiff_t)in->slot.trace, traces.begin() + (ptrdiff_t)(in->slot.trace + (uint64_t)len), in->trace.begin());
-            total += in->slot.pivots;
-        }
+    for (Instance *in : b->inst) {
+        if (in->on_device) total += in->slot.pivots;
         finish_instance(in);
     }
     b->stats.total_pivots = total;
-    b->stats.kernel_ns = kernel_ns;
-    b->stats.host_ns = mcf::now_ns() - t_start - kernel_ns;
+    b->stats.kernel_ns = t.kernel_ns;
+    b->stats.host_ns = mcf::now_ns() - t_start - t.kernel_ns;
+    return MCF_OK;
+}
+
+int mcf_batch_set_costs(mcf_batch *b, int32_t index, const int64_t *cost)
+{
+    Instance *in = nullptr;
+    if (!b || !cost) return mcf::fail(MCF_ERR_INVALID, "mcf_batch_set_costs: null argument");
+    if (const int rc = at(b, index, &in)) return rc;        // MCF_ERR_STATE before a solve: until then the costs come with mcf_batch_add
+    in->new_cost.assign(cost, cost + in->core.m);
+    in->changed = true;
+    return MCF_OK;
+}
+
+int mcf_batch_rerun_on_host(mcf_batch *b)
+{
+    if (const int rc = begin_resolve(b, "mcf_batch_rerun_on_host")) return rc;
+    const double t0 = mcf::now_ns();
+    mcf_batch_resolve_stats st{};
+    for (Instance *in : b->inst) {
+        if (!in->changed) { st.untouched_instances++; continue; }
+        bool warm = false;
+        if (const int rc = prepare_resolve(b, in, &warm)) return rc;
+        if (warm) st.warm_instances++; else st.cold_instances++;
+        if (in->on_device) {
+            run_instance_on_host(in);
+            st.total_pivots += in->slot.pivots;
+            in->on_slab = false;            // the device's copy is stale: the next mcf_batch_resolve packs this instance again
+        }
+        finish_instance(in);
+    }
+    st.host_ns = mcf::now_ns() - t0;
+    b->resolve_stats = st;
+    return MCF_OK;
+}
+
+int mcf_batch_resolve(mcf_batch *b)
+{
+    if (const int rc = begin_resolve(b, "mcf_batch_resolve")) return rc;
+    const size_t count = b->inst.size();
+    std::vector<int32_t> changed;
+    for (size_t i = 0; i < count; ++i)
+        if (b->inst[i]->changed) changed.push_back((int32_t)i);
+    mcf_batch_resolve_stats st{};
+    st.untouched_instances = (int64_t)(count - changed.size());
+    if (changed.empty()) { b->resolve_stats = st; return MCF_OK; }          // nothing to launch: no device needed either
+    if (const int rc = have_device(b, "mcf_batch_resolve")) return rc;       // the batch is as it was
+    const double t_start = mcf::now_ns();
+    if (const int rc = open_device(b)) return rc;
+    DeviceBuffers &dev = b->dev;
+
+    // Warm instances whose state is in the slab get their new cost[] (through the staging buffer) and their slot; every other instance
+    // that runs -- cold, or never packed since the host hooks last ran it -- gets its whole workspace.
+    std::vector<int32_t> run, staged;
+    uint64_t stage_in = 0, stage_out = 0;
+    for (int32_t i : changed) {
+        Instance *in = b->inst[(size_t)i];
+        bool warm = false;
+        if (const int rc = prepare_resolve(b, in, &warm)) return rc;
+        if (warm) st.warm_instances++; else st.cold_instances++;
+        if (!in->on_device) continue;                                       // infeasible by its bounds, whatever the costs
+        run.push_back(i);
+        if (warm && in->on_slab) {
+            staged.push_back(i);
+            in->slot.staged_cost = stage_in; stage_in += in->layout.upper - in->layout.cost;
+        }
+        in->slot.staged_out = stage_out; stage_out += in->layout.bytes - in->layout.changing;
+    }
+    if (!run.empty() && !dev.slab)                                          // the first solve was mcf_batch_run_on_host
+        if (const int rc = allocate(b)) return rc;
+    std::vector<BatchSlot> slots(count);
+    for (size_t i = 0; i < count; ++i) slots[i] = b->inst[i]->slot;
+    LaunchTotals t;
+    if (!run.empty()) {
+        const uint64_t stage_need = std::max(stage_in, stage_out);
+        if (dev.stage_bytes < stage_need) {
+            if (dev.stage) { HIP_TRY(hipFree(dev.stage)); dev.stage = nullptr; dev.stage_bytes = 0; }
+            HIP_TRY(hipMalloc((void **)&dev.stage, (size_t)stage_need));
+            dev.stage_bytes = (size_t)stage_need;
+        }
+        const size_t lo = (size_t)run.front(), span = (size_t)run.back() - lo + 1;
+        HIP_TRY(hipMemcpy(dev.slots + lo, slots.data() + lo, span * sizeof(BatchSlot), hipMemcpyHostToDevice));
+        st.bytes_uploaded += (int64_t)(span * sizeof(BatchSlot));
+        std::vector<unsigned char> buffer;
+        if (!staged.empty()) {
+            buffer.assign((size_t)stage_in, 0);
+            for (int32_t i : staged) {
+                const Instance *in = b->inst[(size_t)i];
+                memcpy(buffer.data() + in->slot.staged_cost, in->core.cost.data(), 8 * (size_t)in->core.all_arcs);
+            }
+            HIP_TRY(hipMemcpy(dev.stage, buffer.data(), (size_t)stage_in, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(dev.ids, staged.data(), staged.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(stage_kernel<true>, dim3((unsigned)staged.size()), dim3(kStageThreads), 0, 0, dev.slots, dev.ids, dev.slab, dev.stage);
+            HIP_TRY(hipGetLastError());
+            st.bytes_uploaded += (int64_t)stage_in;
+        }
+        // whole workspaces: neighbours in the slab go in one copy
+        for (size_t k = 0; k < run.size();) {
+            Instance *in = b->inst[(size_t)run[k]];
+            if (in->on_slab && in->slot.reprice) { ++k; continue; }
+            const uint64_t begin = in->slot.workspace;
+            uint64_t end = begin;
+            size_t j = k;
+            for (; j < run.size(); ++j) {
+                Instance *next = b->inst[(size_t)run[j]];
+                if ((next->on_slab && next->slot.reprice) || next->slot.workspace != end) break;
+                end += next->layout.bytes;
+            }
+            buffer.assign((size_t)(end - begin), 0);
+            for (size_t q = k; q < j; ++q) {
+                Instance *next = b->inst[(size_t)run[q]];
+                pack(next, buffer.data() + (next->slot.workspace - begin));
+                next->on_slab = true;
+            }
+            HIP_TRY(hipMemcpy(dev.slab + begin, buffer.data(), (size_t)(end - begin), hipMemcpyHostToDevice));
+            st.bytes_uploaded += (int64_t)(end - begin);
+            k = j;
+        }
+        if (const int rc = run_launches(b, slots, run, &t)) return rc;
+        // only the changing part of the instances that ran comes home
+        HIP_TRY(hipMemcpy(dev.ids, run.data(), run.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(stage_kernel<false>, dim3((unsigned)run.size()), dim3(kStageThreads), 0, 0, dev.slots, dev.ids, dev.slab, dev.stage);
+        HIP_TRY(hipGetLastError());
+        buffer.resize((size_t)stage_out);
+        HIP_TRY(hipMemcpy(buffer.data(), dev.stage, (size_t)stage_out, hipMemcpyDeviceToHost));
+        t.bytes_down += (int64_t)stage_out;
+        for (int32_t i : run) {
+            Instance *in = b->inst[(size_t)i];
+            const uint64_t staged_out = in->slot.staged_out;
+            in->slot = slots[(size_t)i];
+            unpack(in, buffer.data() + staged_out);
+        }
+        if (const int rc = fetch_traces(b, run, &t.bytes_down)) return rc;
+    }
+    for (int32_t i : changed) {
+        Instance *in = b->inst[(size_t)i];
+        if (in->on_device) st.total_pivots += in->slot.pivots;
+        finish_instance(in);
+    }
+    st.launches = t.launches;
+    st.bytes_downloaded = t.bytes_down;
+    st.kernel_ns = t.kernel_ns;
+    st.host_ns = mcf::now_ns() - t_start - t.kernel_ns;
+    b->resolve_stats = st;
+    return MCF_OK;
+}
+
+int mcf_batch_get_resolve_stats(mcf_batch *b, mcf_batch_resolve_stats *out)
+{
+    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
+    if (!b->solved) return mcf::fail(MCF_ERR_STATE, "the batch has not been solved");
+    *out = b->resolve_stats;
     return MCF_OK;
 }
 

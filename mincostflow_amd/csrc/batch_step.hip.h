@@ -212,6 +212,26 @@ MCF_HD inline bool batch_pivot(BatchWork &w, int in_arc)
     return false;
 }
 
+// ---- the potentials of a basis under costs it was not built with (a warm re-solve): pi[root] = 0, then down the thread
+// list, which is a preorder, so a node's parent has its potential first; each node's tree arc gets reduced cost 0 in batch_reduced_cost's
+// convention (cost + pi[tail] - pi[head]; an arc with par_dir kUp leaves the node, so pi[u] = pi[parent] - par_dir[u] * cost).  Exactly n
+// steps by count: a thread list that is not what rehang_subtree leaves cannot make this spin.  Sequential like batch_pivot: lane 0 runs it.
+MCF_HD inline void batch_reprice(BatchWork &w, int lane, int lanes)
+{
+    (void)lanes;
+    lanes_sync();
+    if (lane == 0) {
+        const int root = w.n;
+        w.pi[root] = 0;
+        int u = w.nxt[root];
+        for (int i = 0; i < w.n && (unsigned)u < (unsigned)root; ++i) {        // a node, not the root: the root has no tree arc
+            w.pi[u] = w.pi[w.par[u]] - w.par_dir[u] * w.cost[w.par_arc[u]];
+            u = w.nxt[u];
+        }
+    }
+    lanes_sync();
+}
+
 // ---- at most `budget` pivots of the main loop (NS.cs:283-336).  Every lane runs this with its own copy of the scalars in w, and they stay equal.
 MCF_HD inline void batch_run(BatchWork &w, int lane, int lanes, int64_t budget)
 {

@@ -15,6 +15,13 @@ bool bounds_ok(const NsCore *s)
     return true;
 }
 
+int64_t art_cost_of(const NsCore *s)
+{
+    int64_t biggest = 0;
+    for (int e = 0; e < s->m; ++e) biggest = std::max<int64_t>(biggest, s->cost[e] < 0 ? -s->cost[e] : s->cost[e]);
+    return (biggest + 1) * (int64_t)s->n;
+}
+
 void to_standard_form(NsCore *s)
 {
     for (int e = 0; e < s->m; ++e) {
@@ -27,9 +34,7 @@ void to_standard_form(NsCore *s)
     }
     s->sum_supply = 0;
     for (int v = 0; v < s->n; ++v) s->sum_supply += s->supply[v];
-    int64_t biggest = 0;
-    for (int e = 0; e < s->m; ++e) biggest = std::max<int64_t>(biggest, s->cost[e] < 0 ? -s->cost[e] : s->cost[e]);
-    s->art_cost = (biggest + 1) * (int64_t)s->n;
+    s->art_cost = art_cost_of(s);
     s->transformed = true;
 }
 
@@ -82,6 +87,7 @@ void start_basis(NsCore *s)
 bool core_begin(NsCore *s)
 {
     s->status = MCF_NOT_SOLVED;
+    s->bounds_restored = false;
     if (!bounds_ok(s)) { s->status = MCF_INFEASIBLE; return false; }   // NS.cs:227-231
     to_standard_form(s);
     start_basis(s);
@@ -101,6 +107,28 @@ void core_finish(NsCore *s)
         s->supply[s->tail[e]] += lo;
         s->supply[s->head[e]] -= lo;
     }
+    s->bounds_restored = true;
+}
+
+void core_reopen(NsCore *s)
+{
+    s->status = MCF_NOT_SOLVED;
+    if (!s->bounds_restored) return;
+    for (int e = 0; e < s->m; ++e) {
+        const int64_t lo = s->orig_lower[e];
+        if (lo == 0) continue;
+        s->flow[e] -= lo;
+        s->supply[s->tail[e]] -= lo;
+        s->supply[s->head[e]] += lo;
+    }
+    s->bounds_restored = false;
+}
+
+void core_recost(NsCore *s, const int64_t *cost)
+{
+    std::copy(cost, cost + s->m, s->cost.begin());
+    s->art_cost = art_cost_of(s);
+    for (int e = s->m + s->n; e < s->all_arcs; ++e) s->cost[e] = s->art_cost;
 }
 
 int64_t core_total_cost(const NsCore *s)

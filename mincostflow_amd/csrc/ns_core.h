@@ -26,6 +26,7 @@ struct NsCore {
     int64_t sum_supply = 0, art_cost = 0;
     int status = MCF_NOT_SOLVED;
     bool transformed = false;
+    bool bounds_restored = false;                     // core_finish has added the lower bounds to flow[] and supply[]; core_reopen takes them out again
 
     // the arrays a pivot touches; valid as long as the vectors are not resized (core_create sizes them, nothing does after it)
     TreeView tree()
@@ -43,6 +44,13 @@ void core_set_problem(NsCore *s, const int64_t *lower, const int64_t *upper, con
 bool core_begin(NsCore *s);
 // NS.cs:359-393 after the loop found no entering arc: feasibility over the root links, lower bounds restored
 void core_finish(NsCore *s);
+// The inverse of core_finish's last step, for a solve that goes on from the basis an earlier one left (the batch solver's warm re-solve):
+// flow[e] -= orig_lower[e] and the supplies moved back, so that flows and supplies are in standard form again; status Not Solved.
+// Does nothing unless core_finish restored the bounds since the last core_begin / core_reopen, so a chain of re-solves cannot drift.
+void core_reopen(NsCore *s);
+// New arc costs for a core that has been through core_begin: cost[0, m), art_cost as to_standard_form derives it and, with it, the
+// artificial arcs [m + n, all_arcs); the root links [m, m + n) keep cost 0.  Tree, flows and State[] are not touched.
+void core_recost(NsCore *s, const int64_t *cost);
 // NS.cs:459-464
 int64_t core_total_cost(const NsCore *s);
 

@@ -319,7 +319,8 @@ class BatchSolver:
 
     add() copies an instance and returns its index; solve() runs the whole batch on the MI355X; the getters answer per index what
     NetworkSimplex answers for a single solve with the same rule and enable_optimized_pivot(False).  run_on_host() is a test hook
-    (the same pivot code with one lane on the CPU), not a supported solver."""
+    (the same pivot code with one lane on the CPU), not a supported solver.  A solved batch stays on the device: set_costs() gives
+    instances new arc costs and resolve() re-solves those from the basis they ended with (rerun_on_host() is its test hook)."""
 
     def __init__(self, rule=PivotRule.BlockSearch, pivot_limit=0, record_trace=0, device=0, pivots_per_launch=0, semantics=L.SEM_PLAIN, flags=0):
         self._h = C.c_void_p()
@@ -355,6 +356,23 @@ class BatchSolver:
 
     def run_on_host(self):
         L.check(L.lib().mcf_batch_run_on_host(self._h)); return self
+
+    def set_costs(self, i: int, cost):
+        """New arc costs for instance i of a solved batch (copied); resolve() then re-solves it from the basis its last solve left."""
+        co = _i64(cost)
+        if co.shape != (self._dims(i)[1],):
+            raise ValueError("cost must have arc_count entries")
+        L.check(L.lib().mcf_batch_set_costs(self._h, i, co.ctypes.data)); return self
+
+    def resolve(self):
+        L.check(L.lib().mcf_batch_resolve(self._h)); return self
+
+    def rerun_on_host(self):
+        """Test hook like run_on_host(): resolve() with one lane on the CPU."""
+        L.check(L.lib().mcf_batch_rerun_on_host(self._h)); return self
+
+    def resolve_stats(self) -> dict:
+        st = L.BatchResolveStats(); L.check(L.lib().mcf_batch_get_resolve_stats(self._h, C.byref(st))); return st.as_dict()
 
     def status(self, i: int) -> int:
         v = C.c_int32(); L.check(L.lib().mcf_batch_get_status(self._h, i, C.byref(v))); return v.value
