@@ -367,7 +367,7 @@ int cand_post_rc(mcf_engine *e)
     // potential change noted up to now is part of it -- the lists are dropped, the state writes travel with the request
     const bool reload = e->reload_pi && e->d_ext_pi != nullptr && (int64_t)e->sync_arcs.size() <= e->mailbox_max_st;
     if (reload) {
-        e->pend_node.clear(); e->pend_val.clear();
+        pend_clear_potentials(e);
         e->sync_nodes.clear(); e->rc_sync.clear(); e->rc_shift_unknown = false;
         blind_clear(e);
         e->reload_pi = false;
@@ -392,15 +392,13 @@ int cand_post_rc(mcf_engine *e)
         if (!rc) rc = flush_pending(e);                          // update_rc_kernel: the device works the differences out itself
         if (rc) return rc;
     }
-    e->prev_seq = e->seq;
-    e->seq += 1;
-    if (e->seq == 0) e->seq = 1;
+    next_request_keep_prev(e);
     int rc = resident_start(e, e->prev_seq);
     if (rc) return rc;
     resident_post(e, e->seq, reload ? kCmdReload : kCmdScan, fast);
     if (reload) e->st.rc_reloads_in_grid += 1;
     if (fast && (!e->pend_node.empty() || !e->pend_arc.empty())) e->st.inline_updates += 1;
-    e->pend_node.clear(); e->pend_val.clear(); e->pend_arc.clear(); e->pend_state.clear();
+    pend_clear(e);
     e->posted_at = e->cand_now;
     e->st.arcs_scanned += e->end - e->begin;
     return MCF_OK;
@@ -417,7 +415,7 @@ int device_sync_from_mirrors(mcf_engine *e)
     HIP_TRY(hipMemcpyAsync(e->d_pi, pi, sizeof(int64_t) * (size_t)e->d.node_count, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(e->d_state, e->h_state.data() + e->begin, (size_t)(e->end - e->begin), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    e->pend_node.clear(); e->pend_val.clear(); e->pend_arc.clear(); e->pend_state.clear();
+    pend_clear(e);
     e->pend_shift = false;
     e->sync_nodes.clear(); e->sync_arcs.clear(); e->rc_sync.clear(); e->rc_shift_unknown = false;
     blind_clear(e); e->blind_sets = 0;
@@ -458,23 +456,12 @@ void shift_post_request(mcf_engine *e, uint32_t seq, uint32_t cmd, size_t val_lo
         shift_write_lines(e, e->shift_streamed, (int)((n_shift + per_line - 1) / per_line), n_shift, runs, seq);
         e->shift_streamed = 0;
     }
-    MailboxLine h{};
-    h.w[kHdrSeq] = seq;
-    h.w[kHdrCmd] = cmd;
+    MailboxLine h = request_header(e, seq, cmd, n_st, n_val, val_lo);
     h.w[kShHdrValues] = (uint32_t)n_val;
     h.w[kShHdrShift] = with_patches ? (uint32_t)n_shift : 0u;
     h.w[kShHdrRuns] = with_patches && runs ? 1u : 0u;
-    h.w[kHdrStates] = (uint32_t)n_st;
-    for (int k = 0; k < n_st && k < 2; ++k) { h.w[kHdrState0 + 2 * k] = (uint32_t)e->pend_arc[k]; h.w[kHdrState0 + 1 + 2 * k] = (uint32_t)e->pend_state[k]; }
-    if (n_val > 0) {
-        const uint64_t v = (uint64_t)e->pend_val[val_lo];
-        h.w[kHdrValue0] = (uint32_t)e->pend_node[val_lo];
-        h.w[kHdrValue0 + 1] = (uint32_t)v;
-        h.w[kHdrValue0 + 2] = (uint32_t)(v >> 32);
-    }
     h.w[kShHdrSigma] = (uint32_t)(uint64_t)sigma;
     h.w[kShHdrSigma + 1] = (uint32_t)((uint64_t)sigma >> 32);
-    h.w[kHdrTag] = seq;
     mailbox_publish(e->mailbox, kPollReplicas, h, vals.n + sts.n > 0 ? &line1 : nullptr);
 }
 // a request without patches: quit, or a scan request put there again for a grid that has just been started with current arrays
@@ -490,17 +477,13 @@ void shift_stream(mcf_engine *e)
     const bool runs = e->blind_lazy;
     const int complete = runs ? (int)(e->blind_runs.size() / 2 / kShiftPairsPerLine) : (int)(e->blind_count / kShiftNodesPerLine);
     if (complete - e->shift_streamed < kShiftStreamMinLines || complete > e->max_shift_lines) return;
-    uint32_t next_seq = e->seq + 1;
-    if (next_seq == 0) next_seq = 1;
+    const uint32_t next_seq = peek_request(e);
     shift_write_lines(e, e->shift_streamed, complete, runs ? e->blind_runs.size() / 2 : e->blind_count, runs, next_seq);
     e->stream_sub += 1;
     if (e->stream_sub == 0) e->stream_sub = 1;
-    MailboxLine h{};
-    h.w[kHdrSeq] = next_seq;
-    h.w[kHdrCmd] = runs ? kCmdApplyRuns : kCmdApply;
+    MailboxLine h = request_header(e, next_seq, runs ? kCmdApplyRuns : kCmdApply);
     h.w[kShHdrShift] = (uint32_t)complete;
     h.w[kShHdrApplySub] = e->stream_sub;
-    h.w[kHdrTag] = next_seq;
     mailbox_publish(e->mailbox, kPollReplicas, h, nullptr);
     e->shift_streamed = complete;
     e->stream_lines = complete;                    // "a list is travelling": what the other paths test before they change their mind about it
@@ -525,15 +508,13 @@ int cand_post_shift(mcf_engine *e)
         }
     }
     if (e->reload_pi) {
-        e->pend_node.clear(); e->pend_val.clear();
+        pend_clear_potentials(e);
         e->sync_nodes.clear();
         blind_clear(e);
         e->pend_arc.assign(e->sync_arcs.begin(), e->sync_arcs.end());
         e->pend_state.resize(e->pend_arc.size());
         for (size_t i = 0; i < e->pend_arc.size(); ++i) e->pend_state[i] = e->h_state[e->pend_arc[i]];
-        e->prev_seq = e->seq;
-        e->seq += 1;
-        if (e->seq == 0) e->seq = 1;
+        next_request_keep_prev(e);
         shift_post_request(e, e->seq, kCmdReload, 0, 0, 0, true);
         e->st.rc_reloads_in_grid += 1;
         e->pend_arc.clear(); e->pend_state.clear();
@@ -569,13 +550,11 @@ int cand_post_shift(mcf_engine *e)
         e->pend_arc.assign(e->sync_arcs.begin(), e->sync_arcs.end());
         e->pend_state.resize(e->pend_arc.size());
         for (size_t i = 0; i < e->pend_arc.size(); ++i) e->pend_state[i] = e->h_state[e->pend_arc[i]];
-        e->prev_seq = e->seq;
-        e->seq += 1;
-        if (e->seq == 0) e->seq = 1;
+        next_request_keep_prev(e);
         shift_post_request(e, e->seq, kCmdScan, val_lo, as_shift ? (runs ? n_pairs : n_b) : 0, e->pend_sigma, true, runs);
         if (!e->pend_node.empty() || !e->pend_arc.empty()) e->st.inline_updates += 1;
         if (as_shift) e->st.shift_lists += 1;
-        e->pend_node.clear(); e->pend_val.clear(); e->pend_arc.clear(); e->pend_state.clear();
+        pend_clear(e);
         e->sync_nodes.clear(); e->sync_arcs.clear();
         blind_clear(e);
         e->stream_lines = 0;
@@ -596,14 +575,12 @@ int cand_post(mcf_engine *e)
         if (!rc) rc = flush_pending(e);
         if (rc) return rc;
     }
-    e->prev_seq = e->seq;
-    e->seq += 1;
-    if (e->seq == 0) e->seq = 1;
+    next_request_keep_prev(e);
     int rc = resident_start(e, e->prev_seq);
     if (rc) return rc;
     resident_post(e, e->seq, kCmdScan, true);
     if (!e->pend_node.empty() || !e->pend_arc.empty()) e->st.inline_updates += 1;
-    e->pend_node.clear(); e->pend_val.clear(); e->pend_arc.clear(); e->pend_state.clear();
+    pend_clear(e);
     e->posted_at = e->cand_now;
     e->st.arcs_scanned += e->end - e->begin;
     return MCF_OK;

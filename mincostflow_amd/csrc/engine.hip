@@ -288,9 +288,8 @@ inline void blind_clear(mcf_engine *e)
     e->blind_runs.clear();
     e->blind_lazy = false;
 }
-}  // namespace
 
-namespace {
+#include "engine_helpers.hip.h"
 
 bool fits32(int64_t v) { return v >= INT32_MIN && v <= INT32_MAX; }
 
@@ -322,14 +321,10 @@ void fill_params(mcf_engine *e, ScanParams<T> &p, bool with_patches)
     p.base = e->begin;
     p.count_padded = e->count_padded;
     p.m_s = e->d.search_arc_num;
-    const int na = e->next_arc >= e->d.search_arc_num ? 0 : e->next_arc;
-    p.next_arc = na;
-    p.block_size = e->block_size;
-    p.rstar = -1;
-    if (e->d.rule == MCF_RULE_BLOCK_SEARCH && e->d.semantics == MCF_SEM_OPTIMIZED && e->next_arc < e->d.search_arc_num) {
-        const int len1 = e->d.search_arc_num - e->next_arc;   // BSPO.cs:49 first range
-        if (len1 % e->block_size != 0) p.rstar = len1 / e->block_size;
-    }
+    const SearchHeader h = search_header(e);
+    p.next_arc = h.next_arc;
+    p.block_size = h.block_size;
+    p.rstar = h.rstar;
     p.seq = e->seq;
     p.n_pi = 0;
     p.n_st = 0;
@@ -341,83 +336,14 @@ void fill_params(mcf_engine *e, ScanParams<T> &p, bool with_patches)
     }
 }
 
-template <typename T, int RULE, bool OPT, int UNROLL>
-void launch_scan_k(mcf_engine *e, const ScanParams<T> &p, hipEvent_t start, hipEvent_t stop)
-{
-    const dim3 grid(e->grid), block(kThreads);
-    if constexpr (RULE == MCF_RULE_BEST_ELIGIBLE) {
-        if (e->bucket_nodes > 0) {
-            if (start) hipExtLaunchKernelGGL((scan_kernel<T, RULE, OPT, UNROLL, true>), grid, block, 0, e->stream, start, stop, 0, p);
-            else hipLaunchKernelGGL((scan_kernel<T, RULE, OPT, UNROLL, true>), grid, block, 0, e->stream, p);
-            return;
-        }
-    }
-    if (start) hipExtLaunchKernelGGL((scan_kernel<T, RULE, OPT, UNROLL>), grid, block, 0, e->stream, start, stop, 0, p);
-    else hipLaunchKernelGGL((scan_kernel<T, RULE, OPT, UNROLL>), grid, block, 0, e->stream, p);
-}
-
-template <typename T, int RULE, bool OPT>
-void launch_scan_u(mcf_engine *e, const ScanParams<T> &p, hipEvent_t start, hipEvent_t stop)
-{
-    if (e->lds_pi) {
-        const dim3 grid(e->grid), block(kResidentThreads);
-        if (e->unroll >= 2) {
-            if (start) hipExtLaunchKernelGGL((scan_kernel_lds<T, RULE, OPT, 2>), grid, block, 0, e->stream, start, stop, 0, p, e->d.node_count);
-            else hipLaunchKernelGGL((scan_kernel_lds<T, RULE, OPT, 2>), grid, block, 0, e->stream, p, e->d.node_count);
-        } else {
-            if (start) hipExtLaunchKernelGGL((scan_kernel_lds<T, RULE, OPT, 1>), grid, block, 0, e->stream, start, stop, 0, p, e->d.node_count);
-            else hipLaunchKernelGGL((scan_kernel_lds<T, RULE, OPT, 1>), grid, block, 0, e->stream, p, e->d.node_count);
-        }
-        return;
-    }
-    if (e->unroll == 2) launch_scan_k<T, RULE, OPT, 2>(e, p, start, stop);
-    else launch_scan_k<T, RULE, OPT, 1>(e, p, start, stop);
-}
-
-template <typename T>
-void dispatch_scan(mcf_engine *e, const ScanParams<T> &p, hipEvent_t start, hipEvent_t stop)
-{
-    const bool opt = e->d.semantics == MCF_SEM_OPTIMIZED;
-    switch (e->d.rule) {
-    case MCF_RULE_BEST_ELIGIBLE: launch_scan_u<T, MCF_RULE_BEST_ELIGIBLE, false>(e, p, start, stop); break;
-    case MCF_RULE_FIRST_ELIGIBLE: launch_scan_u<T, MCF_RULE_FIRST_ELIGIBLE, false>(e, p, start, stop); break;
-    default:
-        if (opt) launch_scan_u<T, MCF_RULE_BLOCK_SEARCH, true>(e, p, start, stop);
-        else launch_scan_u<T, MCF_RULE_BLOCK_SEARCH, false>(e, p, start, stop);
-    }
-}
-
-template <typename T>
-int launch_scan(mcf_engine *e, bool with_patches, bool timed)
-{
-    ScanParams<T> p;
-    fill_params(e, p, with_patches);
-    hipEvent_t start = nullptr, stop = nullptr;
-    if (timed) {
-        if (e->ev_head - e->ev_tail >= mcf_engine::kEvRing) { int rc = drain_events(e, true); if (rc) return rc; }
-        const int i = e->ev_head % mcf_engine::kEvRing;
-        start = e->ev_start[i];
-        stop = e->ev_stop[i];
-        e->ev_head++;
-    }
-    dispatch_scan<T>(e, p, start, stop);
-    HIP_TRY(hipGetLastError());
-    e->st.scan_launches += 1;
-    e->st.arcs_scanned += e->end - e->begin;
-    return MCF_OK;
-}
-
 void fill_rc_params(mcf_engine *e, RcParams &p, bool with_states)
 {
     p.state_ro = e->d_state; p.state = e->d_state; p.rc = e->d_rc; p.slots = e->slots_target ? e->slots_target : e->d_slots;
     p.base = e->begin; p.count_padded = e->count_padded; p.m_s = e->d.search_arc_num;
-    p.next_arc = e->next_arc >= e->d.search_arc_num ? 0 : e->next_arc;
-    p.block_size = e->block_size;
-    p.rstar = -1;
-    if (e->d.rule == MCF_RULE_BLOCK_SEARCH && e->d.semantics == MCF_SEM_OPTIMIZED && e->next_arc < e->d.search_arc_num) {
-        const int len1 = e->d.search_arc_num - e->next_arc;   // BSPO.cs:49 first range
-        if (len1 % e->block_size != 0) p.rstar = len1 / e->block_size;
-    }
+    const SearchHeader h = search_header(e);
+    p.next_arc = h.next_arc;
+    p.block_size = h.block_size;
+    p.rstar = h.rstar;
     p.seq = e->seq;
     p.n_st = 0;
     p.n_pi = 0;
@@ -451,34 +377,45 @@ bool rc_inline_ok(const mcf_engine *e)
     return entries <= kRcInlineEntries;
 }
 
-template <int RULE, bool OPT>
-void launch_rc_u(mcf_engine *e, const RcParams &p, hipEvent_t start, hipEvent_t stop)
+// one dispatch of the search kernel that the engine's layout, rule and width select, timed by the two events when they are given
+void dispatch_search(mcf_engine *e, bool with_patches, hipEvent_t start, hipEvent_t stop)
 {
-    const dim3 grid(e->grid), block(kThreads);
-    if (e->unroll == 2) {
-        if (start) hipExtLaunchKernelGGL((scan_rc_kernel<RULE, OPT, 2>), grid, block, 0, e->stream, start, stop, 0, p);
-        else hipLaunchKernelGGL((scan_rc_kernel<RULE, OPT, 2>), grid, block, 0, e->stream, p);
-    } else {
-        if (start) hipExtLaunchKernelGGL((scan_rc_kernel<RULE, OPT, 1>), grid, block, 0, e->stream, start, stop, 0, p);
-        else hipLaunchKernelGGL((scan_rc_kernel<RULE, OPT, 1>), grid, block, 0, e->stream, p);
-    }
+    with_rule(e, [&](auto rule, auto opt) {
+        constexpr int RULE = decltype(rule)::value;
+        constexpr bool OPT = decltype(opt)::value;
+        const dim3 grid(e->grid), block(kThreads);
+        if (e->rc_mode) {
+            RcParams p;
+            fill_rc_params(e, p, with_patches);
+            if (e->unroll == 2) launch(scan_rc_kernel<RULE, OPT, 2>, grid, block, e->stream, start, stop, p);
+            else launch(scan_rc_kernel<RULE, OPT, 1>, grid, block, e->stream, start, stop, p);
+            return;
+        }
+        with_width(e, [&](auto width) {
+            using T = decltype(width);
+            ScanParams<T> p;
+            fill_params(e, p, with_patches);
+            if (e->lds_pi) {
+                if (e->unroll >= 2) launch(scan_kernel_lds<T, RULE, OPT, 2>, grid, dim3(kResidentThreads), e->stream, start, stop, p, e->d.node_count);
+                else launch(scan_kernel_lds<T, RULE, OPT, 1>, grid, dim3(kResidentThreads), e->stream, start, stop, p, e->d.node_count);
+                return;
+            }
+            if constexpr (RULE == MCF_RULE_BEST_ELIGIBLE) {
+                if (e->bucket_nodes > 0) {
+                    if (e->unroll == 2) launch(scan_kernel<T, RULE, OPT, 2, true>, grid, block, e->stream, start, stop, p);
+                    else launch(scan_kernel<T, RULE, OPT, 1, true>, grid, block, e->stream, start, stop, p);
+                    return;
+                }
+            }
+            if (e->unroll == 2) launch(scan_kernel<T, RULE, OPT, 2>, grid, block, e->stream, start, stop, p);
+            else launch(scan_kernel<T, RULE, OPT, 1>, grid, block, e->stream, start, stop, p);
+        });
+    });
 }
 
-void dispatch_scan_rc(mcf_engine *e, const RcParams &p, hipEvent_t start, hipEvent_t stop)
+// a search's dispatch; timed: its duration is sampled through the event ring (drain_events)
+int launch_search(mcf_engine *e, bool with_patches, bool timed)
 {
-    switch (e->d.rule) {
-    case MCF_RULE_BEST_ELIGIBLE: launch_rc_u<MCF_RULE_BEST_ELIGIBLE, false>(e, p, start, stop); break;
-    case MCF_RULE_FIRST_ELIGIBLE: launch_rc_u<MCF_RULE_FIRST_ELIGIBLE, false>(e, p, start, stop); break;
-    default:
-        if (e->d.semantics == MCF_SEM_OPTIMIZED) launch_rc_u<MCF_RULE_BLOCK_SEARCH, true>(e, p, start, stop);
-        else launch_rc_u<MCF_RULE_BLOCK_SEARCH, false>(e, p, start, stop);
-    }
-}
-
-int launch_scan_rc(mcf_engine *e, bool with_states, bool timed)
-{
-    RcParams p;
-    fill_rc_params(e, p, with_states);
     hipEvent_t start = nullptr, stop = nullptr;
     if (timed) {
         if (e->ev_head - e->ev_tail >= mcf_engine::kEvRing) { int rc = drain_events(e, true); if (rc) return rc; }
@@ -487,7 +424,7 @@ int launch_scan_rc(mcf_engine *e, bool with_states, bool timed)
         stop = e->ev_stop[i];
         e->ev_head++;
     }
-    dispatch_scan_rc(e, p, start, stop);
+    dispatch_search(e, with_patches, start, stop);
     HIP_TRY(hipGetLastError());
     e->st.scan_launches += 1;
     e->st.arcs_scanned += e->end - e->begin;
@@ -497,11 +434,10 @@ int launch_scan_rc(mcf_engine *e, bool with_states, bool timed)
 // (re)computes the per-arc reduced costs of the RC layout from the arrays on the device
 int rc_recompute(mcf_engine *e)
 {
-    const int blocks = e->count_padded / kThreads;
-    if (e->d.int_width == 32)
-        hipLaunchKernelGGL(rc_init_kernel<int32_t>, dim3(blocks), dim3(kThreads), 0, e->stream, e->d_src, e->d_tgt, (const int32_t *)e->d_cost, (const int32_t *)e->d_pi, e->d_rc, e->count_padded);
-    else
-        hipLaunchKernelGGL(rc_init_kernel<int64_t>, dim3(blocks), dim3(kThreads), 0, e->stream, e->d_src, e->d_tgt, (const int64_t *)e->d_cost, (const int64_t *)e->d_pi, e->d_rc, e->count_padded);
+    with_width(e, [&](auto width) {
+        using T = decltype(width);
+        launch(rc_init_kernel<T>, dim3(e->count_padded / kThreads), dim3(kThreads), e->stream, nullptr, nullptr, e->d_src, e->d_tgt, (const T *)e->d_cost, (const T *)e->d_pi, e->d_rc, e->count_padded);
+    });
     HIP_TRY(hipGetLastError());
     return MCF_OK;
 }
@@ -525,6 +461,19 @@ int rc_build_adjacency(mcf_engine *e, const int32_t *src_local, const int32_t *t
     return MCF_OK;
 }
 
+// One launch over a potential list and a state list in device-visible memory (timed by the two events when they are given).  per_arc: the RC
+// layout's update_rc_kernel, which also shifts the reduced costs of the nodes' arcs; otherwise update_kernel
+void launch_list_update(mcf_engine *e, bool per_arc, hipEvent_t start, hipEvent_t stop, const int32_t *nodes, const int64_t *values, int n_pi, const int32_t *arcs,
+                        const int32_t *states, int n_st)
+{
+    const dim3 grid((std::max(n_pi, n_st) + kThreads - 1) / kThreads), block(kThreads);
+    with_width(e, [&](auto width) {
+        using T = decltype(width);
+        if (per_arc) launch(update_rc_kernel<T>, grid, block, e->stream, start, stop, (T *)e->d_pi, nodes, values, n_pi, e->d_state, arcs, states, n_st, e->begin, e->count_padded, e->d_rc, e->d_adj_start, e->d_adj);
+        else launch(update_kernel<T>, grid, block, e->stream, start, stop, (T *)e->d_pi, nodes, values, n_pi, e->d_state, arcs, states, n_st, e->begin, e->count_padded);
+    });
+}
+
 // ship the pending patches with update_kernel (lists too long for the kernel arguments, or explicit flush)
 int cand_build_patches(mcf_engine *e);
 int flush_pending(mcf_engine *e)
@@ -536,7 +485,7 @@ int flush_pending(mcf_engine *e)
     if (reload) {
         // mcf_engine_reload_potentials: the caller's whole array instead of lists (whatever was noted since is part of it), then -- below, after
         // the state writes -- every reduced cost of the shard again
-        e->pend_node.clear(); e->pend_val.clear();
+        pend_clear_potentials(e);
         HIP_TRY(hipMemcpyAsync(e->d_pi, e->ext_pi, sizeof(int64_t) * (size_t)e->d.node_count, hipMemcpyHostToDevice, e->stream));
         e->reload_pi = false;
     }
@@ -553,38 +502,21 @@ int flush_pending(mcf_engine *e)
         if (s.busy) { HIP_TRY(hipEventSynchronize(s.done)); s.busy = false; }
         if (n_pi) { memcpy(s.nodes, e->pend_node.data(), sizeof(int32_t) * n_pi); memcpy(s.values, e->pend_val.data(), sizeof(int64_t) * n_pi); }
         if (n_st) { memcpy(s.arcs, e->pend_arc.data() + st0, sizeof(int32_t) * n_st); memcpy(s.states, e->pend_state.data() + st0, sizeof(int32_t) * n_st); }
-        const int blocks = (std::max(n_pi, n_st) + kThreads - 1) / kThreads;
         // RC layout, a list that names more than a sixteenth of the nodes: shifting their arcs one by one (2 ns per node on config 5: 18 atomics in
         // memory each) costs more than writing the potentials and computing every reduced cost of the shard again (12 ps per arc: 107 us for 9 M arcs)
         const bool recompute = e->rc_mode && n_pi > e->rc_recompute_above;
+        launch_list_update(e, e->rc_mode && !recompute, nullptr, nullptr, (const int32_t *)s.d_nodes, (const int64_t *)s.d_values, n_pi, (const int32_t *)s.d_arcs,
+                           (const int32_t *)s.d_states, n_st);
+        HIP_TRY(hipGetLastError());
         if (recompute) {
-            if (e->d.int_width == 32)
-                hipLaunchKernelGGL(update_kernel<int32_t>, dim3(blocks), dim3(kThreads), 0, e->stream, (int32_t *)e->d_pi, (const int32_t *)s.d_nodes,
-                                   (const int64_t *)s.d_values, n_pi, e->d_state, (const int32_t *)s.d_arcs, (const int32_t *)s.d_states, n_st, e->begin, e->count_padded);
-            else
-                hipLaunchKernelGGL(update_kernel<int64_t>, dim3(blocks), dim3(kThreads), 0, e->stream, (int64_t *)e->d_pi, (const int32_t *)s.d_nodes,
-                                   (const int64_t *)s.d_values, n_pi, e->d_state, (const int32_t *)s.d_arcs, (const int32_t *)s.d_states, n_st, e->begin, e->count_padded);
-            HIP_TRY(hipGetLastError());
             if (int rcr = rc_recompute(e)) return rcr;
             e->st.rc_recomputes += 1;
-        } else if (e->rc_mode && e->d.int_width == 32)
-            hipLaunchKernelGGL(update_rc_kernel<int32_t>, dim3(blocks), dim3(kThreads), 0, e->stream, (int32_t *)e->d_pi, (const int32_t *)s.d_nodes, (const int64_t *)s.d_values, n_pi,
-                               e->d_state, (const int32_t *)s.d_arcs, (const int32_t *)s.d_states, n_st, e->begin, e->count_padded, e->d_rc, e->d_adj_start, e->d_adj);
-        else if (e->rc_mode)
-            hipLaunchKernelGGL(update_rc_kernel<int64_t>, dim3(blocks), dim3(kThreads), 0, e->stream, (int64_t *)e->d_pi, (const int32_t *)s.d_nodes, (const int64_t *)s.d_values, n_pi,
-                               e->d_state, (const int32_t *)s.d_arcs, (const int32_t *)s.d_states, n_st, e->begin, e->count_padded, e->d_rc, e->d_adj_start, e->d_adj);
-        else if (e->d.int_width == 32)
-            hipLaunchKernelGGL(update_kernel<int32_t>, dim3(blocks), dim3(kThreads), 0, e->stream, (int32_t *)e->d_pi, (const int32_t *)s.d_nodes,
-                               (const int64_t *)s.d_values, n_pi, e->d_state, (const int32_t *)s.d_arcs, (const int32_t *)s.d_states, n_st, e->begin, e->count_padded);
-        else
-            hipLaunchKernelGGL(update_kernel<int64_t>, dim3(blocks), dim3(kThreads), 0, e->stream, (int64_t *)e->d_pi, (const int32_t *)s.d_nodes,
-                               (const int64_t *)s.d_values, n_pi, e->d_state, (const int32_t *)s.d_arcs, (const int32_t *)s.d_states, n_st, e->begin, e->count_padded);
-        HIP_TRY(hipGetLastError());
+        }
         HIP_TRY(hipEventRecord(s.done, e->stream));
         s.busy = true;
         e->st.update_launches += 1;
     }
-    e->pend_node.clear(); e->pend_val.clear(); e->pend_arc.clear(); e->pend_state.clear();
+    pend_clear(e);
     if (reload) { if (int rcr = rc_recompute(e)) return rcr; e->st.rc_recomputes += 1; }
     return MCF_OK;
 }
@@ -681,7 +613,7 @@ int search_begin(mcf_engine *e)
             // reload of the bound potentials is a request too (cmd 3) when the device can read the array itself.  Anything else -- a change
             // that came without its shift, a reload of an array the device cannot see -- goes through update_rc_kernel with the grid stopped
             rc_reload = e->reload_pi && e->d_ext_pi != nullptr;
-            if (rc_reload) { e->pend_node.clear(); e->pend_val.clear(); e->reload_pi = false; }          // whatever was announced since is part of the array
+            if (rc_reload) { pend_clear_potentials(e); e->reload_pi = false; }          // whatever was announced since is part of the array
             const int64_t n_pi = (int64_t)e->pend_node.size(), n_st = (int64_t)e->pend_arc.size();
             fits = !e->reload_pi && (n_pi == 0 || e->pend_shift) && n_pi <= (int64_t)e->rc_list_max && n_st <= e->mailbox_max_st;
             if (fits && n_pi > 0) std::fill(e->pend_val.begin(), e->pend_val.end(), e->pend_sigma);      // the entries carry the shift, not the value
@@ -692,16 +624,14 @@ int search_begin(mcf_engine *e)
             if (!rc) rc = flush_pending(e);
             if (rc) return rc;
         }
-        e->prev_seq = e->seq;
-        e->seq += 1;
-        if (e->seq == 0) e->seq = 1;
+        next_request_keep_prev(e);
         int rc = resident_start(e, e->prev_seq);
         if (rc) return rc;
-        resident_post(e, e->seq, rc_reload ? 3u : 0u, fits);
+        resident_post(e, e->seq, rc_reload ? kCmdReload : kCmdScan, fits);
         if (rc_reload) e->st.rc_reloads_in_grid += 1;
         if (fits) {
             if (had) e->st.inline_updates += 1;
-            e->pend_node.clear(); e->pend_val.clear(); e->pend_arc.clear(); e->pend_state.clear();
+            pend_clear(e);
         }
         e->launch_ticks += (double)__rdtsc() - t0;
         e->st.searches += 1;
@@ -709,8 +639,7 @@ int search_begin(mcf_engine *e)
         e->in_flight = mcf_engine::kResidentSearch;
         return MCF_OK;
     }
-    e->seq += 1;
-    if (e->seq == 0) e->seq = 1;
+    next_request(e);
     // RC layout: a potential change is a shift of the reduced costs of the node's arcs.  A short list with one common shift rides in the
     // scan's arguments (every workgroup shifts the arcs it scans itself); anything else goes through update_rc_kernel first
     const bool inline_ok = !(e->d.flags & MCF_ENGINE_NO_INLINE_UPDATE) && !e->reload_pi && (e->rc_mode ? rc_inline_ok(e) : (int)e->pend_node.size() <= kInlinePi) &&
@@ -718,11 +647,11 @@ int search_begin(mcf_engine *e)
     if (!inline_ok) { int rc = flush_pending(e); if (rc) return rc; }
     const bool timed = (e->d.flags & MCF_ENGINE_TIME_EVERY_KERNEL) ||
                        ((e->d.flags & MCF_ENGINE_SAMPLE_KERNEL_TIME) && (e->st.scan_launches & 15) == 0);
-    int rc = e->rc_mode ? launch_scan_rc(e, inline_ok, timed) : (e->d.int_width == 32 ? launch_scan<int32_t>(e, inline_ok, timed) : launch_scan<int64_t>(e, inline_ok, timed));
+    int rc = launch_search(e, inline_ok, timed);
     if (rc) return rc;
     if (inline_ok) {
         if (had) e->st.inline_updates += 1;
-        e->pend_node.clear(); e->pend_val.clear(); e->pend_arc.clear(); e->pend_state.clear();
+        pend_clear(e);
     }
     e->launch_ticks += (double)__rdtsc() - t0;
     e->st.searches += 1;
@@ -830,28 +759,16 @@ void resolve_key(mcf_engine *e, const Key &k, int32_t *found, int32_t *arc, int6
 // MINLOC over the shards' candidates with the rule's ordering; *range_out = the same over their range keys (OPTIMIZED Block Search)
 Key merge_candidates(int rule, int semantics, int m_s, int B, int next_arc, int count, const mcf_candidate *all, Key *range_out)
 {
-    const bool block_rule = rule == MCF_RULE_BLOCK_SEARCH, best_rule = rule == MCF_RULE_BEST_ELIGIBLE;
-    int rstar = -1;
-    if (block_rule && semantics == MCF_SEM_OPTIMIZED && next_arc < m_s) {
-        const int len1 = m_s - next_arc;
-        if (len1 % B) rstar = len1 / B;
-    }
+    const SearchHeader h = search_header(rule, semantics, m_s, next_arc, B);
     Key best{0, kNone, kNone}, range{0, kNone, kNone};
     for (int i = 0; i < count; ++i) {
         if (all[i].pos == kNone) continue;
         Key k{all[i].reduced_cost, 0, all[i].pos};
-        bool take;
-        if (best_rule) take = best.p == kNone || k.c < best.c || (k.c == best.c && k.p < best.p);
-        else if (!block_rule) take = k.p < best.p;
-        else {
-            const uint32_t r = k.p / (uint32_t)B;
-            k.r = 2 * r + ((rstar >= 0 && (int)r == rstar && all[i].arc < next_arc) ? 1u : 0u);
-            take = best.p == kNone || k.r < best.r || (k.r == best.r && (k.c < best.c || (k.c == best.c && k.p < best.p)));
-        }
-        if (take) best = k;
-        if (block_rule && semantics == MCF_SEM_OPTIMIZED && all[i].range_pos != kNone) {
-            Key q{all[i].range_cost, (next_arc < m_s && all[i].range_arc < next_arc) ? 1u : 0u, all[i].range_pos};
-            if (range.p == kNone || q.r < range.r || (q.r == range.r && (q.c < range.c || (q.c == range.c && q.p < range.p)))) range = q;
+        if (rule == MCF_RULE_BLOCK_SEARCH) k.r = h.block_rank(k.p, all[i].arc);
+        if (key_better(rule, k, best)) best = k;
+        if (h.dual && all[i].range_pos != kNone) {
+            const Key q{all[i].range_cost, h.wrapped(all[i].range_arc), all[i].range_pos};
+            if (range_better(q, range)) range = q;
         }
     }
     if (range_out) *range_out = range;
@@ -1274,7 +1191,7 @@ int mcf_engine_upload(mcf_engine *e, const int32_t *source, const int32_t *targe
     }
     // the pending lists grow to a subtree's size: get (and touch) their memory now, not in the middle of a solve
     e->pend_node.assign((size_t)e->patch_capacity, 0); e->pend_val.assign((size_t)e->patch_capacity, 0);
-    e->pend_node.clear(); e->pend_val.clear(); e->pend_arc.clear(); e->pend_state.clear();
+    pend_clear(e);
     e->next_arc = 0;
     e->uploaded = true;
     return MCF_OK;
@@ -1367,9 +1284,9 @@ int mcf_engine_update_potential(mcf_engine *e, int32_t count, const int32_t *nod
     e->pend_val.resize(count);
     for (int i = 0; i < count; ++i) {
         const int u = nodes[i];
-        if ((unsigned)u >= (unsigned)e->d.node_count) { e->pend_node.clear(); e->pend_val.clear(); return mcf::fail(MCF_ERR_INVALID, "node %d out of range", u); }
+        if ((unsigned)u >= (unsigned)e->d.node_count) { pend_clear_potentials(e); return mcf::fail(MCF_ERR_INVALID, "node %d out of range", u); }
         const int64_t v = e->pi[u] + sigma;
-        if (e->d.int_width == 32 && !fits32(v)) { e->pend_node.clear(); e->pend_val.clear(); return mcf::fail(MCF_ERR_OVERFLOW, "potential of node %d leaves int32; create the engine with int_width 64", u); }
+        if (e->d.int_width == 32 && !fits32(v)) { pend_clear_potentials(e); return mcf::fail(MCF_ERR_OVERFLOW, "potential of node %d leaves int32; create the engine with int_width 64", u); }
         e->pend_node[i] = u;
         e->pend_val[i] = v;
     }
@@ -1540,7 +1457,7 @@ int mcf_engine_reload_potentials(mcf_engine *e, int32_t changed_nodes)
     }
     // every potential change that is still waiting for the device is part of the array: the lists are dropped, the state writes stay
     if (e->stream_lines > 0) { const int rc = resident_stop(e); if (rc) return rc; }
-    e->pend_node.clear(); e->pend_val.clear();
+    pend_clear_potentials(e);
     e->pend_shift = false;
     if (e->cand_on) {
         e->pivot_overflow = true;           // nothing is evaluated on the host: the device searches next (cand_absorb_pivot notes the gap)
@@ -1661,10 +1578,11 @@ int mcf_engine_check_reduced_costs(mcf_engine *e, int64_t *mismatches, int32_t *
     HIP_TRY(hipMemsetAsync(d_bad, 0, 8, e->stream));
     HIP_TRY(hipMemcpyAsync((char *)d_bad + 8, &big, 4, hipMemcpyHostToDevice, e->stream));
     const int count = e->end - e->begin, blocks = (count + kThreads - 1) / kThreads;
-    if (count > 0) {
-        if (e->d.int_width == 32) hipLaunchKernelGGL(rc_check_kernel<int32_t>, dim3(blocks), dim3(kThreads), 0, e->stream, e->d_src, e->d_tgt, (const int32_t *)e->d_cost, (const int32_t *)e->d_pi, e->d_rc, count, d_bad, (int *)((char *)d_bad + 8));
-        else hipLaunchKernelGGL(rc_check_kernel<int64_t>, dim3(blocks), dim3(kThreads), 0, e->stream, e->d_src, e->d_tgt, (const int64_t *)e->d_cost, (const int64_t *)e->d_pi, e->d_rc, count, d_bad, (int *)((char *)d_bad + 8));
-    }
+    if (count > 0)
+        with_width(e, [&](auto width) {
+            using T = decltype(width);
+            launch(rc_check_kernel<T>, dim3(blocks), dim3(kThreads), e->stream, nullptr, nullptr, e->d_src, e->d_tgt, (const T *)e->d_cost, (const T *)e->d_pi, e->d_rc, count, d_bad, (int *)((char *)d_bad + 8));
+        });
     unsigned long long bad = 0; int first = 0;
     hipError_t err = hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, e->stream);
     if (err == hipSuccess) err = hipMemcpyAsync(&first, (char *)d_bad + 8, 4, hipMemcpyDeviceToHost, e->stream);
@@ -1706,7 +1624,7 @@ int mcf_engine_renumber_nodes(mcf_engine *e, const int32_t *new_of)
     int rc = resident_stop(e);
     if (rc) return rc;
     if (e->ext_pi) {
-        e->pend_node.clear(); e->pend_val.clear(); e->pend_shift = false;
+        pend_clear_potentials(e); e->pend_shift = false;
         e->reload_pi = false;
         if (e->cand_on) { e->sync_nodes.clear(); e->rc_sync.clear(); e->rc_shift_unknown = false; blind_clear(e); }
     }
@@ -1808,11 +1726,12 @@ void key_to_candidate(const mcf_engine *e, const Key &k, mcf_candidate *out)
 {
     out->reduced_cost = k.p == kNone ? 0 : k.c;
     out->pos = k.p;
-    const int na = e->next_arc >= e->d.search_arc_num ? 0 : e->next_arc;
+    const SearchHeader h = search_header(e);
+    const int na = h.next_arc;
     if (k.p == kNone) out->arc = -1;
     else if (e->d.rule == MCF_RULE_BEST_ELIGIBLE) out->arc = (int32_t)k.p;
     else out->arc = (int32_t)(((int64_t)k.p + na) % e->d.search_arc_num);
-    const bool dual = e->d.rule == MCF_RULE_BLOCK_SEARCH && e->d.semantics == MCF_SEM_OPTIMIZED && e->range_key.p != kNone;
+    const bool dual = h.dual && e->range_key.p != kNone;
     out->range_cost = dual ? e->range_key.c : 0;
     out->range_pos = dual ? e->range_key.p : kNone;
     out->range_arc = dual ? (int32_t)(((int64_t)e->range_key.p + na) % e->d.search_arc_num) : -1;
@@ -1877,10 +1796,10 @@ int launch_collect(mcf_engine *e, const mcf_collect_request *rq, int capacity, i
     a.limit = rq->mode == MCF_COLLECT_FIRST_N ? rq->limit : 0;
     a.block_size = rq->mode == MCF_COLLECT_BLOCKS ? rq->block_size : 0;
     a.head_length = rq->head_length; a.survivors = rq->survivors;
-    hipLaunchKernelGGL(collect_count_kernel<T>, dim3(n_tiles), dim3(kCollectThreads), 0, e->stream, a, e->d_tiles);
+    launch(collect_count_kernel<T>, dim3(n_tiles), dim3(kCollectThreads), e->stream, nullptr, nullptr, a, e->d_tiles);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(collect_emit_kernel<T>, dim3(n_tiles), dim3(kCollectThreads), 0, e->stream, a, (const CollectTile *)e->d_tiles, n_tiles,
-                       e->d_collect, capacity, e->d_collect_hdr);
+    launch(collect_emit_kernel<T>, dim3(n_tiles), dim3(kCollectThreads), e->stream, nullptr, nullptr, a, (const CollectTile *)e->d_tiles, n_tiles, e->d_collect, capacity,
+           e->d_collect_hdr);
     HIP_TRY(hipGetLastError());
     return MCF_OK;
 }
@@ -1925,7 +1844,7 @@ int mcf_engine_collect_eligible(mcf_engine *e, const mcf_collect_request *rq, in
     const int n_tiles = (m_s + tile_len - 1) / tile_len;     // <= kCollectMaxTiles
     volatile CollectHeader *hdr = e->h_collect_hdr;
     hdr->count = -1;
-    rc = e->d.int_width == 32 ? launch_collect<int32_t>(e, rq, capacity, rounds, n_tiles) : launch_collect<int64_t>(e, rq, capacity, rounds, n_tiles);
+    rc = with_width(e, [&](auto width) { return launch_collect<decltype(width)>(e, rq, capacity, rounds, n_tiles); });
     if (rc) return rc;
     const double t1 = (double)__rdtsc();
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -2076,12 +1995,8 @@ int mcf_engine_bench_scan(mcf_engine *e, int32_t reps, int32_t cold, int64_t flu
     double sum = 0, mn = 1e30;
     for (int r = 0; r < reps; ++r) {
         if (cold) hipLaunchKernelGGL(flush_kernel, dim3(2048), dim3(256), 0, e->stream, (uint4 *)e->d_flush, e->flush_bytes / 16);
-        e->seq += 1;
-        if (e->seq == 0) e->seq = 1;
-        // same dispatch as a search, timed on the engine's stream; the records are simply not merged
-        if (e->rc_mode) { RcParams p; fill_rc_params(e, p, false); dispatch_scan_rc(e, p, a, b); }
-        else if (e->d.int_width == 32) { ScanParams<int32_t> p; fill_params(e, p, false); dispatch_scan<int32_t>(e, p, a, b); }
-        else { ScanParams<int64_t> p; fill_params(e, p, false); dispatch_scan<int64_t>(e, p, a, b); }
+        next_request(e);
+        dispatch_search(e, false, a, b);      // same dispatch as a search, timed on the engine's stream; the records are simply not merged
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventSynchronize(b));
         float ms = 0.f;
@@ -2138,16 +2053,11 @@ int mcf_engine_bench_update(mcf_engine *e, int32_t count, int32_t reps, double *
     hipEvent_t a, b;
     HIP_TRY(hipEventCreate(&a));
     HIP_TRY(hipEventCreate(&b));
-    const int blocks = (k + kThreads - 1) / kThreads;
     const int rounds = (reps + 1) / 2 * 2;
     double sum = 0, mn = 1e30;
     for (int r = 0; r < rounds; ++r) {
         const int64_t *vals = d_vals[(r + 1) & 1];          // +1 first, back second
-        const dim3 grid(blocks), block(kThreads);
-        if (e->rc_mode && e->d.int_width == 32) hipExtLaunchKernelGGL(update_rc_kernel<int32_t>, grid, block, 0, e->stream, a, b, 0, (int32_t *)e->d_pi, (const int32_t *)d_nodes, vals, k, e->d_state, (const int32_t *)nullptr, (const int32_t *)nullptr, 0, e->begin, e->count_padded, e->d_rc, e->d_adj_start, e->d_adj);
-        else if (e->rc_mode) hipExtLaunchKernelGGL(update_rc_kernel<int64_t>, grid, block, 0, e->stream, a, b, 0, (int64_t *)e->d_pi, (const int32_t *)d_nodes, vals, k, e->d_state, (const int32_t *)nullptr, (const int32_t *)nullptr, 0, e->begin, e->count_padded, e->d_rc, e->d_adj_start, e->d_adj);
-        else if (e->d.int_width == 32) hipExtLaunchKernelGGL(update_kernel<int32_t>, grid, block, 0, e->stream, a, b, 0, (int32_t *)e->d_pi, (const int32_t *)d_nodes, vals, k, e->d_state, (const int32_t *)nullptr, (const int32_t *)nullptr, 0, e->begin, e->count_padded);
-        else hipExtLaunchKernelGGL(update_kernel<int64_t>, grid, block, 0, e->stream, a, b, 0, (int64_t *)e->d_pi, (const int32_t *)d_nodes, vals, k, e->d_state, (const int32_t *)nullptr, (const int32_t *)nullptr, 0, e->begin, e->count_padded);
+        launch_list_update(e, e->rc_mode, a, b, d_nodes, vals, k, nullptr, nullptr, 0);
         hipError_t err = hipGetLastError();
         if (err == hipSuccess) err = hipEventSynchronize(b);
         float ms = 0.f;
@@ -2314,19 +2224,11 @@ int mcf_engine_find_entering_sharded(mcf_engine *e, int32_t *found, int32_t *arc
     if (e->in_flight != mcf_engine::kDispatchSearch) return mcf::fail(MCF_ERR_STATE, "sharded search did not dispatch");
     e->in_flight = mcf_engine::kNoSearch;    // nothing will be collected from the host records
     {
-        const int na = e->next_arc >= e->d.search_arc_num ? 0 : e->next_arc;
-        int rstar = -1;
-        if (e->d.rule == MCF_RULE_BLOCK_SEARCH && e->d.semantics == MCF_SEM_OPTIMIZED && e->next_arc < e->d.search_arc_num) {
-            const int len1 = e->d.search_arc_num - e->next_arc;
-            if (len1 % e->block_size) rstar = len1 / e->block_size;
-        }
-        const dim3 one(1), block(kThreads);
-        const int dual = e->d.rule == MCF_RULE_BLOCK_SEARCH && e->d.semantics == MCF_SEM_OPTIMIZED ? 1 : 0;
-        switch (e->d.rule) {
-        case MCF_RULE_BEST_ELIGIBLE: hipLaunchKernelGGL(reduce_records_kernel<MCF_RULE_BEST_ELIGIBLE>, one, block, 0, e->stream, e->d_dev_slots, e->grid, e->d.search_arc_num, na, e->next_arc, e->block_size, rstar, dual, e->d_cand_local); break;
-        case MCF_RULE_FIRST_ELIGIBLE: hipLaunchKernelGGL(reduce_records_kernel<MCF_RULE_FIRST_ELIGIBLE>, one, block, 0, e->stream, e->d_dev_slots, e->grid, e->d.search_arc_num, na, e->next_arc, e->block_size, rstar, dual, e->d_cand_local); break;
-        default: hipLaunchKernelGGL(reduce_records_kernel<MCF_RULE_BLOCK_SEARCH>, one, block, 0, e->stream, e->d_dev_slots, e->grid, e->d.search_arc_num, na, e->next_arc, e->block_size, rstar, dual, e->d_cand_local);
-        }
+        const SearchHeader h = search_header(e);
+        with_rule(e, [&](auto rule, auto) {
+            launch(reduce_records_kernel<decltype(rule)::value>, dim3(1), dim3(kThreads), e->stream, nullptr, nullptr, e->d_dev_slots, e->grid, e->d.search_arc_num, h.next_arc,
+                   e->next_arc, h.block_size, h.rstar, h.dual ? 1 : 0, e->d_cand_local);
+        });
         HIP_TRY(hipGetLastError());
     }
     // MINLOC over (key, arc): RCCL has no MINLOC, so all-gather the 32-byte records and reduce locally

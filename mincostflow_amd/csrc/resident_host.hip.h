@@ -65,52 +65,56 @@ constexpr int kPollReplicas = 8;             // copies of the poll unit the host
 constexpr int kPollSleep = 1;                // s_sleep(1) between two polls of an idle grid
 constexpr uint32_t kResidentIdleTicks = 25000000u;   // 0.25 s of s_memrealtime (MCF_HIP_IDLE_MS: tests shorten it so that grids leave between two searches)
 
+// every resident grid is launched on its own stream, between the two events that time the launch (resident_harvest)
+template <typename... Params, typename... Args>
+void launch_grid(mcf_engine *e, void (*kernel)(Params...), const Args &...args)
+{
+    launch(kernel, dim3(e->res_grid), dim3(e->res_threads), e->res_stream, e->res_start, e->res_stop, args...);
+}
+
 template <typename T, int RULE, bool OPT>
 void launch_resident_r(mcf_engine *e, const ResidentParams<T> &p)
 {
-    const dim3 grid(e->res_grid), block(e->res_threads);
     const bool lpi = e->lds_pi;
     if (e->cand_on) {     // candidates: Best Eligible, register-resident tiles only
         if (e->shift_grid) {
             if constexpr (sizeof(T) == 8) {
-                if (e->cand_tiles == 2) hipExtLaunchKernelGGL((resident_cand_kernel<T, 2>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p, e->shift_base, e->max_shift_lines);
-                else hipExtLaunchKernelGGL((resident_cand_kernel<T, 4>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p, e->shift_base, e->max_shift_lines);
+                if (e->cand_tiles == 2) launch_grid(e, resident_cand_kernel<T, 2>, p, e->shift_base, e->max_shift_lines);
+                else launch_grid(e, resident_cand_kernel<T, 4>, p, e->shift_base, e->max_shift_lines);
             }
         }
-        else if (lpi) hipExtLaunchKernelGGL((resident_kernel<T, MCF_RULE_BEST_ELIGIBLE, false, true, true, true>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
+        else if (lpi) launch_grid(e, resident_kernel<T, MCF_RULE_BEST_ELIGIBLE, false, true, true, true>, p);
         else if (e->res_threads <= kPiRegThreads && !e->no_pireg)       // the end points' potentials stay in registers between the requests
-            hipExtLaunchKernelGGL((resident_kernel<T, MCF_RULE_BEST_ELIGIBLE, false, true, false, true, true>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
-        else hipExtLaunchKernelGGL((resident_kernel<T, MCF_RULE_BEST_ELIGIBLE, false, true, false, true>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
+            launch_grid(e, resident_kernel<T, MCF_RULE_BEST_ELIGIBLE, false, true, false, true, true>, p);
+        else launch_grid(e, resident_kernel<T, MCF_RULE_BEST_ELIGIBLE, false, true, false, true>, p);
     }
-    else if (e->resident_reg && lpi) hipExtLaunchKernelGGL((resident_kernel<T, RULE, OPT, true, true, false>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
-    else if (e->resident_reg && e->res_threads <= kPiRegThreads && !e->no_pireg)
-        hipExtLaunchKernelGGL((resident_kernel<T, RULE, OPT, true, false, false, true>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
-    else if (e->resident_reg) hipExtLaunchKernelGGL((resident_kernel<T, RULE, OPT, true, false, false>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
-    else if (lpi) hipExtLaunchKernelGGL((resident_kernel<T, RULE, OPT, false, true, false>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
+    else if (e->resident_reg && lpi) launch_grid(e, resident_kernel<T, RULE, OPT, true, true, false>, p);
+    else if (e->resident_reg && e->res_threads <= kPiRegThreads && !e->no_pireg) launch_grid(e, resident_kernel<T, RULE, OPT, true, false, false, true>, p);
+    else if (e->resident_reg) launch_grid(e, resident_kernel<T, RULE, OPT, true, false, false>, p);
+    else if (lpi) launch_grid(e, resident_kernel<T, RULE, OPT, false, true, false>, p);
     else {
         if constexpr (RULE == MCF_RULE_BEST_ELIGIBLE) {
             if (e->bucket_nodes > 0) {
-                hipExtLaunchKernelGGL((resident_kernel<T, RULE, OPT, false, false, false, false, true>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
+                launch_grid(e, resident_kernel<T, RULE, OPT, false, false, false, false, true>, p);
                 return;
             }
         }
-        hipExtLaunchKernelGGL((resident_kernel<T, RULE, OPT, false, false, false>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
+        launch_grid(e, resident_kernel<T, RULE, OPT, false, false, false>, p);
     }
 }
 
 template <int RULE, bool OPT>
 void launch_resident_rc_r(mcf_engine *e, const ResidentRcParams &p)
 {
-    const dim3 grid(e->res_grid), block(e->res_threads);
     if constexpr (RULE == MCF_RULE_BEST_ELIGIBLE) {
         if (e->cand_on) {          // the candidate cache's grid: every search publishes each group's smallest few, not only the best
-            if (e->rc_lds) hipExtLaunchKernelGGL((resident_rc_kernel<RULE, OPT, true, true>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
-            else hipExtLaunchKernelGGL((resident_rc_kernel<RULE, OPT, false, true>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
+            if (e->rc_lds) launch_grid(e, resident_rc_kernel<RULE, OPT, true, true>, p);
+            else launch_grid(e, resident_rc_kernel<RULE, OPT, false, true>, p);
             return;
         }
     }
-    if (e->rc_lds) hipExtLaunchKernelGGL((resident_rc_kernel<RULE, OPT, true>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
-    else hipExtLaunchKernelGGL((resident_rc_kernel<RULE, OPT, false>), grid, block, 0, e->res_stream, e->res_start, e->res_stop, 0, p);
+    if (e->rc_lds) launch_grid(e, resident_rc_kernel<RULE, OPT, true>, p);
+    else launch_grid(e, resident_rc_kernel<RULE, OPT, false>, p);
 }
 
 // the kernel arguments that every resident grid takes; host_pi: what a kCmdReload reads, or null
@@ -133,13 +137,7 @@ int launch_resident_rc(mcf_engine *e, uint32_t start_seq)
     p.src = e->d_src; p.tgt = e->d_tgt; p.cost = e->d_cost; p.n_nodes = e->d.node_count;
     p.mb = mailbox_params(e, start_seq, e->d_ext_pi);
     if (e->d_barrier) HIP_TRY(hipMemsetAsync(e->d_barrier, 0, 64, e->res_stream));
-    switch (e->d.rule) {
-    case MCF_RULE_BEST_ELIGIBLE: launch_resident_rc_r<MCF_RULE_BEST_ELIGIBLE, false>(e, p); break;
-    case MCF_RULE_FIRST_ELIGIBLE: launch_resident_rc_r<MCF_RULE_FIRST_ELIGIBLE, false>(e, p); break;
-    default:
-        if (e->d.semantics == MCF_SEM_OPTIMIZED) launch_resident_rc_r<MCF_RULE_BLOCK_SEARCH, true>(e, p);
-        else launch_resident_rc_r<MCF_RULE_BLOCK_SEARCH, false>(e, p);
-    }
+    with_rule(e, [&](auto rule, auto opt) { launch_resident_rc_r<decltype(rule)::value, decltype(opt)::value>(e, p); });
     HIP_TRY(hipGetLastError());
     return MCF_OK;
 }
@@ -153,14 +151,7 @@ int launch_resident(mcf_engine *e, uint32_t start_seq)
     p.base = e->begin; p.count_padded = e->count_padded; p.m_s = e->d.search_arc_num; p.n_nodes = e->d.node_count;
     p.mb = mailbox_params(e, start_seq, e->shift_grid && e->d_barrier ? e->d_ext_pi : nullptr);
     if (p.mb.host_pi) HIP_TRY(hipMemsetAsync(e->d_barrier, 0, 64, e->res_stream));
-    const bool opt = e->d.semantics == MCF_SEM_OPTIMIZED;
-    switch (e->d.rule) {
-    case MCF_RULE_BEST_ELIGIBLE: launch_resident_r<T, MCF_RULE_BEST_ELIGIBLE, false>(e, p); break;
-    case MCF_RULE_FIRST_ELIGIBLE: launch_resident_r<T, MCF_RULE_FIRST_ELIGIBLE, false>(e, p); break;
-    default:
-        if (opt) launch_resident_r<T, MCF_RULE_BLOCK_SEARCH, true>(e, p);
-        else launch_resident_r<T, MCF_RULE_BLOCK_SEARCH, false>(e, p);
-    }
+    with_rule(e, [&](auto rule, auto opt) { launch_resident_r<T, decltype(rule)::value, decltype(opt)::value>(e, p); });
     HIP_TRY(hipGetLastError());
     return MCF_OK;
 }
@@ -212,11 +203,30 @@ int resident_start(mcf_engine *e, uint32_t start_seq)
         HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
         HIP_TRY(hipStreamCreateWithPriority(&e->res_stream, hipStreamNonBlocking, greatest));
     }
-    int rc = e->rc_mode ? launch_resident_rc(e, start_seq) : (e->d.int_width == 32 ? launch_resident<int32_t>(e, start_seq) : launch_resident<int64_t>(e, start_seq));
+    int rc = e->rc_mode ? launch_resident_rc(e, start_seq) : with_width(e, [&](auto width) { return launch_resident<decltype(width)>(e, start_seq); });
     if (rc) return rc;
     e->resident_running = true;
     e->st.resident_launches += 1;
     return MCF_OK;
+}
+
+// What every request's header line holds, whichever grid reads it: number, command and tag; with `n_st` state writes and `n_val` value
+// entries (pend_node / pend_val from val_lo on), the first two state writes and the first value
+MailboxLine request_header(const mcf_engine *e, uint32_t seq, uint32_t cmd, int n_st = 0, int n_val = 0, size_t val_lo = 0)
+{
+    MailboxLine h{};
+    h.w[kHdrSeq] = seq;
+    h.w[kHdrCmd] = cmd;
+    h.w[kHdrStates] = (uint32_t)n_st;
+    for (int k = 0; k < n_st && k < 2; ++k) { h.w[kHdrState0 + 2 * k] = (uint32_t)e->pend_arc[k]; h.w[kHdrState0 + 1 + 2 * k] = (uint32_t)e->pend_state[k]; }
+    if (n_val > 0) {
+        const uint64_t v = (uint64_t)e->pend_val[val_lo];
+        h.w[kHdrValue0] = (uint32_t)e->pend_node[val_lo];
+        h.w[kHdrValue0 + 1] = (uint32_t)v;
+        h.w[kHdrValue0 + 2] = (uint32_t)(v >> 32);
+    }
+    h.w[kHdrTag] = seq;
+    return h;
 }
 
 void resident_post(mcf_engine *e, uint32_t seq, uint32_t cmd, bool with_patches)
@@ -228,28 +238,12 @@ void resident_post(mcf_engine *e, uint32_t seq, uint32_t cmd, bool with_patches)
     const int entries = vals.n + sts.n;
     const MailboxLine line1 = mailbox_encode_entries(e->mailbox, vals, sts, seq, e->stream_lines);
     if (with_patches) e->stream_lines = 0;
-    MailboxLine h{};
-    h.w[kHdrSeq] = seq;
-    h.w[kHdrCmd] = cmd;
-    const int na = e->next_arc >= e->d.search_arc_num ? 0 : e->next_arc;
-    h.w[kHdrNextArc] = (uint32_t)na;
-    int rstar = -1;
-    if (e->d.rule == MCF_RULE_BLOCK_SEARCH && e->d.semantics == MCF_SEM_OPTIMIZED && e->next_arc < e->d.search_arc_num) {
-        const int len1 = e->d.search_arc_num - e->next_arc;
-        if (len1 % e->block_size != 0) rstar = len1 / e->block_size;
-    }
-    h.w[kHdrRstar] = (uint32_t)rstar;
-    h.w[kHdrBlockSize] = (uint32_t)e->block_size;      // per request: the adaptive rule of the plain Block Search changes it between searches
+    MailboxLine h = request_header(e, seq, cmd, n_st, n_pi);
+    const SearchHeader sh = search_header(e);
+    h.w[kHdrNextArc] = (uint32_t)sh.next_arc;
+    h.w[kHdrRstar] = (uint32_t)sh.rstar;
+    h.w[kHdrBlockSize] = (uint32_t)sh.block_size;      // per request: the adaptive rule of the plain Block Search changes it between searches
     h.w[kHdrValues] = (uint32_t)n_pi;
-    h.w[kHdrStates] = (uint32_t)n_st;
-    for (int k = 0; k < n_st && k < 2; ++k) { h.w[kHdrState0 + 2 * k] = (uint32_t)e->pend_arc[k]; h.w[kHdrState0 + 1 + 2 * k] = (uint32_t)e->pend_state[k]; }
-    if (n_pi > 0) {
-        const uint64_t v = (uint64_t)e->pend_val[0];
-        h.w[kHdrValue0] = (uint32_t)e->pend_node[0];
-        h.w[kHdrValue0 + 1] = (uint32_t)v;
-        h.w[kHdrValue0 + 2] = (uint32_t)(v >> 32);
-    }
-    h.w[kHdrTag] = seq;
     mailbox_publish(e->mailbox, kPollReplicas, h, entries > 0 ? &line1 : nullptr, entries > kMailboxPatchesPerLine);
 }
 
@@ -267,20 +261,16 @@ void resident_stream(mcf_engine *e)
     const int n_pi = (int)e->pend_node.size();
     const int complete = (n_pi > 1 ? n_pi - 1 : 0) / kMailboxPatchesPerLine;
     if (complete - e->stream_lines < kStreamMinLines) return;
-    uint32_t next_seq = e->seq + 1;
-    if (next_seq == 0) next_seq = 1;
+    const uint32_t next_seq = peek_request(e);
     // the complete entry lines not in place yet (entry line 0 goes out with the first post's header)
     const MailboxLine line1 = mailbox_encode_entries(e->mailbox, ValueEntries{e->pend_node.data(), e->pend_val.data(), 1, complete * kMailboxPatchesPerLine},
                                                      StateEntries{nullptr, nullptr, 0, 0}, next_seq, e->stream_lines);
     const bool first_post = e->stream_lines == 0;
     e->stream_sub += 1;
     if (e->stream_sub == 0) e->stream_sub = 1;
-    MailboxLine h{};
-    h.w[kHdrSeq] = next_seq;
-    h.w[kHdrCmd] = kCmdApply;
+    MailboxLine h = request_header(e, next_seq, kCmdApply);
     h.w[kHdrApplyLines] = (uint32_t)complete;
     h.w[kHdrApplySub] = e->stream_sub;
-    h.w[kHdrTag] = next_seq;
     mailbox_publish(e->mailbox, kPollReplicas, h, first_post ? &line1 : nullptr);
     e->stream_lines = complete;
 }
@@ -340,9 +330,7 @@ int resident_stop(mcf_engine *e)
         e->answered = k;
         e->in_flight = mcf_engine::kAnswered;
     }
-    e->prev_seq = e->seq;
-    e->seq += 1;
-    if (e->seq == 0) e->seq = 1;
+    next_request_keep_prev(e);
     if (e->shift_grid) shift_post(e, e->seq, kCmdQuit, false);
     else resident_post(e, e->seq, kCmdQuit, false);
     { const int rcj = resident_join(e); if (rcj) return rcj; }       // bounded: the grid leaves on quit, or by itself after kResidentIdleTicks; counts what the launch served
@@ -377,18 +365,12 @@ int collect(mcf_engine *e, int grid, Key *out)
     constexpr int stride = kSlotStride;
     const double t0 = (double)__rdtsc();
     double t0_wall = 0;
-    const bool block_rule = e->d.rule == MCF_RULE_BLOCK_SEARCH, best_rule = e->d.rule == MCF_RULE_BEST_ELIGIBLE;
     Key best{0, kNone, kNone};
     const volatile Slot *slots = e->h_slots;
     const uint32_t seq = e->seq;
-    const int rstar = [&] {
-        if (!(block_rule && e->d.semantics == MCF_SEM_OPTIMIZED) || e->next_arc >= e->d.search_arc_num) return -1;
-        const int len1 = e->d.search_arc_num - e->next_arc;
-        return len1 % e->block_size ? len1 / e->block_size : -1;
-    }();
-    const int na = e->next_arc >= e->d.search_arc_num ? 0 : e->next_arc;
+    const SearchHeader h = search_header(e);
     // OPTIMIZED Block Search: records 0, 1 of a line = the block key, records 2, 3 = the range key (kernels.hip.h: kDual)
-    const bool dual = block_rule && e->d.semantics == MCF_SEM_OPTIMIZED;
+    const bool dual = h.dual;
     Key range{0, kNone, kNone};
     for (int g = 0; g < grid; ++g) {
         uint64_t spins = 0;
@@ -419,23 +401,16 @@ int collect(mcf_engine *e, int grid, Key *out)
         k.p = slots[(size_t)g * stride].p;
         k.r = 0;
         if (k.p == kNone) continue;
-        bool take;
-        if (best_rule) take = best.p == kNone || k.c < best.c || (k.c == best.c && k.p < best.p);
-        else if (!block_rule) take = k.p < best.p;
-        else {
-            uint32_t r = k.p / (uint32_t)e->block_size;
-            const int arc = (int)((k.p + (uint32_t)na) % (uint32_t)e->d.search_arc_num);
-            k.r = 2 * r + ((rstar >= 0 && (int)r == rstar && arc < e->next_arc) ? 1u : 0u);
-            take = best.p == kNone || k.r < best.r || (k.r == best.r && (k.c < best.c || (k.c == best.c && k.p < best.p)));
-        }
-        if (take) best = k;
+        auto arc_at = [&](uint32_t p) { return (int)((p + (uint32_t)h.next_arc) % (uint32_t)e->d.search_arc_num); };
+        if (e->d.rule == MCF_RULE_BLOCK_SEARCH) k.r = h.block_rank(k.p, arc_at(k.p));
+        if (key_better(e->d.rule, k, best)) best = k;
         if (dual) {
             Key q;
             q.c = slots[(size_t)g * stride + 2].c;
             q.p = slots[(size_t)g * stride + 2].p;
             if (q.p != kNone) {
-                q.r = (int)((q.p + (uint32_t)na) % (uint32_t)e->d.search_arc_num) < na ? 1u : 0u;
-                if (range.p == kNone || q.r < range.r || (q.r == range.r && (q.c < range.c || (q.c == range.c && q.p < range.p)))) range = q;
+                q.r = h.wrapped(arc_at(q.p));
+                if (range_better(q, range)) range = q;
             }
         }
     }

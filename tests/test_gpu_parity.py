@@ -1421,3 +1421,118 @@ def test_grid_that_left_on_its_idle_timeout_comes_back(mode, monkeypatch):
             assert st["resident_launches"] >= 4, st["resident_launches"]
         assert np.array_equal(eng.download_pi(), a["pi"]) and np.array_equal(eng.download_state()[:m_s], a["state"][:m_s])
         assert eng.check_reduced_costs() == (0, -1)
+
+
+def _layout_env(layout, monkeypatch):
+    """"rc": reduced costs kept per arc, forced onto any size; "gather": whatever the sizes select without it."""
+    if layout == "rc":
+        monkeypatch.setenv("MCF_HIP_RC", "1")
+    else:
+        monkeypatch.delenv("MCF_HIP_RC", raising=False)
+
+
+# (m_s, n, layout): potentials in LDS with one arc over a tile; n + 1 > 16384, the gathering scan; the same two with reduced costs per arc
+TIMED_SHAPES = [pytest.param(1025, 40, "gather", id="lds"), pytest.param(4097, 17000, "gather", id="gather"),
+                pytest.param(1025, 40, "rc", id="rc-small"), pytest.param(4097, 17000, "rc", id="rc")]
+
+
+def _timed_dispatch_case(width, rule, optimized, vw, m_s, n, layout, monkeypatch):
+    _layout_env(layout, monkeypatch)
+    rng = np.random.default_rng(4321 + width + 10 * rule + optimized + vw + m_s)
+    a = _random_soa(rng, m_s, n, 3, 9)
+    block = int(rng.integers(1, min(m_s, 700)))
+    eng = M.PivotEngine(n, len(a["src"]), m_s, rule=RULES[rule], optimized=optimized, int_width=width, block_size=block,
+                        flags=M.ENGINE_DISPATCH | M.ENGINE_TIME_EVERY_KERNEL, vector_width=vw)
+    eng.upload(a["src"], a["tgt"], a["cost"], a["state"], a["pi"])
+    next_arc = 0
+    for it, k in enumerate([0, 5, 97, None]):      # list sizes: none, rides in the scan's arguments, one above kInlinePi (update_kernel / update_rc_kernel)
+        f, e, c, na = _oracle_scan(rule, optimized, a, m_s, block, next_arc, vw)
+        assert eng.find_entering() == ((True, e, c) if f else (False, -1, 0)), (it, next_arc, block)
+        if f and rule != O.RULE_BEST:
+            assert eng.next_arc == na, (it, eng.next_arc, na, next_arc, block)
+        if f:
+            next_arc = na
+        if k is None:
+            break
+        arcs = rng.choice(m_s, size=1 + it % 2, replace=False).astype(np.int32)
+        vals = rng.integers(-1, 2, len(arcs)).astype(np.int8)
+        a["state"][arcs] = vals
+        eng.patch_state(arcs, vals)
+        nodes = rng.choice(n, size=min(k, n), replace=False).astype(np.int32)
+        sigma = int(rng.integers(1, 4))
+        a["pi"][nodes] += sigma
+        eng.update_potential(nodes, sigma)
+    st = eng.stats()
+    assert st["timed_scans"] == st["searches"] == 4 and st["timed_scan_ns"] > 0, st
+    assert st["resident"] == 0 and st["rc_layout"] == int(layout == "rc")
+    assert np.array_equal(eng.download_pi(), a["pi"])
+    assert np.array_equal(eng.download_state()[:m_s], a["state"][:m_s])
+    assert eng.check_reduced_costs() == (0, -1)
+
+
+@pytest.mark.parametrize("m_s,n,layout", TIMED_SHAPES)
+@pytest.mark.parametrize("width", [64, 32])
+@pytest.mark.parametrize("rule,optimized,vw", RULE_CASES)
+def test_every_dispatch_timed_matches_oracle(width, rule, optimized, vw, m_s, n, layout, monkeypatch):
+    """MCF_ENGINE_DISPATCH | MCF_ENGINE_TIME_EVERY_KERNEL: every search is one dispatch between two events of the engine's ring -- each
+    dispatched search kernel (potentials in LDS, gathering, reduced costs per arc) in its timed form, with the patches in its arguments or
+    shipped by the update kernel before it.  Same answers as the oracle, and every search's duration is counted."""
+    _timed_dispatch_case(width, rule, optimized, vw, m_s, n, layout, monkeypatch)
+
+
+@pytest.mark.parametrize("width", [64, 32])
+def test_every_dispatch_timed_where_the_lds_scan_unrolls_twice(width, monkeypatch):
+    """2^21 + 5 arcs beside potentials in LDS: the smallest shard whose LDS-potential scan takes two tiles per trip (Best Eligible)."""
+    _timed_dispatch_case(width, O.RULE_BEST, True, 4, 2 ** 21 + 5, 40, "gather", monkeypatch)
+
+
+@pytest.mark.parametrize("layout", ["gather", "rc"])
+@pytest.mark.parametrize("width", [64, 32])
+def test_bench_update_times_the_update_kernel_and_leaves_the_engine_as_it_was(width, layout, monkeypatch):
+    """mcf_engine_bench_update: update_kernel (update_rc_kernel in the RC layout) over every (n / count)-th node, +1 and back, between two
+    events.  Afterwards the potentials, the per-arc reduced costs and the next search are what they were, and the byte count is the one the
+    function documents: 20 (12 with 32-bit potentials) per node, plus per node 8 and per entry of its arc list 20 in the RC layout."""
+    _layout_env(layout, monkeypatch)
+    rng = np.random.default_rng(808 + width)
+    m_s, n = 1025, 300
+    a = _random_soa(rng, m_s, n, 3, 9, extra=0)
+    eng = M.PivotEngine(n, m_s, m_s, rule=M.PivotRule.BestEligible, int_width=width, flags=M.ENGINE_DISPATCH)
+    eng.upload(a["src"], a["tgt"], a["cost"], a["state"], a["pi"])
+    assert eng.stats()["rc_layout"] == int(layout == "rc")
+    degree_of = np.bincount(a["src"][:m_s], minlength=n) + np.bincount(a["tgt"][:m_s], minlength=n)
+    want = O.scan_best(m_s, a["state"], a["cost"], a["src"], a["tgt"], a["pi"])
+    for count in (1, 257, 300):         # one node; one above a 256-thread block; every node
+        avg, mn, nbytes = eng.bench_update(count, reps=4)
+        assert 0 < mn <= avg, (count, mn, avg)
+        nodes = sorted({(i * max(1, n // count)) % n for i in range(count)})
+        k = len(nodes)
+        assert nbytes == (20 if width == 64 else 12) * k + ((8 * k + 20 * int(degree_of[nodes].sum())) if layout == "rc" else 0), (count, k, nbytes)
+        assert np.array_equal(eng.download_pi(), a["pi"])
+        assert eng.check_reduced_costs() == (0, -1)
+        assert eng.find_entering() == want, count
+
+
+@pytest.mark.parametrize("layout", ["gather", "rc"])
+@pytest.mark.parametrize("width", [64, 32])
+@pytest.mark.parametrize("rule,optimized,vw", RULE_CASES)
+def test_bench_scan_dispatches_every_rule_and_leaves_the_search_alone(width, rule, optimized, vw, layout, monkeypatch):
+    """mcf_engine_bench_scan launches the search's own dispatch between its own events, warm and behind a cache flush: whatever the rule, the
+    width and the layout, next_arc stays and the search that follows answers as the oracle does."""
+    _layout_env(layout, monkeypatch)
+    rng = np.random.default_rng(606 + width + 10 * rule + optimized + vw)
+    m_s, n = 1025, 40
+    a = _random_soa(rng, m_s, n, 3, 9)
+    block = int(rng.integers(1, 700))
+    eng = M.PivotEngine(n, len(a["src"]), m_s, rule=RULES[rule], optimized=optimized, int_width=width, block_size=block, flags=M.ENGINE_DISPATCH,
+                        vector_width=vw)
+    eng.upload(a["src"], a["tgt"], a["cost"], a["state"], a["pi"])
+    next_arc = 0 if rule == O.RULE_BEST else int(rng.integers(1, m_s))
+    eng.next_arc = next_arc
+    for cold in (False, True):
+        avg, mn = eng.bench_scan(reps=3, cold=cold, flush_bytes=1 << 20)
+        assert 0 < mn <= avg
+        assert eng.next_arc == next_arc
+    f, e, c, na = _oracle_scan(rule, optimized, a, m_s, block, next_arc, vw)
+    assert eng.find_entering() == ((True, e, c) if f else (False, -1, 0))
+    if f and rule != O.RULE_BEST:
+        assert eng.next_arc == na
