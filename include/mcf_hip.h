@@ -724,6 +724,87 @@ MCF_API int mcf_batch_rerun_on_host(mcf_batch *b);
 /* what the last mcf_batch_resolve / mcf_batch_rerun_on_host did (all zero before one) */
 MCF_API int mcf_batch_get_resolve_stats(mcf_batch *b, mcf_batch_resolve_stats *out);
 
+/* ---- Uniform batch: `count` instances of ONE topology, problem data in and results out where they are ("Uniform batch").
+ * mcf_batch_* above sets every instance up and finishes it on one host thread, and every number passes through the host.  Where the
+ * instances share their graph and differ in costs, supplies and bounds, all of that runs on the device: one launch sets every
+ * instance up from the caller's arrays (bounds check, standard form, start basis), the launches of mcf_batch_solve carry the pivots
+ * (the same kernel), one launch writes status, pivot count, total cost, flows, potentials and trace into the caller's rows.  With
+ * MCF_MEM_DEVICE nothing that scales with the arcs or the nodes crosses the bus in a call (the topology goes up once per handle, with
+ * its first device call, and is not counted in the statistics of a call).
+ * Results are those of mcf_batch_*: bit for bit what mcf_batch_add + mcf_batch_solve give for the same instances.  Workspaces sit at a
+ * fixed stride (the footprint of an instance whose every node needs an artificial arc), so the whole batch runs in ONE tier, LDS or
+ * global memory, by that stride; both tiers give the same results.
+ * Limits and refusals are mcf_batch_create's and mcf_batch_add's: the three rules in MCF_SEM_PLAIN, MCF_BATCH_MAX_ARCS / _NODES /
+ * _INSTANCES, end points validated at create. */
+#define MCF_MEM_HOST 0
+#define MCF_MEM_DEVICE 1
+
+typedef struct mcf_ubatch mcf_ubatch;
+typedef struct mcf_ubatch_desc {
+    int32_t device;               /* as mcf_batch_desc, field for field ... */
+    int32_t pivot_rule;
+    int32_t semantics;
+    int32_t reserved;
+    int64_t pivot_limit;
+    int32_t pivots_per_launch;
+    int32_t trace_capacity;
+    int32_t flags;
+    int32_t node_count;           /* ... then the topology every instance shares */
+    int32_t arc_count;
+    int32_t count;                /* instances, >= 0 */
+    const int32_t *source;        /* [arc_count], HOST memory, copied and validated by mcf_ubatch_create */
+    const int32_t *target;
+} mcf_ubatch_desc;
+typedef struct mcf_ubatch_io {
+    int32_t memory;               /* MCF_MEM_HOST / MCF_MEM_DEVICE: where EVERY pointer below points (device = mcf_ubatch_desc.device) */
+    int32_t supply_type;          /* MCF_SUPPLY_GEQ / _LEQ, for every instance of this call */
+    const int64_t *lower;         /* [arc_count] per instance; NULL = 0 */
+    const int64_t *upper;         /* NULL = uncapacitated; MCF_INF_CAP as in mcf_ns_set_problem */
+    const int64_t *cost;          /* NULL = 0 */
+    const int64_t *supply;        /* [node_count] per instance; NULL = 0 */
+    int64_t lower_stride, upper_stride, cost_stride, supply_stride;     /* ELEMENTS between instance i and i + 1; 0 = one array shared by all */
+    const uint8_t *changed;       /* mcf_ubatch_resolve / _rerun_on_host only: [count], nonzero = re-solve this instance; NULL = all */
+    /* results, any may be NULL.  Rows of instances that are not MCF_OPTIMAL are zero-filled (total cost 0); status, pivots and trace are
+     * always written, a trace row is zero behind min(pivots, trace_capacity) */
+    int32_t *status;              /* [count] */
+    int64_t *pivots;              /* [count] */
+    int64_t *total_cost;          /* [count] */
+    int64_t *flows;               /* [count * arc_count] */
+    int64_t *potentials;          /* [count * node_count] */
+    int32_t *trace;               /* [count * trace_capacity] */
+} mcf_ubatch_io;
+typedef struct mcf_ubatch_stats { /* of the last solve call of any kind; the first nine as mcf_batch_stats */
+    int64_t instances;
+    int64_t lds_instances;        /* the whole batch or none: the tier goes by the stride */
+    int64_t global_instances;
+    int64_t launches;             /* batch_kernel launches (the set-up, re-cost and finish launches are one each and not counted) */
+    int64_t total_pivots;
+    int64_t workspace_bytes;      /* count * stride */
+    int64_t lds_bytes_max;        /* the stride, when a launch ran in LDS */
+    double kernel_ns;             /* host clock round the batch_kernel rounds */
+    double host_ns;               /* the rest of the call */
+    int64_t bytes_up;             /* MCF_MEM_DEVICE: the slot template and the instance ids of every round of launches */
+    int64_t bytes_down;           /* MCF_MEM_DEVICE: the slots, once after the set-up and once per round.  MCF_MEM_HOST adds the arrays */
+    double begin_ns, finish_ns;   /* host clock round the set-up (or re-cost) launch with the slots' download, and round the finish launch */
+} mcf_ubatch_stats;
+
+MCF_API int mcf_ubatch_create(mcf_ubatch **out, const mcf_ubatch_desc *desc);
+MCF_API void mcf_ubatch_destroy(mcf_ubatch *b);
+/* Solves all `count` instances on the device, on the null stream; returns synchronised.  May be called again: every call is a fresh solve
+ * on the same buffers, and it is how supplies or bounds change.  MCF_ERR_NO_DEVICE without a GPU; the handle is left as it was. */
+MCF_API int mcf_ubatch_solve(mcf_ubatch *b, const mcf_ubatch_io *io);
+/* Re-solves the instances `changed` marks with the costs in io, as mcf_batch_resolve does: from the kept basis where the instance's last
+ * solve ended MCF_OPTIMAL with no flow on an artificial arc, from the start basis otherwise (the limit stated there holds here too).
+ * io->cost is read for every marked instance; io->lower / upper / supply are read for the ones that start again and for the output
+ * flows, and MUST be what the last mcf_ubatch_solve was given (supply_type too).  Rows of unmarked instances are not written.
+ * MCF_ERR_STATE before a solve of either kind. */
+MCF_API int mcf_ubatch_resolve(mcf_ubatch *b, const mcf_ubatch_io *io);
+/* TEST HOOKS, not supported solvers: the same step functions (csrc/uniform_step.hip.h, csrc/batch_step.hip.h) with one lane on the CPU.
+ * io->memory must be MCF_MEM_HOST.  May be mixed with the device calls in any order: the results are the same. */
+MCF_API int mcf_ubatch_run_on_host(mcf_ubatch *b, const mcf_ubatch_io *io);
+MCF_API int mcf_ubatch_rerun_on_host(mcf_ubatch *b, const mcf_ubatch_io *io);
+MCF_API int mcf_ubatch_get_stats(mcf_ubatch *b, mcf_ubatch_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,11 @@ device operation fails with McfError when no MI355X is usable.
 from __future__ import annotations
 
 import ctypes as C
+import importlib.util
 import os
+import re
+import sys
+import warnings
 
 import numpy as np
 
@@ -143,6 +147,27 @@ class BatchResolveStats(C.Structure):
 
 
 BATCH_MAX_ARCS, BATCH_MAX_NODES, BATCH_MAX_INSTANCES, BATCH_SHARDED = 65536, 32768, 65536, 1
+MEM_HOST, MEM_DEVICE = 0, 1
+
+
+class UBatchDesc(C.Structure):
+    """mcf_ubatch_desc"""
+    _fields_ = BatchDesc._fields_ + [("node_count", C.c_int32), ("arc_count", C.c_int32), ("count", C.c_int32), ("source", C.c_void_p), ("target", C.c_void_p)]
+
+
+class UBatchIo(C.Structure):
+    """mcf_ubatch_io"""
+    _fields_ = [("memory", C.c_int32), ("supply_type", C.c_int32), ("lower", C.c_void_p), ("upper", C.c_void_p), ("cost", C.c_void_p), ("supply", C.c_void_p),
+                ("lower_stride", C.c_int64), ("upper_stride", C.c_int64), ("cost_stride", C.c_int64), ("supply_stride", C.c_int64), ("changed", C.c_void_p),
+                ("status", C.c_void_p), ("pivots", C.c_void_p), ("total_cost", C.c_void_p), ("flows", C.c_void_p), ("potentials", C.c_void_p), ("trace", C.c_void_p)]
+
+
+class UBatchStats(C.Structure):
+    """mcf_ubatch_stats"""
+    _fields_ = BatchStats._fields_ + [("bytes_up", C.c_int64), ("bytes_down", C.c_int64), ("begin_ns", C.c_double), ("finish_ns", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class ProblemStruct(C.Structure):
@@ -285,6 +310,13 @@ SIGNATURES = {
     "mcf_batch_resolve": (C.c_int, [C.c_void_p]),
     "mcf_batch_rerun_on_host": (C.c_int, [C.c_void_p]),
     "mcf_batch_get_resolve_stats": (C.c_int, [C.c_void_p, _P(BatchResolveStats)]),
+    "mcf_ubatch_create": (C.c_int, [_P(C.c_void_p), _P(UBatchDesc)]),
+    "mcf_ubatch_destroy": (None, [C.c_void_p]),
+    "mcf_ubatch_solve": (C.c_int, [C.c_void_p, _P(UBatchIo)]),
+    "mcf_ubatch_resolve": (C.c_int, [C.c_void_p, _P(UBatchIo)]),
+    "mcf_ubatch_run_on_host": (C.c_int, [C.c_void_p, _P(UBatchIo)]),
+    "mcf_ubatch_rerun_on_host": (C.c_int, [C.c_void_p, _P(UBatchIo)]),
+    "mcf_ubatch_get_stats": (C.c_int, [C.c_void_p, _P(UBatchStats)]),
     "mcf_problem_free": (None, [_P(ProblemStruct)]),
     "mcf_gen_netgen_like": (C.c_int, [_P(ProblemStruct), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
@@ -298,6 +330,39 @@ SIGNATURES = {
 _lib = None
 
 
+def _hip_sonames(path):
+    """Every libamdhip64.so.N named in a shared library: the runtime it needs, or -- in the runtime itself -- its own soname."""
+    with open(path, "rb") as fh:
+        return set(re.findall(rb"libamdhip64\.so\.\d+", fh.read()))
+
+
+def _share_torchs_hip_runtime():
+    """torch's ROCm wheels bring a HIP runtime of their own (torch/lib/libamdhip64.so), and a process can open the GPU through one runtime
+    only: with two loaded, the second finds no device.  torch asks for its copy by file name, so it never reuses a runtime that is
+    already there; this library asks by soname and takes the one that is loaded.  So where torch is installed but not imported yet, and
+    its runtime has the soname libmcf_hip.so was linked against, that runtime is loaded first, and a later `import torch` (UniformBatch
+    takes tensors) still finds the GPU.  torch itself is not imported.  With another soname (a torch wheel of another ROCm major) nothing
+    is preloaded: the library runs on the system's runtime as long as torch.cuda stays unused, as it always did.
+    MCF_HIP_RUNTIME=system switches the preload off."""
+    if os.environ.get("MCF_HIP_RUNTIME", "").lower() == "system" or "torch" in sys.modules:
+        return
+    try:
+        spec = importlib.util.find_spec("torch")
+    except (ImportError, ValueError):
+        return
+    if spec is None or not spec.origin:
+        return
+    path = os.path.join(os.path.dirname(spec.origin), "lib", "libamdhip64.so")
+    if not os.path.exists(path):
+        return
+    try:
+        if not _hip_sonames(LIB_PATH) & _hip_sonames(path):
+            return
+        C.CDLL(path, mode=C.RTLD_GLOBAL)
+    except OSError as e:
+        warnings.warn(f"mincostflow_amd: torch's HIP runtime {path} could not be loaded first ({e}); torch.cuda may find no device in this process")
+
+
 def lib():
     """The loaded library.  Raises if libmcf_hip.so has not been built (python -c 'import __graft_entry__ as g; g.build()')."""
     global _lib
@@ -305,6 +370,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"{LIB_PATH} is missing: build it with `make -C mincostflow_amd/csrc` "
                               "(there is no Python/CPU implementation to fall back to)")
+        _share_torchs_hip_runtime()
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(L, name)

@@ -18,9 +18,11 @@
 #include <cstring>
 #include <vector>
 
+#include "batch_layout.hip.h"
 #include "batch_step.hip.h"
 #include "common.h"
 #include "ns_core.h"
+#include "uniform_step.hip.h"
 
 namespace {
 
@@ -33,84 +35,13 @@ namespace {
 constexpr int kBatchThreads = 64;          // one wave: the sequential and the lane-parallel half alternate without a workgroup of waves to hold
 constexpr int kDefaultPivotsPerLaunch = 2048;   // 15 us per pivot in LDS, 35 in place -> launches of 30 - 70 ms
 
-// ---- workspace of one instance: A = all_arcs arcs, N = n + 1 nodes; every array starts on a 16-byte boundary.
-//   constant part:  tail[A] i32 | head[A] i32 | cost[A] i64 | upper[A] i64
-//   changing part:  flow[A] i64 | pi[N] i64 | par, par_arc, nxt, prv, sub, fin [N] i32 each | scratch[N + 1] i32 | state[A] i8 | par_dir[N] i8
-// bytes = 33 A + 37 N + 4 + padding (at most 15 per array)
-struct Layout {
-    uint32_t tail, head, cost, upper, flow, pi, par, par_arc, nxt, prv, sub, fin, scratch, state, par_dir;
-    uint32_t changing;      // = flow: first byte of the part a launch writes back
-    uint32_t bytes;
-};
-__host__ __device__ inline uint32_t up16(uint32_t x) { return (x + 15u) & ~15u; }
-__host__ __device__ inline Layout layout_of(uint32_t A, uint32_t N)
-{
-    Layout l;
-    uint32_t o = 0;
-    l.tail = o; o = up16(o + 4 * A);
-    l.head = o; o = up16(o + 4 * A);
-    l.cost = o; o = up16(o + 8 * A);
-    l.upper = o; o = up16(o + 8 * A);
-    l.flow = l.changing = o; o = up16(o + 8 * A);
-    l.pi = o; o = up16(o + 8 * N);
-    l.par = o; o = up16(o + 4 * N);
-    l.par_arc = o; o = up16(o + 4 * N);
-    l.nxt = o; o = up16(o + 4 * N);
-    l.prv = o; o = up16(o + 4 * N);
-    l.sub = o; o = up16(o + 4 * N);
-    l.fin = o; o = up16(o + 4 * N);
-    l.scratch = o; o = up16(o + 4 * (N + 1));
-    l.state = o; o = up16(o + A);
-    l.par_dir = o; o = up16(o + N);
-    l.bytes = o;
-    return l;
-}
-__host__ __device__ inline void bind(mcf::BatchWork &w, unsigned char *base, const Layout &l)
-{
-    w.tail = (const int32_t *)(base + l.tail); w.head = (const int32_t *)(base + l.head);
-    w.cost = (const int64_t *)(base + l.cost); w.upper = (const int64_t *)(base + l.upper);
-    w.flow = (int64_t *)(base + l.flow); w.pi = (int64_t *)(base + l.pi);
-    w.par = (int32_t *)(base + l.par); w.par_arc = (int32_t *)(base + l.par_arc); w.nxt = (int32_t *)(base + l.nxt);
-    w.prv = (int32_t *)(base + l.prv); w.sub = (int32_t *)(base + l.sub); w.fin = (int32_t *)(base + l.fin);
-    w.scratch = (int32_t *)(base + l.scratch); w.state = (int8_t *)(base + l.state); w.par_dir = (int8_t *)(base + l.par_dir);
-}
-
-// what a launch needs to know of an instance and what it leaves behind; one per instance, in device memory
-struct BatchSlot {
-    uint64_t workspace;         // byte offset of the workspace in the slab
-    uint64_t trace;             // index of the first trace entry in the trace buffer
-    int64_t pivots, pivot_limit, max_iter;
-    int32_t n, all_arcs, search_arcs, rule;
-    int32_t next_arc, block_size, dyn_min, counters[2];
-    int32_t trace_cap;
-    int32_t run;                // mcf::BatchRun
-    int32_t reprice;            // a warm re-solve: the potentials are recomputed from the basis before the first pivot; the launch that did it clears this
-    uint64_t staged_cost;       // a re-solve's staging buffer: where this instance's new cost[] waits (stage_kernel<true>) ...
-    uint64_t staged_out;        // ... and where its changing part goes for the download (stage_kernel<false>)
-    mcf_block_config cfg;
-};
-
-static_assert(sizeof(BatchSlot) == 104 + sizeof(mcf_block_config), "BatchSlot has no padding: a re-solve counts the bytes it uploads by it");
-
-__host__ __device__ inline void load_slot(mcf::BatchWork &w, const BatchSlot &s, int32_t *trace_base)
-{
-    w.n = s.n; w.search_arcs = s.search_arcs; w.rule = s.rule;
-    w.next_arc = s.next_arc; w.block_size = s.block_size; w.dyn_min = s.dyn_min;
-    w.counters[0] = s.counters[0]; w.counters[1] = s.counters[1];
-    w.cfg = s.cfg;
-    w.pivots = s.pivots; w.pivot_limit = s.pivot_limit; w.max_iter = s.max_iter;
-    w.trace_cap = s.trace_cap;
-    w.trace = s.trace_cap > 0 ? trace_base + s.trace : nullptr;
-    w.run = s.run;
-}
-__host__ __device__ inline void store_slot(BatchSlot &s, const mcf::BatchWork &w)
-{
-    s.next_arc = w.next_arc; s.block_size = w.block_size;
-    s.counters[0] = w.counters[0]; s.counters[1] = w.counters[1];
-    s.pivots = w.pivots;
-    s.run = w.run;
-    s.reprice = 0;
-}
+// the workspace layout and the per-instance slot: batch_layout.hip.h
+using mcf::BatchSlot;
+using mcf::Layout;
+using mcf::bind;
+using mcf::layout_of;
+using mcf::load_slot;
+using mcf::store_slot;
 
 // One workgroup = one wave = one instance: ids[blockIdx.x].  kLds: dynamic LDS holds the workspace (the host launches with at least
 // layout.bytes of it); otherwise the pivots run on the workspace itself.
@@ -161,6 +92,29 @@ __global__ __launch_bounds__(kStageThreads) void stage_kernel(const BatchSlot *s
     for (uint32_t i = threadIdx.x; i < count; i += kStageThreads) dst[i] = src[i];
 }
 
+// The uniform batch (mcf_ubatch_*): the steps of uniform_step.hip.h, one workgroup of one wave per instance like batch_kernel -- the
+// start basis numbers the artificial arcs by a wave-wide prefix count, and all three combine their lanes by wave reductions.  Block i
+// serves instance i and leaves at once where `changed` (a re-solve's mask) says so.  They work on the workspace in device memory; the
+// caller's arrays are read and written as base + i * stride, consecutive lanes on consecutive arcs or nodes.
+__global__ __launch_bounds__(kBatchThreads) void uniform_begin_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
+{
+    const int64_t i = (int64_t)blockIdx.x;
+    mcf::uniform_begin(p, i, *tmpl, slots[i], slab + (uint64_t)i * p.stride, (int)threadIdx.x, kBatchThreads);
+}
+__global__ __launch_bounds__(kBatchThreads) void uniform_recost_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
+{
+    const int64_t i = (int64_t)blockIdx.x;
+    if (p.changed && !p.changed[i]) return;
+    mcf::uniform_recost(p, i, *tmpl, slots[i], slab + (uint64_t)i * p.stride, (int)threadIdx.x, kBatchThreads);
+}
+__global__ __launch_bounds__(kBatchThreads) void uniform_finish_kernel(mcf::UniformProblem p, mcf::UniformOutputs o, const BatchSlot *slots, const unsigned char *slab,
+                                                                       const int32_t *traces)
+{
+    const int64_t i = (int64_t)blockIdx.x;
+    if (p.changed && !p.changed[i]) return;
+    mcf::uniform_finish(p, o, i, slots[i], slab + (uint64_t)i * p.stride, traces, (int)threadIdx.x, kBatchThreads);
+}
+
 struct Instance {
     mcf::NsCore core;
     Layout layout{};
@@ -178,6 +132,9 @@ struct DeviceBuffers {
     BatchSlot *slots = nullptr;
     int32_t *ids = nullptr, *traces = nullptr;
     size_t stage_bytes = 0;
+    DeviceBuffers() = default;
+    DeviceBuffers(const DeviceBuffers &) = delete;
+    DeviceBuffers &operator=(const DeviceBuffers &) = delete;
     ~DeviceBuffers()
     {
         if (slab) (void)hipFree(slab);
@@ -205,26 +162,43 @@ struct mcf_batch {
 
 namespace {
 
-// the rule's state at a cold start (NS.cs:237-270: the constructor's block size), the counts and the limits
-int reset_run_state(const mcf_batch *b, Instance *in)
+// what a handle's descriptor says of every solve it runs (mcf_batch_desc and mcf_ubatch_desc agree on these)
+struct RunLimits {
+    int32_t rule;
+    int64_t pivot_limit;
+    int32_t trace_capacity;
+};
+template <class Desc>
+RunLimits limits_of(const Desc &d) { return RunLimits{d.pivot_rule, d.pivot_limit, d.trace_capacity}; }
+
+// the rule's state at a cold start (NS.cs:237-270: the constructor's block size), the counts and the limits, for a slot whose graph
+// (n, search_arcs, rule, cfg) is set; m = its arcs without the root links
+int reset_run_state(BatchSlot &s, const RunLimits &lim, int32_t m)
 {
-    const mcf::NsCore &c = in->core;
-    BatchSlot &s = in->slot;
     s.next_arc = 0; s.block_size = 0; s.dyn_min = 0; s.counters[0] = s.counters[1] = 0;
     if (s.rule == MCF_RULE_BLOCK_SEARCH) {
         int32_t block = 0, dyn_min = 0;
-        if (const int rc = mcf_block_initial_size(&s.cfg, c.search_arcs, c.n, &block, &dyn_min)) return rc;
+        if (const int rc = mcf_block_initial_size(&s.cfg, s.search_arcs, s.n, &block, &dyn_min)) return rc;
         s.block_size = std::max(1, block);
         s.dyn_min = dyn_min;
     }
     s.pivots = 0;
-    s.pivot_limit = b->d.pivot_limit > 0 ? b->d.pivot_limit : 64 * ((int64_t)c.m + 2 * (int64_t)c.n) + 1024;
-    s.max_iter = std::max<int64_t>(1000000, (int64_t)c.n * (int64_t)c.m);      // NS.cs:280
-    s.trace_cap = b->d.trace_capacity;
+    s.pivot_limit = lim.pivot_limit > 0 ? lim.pivot_limit : 64 * ((int64_t)m + 2 * (int64_t)s.n) + 1024;
+    s.max_iter = std::max<int64_t>(1000000, (int64_t)s.n * (int64_t)m);      // NS.cs:280
+    s.trace_cap = lim.trace_capacity;
     s.run = mcf::kBatchRunning;
     s.reprice = 0;
-    in->trace_len = 0;
     return MCF_OK;
+}
+
+// NS.cs:237-270 for one graph: the configuration `new NetworkSimplex(g).Solve()` chooses, the search range, the rule and its start state.
+// Everything in a slot that depends on the topology and the descriptor alone: mcf_batch fills one per instance, mcf_ubatch one per handle
+// (the template uniform_begin copies).  all_arcs, workspace and trace are the caller's.
+int configure_slot(BatchSlot &s, const RunLimits &lim, int32_t n, int32_t m, const int32_t *tail, const int32_t *head)
+{
+    if (const int rc = mcf_block_config_auto(&s.cfg, n, m, tail, head)) return rc;
+    s.n = n; s.search_arcs = m + n; s.rule = lim.rule;
+    return reset_run_state(s, lim, m);
 }
 
 // NS.cs:237-270 per instance: the configuration `new NetworkSimplex(g).Solve()` chooses, the constructor's block size, the limits.
@@ -239,10 +213,8 @@ int prepare_instance(const mcf_batch *b, Instance *in)
     in->trace_len = 0;
     in->on_device = mcf::core_begin(&c);
     if (!in->on_device) return MCF_OK;
-    int rc = mcf_block_config_auto(&s.cfg, c.n, c.m, c.tail.data(), c.head.data());
-    if (rc) return rc;
-    s.n = c.n; s.all_arcs = c.all_arcs; s.search_arcs = c.search_arcs; s.rule = b->d.pivot_rule;
-    if ((rc = reset_run_state(b, in))) return rc;
+    if (const int rc = configure_slot(s, limits_of(b->d), c.n, c.m, c.tail.data(), c.head.data())) return rc;
+    s.all_arcs = c.all_arcs;
     in->layout = layout_of((uint32_t)c.all_arcs, (uint32_t)c.n + 1u);
     in->trace.assign((size_t)std::max(0, b->d.trace_capacity), 0);
     return MCF_OK;
@@ -266,7 +238,8 @@ int prepare_resolve(const mcf_batch *b, Instance *in, bool *warm)
         return prepare_instance(b, in);
     }
     mcf::core_recost(&c, in->new_cost.data());
-    if (const int rc = reset_run_state(b, in)) return rc;
+    if (const int rc = reset_run_state(in->slot, limits_of(b->d), c.m)) return rc;
+    in->trace_len = 0;
     in->slot.reprice = 1;
     return MCF_OK;
 }
@@ -349,39 +322,40 @@ int begin_resolve(mcf_batch *b, const char *what)
     return MCF_OK;
 }
 
-int have_device(const mcf_batch *b, const char *what)
+int have_device(int32_t device, const char *what)
 {
     int devices = 0;
     if (hipGetDeviceCount(&devices) != hipSuccess || devices < 1) { (void)hipGetLastError(); return mcf::fail(MCF_ERR_NO_DEVICE, "%s: no HIP device (the host hooks are test hooks, not solvers)", what); }
-    if (b->d.device >= devices) return mcf::fail(MCF_ERR_NO_DEVICE, "%s: device %d of %d", what, b->d.device, devices);
+    if (device >= devices) return mcf::fail(MCF_ERR_NO_DEVICE, "%s: device %d of %d", what, device, devices);
     return MCF_OK;
 }
 
-int open_device(mcf_batch *b)
+// makes the device current; *lds_max_out = the dynamic LDS one workgroup of batch_kernel<true> may have
+int open_device(int32_t device, int *lds_max_out)
 {
-    HIP_TRY(hipSetDevice(b->d.device));
+    HIP_TRY(hipSetDevice(device));
     // the LDS one workgroup may have: the device's figure, never a constant of ours
     int lds_max = 0, lds_optin = 0;
-    HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, b->d.device));
-    if (hipDeviceGetAttribute(&lds_optin, hipDeviceAttributeSharedMemPerBlockOptin, b->d.device) != hipSuccess) { (void)hipGetLastError(); lds_optin = 0; }
+    HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+    if (hipDeviceGetAttribute(&lds_optin, hipDeviceAttributeSharedMemPerBlockOptin, device) != hipSuccess) { (void)hipGetLastError(); lds_optin = 0; }
     if (lds_optin > lds_max) lds_max = lds_optin;
     // the opt-in for dynamic LDS above the default limit; where the runtime refuses it, the default limit of 64 KiB holds
     if (hipFuncSetAttribute((const void *)batch_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) {
         (void)hipGetLastError();
         lds_max = std::min(lds_max, 64 << 10);
     }
-    b->lds_max = lds_max;
+    *lds_max_out = lds_max;
     return MCF_OK;
 }
 
 // Groups: the LDS tier in classes of the footprint (lds_max / 16, / 8, / 4, / 3, / 2, / 1: the steps at which one more workgroup fits a CU),
 // each launched with the largest footprint it holds, so that no launch sizes every workgroup for the batch's largest; the global tier last.
 constexpr int kClasses = 7;
-int class_of(const mcf_batch *b, const Instance *in)
+int class_of(int lds_max, uint32_t bytes)
 {
     const int divisor[kClasses - 1] = {16, 8, 4, 3, 2, 1};
     for (int k = 0; k < kClasses - 1; ++k)
-        if ((int64_t)in->layout.bytes <= (int64_t)b->lds_max / divisor[k]) return k;
+        if ((int64_t)bytes <= (int64_t)lds_max / divisor[k]) return k;
     return kClasses - 1;
 }
 
@@ -404,20 +378,32 @@ int allocate(mcf_batch *b)
 }
 
 struct LaunchTotals {
-    int64_t launches = 0, lds_bytes_max = 0, bytes_down = 0;
+    int64_t launches = 0, lds_bytes_max = 0, bytes_down = 0, bytes_up = 0;
     double kernel_ns = 0;
+};
+
+// what the launch loop needs of a handle: the device's buffers, the LDS limit, the budget of a launch and every instance's footprint --
+// one figure per instance (mcf_batch: the instances differ) or one for all (mcf_ubatch: one topology, workspaces at a fixed stride, so
+// the whole batch is one class)
+struct LaunchPlan {
+    DeviceBuffers *dev;
+    int lds_max;
+    int32_t pivots_per_launch;          // the descriptor's: 0 = the default
+    const uint32_t *footprint;          // per instance, or null:
+    uint32_t footprint_all;
+    uint32_t bytes(int32_t i) const { return footprint ? footprint[(size_t)i] : footprint_all; }
 };
 
 // Relaunches the instances `run` (ascending; their slots are on the device) until none is left running; every round ends in a
 // synchronising copy of the slots between the first and the last of them.  slots: the host's copy of every slot.
-int run_launches(mcf_batch *b, std::vector<BatchSlot> &slots, const std::vector<int32_t> &run, LaunchTotals *t)
+int run_launches(const LaunchPlan &plan, std::vector<BatchSlot> &slots, const std::vector<int32_t> &run, LaunchTotals *t)
 {
     if (run.empty()) return MCF_OK;
     std::vector<int32_t> group[kClasses];
-    for (int32_t i : run) group[class_of(b, b->inst[(size_t)i])].push_back(i);
+    for (int32_t i : run) group[class_of(plan.lds_max, plan.bytes(i))].push_back(i);
     const size_t lo = (size_t)run.front(), span = (size_t)run.back() - lo + 1;
-    const int32_t budget = b->d.pivots_per_launch > 0 ? b->d.pivots_per_launch : kDefaultPivotsPerLaunch;
-    DeviceBuffers &dev = b->dev;
+    const int32_t budget = plan.pivots_per_launch > 0 ? plan.pivots_per_launch : kDefaultPivotsPerLaunch;
+    DeviceBuffers &dev = *plan.dev;
     std::vector<int32_t> ids;
     for (;;) {
         ids.clear();
@@ -429,13 +415,14 @@ int run_launches(mcf_batch *b, std::vector<BatchSlot> &slots, const std::vector<
                 if (slots[(size_t)i].run != mcf::kBatchRunning) continue;
                 ids.push_back(i);
                 L.n++;
-                L.lds = std::max(L.lds, b->inst[(size_t)i]->layout.bytes);
+                L.lds = std::max(L.lds, plan.bytes(i));
             }
             if (L.n) launches.push_back(L);
         }
         if (launches.empty()) break;
         const double tk = mcf::now_ns();
         HIP_TRY(hipMemcpy(dev.ids, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        t->bytes_up += (int64_t)(ids.size() * sizeof(int32_t));
         for (const Launch &L : launches) {
             if (L.in_lds) {
                 hipLaunchKernelGGL(batch_kernel<true>, dim3((unsigned)L.n), dim3(kBatchThreads), L.lds, 0, dev.slots, dev.ids + L.first, dev.slab, dev.traces, budget);
@@ -471,6 +458,32 @@ int fetch_traces(mcf_batch *b, const std::vector<int32_t> &run, int64_t *bytes_d
     return MCF_OK;
 }
 
+// rules, semantics, flags and limits of a batch of either kind (mcf_batch_desc and mcf_ubatch_desc agree on these fields)
+template <class Desc>
+int check_batch_desc(const Desc &d, const char *who)
+{
+    if (d.pivot_rule == MCF_RULE_CANDIDATE_LIST || d.pivot_rule == MCF_RULE_ALTERING_LIST)
+        return mcf::fail(MCF_ERR_INVALID, "%s: the list rules (Candidate List, Altering List) are not part of the batch solver; use mcf_ns_set_list_pivot_rule", who);
+    if (d.pivot_rule != MCF_RULE_FIRST_ELIGIBLE && d.pivot_rule != MCF_RULE_BEST_ELIGIBLE && d.pivot_rule != MCF_RULE_BLOCK_SEARCH)
+        return mcf::fail(MCF_ERR_INVALID, "%s: unknown pivot rule %d", who, d.pivot_rule);
+    if (d.semantics == MCF_SEM_OPTIMIZED)
+        return mcf::fail(MCF_ERR_INVALID, "%s: MCF_SEM_OPTIMIZED (BlockSearchPivotOptimized and its vector-width reading) is not part of the batch solver; use mcf_ns_solve", who);
+    if (d.semantics != 0 && d.semantics != MCF_SEM_PLAIN) return mcf::fail(MCF_ERR_INVALID, "%s: unknown semantics %d", who, d.semantics);
+    if (d.flags & MCF_BATCH_SHARDED) return mcf::fail(MCF_ERR_INVALID, "%s: sharding is not part of the batch solver (a batch runs on one device)", who);
+    if (d.flags & ~MCF_BATCH_SHARDED) return mcf::fail(MCF_ERR_INVALID, "%s: unknown flags %d", who, d.flags);
+    if (d.device < 0 || d.pivot_limit < 0 || d.pivots_per_launch < 0 || d.trace_capacity < 0)
+        return mcf::fail(MCF_ERR_INVALID, "%s: negative device, pivot limit, pivots per launch or trace capacity", who);
+    return MCF_OK;
+}
+
+// the launch plan of a mcf_batch: `footprints` gets every instance's workspace size and must outlive the plan
+LaunchPlan plan_of(mcf_batch *b, std::vector<uint32_t> &footprints)
+{
+    footprints.resize(b->inst.size());
+    for (size_t i = 0; i < b->inst.size(); ++i) footprints[i] = b->inst[i]->layout.bytes;
+    return LaunchPlan{&b->dev, b->lds_max, b->d.pivots_per_launch, footprints.data(), 0};
+}
+
 }  // namespace
 
 extern "C" {
@@ -479,17 +492,7 @@ int mcf_batch_create(mcf_batch **out, const mcf_batch_desc *desc)
 {
     if (!out || !desc) return mcf::fail(MCF_ERR_INVALID, "mcf_batch_create: null argument");
     *out = nullptr;
-    if (desc->pivot_rule == MCF_RULE_CANDIDATE_LIST || desc->pivot_rule == MCF_RULE_ALTERING_LIST)
-        return mcf::fail(MCF_ERR_INVALID, "mcf_batch_create: the list rules (Candidate List, Altering List) are not part of the batch solver; use mcf_ns_set_list_pivot_rule");
-    if (desc->pivot_rule != MCF_RULE_FIRST_ELIGIBLE && desc->pivot_rule != MCF_RULE_BEST_ELIGIBLE && desc->pivot_rule != MCF_RULE_BLOCK_SEARCH)
-        return mcf::fail(MCF_ERR_INVALID, "mcf_batch_create: unknown pivot rule %d", desc->pivot_rule);
-    if (desc->semantics == MCF_SEM_OPTIMIZED)
-        return mcf::fail(MCF_ERR_INVALID, "mcf_batch_create: MCF_SEM_OPTIMIZED (BlockSearchPivotOptimized and its vector-width reading) is not part of the batch solver; use mcf_ns_solve");
-    if (desc->semantics != 0 && desc->semantics != MCF_SEM_PLAIN) return mcf::fail(MCF_ERR_INVALID, "mcf_batch_create: unknown semantics %d", desc->semantics);
-    if (desc->flags & MCF_BATCH_SHARDED) return mcf::fail(MCF_ERR_INVALID, "mcf_batch_create: sharding is not part of the batch solver (a batch runs on one device)");
-    if (desc->flags & ~MCF_BATCH_SHARDED) return mcf::fail(MCF_ERR_INVALID, "mcf_batch_create: unknown flags %d", desc->flags);
-    if (desc->device < 0 || desc->pivot_limit < 0 || desc->pivots_per_launch < 0 || desc->trace_capacity < 0)
-        return mcf::fail(MCF_ERR_INVALID, "mcf_batch_create: negative device, pivot limit, pivots per launch or trace capacity");
+    if (const int rc = check_batch_desc(*desc, "mcf_batch_create")) return rc;
     mcf_batch *b = new mcf_batch();
     b->d = *desc;
     b->d.semantics = MCF_SEM_PLAIN;
@@ -541,10 +544,10 @@ int mcf_batch_run_on_host(mcf_batch *b)
 int mcf_batch_solve(mcf_batch *b)
 {
     if (const int rc = begin_solve(b)) return rc;
-    if (const int rc = have_device(b, "mcf_batch_solve")) return rc;
+    if (const int rc = have_device(b->d.device, "mcf_batch_solve")) return rc;
     const double t_start = mcf::now_ns();
     b->solved = true;
-    if (const int rc = open_device(b)) return rc;
+    if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
 
     // set every instance up; place the workspaces
     const size_t count = b->inst.size();
@@ -558,7 +561,7 @@ int mcf_batch_solve(mcf_batch *b)
         slots[i] = in->slot;
         if (!in->on_device) continue;
         run.push_back((int32_t)i);
-        if (class_of(b, in) == kClasses - 1) b->stats.global_instances++; else b->stats.lds_instances++;
+        if (class_of(b->lds_max, in->layout.bytes) == kClasses - 1) b->stats.global_instances++; else b->stats.lds_instances++;
     }
     b->stats.workspace_bytes = (int64_t)b->slab_bytes;
 
@@ -570,7 +573,8 @@ int mcf_batch_solve(mcf_batch *b)
         HIP_TRY(hipMemcpy(dev.slots, slots.data(), count * sizeof(BatchSlot), hipMemcpyHostToDevice));
     }
     LaunchTotals t;
-    if (const int rc = run_launches(b, slots, run, &t)) return rc;
+    std::vector<uint32_t> footprints;
+    if (const int rc = run_launches(plan_of(b, footprints), slots, run, &t)) return rc;
     b->stats.launches = t.launches;
     b->stats.lds_bytes_max = t.lds_bytes_max;
     // the state comes home; the host finishes every instance
@@ -635,9 +639,9 @@ int mcf_batch_resolve(mcf_batch *b)
     mcf_batch_resolve_stats st{};
     st.untouched_instances = (int64_t)(count - changed.size());
     if (changed.empty()) { b->resolve_stats = st; return MCF_OK; }          // nothing to launch: no device needed either
-    if (const int rc = have_device(b, "mcf_batch_resolve")) return rc;       // the batch is as it was
+    if (const int rc = have_device(b->d.device, "mcf_batch_resolve")) return rc;       // the batch is as it was
     const double t_start = mcf::now_ns();
-    if (const int rc = open_device(b)) return rc;
+    if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
     DeviceBuffers &dev = b->dev;
 
     // Warm instances whose state is in the slab get their new cost[] (through the staging buffer) and their slot; every other instance
@@ -707,7 +711,8 @@ int mcf_batch_resolve(mcf_batch *b)
             st.bytes_uploaded += (int64_t)(end - begin);
             k = j;
         }
-        if (const int rc = run_launches(b, slots, run, &t)) return rc;
+        std::vector<uint32_t> footprints;
+        if (const int rc = run_launches(plan_of(b, footprints), slots, run, &t)) return rc;
         // only the changing part of the instances that ran comes home
         HIP_TRY(hipMemcpy(dev.ids, run.data(), run.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(stage_kernel<false>, dim3((unsigned)run.size()), dim3(kStageThreads), 0, 0, dev.slots, dev.ids, dev.slab, dev.stage);
@@ -799,6 +804,298 @@ int mcf_batch_get_trace(mcf_batch *b, int32_t index, int32_t *out, int64_t capac
     return MCF_OK;
 }
 int mcf_batch_get_stats(mcf_batch *b, mcf_batch_stats *out)
+{
+    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
+    *out = b->stats;
+    return MCF_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================
+// mcf_ubatch_*: one topology, problem data in and results out where they are ("Uniform batch")
+// ================================================================================================
+struct mcf_ubatch {
+    mcf_ubatch_desc d{};
+    std::vector<int32_t> source, target;
+    BatchSlot tmpl{};                   // everything of a slot that the topology and the descriptor decide (configure_slot), filled once
+    uint32_t stride = 0;                // bytes between workspaces
+    enum Where { kNowhere, kOnHost, kOnDevice } where = kNowhere;      // who holds the state the last solve of either kind left
+    mcf_ubatch_stats stats{};
+    int lds_max = 0;
+    DeviceBuffers dev;                  // slab (count * stride), slots, ids, traces
+    BatchSlot *d_tmpl = nullptr;
+    int32_t *d_source = nullptr, *d_target = nullptr;
+    unsigned char *d_io = nullptr;      // MCF_MEM_HOST: the caller's arrays on their way up and down
+    size_t d_io_bytes = 0;
+    std::vector<unsigned char> h_slab;  // the host hooks' slab, slots and traces: the device's layout
+    std::vector<BatchSlot> h_slots;
+    std::vector<int32_t> h_traces;
+    ~mcf_ubatch()
+    {
+        if (d_tmpl) (void)hipFree(d_tmpl);
+        if (d_source) (void)hipFree(d_source);
+        if (d_target) (void)hipFree(d_target);
+        if (d_io) (void)hipFree(d_io);
+    }
+};
+
+namespace {
+
+// the calls make the handle's device current while they run and leave the caller's (torch's, in a process that has it) as it was
+struct DeviceGuard {
+    int previous = -1;
+    DeviceGuard() { if (hipGetDevice(&previous) != hipSuccess) { (void)hipGetLastError(); previous = -1; } }
+    ~DeviceGuard() { if (previous >= 0) (void)hipSetDevice(previous); }
+};
+
+int check_io(const mcf_ubatch *b, const mcf_ubatch_io *io, const char *what, bool host_only, bool resolve)
+{
+    if (!b || !io) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
+    if (io->memory != MCF_MEM_HOST && io->memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io->memory);
+    if (host_only && io->memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
+    if (io->supply_type != MCF_SUPPLY_GEQ && io->supply_type != MCF_SUPPLY_LEQ) return mcf::fail(MCF_ERR_INVALID, "Invalid supply type");
+    if (io->lower_stride < 0 || io->upper_stride < 0 || io->cost_stride < 0 || io->supply_stride < 0)
+        return mcf::fail(MCF_ERR_INVALID, "%s: negative stride", what);
+    if (resolve && b->where == mcf_ubatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
+    return MCF_OK;
+}
+
+mcf::UniformProblem problem_of(const mcf_ubatch *b, const mcf_ubatch_io *io, const int32_t *source, const int32_t *target, bool resolve)
+{
+    mcf::UniformProblem p{};
+    p.n = b->d.node_count; p.m = b->d.arc_count; p.supply_type = io->supply_type; p.trace_cap = b->d.trace_capacity;
+    p.source = source; p.target = target;
+    p.lower = io->lower; p.upper = io->upper; p.cost = io->cost; p.supply = io->supply;
+    p.lower_stride = io->lower_stride; p.upper_stride = io->upper_stride; p.cost_stride = io->cost_stride; p.supply_stride = io->supply_stride;
+    p.stride = b->stride;
+    p.changed = resolve ? io->changed : nullptr;
+    return p;
+}
+mcf::UniformOutputs outputs_of(const mcf_ubatch_io *io)
+{
+    return mcf::UniformOutputs{io->status, io->pivots, io->total_cost, io->flows, io->potentials, io->trace};
+}
+
+int ensure_device_buffers(mcf_ubatch *b)
+{
+    if (b->dev.slab) return MCF_OK;
+    const size_t count = (size_t)b->d.count, m = (size_t)b->d.arc_count;
+    HIP_TRY(hipMalloc((void **)&b->dev.slab, count * (size_t)b->stride));
+    HIP_TRY(hipMalloc((void **)&b->dev.slots, count * sizeof(BatchSlot)));
+    HIP_TRY(hipMalloc((void **)&b->dev.ids, count * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void **)&b->dev.traces, std::max<size_t>(count * (size_t)b->d.trace_capacity, 1) * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void **)&b->d_tmpl, sizeof(BatchSlot)));
+    HIP_TRY(hipMalloc((void **)&b->d_source, std::max<size_t>(m, 1) * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void **)&b->d_target, std::max<size_t>(m, 1) * sizeof(int32_t)));
+    // the topology goes up once per handle
+    if (m) {
+        HIP_TRY(hipMemcpy(b->d_source, b->source.data(), m * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(b->d_target, b->target.data(), m * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    return MCF_OK;
+}
+
+// MCF_MEM_HOST: one copy up per input array and one down per output array, through one device buffer
+struct Staged {
+    struct Piece { const void *host_in; void *host_out; size_t offset, bytes; };
+    std::vector<Piece> pieces;
+    size_t total = 0;
+    // returns the offset; the device pointer is known once the buffer is
+    size_t add(const void *in, void *out, size_t bytes)
+    {
+        const size_t at = total;
+        pieces.push_back(Piece{in, out, at, bytes});
+        total += (bytes + 15) & ~(size_t)15;
+        return at;
+    }
+};
+size_t input_elements(size_t count, int64_t stride, size_t length) { return count ? (count - 1) * (size_t)stride + length : 0; }
+
+// the caller's io as the kernels see it: itself for MCF_MEM_DEVICE, staged copies for MCF_MEM_HOST (uploaded here).  keep_rows: the
+// output arrays go up too, because the call will not write every row (a masked re-solve)
+int stage_up(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve, mcf_ubatch_io *dio, Staged *st)
+{
+    *dio = *io;
+    if (io->memory == MCF_MEM_DEVICE) return MCF_OK;
+    const size_t count = (size_t)b->d.count, n = (size_t)b->d.node_count, m = (size_t)b->d.arc_count, cap = (size_t)b->d.trace_capacity;
+    const bool keep_rows = resolve && io->changed;
+    struct In { const void *p; size_t bytes; const void **slot; };
+    const In ins[] = {{io->lower, 8 * input_elements(count, io->lower_stride, m), (const void **)&dio->lower},
+                      {io->upper, 8 * input_elements(count, io->upper_stride, m), (const void **)&dio->upper},
+                      {io->cost, 8 * input_elements(count, io->cost_stride, m), (const void **)&dio->cost},
+                      {io->supply, 8 * input_elements(count, io->supply_stride, n), (const void **)&dio->supply},
+                      {resolve ? io->changed : nullptr, count, (const void **)&dio->changed}};
+    struct Out { void *p; size_t bytes; void **slot; };
+    const Out outs[] = {{io->status, 4 * count, (void **)&dio->status},       {io->pivots, 8 * count, (void **)&dio->pivots},
+                        {io->total_cost, 8 * count, (void **)&dio->total_cost}, {io->flows, 8 * count * m, (void **)&dio->flows},
+                        {io->potentials, 8 * count * n, (void **)&dio->potentials}, {io->trace, 4 * count * cap, (void **)&dio->trace}};
+    size_t at_in[5], at_out[6];
+    for (int k = 0; k < 5; ++k) at_in[k] = ins[k].p ? st->add(ins[k].p, nullptr, ins[k].bytes) : 0;
+    for (int k = 0; k < 6; ++k) at_out[k] = outs[k].p ? st->add(keep_rows ? outs[k].p : nullptr, outs[k].p, outs[k].bytes) : 0;
+    if (b->d_io_bytes < st->total) {
+        if (b->d_io) { HIP_TRY(hipFree(b->d_io)); b->d_io = nullptr; b->d_io_bytes = 0; }
+        HIP_TRY(hipMalloc((void **)&b->d_io, st->total));
+        b->d_io_bytes = st->total;
+    }
+    for (int k = 0; k < 5; ++k) *ins[k].slot = ins[k].p ? b->d_io + at_in[k] : nullptr;
+    for (int k = 0; k < 6; ++k) *outs[k].slot = outs[k].p ? b->d_io + at_out[k] : nullptr;
+    for (const Staged::Piece &pc : st->pieces)
+        if (pc.host_in && pc.bytes) {
+            HIP_TRY(hipMemcpy(b->d_io + pc.offset, pc.host_in, pc.bytes, hipMemcpyHostToDevice));
+            b->stats.bytes_up += (int64_t)pc.bytes;
+        }
+    return MCF_OK;
+}
+int stage_down(mcf_ubatch *b, const Staged &st)
+{
+    for (const Staged::Piece &pc : st.pieces)
+        if (pc.host_out && pc.bytes) {
+            HIP_TRY(hipMemcpy(pc.host_out, b->d_io + pc.offset, pc.bytes, hipMemcpyDeviceToHost));
+            b->stats.bytes_down += (int64_t)pc.bytes;
+        }
+    return MCF_OK;
+}
+
+// mcf_ubatch_solve and mcf_ubatch_resolve: set-up (or re-cost) launch, the launch loop of mcf_batch_solve, finish launch
+int ubatch_on_device(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve)
+{
+    const char *const what = resolve ? "mcf_ubatch_resolve" : "mcf_ubatch_solve";
+    if (const int rc = check_io(b, io, what, false, resolve)) return rc;
+    if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
+    const double t_start = mcf::now_ns();
+    const DeviceGuard guard;
+    if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
+    const size_t count = (size_t)b->d.count;
+    const bool in_lds = class_of(b->lds_max, b->stride) != kClasses - 1;
+    b->stats = mcf_ubatch_stats{};
+    b->stats.instances = (int64_t)count;
+    (in_lds ? b->stats.lds_instances : b->stats.global_instances) = (int64_t)count;
+    b->stats.workspace_bytes = (int64_t)(count * (size_t)b->stride);
+    if (!count) { b->where = mcf_ubatch::kOnDevice; b->stats.host_ns = mcf::now_ns() - t_start; return MCF_OK; }
+    if (const int rc = ensure_device_buffers(b)) return rc;
+    DeviceBuffers &dev = b->dev;
+    if (resolve && b->where == mcf_ubatch::kOnHost) {                       // the last solve was a host hook's: its state goes up whole
+        HIP_TRY(hipMemcpy(dev.slab, b->h_slab.data(), b->h_slab.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dev.slots, b->h_slots.data(), count * sizeof(BatchSlot), hipMemcpyHostToDevice));
+        b->stats.bytes_up += (int64_t)(b->h_slab.size() + count * sizeof(BatchSlot));
+    }
+    mcf_ubatch_io dio;
+    Staged staged;
+    if (const int rc = stage_up(b, io, resolve, &dio, &staged)) return rc;
+    const mcf::UniformProblem p = problem_of(b, &dio, b->d_source, b->d_target, resolve);
+
+    const double t_begin = mcf::now_ns();
+    HIP_TRY(hipMemcpy(b->d_tmpl, &b->tmpl, sizeof(BatchSlot), hipMemcpyHostToDevice));
+    b->stats.bytes_up += (int64_t)sizeof(BatchSlot);
+    if (resolve) hipLaunchKernelGGL(uniform_recost_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
+    else hipLaunchKernelGGL(uniform_begin_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
+    HIP_TRY(hipGetLastError());
+    b->where = mcf_ubatch::kOnDevice;
+    std::vector<BatchSlot> slots(count);
+    HIP_TRY(hipMemcpy(slots.data(), dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));      // waits for the launch; says who runs
+    b->stats.bytes_down += (int64_t)(count * sizeof(BatchSlot));
+    b->stats.begin_ns = mcf::now_ns() - t_begin;
+
+    std::vector<int32_t> run;
+    for (size_t i = 0; i < count; ++i)
+        if (slots[i].run == mcf::kBatchRunning) run.push_back((int32_t)i);   // a re-solve's unmarked instances ended their last solve: not running
+    LaunchTotals t;
+    if (const int rc = run_launches(LaunchPlan{&dev, b->lds_max, b->d.pivots_per_launch, nullptr, b->stride}, slots, run, &t)) return rc;
+    for (int32_t i : run) b->stats.total_pivots += slots[(size_t)i].pivots;
+    b->stats.launches = t.launches;
+    b->stats.lds_bytes_max = t.lds_bytes_max;
+    b->stats.bytes_up += t.bytes_up;
+    b->stats.bytes_down += t.bytes_down;
+    b->stats.kernel_ns = t.kernel_ns;
+
+    const double t_finish = mcf::now_ns();
+    hipLaunchKernelGGL(uniform_finish_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, outputs_of(&dio), dev.slots, dev.slab, dev.traces);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    b->stats.finish_ns = mcf::now_ns() - t_finish;
+    if (const int rc = stage_down(b, staged)) return rc;
+    b->stats.host_ns = mcf::now_ns() - t_start - t.kernel_ns;
+    return MCF_OK;
+}
+
+// the host hooks: the three steps and batch_run with one lane, on a host slab of the device's layout
+int ubatch_on_host(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve)
+{
+    const char *const what = resolve ? "mcf_ubatch_rerun_on_host" : "mcf_ubatch_run_on_host";
+    if (const int rc = check_io(b, io, what, true, resolve)) return rc;
+    const double t_start = mcf::now_ns();
+    const size_t count = (size_t)b->d.count;
+    b->h_slab.resize(count * (size_t)b->stride);
+    b->h_slots.resize(count);
+    b->h_traces.resize(std::max<size_t>(count * (size_t)b->d.trace_capacity, 1));
+    if (resolve && b->where == mcf_ubatch::kOnDevice && count) {            // the last solve was the device's: its state comes down whole
+        const DeviceGuard guard;
+        HIP_TRY(hipSetDevice(b->d.device));
+        HIP_TRY(hipMemcpy(b->h_slab.data(), b->dev.slab, b->h_slab.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(b->h_slots.data(), b->dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));
+    }
+    b->stats = mcf_ubatch_stats{};
+    b->stats.instances = (int64_t)count;
+    b->stats.workspace_bytes = (int64_t)b->h_slab.size();
+    const mcf::UniformProblem p = problem_of(b, io, b->source.data(), b->target.data(), resolve);
+    const mcf::UniformOutputs o = outputs_of(io);
+    for (size_t i = 0; i < count; ++i) {
+        if (p.changed && !p.changed[i]) continue;
+        BatchSlot &slot = b->h_slots[i];
+        unsigned char *const home = b->h_slab.data() + i * (size_t)b->stride;
+        if (resolve) mcf::uniform_recost(p, (int64_t)i, b->tmpl, slot, home, 0, 1);
+        else mcf::uniform_begin(p, (int64_t)i, b->tmpl, slot, home, 0, 1);
+        if (slot.run == mcf::kBatchRunning) {
+            mcf::BatchWork w{};
+            load_slot(w, slot, b->h_traces.data());
+            bind(w, home, layout_of((uint32_t)slot.all_arcs, (uint32_t)slot.n + 1u));
+            if (slot.reprice) mcf::batch_reprice(w, 0, 1);
+            mcf::batch_run(w, 0, 1, INT64_MAX);
+            store_slot(slot, w);
+            b->stats.total_pivots += slot.pivots;
+        }
+        mcf::uniform_finish(p, o, (int64_t)i, slot, home, b->h_traces.data(), 0, 1);
+    }
+    b->where = mcf_ubatch::kOnHost;
+    b->stats.host_ns = mcf::now_ns() - t_start;
+    return MCF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcf_ubatch_create(mcf_ubatch **out, const mcf_ubatch_desc *desc)
+{
+    if (!out || !desc) return mcf::fail(MCF_ERR_INVALID, "mcf_ubatch_create: null argument");
+    *out = nullptr;
+    if (const int rc = check_batch_desc(*desc, "mcf_ubatch_create")) return rc;
+    if (desc->count < 0) return mcf::fail(MCF_ERR_INVALID, "mcf_ubatch_create: negative instance count");
+    if (desc->arc_count > MCF_BATCH_MAX_ARCS || desc->node_count > MCF_BATCH_MAX_NODES)
+        return mcf::fail(MCF_ERR_INVALID, "mcf_ubatch_create: %d nodes / %d arcs is above the batch solver's limit of %d / %d per instance; solve it with mcf_ns_solve",
+                         desc->node_count, desc->arc_count, MCF_BATCH_MAX_NODES, MCF_BATCH_MAX_ARCS);
+    if (desc->count > MCF_BATCH_MAX_INSTANCES) return mcf::fail(MCF_ERR_INVALID, "mcf_ubatch_create: a batch holds at most %d instances", MCF_BATCH_MAX_INSTANCES);
+    mcf::NsCore checked;                                                    // end points, as mcf_batch_add validates them
+    if (const int rc = mcf::core_create(&checked, desc->node_count, desc->arc_count, desc->source, desc->target)) return rc;
+    mcf_ubatch *b = new mcf_ubatch();
+    b->d = *desc;
+    b->d.semantics = MCF_SEM_PLAIN;                                         // 0 means the same
+    b->source.assign(desc->source, desc->source + desc->arc_count);
+    b->target.assign(desc->target, desc->target + desc->arc_count);
+    b->d.source = b->d.target = nullptr;                                    // the caller's arrays are not kept
+    if (const int rc = configure_slot(b->tmpl, limits_of(b->d), desc->node_count, desc->arc_count, b->source.data(), b->target.data())) { delete b; return rc; }
+    b->stride = layout_of((uint32_t)(desc->arc_count + 2 * desc->node_count), (uint32_t)desc->node_count + 1u).bytes;
+    *out = b;
+    return MCF_OK;
+}
+
+void mcf_ubatch_destroy(mcf_ubatch *b) { delete b; }
+int mcf_ubatch_solve(mcf_ubatch *b, const mcf_ubatch_io *io) { return ubatch_on_device(b, io, false); }
+int mcf_ubatch_resolve(mcf_ubatch *b, const mcf_ubatch_io *io) { return ubatch_on_device(b, io, true); }
+int mcf_ubatch_run_on_host(mcf_ubatch *b, const mcf_ubatch_io *io) { return ubatch_on_host(b, io, false); }
+int mcf_ubatch_rerun_on_host(mcf_ubatch *b, const mcf_ubatch_io *io) { return ubatch_on_host(b, io, true); }
+int mcf_ubatch_get_stats(mcf_ubatch *b, mcf_ubatch_stats *out)
 {
     if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
     *out = b->stats;

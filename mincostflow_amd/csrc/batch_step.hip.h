@@ -27,7 +27,8 @@ enum BatchRun : int32_t {
     kBatchNoEntering = 1,  // no eligible arc: the host finishes (feasibility, lower bounds)
     kBatchUnbounded = 2,   // NS.cs:321-325
     kBatchLimit = 3,       // the instance's pivot limit
-    kBatchMaxIter = 4      // the reference's own iteration guard (NS.cs:280, :311-317): Infeasible
+    kBatchMaxIter = 4,     // the reference's own iteration guard (NS.cs:280, :311-317): Infeasible
+    kBatchByBounds = 5     // never ran: an upper bound below its lower bound (set by uniform_begin of uniform_step.hip.h only)
 };
 
 struct BatchWork : TreeView {

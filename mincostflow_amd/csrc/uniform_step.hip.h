@@ -1,0 +1,284 @@
+// uniform_step.hip.h -- the set-up and the end of a solve for a batch that shares ONE topology (mcf_ubatch_*, DESIGN.md 3.14 "Uniform
+// batch"), stated once for host and device like the pivot in batch_step.hip.h.
+//
+// Three steps per instance, each over (lane, lanes): 64 lanes of one wave on the device, one "lane" on the host (the test hooks).
+//   uniform_begin   bounds check, standard form, art_cost, the star start basis of start_basis (ns_core.cpp) and the instance's slot;
+//   uniform_finish  the status (finish_instance + core_finish of batch.hip / ns_core.cpp) and the output rows;
+//   uniform_recost  a re-solve with new costs: from the kept basis where the last solve ended Optimal, else uniform_begin again.
+// The pivots between them are batch_run on the workspace these steps leave, unchanged.
+// Problem data are read straight from the caller's arrays (base + instance * stride, stride 0 = one array for all), results are written
+// straight into the caller's rows.  The steps never learn whether those pointers are device or host memory.
+// Nothing here depends on the order in which lanes add: the supply shift and the total cost are integer sums (they wrap, they commute),
+// so one lane and 64 lanes give the same bits, and both give ns_core.cpp's.
+#pragma once
+
+#include <stdint.h>
+
+#include "batch_layout.hip.h"
+#include "batch_step.hip.h"
+
+namespace mcf {
+
+// one topology, `count` instances of it; every pointer points into the memory the step runs in
+struct UniformProblem {
+    int32_t n, m, supply_type, trace_cap;
+    const int32_t *source, *target;                      // [m], validated by mcf_ubatch_create
+    const int64_t *lower, *upper, *cost, *supply;        // null: 0 / uncapacitated / 0 / 0
+    int64_t lower_stride, upper_stride, cost_stride, supply_stride;     // elements between instances, 0 = shared
+    uint64_t stride;                                     // bytes between workspaces: layout_of(m + 2n, n + 1).bytes
+    const uint8_t *changed;                              // re-solve: [count], null = all
+};
+struct UniformOutputs {                                  // any may be null
+    int32_t *status;
+    int64_t *pivots, *total_cost, *flows, *potentials;   // [count], [count], [count * m], [count * n]
+    int32_t *trace;                                      // [count * trace_cap]
+};
+
+// ---- what the lanes share (device: all 64 lanes of the wave call these together; host: one lane, the identity)
+MCF_HD inline uint64_t lanes_ballot(bool p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint64_t)__ballot(p ? 1 : 0);
+#else
+    return p ? 1u : 0u;
+#endif
+}
+MCF_HD inline int popcount64(uint64_t v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __popcll(v);
+#else
+    return __builtin_popcountll(v);
+#endif
+}
+MCF_HD inline bool lanes_any(bool p) { return lanes_ballot(p) != 0; }
+MCF_HD inline int64_t lanes_max_i64(int64_t v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    for (int d = 32; d > 0; d >>= 1) { const int64_t o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
+#endif
+    return v;
+}
+MCF_HD inline uint64_t lanes_sum_u64(uint64_t v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    for (int d = 32; d > 0; d >>= 1) v += (uint64_t)__shfl_xor((int64_t)v, d, 64);
+#endif
+    return v;
+}
+// *p += v where several lanes may meet on one p
+MCF_HD inline void lanes_add_i64(int64_t *p, int64_t v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicAdd((unsigned long long *)p, (unsigned long long)v);
+#else
+    *p = (int64_t)((uint64_t)*p + (uint64_t)v);
+#endif
+}
+
+MCF_HD inline const int64_t *uniform_row(const int64_t *base, int64_t stride, int64_t i) { return base ? base + i * stride : nullptr; }
+MCF_HD inline int64_t uniform_upper(const int64_t *upper, int e) { return !upper || upper[e] == MCF_INF_CAP ? kInf : upper[e]; }       // core_set_problem
+MCF_HD inline int64_t uniform_art_cost(const int64_t *cost, int n, int m, int lane, int lanes)     // art_cost_of
+{
+    int64_t biggest = 0;
+    if (cost)
+        for (int e = lane; e < m; e += lanes) {
+            const int64_t a = cost[e] < 0 ? -cost[e] : cost[e];
+            biggest = a > biggest ? a : biggest;
+        }
+    return (lanes_max_i64(biggest) + 1) * (int64_t)n;
+}
+// the slot of instance i at the start of a solve: the handle's template, placed
+MCF_HD inline void uniform_place_slot(BatchSlot &slot, const BatchSlot &tmpl, const UniformProblem &p, int64_t i, int32_t all_arcs, int32_t run)
+{
+    slot = tmpl;
+    slot.all_arcs = all_arcs;
+    slot.workspace = (uint64_t)i * p.stride;
+    slot.trace = (uint64_t)i * (uint64_t)p.trace_cap;
+    slot.run = run;
+}
+
+// ---- core_begin for instance i on its workspace `home`.  The slot says afterwards whether there is anything to run.
+MCF_HD inline void uniform_begin(const UniformProblem &p, int64_t i, const BatchSlot &tmpl, BatchSlot &slot, unsigned char *home, int lane, int lanes)
+{
+    const int n = p.n, m = p.m, root = n;
+    const int64_t *const lower = uniform_row(p.lower, p.lower_stride, i), *const upper = uniform_row(p.upper, p.upper_stride, i);
+    const int64_t *const cost = uniform_row(p.cost, p.cost_stride, i), *const supply = uniform_row(p.supply, p.supply_stride, i);
+    // NS.cs:227-231
+    bool inverted = false;
+    for (int e = lane; e < m; e += lanes) inverted |= uniform_upper(upper, e) < (lower ? lower[e] : 0);
+    if (lanes_any(inverted)) {
+        lanes_sync();
+        if (lane == 0) uniform_place_slot(slot, tmpl, p, i, m + n, kBatchByBounds);
+        return;
+    }
+    // to_standard_form.  The supplies are not part of the workspace and all_arcs -- with it, where every array lies -- is known only once they
+    // have been shifted by the lower bounds.  They are shifted where pi[] lies when every node needs an artificial arc (no layout of this
+    // instance puts pi[] further back), then moved down to where pi[] does lie; the start basis below reads each and overwrites it.
+    // Order on the device: plain stores of shifted[v], barrier, atomic adds on the same words (they meet in L2), barrier, plain loads by
+    // other lanes.  It is the fence that comes with each lanes_sync() (a workgroup-scope release / acquire round the barrier) that puts
+    // the stores before the atomics and the atomics before the loads; that covers every lane that touches the words only because the
+    // workgroup is ONE wave on one CU.  Several workgroups on one instance would need agent-scope fences.
+    int64_t *const shifted = (int64_t *)(home + layout_of((uint32_t)(m + 2 * n), (uint32_t)n + 1u).pi);
+    for (int v = lane; v < n; v += lanes) shifted[v] = supply ? supply[v] : 0;
+    lanes_sync();
+    if (lower)
+        for (int e = lane; e < m; e += lanes) {
+            const int64_t lo = lower[e];
+            if (lo == 0) continue;
+            lanes_add_i64(&shifted[p.source[e]], -lo);
+            lanes_add_i64(&shifted[p.target[e]], lo);
+        }
+    lanes_sync();
+    const int64_t art_cost = uniform_art_cost(cost, n, m, lane, lanes);
+    const bool geq = p.supply_type == MCF_SUPPLY_GEQ;
+    int32_t hung = 0;               // nodes that cannot hang on their root link
+    for (int base = 0; base < n; base += lanes) {
+        const int v = base + lane;
+        hung += popcount64(lanes_ballot(v < n && (geq ? shifted[v] > 0 : shifted[v] < 0)));
+    }
+    const int32_t all_arcs = m + n + hung;
+    const Layout l = layout_of((uint32_t)all_arcs, (uint32_t)n + 1u);
+    int32_t *const tail = (int32_t *)(home + l.tail), *const head = (int32_t *)(home + l.head);
+    int64_t *const cost_w = (int64_t *)(home + l.cost), *const upper_w = (int64_t *)(home + l.upper);
+    int64_t *const flow = (int64_t *)(home + l.flow), *const pi = (int64_t *)(home + l.pi);
+    int32_t *const par = (int32_t *)(home + l.par), *const par_arc = (int32_t *)(home + l.par_arc), *const nxt = (int32_t *)(home + l.nxt);
+    int32_t *const prv = (int32_t *)(home + l.prv), *const sub = (int32_t *)(home + l.sub), *const fin = (int32_t *)(home + l.fin);
+    int8_t *const state = (int8_t *)(home + l.state), *const par_dir = (int8_t *)(home + l.par_dir);
+    // pi <= shifted, both on 16-byte boundaries: moving up the array, an entry lands on entries that have been read
+    if (pi != shifted)
+        for (int base = 0; base < n; base += lanes) {
+            const int v = base + lane;
+            const int64_t s = v < n ? shifted[v] : 0;
+            lanes_sync();
+            if (v < n) pi[v] = s;
+        }
+    lanes_sync();
+    // the arcs of the problem (start_basis: at their lower bound, which is 0 now)
+    for (int e = lane; e < m; e += lanes) {
+        tail[e] = p.source[e]; head[e] = p.target[e];
+        cost_w[e] = cost ? cost[e] : 0;
+        upper_w[e] = uniform_upper(upper, e) - (lower ? lower[e] : 0);
+        flow[e] = 0;
+        state[e] = MCF_STATE_LOWER;
+    }
+    // NS.cs:671-845, the star on the artificial root.  Node v's artificial arc is m + n + (nodes below v that need one): an exclusive prefix
+    // count, per stride a ballot and the bits below the lane, with the strides before it as the running base.
+    int32_t before = 0;
+    for (int base = 0; base < n; base += lanes) {
+        const int v = base + lane;
+        const int64_t s = v < n ? pi[v] : 0;
+        const bool plain = geq ? s <= 0 : s >= 0;
+        const uint64_t mask = lanes_ballot(v < n && !plain);
+        const int extra = m + n + before + popcount64(mask & (((uint64_t)1 << lane) - 1));
+        before += popcount64(mask);
+        if (v >= n) continue;
+        const int link = m + v;
+        const int lt = geq ? root : v, lh = geq ? v : root;         // the zero-cost link: GEQ root->v, LEQ v->root
+        par[v] = root; sub[v] = 1; fin[v] = v;
+        nxt[v] = v + 1 < n ? v + 1 : root;
+        prv[v] = v > 0 ? v - 1 : root;
+        tail[link] = lt; head[link] = lh; upper_w[link] = kInf; cost_w[link] = 0;
+        if (plain) {
+            par_dir[v] = geq ? kDown : kUp;
+            pi[v] = 0;
+            par_arc[v] = link;
+            flow[link] = geq ? -s : s;
+            state[link] = MCF_STATE_TREE;
+        } else {
+            par_dir[v] = geq ? kUp : kDown;
+            pi[v] = geq ? -art_cost : art_cost;
+            par_arc[v] = extra;
+            tail[extra] = lh; head[extra] = lt;
+            upper_w[extra] = kInf;
+            flow[extra] = geq ? s : -s;
+            cost_w[extra] = art_cost;
+            state[extra] = MCF_STATE_TREE;
+            flow[link] = 0;
+            state[link] = MCF_STATE_LOWER;
+        }
+    }
+    if (lane == 0) {
+        par[root] = -1; par_arc[root] = -1; nxt[root] = n > 0 ? 0 : root; prv[root] = n > 0 ? n - 1 : root;
+        sub[root] = n + 1; fin[root] = n - 1; par_dir[root] = 0; pi[root] = 0;
+        uniform_place_slot(slot, tmpl, p, i, all_arcs, kBatchRunning);
+    }
+    lanes_sync();
+}
+
+// ---- finish_instance + core_finish + core_total_cost for instance i, into the caller's rows.  The flows in the workspace stay in standard
+// form: the lower bounds are added into the output row only, so a re-solve goes on from the workspace as it is.
+MCF_HD inline void uniform_finish(const UniformProblem &p, const UniformOutputs &o, int64_t i, const BatchSlot &slot, const unsigned char *home,
+                                  const int32_t *traces, int lane, int lanes)
+{
+    const int n = p.n, m = p.m;
+    const Layout l = layout_of((uint32_t)slot.all_arcs, (uint32_t)n + 1u);
+    const int64_t *const flow = (const int64_t *)(home + l.flow), *const pi = (const int64_t *)(home + l.pi), *const cost = (const int64_t *)(home + l.cost);
+    const int64_t *const lower = uniform_row(p.lower, p.lower_stride, i);
+    int32_t status = MCF_NOT_SOLVED;                                    // the pivot limit
+    switch (slot.run) {
+    case kBatchNoEntering: {
+        // NS.cs:1272-1283 with difference D9: only the n root links
+        bool left = false;
+        for (int e = m + lane; e < m + n; e += lanes) left |= flow[e] != 0;
+        status = lanes_any(left) ? MCF_INFEASIBLE : MCF_OPTIMAL;
+        break;
+    }
+    case kBatchUnbounded: status = MCF_UNBOUNDED; break;
+    case kBatchMaxIter: case kBatchByBounds: status = MCF_INFEASIBLE; break;
+    default: break;
+    }
+    const int64_t pivots = slot.run == kBatchByBounds ? 0 : slot.pivots;
+    const bool optimal = status == MCF_OPTIMAL;
+    uint64_t total = 0;
+    int64_t *const flows = o.flows ? o.flows + i * (int64_t)m : nullptr, *const potentials = o.potentials ? o.potentials + i * (int64_t)n : nullptr;
+    for (int e = lane; e < m; e += lanes) {
+        const int64_t f = optimal ? (int64_t)((uint64_t)flow[e] + (uint64_t)(lower ? lower[e] : 0)) : 0;      // NS.cs:364-388
+        if (optimal) total += (uint64_t)f * (uint64_t)cost[e];                                                // NS.cs:459-464, wrapping
+        if (flows) flows[e] = f;
+    }
+    total = lanes_sum_u64(total);
+    if (potentials)
+        for (int v = lane; v < n; v += lanes) potentials[v] = optimal ? pi[v] : 0;
+    if (o.trace) {
+        const int64_t cap = p.trace_cap, len = pivots < cap ? pivots : cap;
+        int32_t *const row = o.trace + i * cap;
+        for (int64_t k = lane; k < cap; k += lanes) row[k] = k < len ? traces[slot.trace + (uint64_t)k] : 0;
+    }
+    if (lane == 0) {
+        if (o.status) o.status[i] = status;
+        if (o.pivots) o.pivots[i] = pivots;
+        if (o.total_cost) o.total_cost[i] = (int64_t)total;
+    }
+}
+
+// ---- prepare_resolve for instance i with the costs in p.  Warm as there: the last solve ended Optimal with no flow on an artificial arc.
+MCF_HD inline void uniform_recost(const UniformProblem &p, int64_t i, const BatchSlot &tmpl, BatchSlot &slot, unsigned char *home, int lane, int lanes)
+{
+    const int n = p.n, m = p.m;
+    const int32_t all_arcs = slot.all_arcs;
+    bool warm = slot.run == kBatchNoEntering;
+    if (warm) {
+        const Layout l = layout_of((uint32_t)all_arcs, (uint32_t)n + 1u);
+        const int64_t *const flow = (const int64_t *)(home + l.flow);
+        bool left = false;              // on a root link: Infeasible; on an artificial arc: Optimal with a surplus whose place depends on the pivot path
+        for (int e = m + lane; e < all_arcs; e += lanes) left |= flow[e] != 0;
+        warm = !lanes_any(left);
+    }
+    if (!warm) { uniform_begin(p, i, tmpl, slot, home, lane, lanes); return; }
+    // core_recost: cost[0, m), art_cost as to_standard_form derives it, the artificial arcs; the root links keep 0
+    const Layout l = layout_of((uint32_t)all_arcs, (uint32_t)n + 1u);
+    int64_t *const cost_w = (int64_t *)(home + l.cost);
+    const int64_t *const cost = uniform_row(p.cost, p.cost_stride, i);
+    const int64_t art_cost = uniform_art_cost(cost, n, m, lane, lanes);
+    for (int e = lane; e < m; e += lanes) cost_w[e] = cost ? cost[e] : 0;
+    for (int e = m + n + lane; e < all_arcs; e += lanes) cost_w[e] = art_cost;
+    lanes_sync();
+    if (lane == 0) {                    // the rule starts as at a cold start, the count and the trace start again
+        uniform_place_slot(slot, tmpl, p, i, all_arcs, kBatchRunning);
+        slot.reprice = 1;
+    }
+    lanes_sync();
+}
+
+}  // namespace mcf

@@ -407,6 +407,158 @@ class BatchSolver:
         st = L.BatchStats(); L.check(L.lib().mcf_batch_get_stats(self._h, C.byref(st))); return st.as_dict()
 
 
+class UniformResult:
+    """What UniformBatch.solve / .resolve return: one row per instance, numpy arrays or tensors like the inputs.  Rows of instances that
+    are not Optimal are zero; trace rows are zero behind min(pivots, record_trace)."""
+    __slots__ = ("status", "pivots", "total_cost", "flows", "potentials", "trace")
+    FIELDS = (("status", "int32", ""), ("pivots", "int64", ""), ("total_cost", "int64", ""), ("flows", "int64", "m"), ("potentials", "int64", "n"),
+              ("trace", "int32", "t"))
+
+    def __init__(self, **arrays):
+        for name, _, _ in self.FIELDS:
+            setattr(self, name, arrays[name])
+
+
+def _is_tensor(a) -> bool:
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+class UniformBatch:
+    """`count` instances of ONE graph, solved on the device from arrays that already are there (mcf_ubatch_*, DESIGN.md 3.14 "Uniform
+    batch").  solve() and resolve() take either numpy arrays (copied up and down, one copy per array) or torch tensors on the handle's
+    device (read and written in place: nothing that scales with the graph crosses the bus) -- never a mix; each array is [count, m]
+    ([count, n] for supply) or [m] ([n]) for one row shared by all, int64, contiguous in its last dimension.  Results equal
+    BatchSolver's for the same instances bit for bit.  run_on_host() / rerun_on_host() are test hooks (numpy only)."""
+
+    def __init__(self, node_count, source, target, count, rule=PivotRule.BlockSearch, pivot_limit=0, record_trace=0, device=0, pivots_per_launch=0,
+                 semantics=L.SEM_PLAIN, flags=0):
+        src, tgt = _i32(source), _i32(target)
+        if src.ndim != 1 or src.shape != tgt.shape:
+            raise ValueError("source and target must be one-dimensional and of equal length")
+        self.node_count, self.arc_count, self.count, self.device, self.record_trace = int(node_count), int(src.shape[0]), int(count), int(device), int(record_trace)
+        self._h = C.c_void_p()
+        self._last = None               # the last UniformResult: a masked resolve() starts from its rows
+        d = L.UBatchDesc(self.device, int(rule), int(semantics), 0, int(pivot_limit), int(pivots_per_launch), self.record_trace, int(flags),
+                         self.node_count, self.arc_count, self.count, src.ctypes.data, tgt.ctypes.data)
+        L.check(L.lib().mcf_ubatch_create(C.byref(self._h), C.byref(d)))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            L.lib().mcf_ubatch_destroy(h)
+            self._h = None
+
+    def __len__(self):
+        return self.count
+
+    # ---- one input: (pointer, stride in elements, the object that keeps the memory alive)
+    def _input(self, a, name, length, tensors, dtype="int64", rows_only=False):
+        if a is None:
+            return None, 0, None
+        if tensors:
+            import torch
+            if not _is_tensor(a):
+                raise ValueError(f"{name}: numpy arrays and tensors cannot be mixed in one call")
+            if a.device.type != "cuda" or (a.device.index or 0) != self.device:
+                raise ValueError(f"{name}: tensor on {a.device}, the batch runs on cuda:{self.device}")
+            if a.dtype != getattr(torch, dtype):
+                raise ValueError(f"{name}: dtype {a.dtype}, expected {dtype}")
+            shape, strides = tuple(a.shape), tuple(a.stride())
+        else:
+            if _is_tensor(a):
+                raise ValueError(f"{name}: numpy arrays and tensors cannot be mixed in one call")
+            if not isinstance(a, np.ndarray):
+                a = np.asarray(a, dtype)
+            if a.dtype != np.dtype(dtype):
+                raise ValueError(f"{name}: dtype {a.dtype}, expected {dtype}")
+            shape, strides = a.shape, tuple(s // a.itemsize for s in a.strides)
+        if rows_only:
+            ok = shape == (self.count,)
+        else:
+            ok = shape in ((length,), (self.count, length))
+        if not ok:
+            raise ValueError(f"{name}: shape {tuple(shape)}, expected ({length},) or ({self.count}, {length})" if not rows_only else f"{name}: shape {tuple(shape)}, expected ({self.count},)")
+        if self.count > 0 and shape[-1] > 1 and strides[-1] != 1:
+            raise ValueError(f"{name}: not contiguous in its last dimension")
+        stride = 0 if len(shape) == 1 or rows_only else (strides[0] if self.count > 1 else 0)
+        if stride < 0 or (len(shape) == 2 and self.count > 1 and 0 < stride < length):
+            raise ValueError(f"{name}: rows overlap")
+        ptr = a.data_ptr() if tensors else a.ctypes.data
+        return ptr, int(stride), a
+
+    def _outputs(self, tensors, like):
+        """Fresh rows, or copies of `like` (the last result) for a call that does not write every row."""
+        sizes = {"": (self.count,), "m": (self.count, self.arc_count), "n": (self.count, self.node_count), "t": (self.count, self.record_trace)}
+        out = {}
+        for name, dtype, dim in UniformResult.FIELDS:
+            if like is not None:
+                prev = getattr(like, name)
+                if _is_tensor(prev) != tensors:
+                    raise ValueError("a masked resolve() continues the last result: numpy arrays and tensors cannot be mixed")
+                out[name] = prev.clone() if tensors else prev.copy()
+            elif tensors:
+                import torch
+                out[name] = torch.empty(sizes[dim], dtype=getattr(torch, dtype), device=f"cuda:{self.device}")
+            else:
+                out[name] = np.empty(sizes[dim], dtype)
+        return out
+
+    def _call(self, fn, cost, supply, lower, upper, supply_type, changed=None, masked=False, numpy_only=False):
+        given = [a for a in (cost, supply, lower, upper, changed) if a is not None]
+        tensors = any(_is_tensor(a) for a in given)
+        if tensors and numpy_only:
+            raise ValueError("the host hooks take numpy arrays")
+        keep = []
+        io = L.UBatchIo()
+        io.memory, io.supply_type = (L.MEM_DEVICE if tensors else L.MEM_HOST), int(supply_type)
+        for name, a, length in (("cost", cost, self.arc_count), ("supply", supply, self.node_count), ("lower", lower, self.arc_count), ("upper", upper, self.arc_count)):
+            ptr, stride, obj = self._input(a, name, length, tensors)
+            keep.append(obj)
+            setattr(io, name, ptr)
+            setattr(io, name + "_stride", stride)
+        if changed is not None:
+            if not tensors and not isinstance(changed, np.ndarray):
+                changed = np.asarray(changed)
+            if not tensors and changed.dtype == np.bool_:
+                changed = changed.view(np.uint8)
+            if tensors:
+                import torch
+                if changed.dtype == torch.bool:
+                    changed = changed.view(torch.uint8)
+            ptr, _, obj = self._input(changed, "changed", self.count, tensors, dtype="uint8", rows_only=True)
+            keep.append(obj)
+            io.changed = ptr
+        if masked and changed is not None and self._last is None:
+            raise McfError(L.ERR_STATE, "resolve: the batch has not been solved")
+        out = self._outputs(tensors, self._last if masked and changed is not None else None)
+        for name, arr in out.items():
+            setattr(io, name, arr.data_ptr() if tensors else arr.ctypes.data)
+        L.check(fn(self._h, C.byref(io)))
+        self._last = UniformResult(**out)
+        return self._last
+
+    def solve(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> UniformResult:
+        """A fresh solve of every instance; may be repeated with other supplies, bounds or costs."""
+        return self._call(L.lib().mcf_ubatch_solve, cost, supply, lower, upper, supply_type)
+
+    def resolve(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq, changed=None) -> UniformResult:
+        """New costs for the instances `changed` marks ([count] bool / uint8, None = all): each goes on from the basis its last solve left
+        where that ended Optimal.  supply, lower, upper and supply_type must be what the last solve() was given.  Rows of unmarked
+        instances are the last result's."""
+        return self._call(L.lib().mcf_ubatch_resolve, cost, supply, lower, upper, supply_type, changed, masked=True)
+
+    def run_on_host(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> UniformResult:
+        """Test hook: solve() with one lane on the CPU.  numpy only."""
+        return self._call(L.lib().mcf_ubatch_run_on_host, cost, supply, lower, upper, supply_type, numpy_only=True)
+
+    def rerun_on_host(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq, changed=None) -> UniformResult:
+        """Test hook: resolve() with one lane on the CPU.  numpy only."""
+        return self._call(L.lib().mcf_ubatch_rerun_on_host, cost, supply, lower, upper, supply_type, changed, masked=True, numpy_only=True)
+
+    def stats(self) -> dict:
+        st = L.UBatchStats(); L.check(L.lib().mcf_ubatch_get_stats(self._h, C.byref(st))); return st.as_dict()
+
+
 def block_config(**kw) -> "L.BlockConfig":
     """new OptimizationConfig { ... } (OptimizationTypes.cs:24-38): the defaults, with the given fields replaced."""
     c = L.BlockConfig()
