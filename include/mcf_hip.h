@@ -837,6 +837,87 @@ MCF_API int mcf_ubatch_validate(mcf_ubatch *b, const mcf_ubatch_check_io *io, mc
 /* TEST HOOK: the same step (uniform_validate, csrc/uniform_step.hip.h) with one lane on the CPU.  io->memory must be MCF_MEM_HOST. */
 MCF_API int mcf_ubatch_validate_on_host(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_check_summary *out);
 
+/* ---- Ragged batch: a SET of graphs in one handle, every instance names its own ("Ragged batch").
+ * mcf_ubatch_* above demands that every instance share one graph.  Here a handle holds `graph_count` graphs and `count` instances;
+ * instance i is an instance of graph graph_of[i].  Problem data and results are RAGGED ROWS of flat arrays: instance i's arcs are the
+ * elements [arc_row[i], arc_row[i + 1]) with arc_row[i] = the sum of the arc counts of the instances before it, its nodes the elements
+ * [node_row[i], node_row[i + 1]) likewise; mcf_rbatch_get_rows returns both.  All offsets are 64-bit.  There are no strides: a shared
+ * row has no meaning across graphs.
+ * Set-up, pivots, finish and validation run on the device as for the uniform batch (the same steps and the same kernel for the pivots);
+ * the only difference is that a block finds its instance's graph, rows and workspace in per-handle tables in device memory instead of
+ * multiplying by strides.  Every instance has the workspace of ITS graph, so one handle mixes the LDS classes and the global tier by
+ * instance, as mcf_batch_* does.  With MCF_MEM_DEVICE nothing that scales with the arcs or the nodes crosses the bus in a call: the
+ * topology, its incidence lists and the tables go up once per handle, with its first device call, and are not counted in a call's
+ * statistics; per call go the slot templates (one per graph, 160 bytes each, counted in bytes_up), the ids of every round of launches
+ * and the slots.
+ * Results: instance i gets bit for bit what mcf_batch_add + mcf_batch_solve give for the same instance; with one graph every row equals
+ * mcf_ubatch_*'s.  Limits per graph are mcf_batch_add's (MCF_BATCH_MAX_ARCS / _NODES), at most MCF_BATCH_MAX_INSTANCES instances; rules
+ * and refusals of the first nine descriptor fields are mcf_batch_create's.  mcf_rbatch_create also refuses, with MCF_ERR_INVALID and a
+ * message: a graph_of entry outside [0, graph_count), a NULL graph_of with count != graph_count, an arc_start that is not monotone, an
+ * end point outside its graph's nodes. */
+typedef struct mcf_rbatch mcf_rbatch;
+typedef struct mcf_rbatch_desc {
+    int32_t device;               /* as mcf_batch_desc, field for field ... */
+    int32_t pivot_rule;
+    int32_t semantics;
+    int32_t reserved;
+    int64_t pivot_limit;          /* 0 = the default of each instance's own graph */
+    int32_t pivots_per_launch;
+    int32_t trace_capacity;
+    int32_t flags;
+    int32_t graph_count;          /* ... then the graphs: distinct topologies, >= 0 */
+    int32_t count;                /* instances, >= 0, <= MCF_BATCH_MAX_INSTANCES */
+    const int32_t *node_count;    /* [graph_count], HOST memory like every pointer here; all are copied by mcf_rbatch_create */
+    const int64_t *arc_start;     /* [graph_count + 1] into source / target: graph g has arc_start[g + 1] - arc_start[g] arcs */
+    const int32_t *source;        /* the graphs' end points, concatenated; node ids are the graph's own, from 0 */
+    const int32_t *target;
+    const int32_t *graph_of;      /* [count] instance -> graph; NULL = instance i is graph i (count must equal graph_count) */
+} mcf_rbatch_desc;
+typedef struct mcf_rbatch_io {
+    int32_t memory;               /* MCF_MEM_HOST / MCF_MEM_DEVICE: where EVERY pointer below points */
+    int32_t supply_type;          /* MCF_SUPPLY_GEQ / _LEQ, for every instance of this call */
+    const int64_t *lower;         /* [arc_row[count]]; NULL = 0 */
+    const int64_t *upper;         /* [arc_row[count]]; NULL = uncapacitated; MCF_INF_CAP as in mcf_ns_set_problem */
+    const int64_t *cost;          /* [arc_row[count]]; NULL = 0 */
+    const int64_t *supply;        /* [node_row[count]]; NULL = 0 */
+    const uint8_t *changed;       /* mcf_rbatch_resolve / _rerun_on_host only: [count], nonzero = re-solve this instance; NULL = all */
+    /* results, any may be NULL; zero-filled as mcf_ubatch_io's */
+    int32_t *status;              /* [count] */
+    int64_t *pivots;              /* [count] */
+    int64_t *total_cost;          /* [count] */
+    int64_t *flows;               /* [arc_row[count]] */
+    int64_t *potentials;          /* [node_row[count]] */
+    int32_t *trace;               /* [count * trace_capacity] */
+} mcf_rbatch_io;
+typedef struct mcf_rbatch_check_io {                   /* mcf_ubatch_check_io without strides */
+    int32_t memory, supply_type;                       /* MCF_MEM_*, MCF_SUPPLY_GEQ / _LEQ / _EQ */
+    const int64_t *lower, *upper, *cost, *supply;      /* as mcf_rbatch_io, NULL as there */
+    const int32_t *status;                             /* the solution to check, rows as mcf_rbatch_io writes them: all four required */
+    const int64_t *total_cost, *flows, *potentials;    /* (flows / potentials may be NULL where the handle has no arc / no node at all) */
+    int32_t *valid;                                    /* results, any may be NULL: [count] */
+    int32_t *errors, *first;                           /* [count * MCF_VAL_KINDS] */
+    int64_t *objective, *dual_cost;                    /* [count] */
+} mcf_rbatch_check_io;
+
+MCF_API int mcf_rbatch_create(mcf_rbatch **out, const mcf_rbatch_desc *desc);
+MCF_API void mcf_rbatch_destroy(mcf_rbatch *b);
+/* arc_row and node_row, each [count + 1] (either may be NULL): where instance i's rows begin; the last entry is the total */
+MCF_API int mcf_rbatch_get_rows(mcf_rbatch *b, int64_t *arc_row, int64_t *node_row);
+/* The contracts of their mcf_ubatch_* namesakes, refusal codes included: null stream, return synchronised, the handle's device is made
+ * current and the caller's restored; MCF_ERR_NO_DEVICE without a GPU leaves the handle as it was; a re-solve before any solve is
+ * MCF_ERR_STATE; the limit stated at mcf_batch_resolve on warm re-solves holds here word for word.  The four solve calls may follow each
+ * other in any order: the state moves whole between host and device, the results are the same. */
+MCF_API int mcf_rbatch_solve(mcf_rbatch *b, const mcf_rbatch_io *io);
+MCF_API int mcf_rbatch_resolve(mcf_rbatch *b, const mcf_rbatch_io *io);
+MCF_API int mcf_rbatch_run_on_host(mcf_rbatch *b, const mcf_rbatch_io *io);        /* TEST HOOKS: one lane on the CPU, MCF_MEM_HOST only */
+MCF_API int mcf_rbatch_rerun_on_host(mcf_rbatch *b, const mcf_rbatch_io *io);
+/* mcf_ubatch_stats of the last solve call of any kind.  Here lds_instances and global_instances may both be non-zero: the tier goes by
+ * each instance's own footprint; workspace_bytes is the sum of the footprints. */
+MCF_API int mcf_rbatch_get_stats(mcf_rbatch *b, mcf_ubatch_stats *out);
+/* mcf_ubatch_validate for ragged rows: block i checks instance i against its own graph's incidence lists. */
+MCF_API int mcf_rbatch_validate(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out);
+MCF_API int mcf_rbatch_validate_on_host(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out);
+
 #ifdef __cplusplus
 }
 #endif

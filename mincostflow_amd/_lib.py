@@ -187,6 +187,26 @@ class UBatchCheckSummary(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RBatchDesc(C.Structure):
+    """mcf_rbatch_desc"""
+    _fields_ = BatchDesc._fields_ + [("graph_count", C.c_int32), ("count", C.c_int32), ("node_count", C.c_void_p), ("arc_start", C.c_void_p),
+                                     ("source", C.c_void_p), ("target", C.c_void_p), ("graph_of", C.c_void_p)]
+
+
+class RBatchIo(C.Structure):
+    """mcf_rbatch_io"""
+    _fields_ = [("memory", C.c_int32), ("supply_type", C.c_int32), ("lower", C.c_void_p), ("upper", C.c_void_p), ("cost", C.c_void_p), ("supply", C.c_void_p),
+                ("changed", C.c_void_p),
+                ("status", C.c_void_p), ("pivots", C.c_void_p), ("total_cost", C.c_void_p), ("flows", C.c_void_p), ("potentials", C.c_void_p), ("trace", C.c_void_p)]
+
+
+class RBatchCheckIo(C.Structure):
+    """mcf_rbatch_check_io"""
+    _fields_ = [("memory", C.c_int32), ("supply_type", C.c_int32), ("lower", C.c_void_p), ("upper", C.c_void_p), ("cost", C.c_void_p), ("supply", C.c_void_p),
+                ("status", C.c_void_p), ("total_cost", C.c_void_p), ("flows", C.c_void_p), ("potentials", C.c_void_p),
+                ("valid", C.c_void_p), ("errors", C.c_void_p), ("first", C.c_void_p), ("objective", C.c_void_p), ("dual_cost", C.c_void_p)]
+
+
 class ProblemStruct(C.Structure):
     _fields_ = [("node_count", C.c_int32), ("arc_count", C.c_int32), ("source", C.POINTER(C.c_int32)),
                 ("target", C.POINTER(C.c_int32)), ("lower", C.POINTER(C.c_int64)), ("upper", C.POINTER(C.c_int64)),
@@ -336,6 +356,16 @@ SIGNATURES = {
     "mcf_ubatch_get_stats": (C.c_int, [C.c_void_p, _P(UBatchStats)]),
     "mcf_ubatch_validate": (C.c_int, [C.c_void_p, _P(UBatchCheckIo), _P(UBatchCheckSummary)]),
     "mcf_ubatch_validate_on_host": (C.c_int, [C.c_void_p, _P(UBatchCheckIo), _P(UBatchCheckSummary)]),
+    "mcf_rbatch_create": (C.c_int, [_P(C.c_void_p), _P(RBatchDesc)]),
+    "mcf_rbatch_destroy": (None, [C.c_void_p]),
+    "mcf_rbatch_get_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcf_rbatch_solve": (C.c_int, [C.c_void_p, _P(RBatchIo)]),
+    "mcf_rbatch_resolve": (C.c_int, [C.c_void_p, _P(RBatchIo)]),
+    "mcf_rbatch_run_on_host": (C.c_int, [C.c_void_p, _P(RBatchIo)]),
+    "mcf_rbatch_rerun_on_host": (C.c_int, [C.c_void_p, _P(RBatchIo)]),
+    "mcf_rbatch_get_stats": (C.c_int, [C.c_void_p, _P(UBatchStats)]),
+    "mcf_rbatch_validate": (C.c_int, [C.c_void_p, _P(RBatchCheckIo), _P(UBatchCheckSummary)]),
+    "mcf_rbatch_validate_on_host": (C.c_int, [C.c_void_p, _P(RBatchCheckIo), _P(UBatchCheckSummary)]),
     "mcf_problem_free": (None, [_P(ProblemStruct)]),
     "mcf_gen_netgen_like": (C.c_int, [_P(ProblemStruct), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64]),

@@ -95,30 +95,62 @@ __global__ __launch_bounds__(kStageThreads) void stage_kernel(const BatchSlot *s
 // The uniform batch (mcf_ubatch_*): the steps of uniform_step.hip.h, one workgroup of one wave per instance like batch_kernel -- the
 // start basis numbers the artificial arcs by a wave-wide prefix count, and all three combine their lanes by wave reductions.  Block i
 // serves instance i and leaves at once where `changed` (a re-solve's mask) says so.  They work on the workspace in device memory; the
-// caller's arrays are read and written as base + i * stride, consecutive lanes on consecutive arcs or nodes.
+// caller's arrays are read and written as base + i * stride, consecutive lanes on consecutive arcs or nodes.  Each forms the placed
+// view of its instance (uniform_view) and hands it to the step.
 __global__ __launch_bounds__(kBatchThreads) void uniform_begin_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
 {
     const int64_t i = (int64_t)blockIdx.x;
-    mcf::uniform_begin(p, i, *tmpl, slots[i], slab + (uint64_t)i * p.stride, (int)threadIdx.x, kBatchThreads);
+    mcf::uniform_begin(mcf::uniform_view(p, nullptr, i, slab), *tmpl, slots[i], (int)threadIdx.x, kBatchThreads);
 }
 __global__ __launch_bounds__(kBatchThreads) void uniform_recost_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
 {
     const int64_t i = (int64_t)blockIdx.x;
     if (p.changed && !p.changed[i]) return;
-    mcf::uniform_recost(p, i, *tmpl, slots[i], slab + (uint64_t)i * p.stride, (int)threadIdx.x, kBatchThreads);
+    mcf::uniform_recost(mcf::uniform_view(p, nullptr, i, slab), *tmpl, slots[i], (int)threadIdx.x, kBatchThreads);
 }
-__global__ __launch_bounds__(kBatchThreads) void uniform_finish_kernel(mcf::UniformProblem p, mcf::UniformOutputs o, const BatchSlot *slots, const unsigned char *slab,
+__global__ __launch_bounds__(kBatchThreads) void uniform_finish_kernel(mcf::UniformProblem p, mcf::UniformOutputs o, const BatchSlot *slots, unsigned char *slab,
                                                                        const int32_t *traces)
 {
     const int64_t i = (int64_t)blockIdx.x;
     if (p.changed && !p.changed[i]) return;
-    mcf::uniform_finish(p, o, i, slots[i], slab + (uint64_t)i * p.stride, traces, (int)threadIdx.x, kBatchThreads);
+    mcf::uniform_finish(mcf::uniform_view(p, &o, i, slab), o, slots[i], traces, (int)threadIdx.x, kBatchThreads);
 }
 // mcf_ubatch_validate: block i checks instance i's rows.  One wave for the same reason: every combine is a wave reduction.  It touches
 // neither slab nor slots; the only words instances share are the two of the summary, and only invalid instances write them.
-__global__ __launch_bounds__(kBatchThreads) void uniform_validate_kernel(mcf::UniformProblem p, mcf::UniformCheck c)
+__global__ __launch_bounds__(kBatchThreads) void uniform_validate_kernel(mcf::UniformProblem p, mcf::UniformCheck c, const int32_t *inc_start, const int32_t *inc,
+                                                                         const int64_t *flows, const int64_t *potentials)
 {
-    mcf::uniform_validate(p, c, (int64_t)blockIdx.x, (int)threadIdx.x, kBatchThreads);
+    mcf::uniform_validate(mcf::uniform_check_view(p, inc_start, inc, flows, potentials, (int64_t)blockIdx.x), c, (int)threadIdx.x, kBatchThreads);
+}
+
+// The ragged batch (mcf_rbatch_*): the same four steps on the same launch shape -- block i = instance i, one wave -- with the view
+// formed from the handle's tables in device memory (ragged_view): the instance's graph record, its rows and its workspace at running
+// sums, its graph's slot template.  Every table entry a block reads is the same for all its lanes.
+__global__ __launch_bounds__(kBatchThreads) void ragged_begin_kernel(mcf::RaggedProblem r, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
+{
+    const int64_t i = (int64_t)blockIdx.x;
+    int32_t t;
+    const mcf::InstanceView v = mcf::ragged_view(r, nullptr, i, slab, &t);
+    mcf::uniform_begin(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
+}
+__global__ __launch_bounds__(kBatchThreads) void ragged_recost_kernel(mcf::RaggedProblem r, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
+{
+    const int64_t i = (int64_t)blockIdx.x;
+    if (r.changed && !r.changed[i]) return;
+    int32_t t;
+    const mcf::InstanceView v = mcf::ragged_view(r, nullptr, i, slab, &t);
+    mcf::uniform_recost(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
+}
+__global__ __launch_bounds__(kBatchThreads) void ragged_finish_kernel(mcf::RaggedProblem r, mcf::UniformOutputs o, const BatchSlot *slots, unsigned char *slab,
+                                                                      const int32_t *traces)
+{
+    const int64_t i = (int64_t)blockIdx.x;
+    if (r.changed && !r.changed[i]) return;
+    mcf::uniform_finish(mcf::ragged_view(r, &o, i, slab, nullptr), o, slots[i], traces, (int)threadIdx.x, kBatchThreads);
+}
+__global__ __launch_bounds__(kBatchThreads) void ragged_validate_kernel(mcf::RaggedProblem r, mcf::UniformCheck c, const int64_t *flows, const int64_t *potentials)
+{
+    mcf::uniform_validate(mcf::ragged_check_view(r, flows, potentials, (int64_t)blockIdx.x), c, (int)threadIdx.x, kBatchThreads);
 }
 
 struct Instance {
@@ -480,6 +512,20 @@ int check_batch_desc(const Desc &d, const char *who)
     if (d.device < 0 || d.pivot_limit < 0 || d.pivots_per_launch < 0 || d.trace_capacity < 0)
         return mcf::fail(MCF_ERR_INVALID, "%s: negative device, pivot limit, pivots per launch or trace capacity", who);
     return MCF_OK;
+}
+
+// the incidence lists of one graph, inc_start[n + 1] and inc[2m]: a stable counting sort of the 2m arc ends by node, so arc ids ascend
+// within a node; a self-loop is there twice
+void build_incidence(size_t n, size_t m, const int32_t *source, const int32_t *target, int32_t *inc_start, int32_t *inc)
+{
+    std::fill(inc_start, inc_start + n + 1, 0);
+    for (size_t e = 0; e < m; ++e) { ++inc_start[(size_t)source[e] + 1]; ++inc_start[(size_t)target[e] + 1]; }
+    for (size_t v = 0; v < n; ++v) inc_start[v + 1] += inc_start[v];
+    std::vector<int32_t> next(inc_start, inc_start + n);
+    for (size_t e = 0; e < m; ++e) {
+        inc[(size_t)next[(size_t)source[e]]++] = (int32_t)(e << 1);
+        inc[(size_t)next[(size_t)target[e]]++] = (int32_t)(e << 1 | 1);
+    }
 }
 
 // the launch plan of a mcf_batch: `footprints` gets every instance's workspace size and must outlive the plan
@@ -936,7 +982,8 @@ struct Staged {
 };
 size_t input_elements(size_t count, int64_t stride, size_t length) { return count ? (count - 1) * (size_t)stride + length : 0; }
 // the staging buffer holds st, and what st brings from the host is in it
-int stage_send(mcf_ubatch *b, const Staged &st, int64_t *bytes_up)
+template <class Handle>
+int stage_send(Handle *b, const Staged &st, int64_t *bytes_up)
 {
     if (b->d_io_bytes < st.total) {
         if (b->d_io) { HIP_TRY(hipFree(b->d_io)); b->d_io = nullptr; b->d_io_bytes = 0; }
@@ -977,7 +1024,8 @@ int stage_up(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve, mcf_ubatch_io
     for (int k = 0; k < 6; ++k) *outs[k].slot = outs[k].p ? b->d_io + at_out[k] : nullptr;
     return MCF_OK;
 }
-int stage_down(mcf_ubatch *b, const Staged &st, int64_t *bytes_down)
+template <class Handle>
+int stage_down(Handle *b, const Staged &st, int64_t *bytes_down)
 {
     for (const Staged::Piece &pc : st.pieces)
         if (pc.host_out && pc.bytes) {
@@ -1073,9 +1121,10 @@ int ubatch_on_host(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve)
     for (size_t i = 0; i < count; ++i) {
         if (p.changed && !p.changed[i]) continue;
         BatchSlot &slot = b->h_slots[i];
-        unsigned char *const home = b->h_slab.data() + i * (size_t)b->stride;
-        if (resolve) mcf::uniform_recost(p, (int64_t)i, b->tmpl, slot, home, 0, 1);
-        else mcf::uniform_begin(p, (int64_t)i, b->tmpl, slot, home, 0, 1);
+        const mcf::InstanceView v = mcf::uniform_view(p, &o, (int64_t)i, b->h_slab.data());
+        unsigned char *const home = v.home;
+        if (resolve) mcf::uniform_recost(v, b->tmpl, slot, 0, 1);
+        else mcf::uniform_begin(v, b->tmpl, slot, 0, 1);
         if (slot.run == mcf::kBatchRunning) {
             mcf::BatchWork w{};
             load_slot(w, slot, b->h_traces.data());
@@ -1085,7 +1134,7 @@ int ubatch_on_host(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve)
             store_slot(slot, w);
             b->stats.total_pivots += slot.pivots;
         }
-        mcf::uniform_finish(p, o, (int64_t)i, slot, home, b->h_traces.data(), 0, 1);
+        mcf::uniform_finish(v, o, slot, b->h_traces.data(), 0, 1);
     }
     b->where = mcf_ubatch::kOnHost;
     b->stats.host_ns = mcf::now_ns() - t_start;
@@ -1115,9 +1164,10 @@ mcf::UniformProblem problem_of(const mcf_ubatch *b, const mcf_ubatch_check_io *i
     p.lower_stride = io->lower_stride; p.upper_stride = io->upper_stride; p.cost_stride = io->cost_stride; p.supply_stride = io->supply_stride;
     return p;
 }
-mcf::UniformCheck check_of(const mcf_ubatch_check_io *io, const int32_t *inc_start, const int32_t *inc, int64_t *summary)
+template <class CheckIo>
+mcf::UniformCheck check_of(const CheckIo *io, int64_t *summary)
 {
-    return mcf::UniformCheck{inc_start, inc, io->status, io->total_cost, io->flows, io->potentials, io->valid, io->errors, io->first, io->objective, io->dual_cost, summary};
+    return mcf::UniformCheck{io->status, io->total_cost, io->valid, io->errors, io->first, io->objective, io->dual_cost, summary};
 }
 void summary_of(const int64_t words[2], int64_t count, mcf_ubatch_check_summary *out)
 {
@@ -1167,7 +1217,7 @@ int validate_on_device(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_
     out->bytes_up += (int64_t)sizeof(words);
     const double t_launch = mcf::now_ns();
     hipLaunchKernelGGL(uniform_validate_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, problem_of(b, &dio, b->d_source, b->d_target),
-                       check_of(&dio, b->d_inc_start, b->d_inc, b->d_summary));
+                       check_of(&dio, b->d_summary), b->d_inc_start, b->d_inc, dio.flows, dio.potentials);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     out->kernel_ns = mcf::now_ns() - t_launch;
@@ -1184,9 +1234,10 @@ int validate_on_host(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_ch
     *out = mcf_ubatch_check_summary{};
     int64_t words[2] = {0, INT64_MAX};
     const mcf::UniformProblem p = problem_of(b, io, b->source.data(), b->target.data());
-    const mcf::UniformCheck c = check_of(io, b->inc_start.data(), b->inc.data(), words);
+    const mcf::UniformCheck c = check_of(io, words);
     const double t_start = mcf::now_ns();
-    for (int64_t i = 0; i < (int64_t)b->d.count; ++i) mcf::uniform_validate(p, c, i, 0, 1);
+    for (int64_t i = 0; i < (int64_t)b->d.count; ++i)
+        mcf::uniform_validate(mcf::uniform_check_view(p, b->inc_start.data(), b->inc.data(), io->flows, io->potentials, i), c, 0, 1);
     out->kernel_ns = mcf::now_ns() - t_start;
     summary_of(words, (int64_t)b->d.count, out);
     return MCF_OK;
@@ -1216,17 +1267,9 @@ int mcf_ubatch_create(mcf_ubatch **out, const mcf_ubatch_desc *desc)
     b->d.source = b->d.target = nullptr;                                    // the caller's arrays are not kept
     if (const int rc = configure_slot(b->tmpl, limits_of(b->d), desc->node_count, desc->arc_count, b->source.data(), b->target.data())) { delete b; return rc; }
     b->stride = layout_of((uint32_t)(desc->arc_count + 2 * desc->node_count), (uint32_t)desc->node_count + 1u).bytes;
-    // the incidence lists: a stable counting sort of the 2m arc ends by node, so arc ids ascend within a node; a self-loop is there twice
-    const size_t n = (size_t)desc->node_count, m = (size_t)desc->arc_count;
-    b->inc_start.assign(n + 1, 0);
-    b->inc.resize(2 * m);
-    for (size_t e = 0; e < m; ++e) { ++b->inc_start[(size_t)b->source[e] + 1]; ++b->inc_start[(size_t)b->target[e] + 1]; }
-    for (size_t v = 0; v < n; ++v) b->inc_start[v + 1] += b->inc_start[v];
-    std::vector<int32_t> next(b->inc_start.begin(), b->inc_start.end() - 1);
-    for (size_t e = 0; e < m; ++e) {
-        b->inc[(size_t)next[(size_t)b->source[e]]++] = (int32_t)(e << 1);
-        b->inc[(size_t)next[(size_t)b->target[e]]++] = (int32_t)(e << 1 | 1);
-    }
+    b->inc_start.resize((size_t)desc->node_count + 1);
+    b->inc.resize(2 * (size_t)desc->arc_count);
+    build_incidence((size_t)desc->node_count, (size_t)desc->arc_count, b->source.data(), b->target.data(), b->inc_start.data(), b->inc.data());
     *out = b;
     return MCF_OK;
 }
@@ -1239,6 +1282,433 @@ int mcf_ubatch_rerun_on_host(mcf_ubatch *b, const mcf_ubatch_io *io) { return ub
 int mcf_ubatch_validate(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_check_summary *out) { return validate_on_device(b, io, out); }
 int mcf_ubatch_validate_on_host(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_check_summary *out) { return validate_on_host(b, io, out); }
 int mcf_ubatch_get_stats(mcf_ubatch *b, mcf_ubatch_stats *out)
+{
+    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
+    *out = b->stats;
+    return MCF_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================
+// mcf_rbatch_*: a set of graphs, every instance names its own; ragged rows in, ragged rows out ("Ragged batch")
+// ================================================================================================
+struct mcf_rbatch {
+    mcf_rbatch_desc d{};
+    // the tables of ragged_view, as the host hooks read them; the device gets one copy of all of them (d_tables)
+    std::vector<int32_t> source, target, inc_start, inc, graph_of;
+    std::vector<mcf::RaggedGraph> graphs;
+    std::vector<int64_t> arc_row, node_row;     // [count + 1]
+    std::vector<uint64_t> workspace;            // [count + 1]: the last entry is the slab's size
+    std::vector<uint32_t> footprint;            // [count]: layout_of(m + 2n, n + 1).bytes of the instance's graph
+    std::vector<BatchSlot> tmpl;                // one per graph (configure_slot): search_arcs, block configuration and limits go by n and m
+    enum Where { kNowhere, kOnHost, kOnDevice } where = kNowhere;
+    mcf_ubatch_stats stats{};
+    int lds_max = 0;
+    DeviceBuffers dev;                          // slab, slots, ids, traces
+    unsigned char *d_tables = nullptr;          // every table and the topology in one allocation; dt = the pointers into it
+    mcf::RaggedProblem dt{};
+    BatchSlot *d_tmpl = nullptr;                // [graph_count], sent with every solve call
+    int64_t *d_summary = nullptr;
+    unsigned char *d_io = nullptr;              // MCF_MEM_HOST: the caller's arrays on their way up and down
+    size_t d_io_bytes = 0;
+    std::vector<unsigned char> h_slab;          // the host hooks' slab, slots and traces: the device's layout
+    std::vector<BatchSlot> h_slots;
+    std::vector<int32_t> h_traces;
+    ~mcf_rbatch()
+    {
+        if (d_tables) (void)hipFree(d_tables);
+        if (d_tmpl) (void)hipFree(d_tmpl);
+        if (d_summary) (void)hipFree(d_summary);
+        if (d_io) (void)hipFree(d_io);
+    }
+};
+
+namespace {
+
+template <class Io>
+int check_ragged_io(const mcf_rbatch *b, const Io *io, const char *what, bool host_only, bool solve_call)
+{
+    if (!b || !io) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
+    if (io->memory != MCF_MEM_HOST && io->memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io->memory);
+    if (host_only && io->memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
+    if (solve_call) {
+        if (io->supply_type != MCF_SUPPLY_GEQ && io->supply_type != MCF_SUPPLY_LEQ) return mcf::fail(MCF_ERR_INVALID, "Invalid supply type");
+    } else if (io->supply_type < MCF_SUPPLY_GEQ || io->supply_type > MCF_SUPPLY_EQ) {
+        return mcf::fail(MCF_ERR_INVALID, "%s: supply type %d", what, io->supply_type);
+    }
+    return MCF_OK;
+}
+
+// the tables where the host hooks read them, with the rows of io
+template <class Io>
+mcf::RaggedProblem ragged_problem(const mcf_rbatch *b, const mcf::RaggedProblem &tables, const Io *io, const uint8_t *changed)
+{
+    mcf::RaggedProblem r = tables;
+    r.supply_type = io->supply_type; r.trace_cap = b->d.trace_capacity;
+    r.lower = io->lower; r.upper = io->upper; r.cost = io->cost; r.supply = io->supply;
+    r.changed = changed;
+    return r;
+}
+mcf::RaggedProblem host_tables(const mcf_rbatch *b)
+{
+    mcf::RaggedProblem r{};
+    r.graph_of = b->graph_of.data(); r.graphs = b->graphs.data();
+    r.arc_row = b->arc_row.data(); r.node_row = b->node_row.data(); r.workspace = b->workspace.data();
+    r.source = b->source.data(); r.target = b->target.data(); r.inc_start = b->inc_start.data(); r.inc = b->inc.data();
+    return r;
+}
+
+// the tables, the topology and its incidence lists go up once per handle, in one copy, with its first device call of any kind
+int ensure_tables(mcf_rbatch *b)
+{
+    if (b->d_summary) return MCF_OK;
+    struct Part { const void *host; size_t bytes; size_t at; };
+    const size_t count = (size_t)b->d.count;
+    Part parts[] = {{b->graph_of.data(), count * sizeof(int32_t), 0},
+                    {b->graphs.data(), b->graphs.size() * sizeof(mcf::RaggedGraph), 0},
+                    {b->arc_row.data(), (count + 1) * sizeof(int64_t), 0},
+                    {b->node_row.data(), (count + 1) * sizeof(int64_t), 0},
+                    {b->workspace.data(), count * sizeof(uint64_t), 0},
+                    {b->source.data(), b->source.size() * sizeof(int32_t), 0},
+                    {b->target.data(), b->target.size() * sizeof(int32_t), 0},
+                    {b->inc_start.data(), b->inc_start.size() * sizeof(int32_t), 0},
+                    {b->inc.data(), b->inc.size() * sizeof(int32_t), 0}};
+    size_t total = 0;
+    for (Part &pt : parts) { pt.at = total; total += (pt.bytes + 15) & ~(size_t)15; }
+    std::vector<unsigned char> image(total, 0);
+    for (const Part &pt : parts)
+        if (pt.bytes) memcpy(image.data() + pt.at, pt.host, pt.bytes);
+    // a call that failed half way left what it had allocated: those are kept and filled again, not allocated twice
+    if (!b->d_tables) HIP_TRY(hipMalloc((void **)&b->d_tables, std::max<size_t>(total, 16)));
+    if (total) HIP_TRY(hipMemcpy(b->d_tables, image.data(), total, hipMemcpyHostToDevice));
+    if (!b->d_tmpl) HIP_TRY(hipMalloc((void **)&b->d_tmpl, std::max<size_t>(b->tmpl.size(), 1) * sizeof(BatchSlot)));
+    unsigned char *const base = b->d_tables;
+    mcf::RaggedProblem &r = b->dt;
+    r = mcf::RaggedProblem{};
+    r.graph_of = (const int32_t *)(base + parts[0].at); r.graphs = (const mcf::RaggedGraph *)(base + parts[1].at);
+    r.arc_row = (const int64_t *)(base + parts[2].at); r.node_row = (const int64_t *)(base + parts[3].at);
+    r.workspace = (const uint64_t *)(base + parts[4].at);
+    r.source = (const int32_t *)(base + parts[5].at); r.target = (const int32_t *)(base + parts[6].at);
+    r.inc_start = (const int32_t *)(base + parts[7].at); r.inc = (const int32_t *)(base + parts[8].at);
+    HIP_TRY(hipMalloc((void **)&b->d_summary, 2 * sizeof(int64_t)));          // last: it says the rest is there
+    return MCF_OK;
+}
+
+int ensure_device_buffers(mcf_rbatch *b)
+{
+    if (const int rc = ensure_tables(b)) return rc;
+    if (b->dev.slab) return MCF_OK;
+    const size_t count = (size_t)b->d.count;
+    HIP_TRY(hipMalloc((void **)&b->dev.slab, std::max<size_t>((size_t)b->workspace[count], 16)));
+    HIP_TRY(hipMalloc((void **)&b->dev.slots, count * sizeof(BatchSlot)));
+    HIP_TRY(hipMalloc((void **)&b->dev.ids, count * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void **)&b->dev.traces, std::max<size_t>(count * (size_t)b->d.trace_capacity, 1) * sizeof(int32_t)));
+    return MCF_OK;
+}
+
+// MCF_MEM_HOST: as stage_up for the uniform batch, with the ragged totals for lengths
+int ragged_stage_up(mcf_rbatch *b, const mcf_rbatch_io *io, bool resolve, mcf_rbatch_io *dio, Staged *st)
+{
+    *dio = *io;
+    if (io->memory == MCF_MEM_DEVICE) return MCF_OK;
+    const size_t count = (size_t)b->d.count, arcs = (size_t)b->arc_row[count], nodes = (size_t)b->node_row[count], cap = (size_t)b->d.trace_capacity;
+    const bool keep_rows = resolve && io->changed;
+    struct In { const void *p; size_t bytes; const void **slot; };
+    const In ins[] = {{io->lower, 8 * arcs, (const void **)&dio->lower}, {io->upper, 8 * arcs, (const void **)&dio->upper},
+                      {io->cost, 8 * arcs, (const void **)&dio->cost},   {io->supply, 8 * nodes, (const void **)&dio->supply},
+                      {resolve ? io->changed : nullptr, count, (const void **)&dio->changed}};
+    struct Out { void *p; size_t bytes; void **slot; };
+    const Out outs[] = {{io->status, 4 * count, (void **)&dio->status},       {io->pivots, 8 * count, (void **)&dio->pivots},
+                        {io->total_cost, 8 * count, (void **)&dio->total_cost}, {io->flows, 8 * arcs, (void **)&dio->flows},
+                        {io->potentials, 8 * nodes, (void **)&dio->potentials}, {io->trace, 4 * count * cap, (void **)&dio->trace}};
+    size_t at_in[5], at_out[6];
+    for (int k = 0; k < 5; ++k) at_in[k] = ins[k].p ? st->add(ins[k].p, nullptr, ins[k].bytes) : 0;
+    for (int k = 0; k < 6; ++k) at_out[k] = outs[k].p ? st->add(keep_rows ? outs[k].p : nullptr, outs[k].p, outs[k].bytes) : 0;
+    if (const int rc = stage_send(b, *st, &b->stats.bytes_up)) return rc;
+    for (int k = 0; k < 5; ++k) *ins[k].slot = ins[k].p ? b->d_io + at_in[k] : nullptr;
+    for (int k = 0; k < 6; ++k) *outs[k].slot = outs[k].p ? b->d_io + at_out[k] : nullptr;
+    return MCF_OK;
+}
+
+mcf::UniformOutputs outputs_of(const mcf_rbatch_io *io)
+{
+    return mcf::UniformOutputs{io->status, io->pivots, io->total_cost, io->flows, io->potentials, io->trace};
+}
+
+// mcf_rbatch_solve and mcf_rbatch_resolve: ubatch_on_device with the ragged kernels round the same launch loop; the footprint per
+// instance decides each instance's class
+int rbatch_on_device(mcf_rbatch *b, const mcf_rbatch_io *io, bool resolve)
+{
+    const char *const what = resolve ? "mcf_rbatch_resolve" : "mcf_rbatch_solve";
+    if (const int rc = check_ragged_io(b, io, what, false, true)) return rc;
+    if (resolve && b->where == mcf_rbatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
+    if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
+    const double t_start = mcf::now_ns();
+    const DeviceGuard guard;
+    if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
+    const size_t count = (size_t)b->d.count;
+    b->stats = mcf_ubatch_stats{};
+    b->stats.instances = (int64_t)count;
+    for (size_t i = 0; i < count; ++i)
+        (class_of(b->lds_max, b->footprint[i]) != kClasses - 1 ? b->stats.lds_instances : b->stats.global_instances)++;
+    b->stats.workspace_bytes = (int64_t)b->workspace[count];
+    if (!count) { b->where = mcf_rbatch::kOnDevice; b->stats.host_ns = mcf::now_ns() - t_start; return MCF_OK; }
+    if (const int rc = ensure_device_buffers(b)) return rc;
+    DeviceBuffers &dev = b->dev;
+    if (resolve && b->where == mcf_rbatch::kOnHost) {                       // the last solve was a host hook's: its state goes up whole
+        if (!b->h_slab.empty()) HIP_TRY(hipMemcpy(dev.slab, b->h_slab.data(), b->h_slab.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dev.slots, b->h_slots.data(), count * sizeof(BatchSlot), hipMemcpyHostToDevice));
+        b->stats.bytes_up += (int64_t)(b->h_slab.size() + count * sizeof(BatchSlot));
+    }
+    mcf_rbatch_io dio;
+    Staged staged;
+    if (const int rc = ragged_stage_up(b, io, resolve, &dio, &staged)) return rc;
+    const mcf::RaggedProblem r = ragged_problem(b, b->dt, &dio, resolve ? dio.changed : nullptr);
+
+    const double t_begin = mcf::now_ns();
+    HIP_TRY(hipMemcpy(b->d_tmpl, b->tmpl.data(), b->tmpl.size() * sizeof(BatchSlot), hipMemcpyHostToDevice));
+    b->stats.bytes_up += (int64_t)(b->tmpl.size() * sizeof(BatchSlot));
+    if (resolve) hipLaunchKernelGGL(ragged_recost_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, r, b->d_tmpl, dev.slots, dev.slab);
+    else hipLaunchKernelGGL(ragged_begin_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, r, b->d_tmpl, dev.slots, dev.slab);
+    HIP_TRY(hipGetLastError());
+    b->where = mcf_rbatch::kOnDevice;
+    std::vector<BatchSlot> slots(count);
+    HIP_TRY(hipMemcpy(slots.data(), dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));      // waits for the launch; says who runs
+    b->stats.bytes_down += (int64_t)(count * sizeof(BatchSlot));
+    b->stats.begin_ns = mcf::now_ns() - t_begin;
+
+    std::vector<int32_t> run;
+    for (size_t i = 0; i < count; ++i)
+        if (slots[i].run == mcf::kBatchRunning) run.push_back((int32_t)i);
+    LaunchTotals t;
+    if (const int rc = run_launches(LaunchPlan{&dev, b->lds_max, b->d.pivots_per_launch, b->footprint.data(), 0}, slots, run, &t)) return rc;
+    for (int32_t i : run) b->stats.total_pivots += slots[(size_t)i].pivots;
+    b->stats.launches = t.launches;
+    b->stats.lds_bytes_max = t.lds_bytes_max;
+    b->stats.bytes_up += t.bytes_up;
+    b->stats.bytes_down += t.bytes_down;
+    b->stats.kernel_ns = t.kernel_ns;
+
+    const double t_finish = mcf::now_ns();
+    hipLaunchKernelGGL(ragged_finish_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, r, outputs_of(&dio), dev.slots, dev.slab, dev.traces);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    b->stats.finish_ns = mcf::now_ns() - t_finish;
+    if (const int rc = stage_down(b, staged, &b->stats.bytes_down)) return rc;
+    b->stats.host_ns = mcf::now_ns() - t_start - t.kernel_ns;
+    return MCF_OK;
+}
+
+// the host hooks: the same steps and batch_run with one lane, on a host slab of the device's layout
+int rbatch_on_host(mcf_rbatch *b, const mcf_rbatch_io *io, bool resolve)
+{
+    const char *const what = resolve ? "mcf_rbatch_rerun_on_host" : "mcf_rbatch_run_on_host";
+    if (const int rc = check_ragged_io(b, io, what, true, true)) return rc;
+    if (resolve && b->where == mcf_rbatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
+    const double t_start = mcf::now_ns();
+    const size_t count = (size_t)b->d.count;
+    b->h_slab.resize((size_t)b->workspace[count]);
+    b->h_slots.resize(count);
+    b->h_traces.resize(std::max<size_t>(count * (size_t)b->d.trace_capacity, 1));
+    if (resolve && b->where == mcf_rbatch::kOnDevice && count) {            // the last solve was the device's: its state comes down whole
+        const DeviceGuard guard;
+        HIP_TRY(hipSetDevice(b->d.device));
+        if (!b->h_slab.empty()) HIP_TRY(hipMemcpy(b->h_slab.data(), b->dev.slab, b->h_slab.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(b->h_slots.data(), b->dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));
+    }
+    b->stats = mcf_ubatch_stats{};
+    b->stats.instances = (int64_t)count;
+    b->stats.workspace_bytes = (int64_t)b->h_slab.size();
+    const mcf::RaggedProblem r = ragged_problem(b, host_tables(b), io, resolve ? io->changed : nullptr);
+    const mcf::UniformOutputs o = outputs_of(io);
+    for (size_t i = 0; i < count; ++i) {
+        if (r.changed && !r.changed[i]) continue;
+        BatchSlot &slot = b->h_slots[i];
+        int32_t t = 0;
+        const mcf::InstanceView v = mcf::ragged_view(r, &o, (int64_t)i, b->h_slab.data(), &t);
+        if (resolve) mcf::uniform_recost(v, b->tmpl[(size_t)t], slot, 0, 1);
+        else mcf::uniform_begin(v, b->tmpl[(size_t)t], slot, 0, 1);
+        if (slot.run == mcf::kBatchRunning) {
+            mcf::BatchWork w{};
+            load_slot(w, slot, b->h_traces.data());
+            bind(w, v.home, layout_of((uint32_t)slot.all_arcs, (uint32_t)slot.n + 1u));
+            if (slot.reprice) mcf::batch_reprice(w, 0, 1);
+            mcf::batch_run(w, 0, 1, INT64_MAX);
+            store_slot(slot, w);
+            b->stats.total_pivots += slot.pivots;
+        }
+        mcf::uniform_finish(v, o, slot, b->h_traces.data(), 0, 1);
+    }
+    b->where = mcf_rbatch::kOnHost;
+    b->stats.host_ns = mcf::now_ns() - t_start;
+    return MCF_OK;
+}
+
+int check_ragged_check_io(const mcf_rbatch *b, const mcf_rbatch_check_io *io, const mcf_ubatch_check_summary *out, const char *what, bool host_only)
+{
+    if (!out) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_ragged_io(b, io, what, host_only, false)) return rc;
+    const size_t count = (size_t)b->d.count;
+    if (count > 0 && (!io->status || !io->total_cost || (b->arc_row[count] && !io->flows) || (b->node_row[count] && !io->potentials)))    // an empty tensor has no address
+        return mcf::fail(MCF_ERR_INVALID, "%s: status, total_cost, flows and potentials are the solution to check, all four are required", what);
+    return MCF_OK;
+}
+
+int rbatch_validate_on_device(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out)
+{
+    const char *const what = "mcf_rbatch_validate";
+    if (const int rc = check_ragged_check_io(b, io, out, what, false)) return rc;
+    if (const int rc = have_device(b->d.device, what)) return rc;
+    *out = mcf_ubatch_check_summary{};
+    out->first_invalid = -1;
+    const size_t count = (size_t)b->d.count;
+    if (!count) return MCF_OK;
+    const size_t arcs = (size_t)b->arc_row[count], nodes = (size_t)b->node_row[count];
+    const DeviceGuard guard;
+    HIP_TRY(hipSetDevice(b->d.device));
+    if (const int rc = ensure_tables(b)) return rc;
+    mcf_rbatch_check_io dio = *io;
+    Staged staged;
+    if (io->memory == MCF_MEM_HOST) {
+        struct Piece { const void *in; void *out; size_t bytes; const void **slot; };
+        const Piece pieces[] = {{io->lower, nullptr, 8 * arcs, (const void **)&dio.lower},
+                                {io->upper, nullptr, 8 * arcs, (const void **)&dio.upper},
+                                {io->cost, nullptr, 8 * arcs, (const void **)&dio.cost},
+                                {io->supply, nullptr, 8 * nodes, (const void **)&dio.supply},
+                                {io->status, nullptr, 4 * count, (const void **)&dio.status},
+                                {io->total_cost, nullptr, 8 * count, (const void **)&dio.total_cost},
+                                {io->flows, nullptr, 8 * arcs, (const void **)&dio.flows},
+                                {io->potentials, nullptr, 8 * nodes, (const void **)&dio.potentials},
+                                {nullptr, io->valid, 4 * count, (const void **)&dio.valid},
+                                {nullptr, io->errors, 4 * count * MCF_VAL_KINDS, (const void **)&dio.errors},
+                                {nullptr, io->first, 4 * count * MCF_VAL_KINDS, (const void **)&dio.first},
+                                {nullptr, io->objective, 8 * count, (const void **)&dio.objective},
+                                {nullptr, io->dual_cost, 8 * count, (const void **)&dio.dual_cost}};
+        constexpr int kPieces = (int)(sizeof(pieces) / sizeof(pieces[0]));
+        size_t at[kPieces];
+        for (int k = 0; k < kPieces; ++k) at[k] = pieces[k].in || pieces[k].out ? staged.add(pieces[k].in, pieces[k].out, pieces[k].bytes) : 0;
+        if (const int rc = stage_send(b, staged, &out->bytes_up)) return rc;
+        for (int k = 0; k < kPieces; ++k) *pieces[k].slot = pieces[k].in || pieces[k].out ? b->d_io + at[k] : nullptr;
+    }
+    int64_t words[2] = {0, INT64_MAX};
+    HIP_TRY(hipMemcpy(b->d_summary, words, sizeof(words), hipMemcpyHostToDevice));
+    out->bytes_up += (int64_t)sizeof(words);
+    const double t_launch = mcf::now_ns();
+    hipLaunchKernelGGL(ragged_validate_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, ragged_problem(b, b->dt, &dio, nullptr),
+                       check_of(&dio, b->d_summary), dio.flows, dio.potentials);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    out->kernel_ns = mcf::now_ns() - t_launch;
+    HIP_TRY(hipMemcpy(words, b->d_summary, sizeof(words), hipMemcpyDeviceToHost));
+    out->bytes_down += (int64_t)sizeof(words);
+    if (const int rc = stage_down(b, staged, &out->bytes_down)) return rc;
+    summary_of(words, (int64_t)count, out);
+    return MCF_OK;
+}
+
+int rbatch_validate_on_host(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out)
+{
+    if (const int rc = check_ragged_check_io(b, io, out, "mcf_rbatch_validate_on_host", true)) return rc;
+    *out = mcf_ubatch_check_summary{};
+    int64_t words[2] = {0, INT64_MAX};
+    const mcf::RaggedProblem r = ragged_problem(b, host_tables(b), io, nullptr);
+    const mcf::UniformCheck c = check_of(io, words);
+    const double t_start = mcf::now_ns();
+    for (int64_t i = 0; i < (int64_t)b->d.count; ++i) mcf::uniform_validate(mcf::ragged_check_view(r, io->flows, io->potentials, i), c, 0, 1);
+    out->kernel_ns = mcf::now_ns() - t_start;
+    summary_of(words, (int64_t)b->d.count, out);
+    return MCF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcf_rbatch_create(mcf_rbatch **out, const mcf_rbatch_desc *desc)
+{
+    const char *const who = "mcf_rbatch_create";
+    if (!out || !desc) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", who);
+    *out = nullptr;
+    if (const int rc = check_batch_desc(*desc, who)) return rc;
+    if (desc->graph_count < 0 || desc->count < 0) return mcf::fail(MCF_ERR_INVALID, "%s: negative graph or instance count", who);
+    if (desc->count > MCF_BATCH_MAX_INSTANCES) return mcf::fail(MCF_ERR_INVALID, "%s: a batch holds at most %d instances", who, MCF_BATCH_MAX_INSTANCES);
+    const size_t G = (size_t)desc->graph_count, count = (size_t)desc->count;
+    if (G && (!desc->node_count || !desc->arc_start)) return mcf::fail(MCF_ERR_INVALID, "%s: null node_count or arc_start", who);
+    if (!desc->graph_of && count != G)
+        return mcf::fail(MCF_ERR_INVALID, "%s: without graph_of instance i is graph i, so count (%d) must equal graph_count (%d)", who, desc->count, desc->graph_count);
+    for (size_t i = 0; desc->graph_of && i < count; ++i)
+        if (desc->graph_of[i] < 0 || (size_t)desc->graph_of[i] >= G)
+            return mcf::fail(MCF_ERR_INVALID, "%s: graph_of[%zu] = %d is not one of the %d graphs", who, i, desc->graph_of[i], desc->graph_count);
+    const int64_t first_arc = G ? desc->arc_start[0] : 0;
+    if (first_arc < 0) return mcf::fail(MCF_ERR_INVALID, "%s: arc_start[0] is negative", who);
+    for (size_t g = 0; g < G; ++g) {
+        const int64_t m = desc->arc_start[g + 1] - desc->arc_start[g];
+        if (m < 0) return mcf::fail(MCF_ERR_INVALID, "%s: arc_start is not monotone at graph %zu", who, g);
+        if (m > MCF_BATCH_MAX_ARCS || desc->node_count[g] > MCF_BATCH_MAX_NODES)
+            return mcf::fail(MCF_ERR_INVALID, "%s: graph %zu: %d nodes / %lld arcs is above the batch solver's limit of %d / %d per instance; solve it with mcf_ns_solve",
+                             who, g, desc->node_count[g], (long long)m, MCF_BATCH_MAX_NODES, MCF_BATCH_MAX_ARCS);
+    }
+    mcf_rbatch *b = new mcf_rbatch();
+    b->d = *desc;
+    b->d.semantics = MCF_SEM_PLAIN;                                         // 0 means the same
+    const size_t arcs = G ? (size_t)(desc->arc_start[G] - first_arc) : 0;
+    if (arcs && (!desc->source || !desc->target)) { delete b; return mcf::fail(MCF_ERR_INVALID, "%s: null source or target", who); }
+    if (arcs) {
+        b->source.assign(desc->source + first_arc, desc->source + first_arc + arcs);
+        b->target.assign(desc->target + first_arc, desc->target + first_arc + arcs);
+    }
+    b->graphs.resize(G);
+    b->tmpl.resize(G);
+    size_t nodes = 0;
+    for (size_t g = 0; g < G; ++g) {                                        // the records; node_count is checked below, by core_create
+        mcf::RaggedGraph &rec = b->graphs[g];
+        rec.n = desc->node_count[g]; rec.m = (int32_t)(desc->arc_start[g + 1] - desc->arc_start[g]); rec.tmpl = (int32_t)g; rec.reserved = 0;
+        rec.ends = desc->arc_start[g] - first_arc; rec.inc_start = (int64_t)(nodes + g); rec.inc = 2 * rec.ends;
+        nodes += (size_t)std::max(rec.n, 0);
+    }
+    b->inc_start.resize(nodes + G);
+    b->inc.resize(2 * arcs);
+    for (size_t g = 0; g < G; ++g) {
+        const mcf::RaggedGraph &rec = b->graphs[g];
+        const int32_t *const src = b->source.data() + rec.ends, *const tgt = b->target.data() + rec.ends;
+        mcf::NsCore checked;                                                // end points, as mcf_batch_add validates them
+        if (const int rc = mcf::core_create(&checked, rec.n, rec.m, src, tgt)) { delete b; return rc; }
+        if (const int rc = configure_slot(b->tmpl[g], limits_of(b->d), rec.n, rec.m, src, tgt)) { delete b; return rc; }
+        build_incidence((size_t)rec.n, (size_t)rec.m, src, tgt, b->inc_start.data() + rec.inc_start, b->inc.data() + rec.inc);
+    }
+    b->graph_of.resize(count);
+    for (size_t i = 0; i < count; ++i) b->graph_of[i] = desc->graph_of ? desc->graph_of[i] : (int32_t)i;
+    // rows and workspaces: running sums.  Every footprint is a multiple of 16 (layout_of), so every workspace starts on a 16-byte boundary
+    b->arc_row.assign(count + 1, 0); b->node_row.assign(count + 1, 0); b->workspace.assign(count + 1, 0);
+    b->footprint.resize(count);
+    for (size_t i = 0; i < count; ++i) {
+        const mcf::RaggedGraph &rec = b->graphs[(size_t)b->graph_of[i]];
+        b->footprint[i] = layout_of((uint32_t)(rec.m + 2 * rec.n), (uint32_t)rec.n + 1u).bytes;
+        b->arc_row[i + 1] = b->arc_row[i] + rec.m;
+        b->node_row[i + 1] = b->node_row[i] + rec.n;
+        b->workspace[i + 1] = b->workspace[i] + b->footprint[i];
+    }
+    b->d.node_count = nullptr; b->d.arc_start = nullptr; b->d.source = b->d.target = nullptr; b->d.graph_of = nullptr;     // the caller's arrays are not kept
+    *out = b;
+    return MCF_OK;
+}
+
+void mcf_rbatch_destroy(mcf_rbatch *b) { delete b; }
+int mcf_rbatch_get_rows(mcf_rbatch *b, int64_t *arc_row, int64_t *node_row)
+{
+    if (!b) return mcf::fail(MCF_ERR_INVALID, "null argument");
+    if (arc_row) std::copy(b->arc_row.begin(), b->arc_row.end(), arc_row);
+    if (node_row) std::copy(b->node_row.begin(), b->node_row.end(), node_row);
+    return MCF_OK;
+}
+int mcf_rbatch_solve(mcf_rbatch *b, const mcf_rbatch_io *io) { return rbatch_on_device(b, io, false); }
+int mcf_rbatch_resolve(mcf_rbatch *b, const mcf_rbatch_io *io) { return rbatch_on_device(b, io, true); }
+int mcf_rbatch_run_on_host(mcf_rbatch *b, const mcf_rbatch_io *io) { return rbatch_on_host(b, io, false); }
+int mcf_rbatch_rerun_on_host(mcf_rbatch *b, const mcf_rbatch_io *io) { return rbatch_on_host(b, io, true); }
+int mcf_rbatch_validate(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out) { return rbatch_validate_on_device(b, io, out); }
+int mcf_rbatch_validate_on_host(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out) { return rbatch_validate_on_host(b, io, out); }
+int mcf_rbatch_get_stats(mcf_rbatch *b, mcf_ubatch_stats *out)
 {
     if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
     *out = b->stats;

@@ -7,8 +7,11 @@
 //   uniform_recost  a re-solve with new costs: from the kept basis where the last solve ended Optimal, else uniform_begin again.
 // The pivots between them are batch_run on the workspace these steps leave, unchanged.
 // A fourth step stands apart from the solve: uniform_validate checks a solution in the caller's rows (mcf_ubatch_validate).
-// Problem data are read straight from the caller's arrays (base + instance * stride, stride 0 = one array for all), results are written
-// straight into the caller's rows.  The steps never learn whether those pointers are device or host memory.
+// Problem data are read straight from the caller's arrays, results are written straight into the caller's rows.  The steps never learn
+// whether those pointers are device or host memory, nor how the rows were found: they work on an InstanceView, the instance PLACED.
+// Two ways lead to a view.  uniform_view: one topology, rows at base + instance * stride (stride 0 = one array for all), workspaces at a
+// fixed stride (mcf_ubatch_*).  ragged_view: a set of graphs, every instance names its own, rows and workspaces at running sums kept in
+// per-handle tables (mcf_rbatch_*, DESIGN.md 3.14 "Ragged batch").
 // Nothing here depends on the order in which lanes add: the supply shift and the total cost are integer sums (they wrap, they commute),
 // so one lane and 64 lanes give the same bits, and both give ns_core.cpp's.
 #pragma once
@@ -33,6 +36,45 @@ struct UniformOutputs {                                  // any may be null
     int32_t *status;
     int64_t *pivots, *total_cost, *flows, *potentials;   // [count], [count], [count * m], [count * n]
     int32_t *trace;                                      // [count * trace_cap]
+};
+
+// the solution and the answers of a validation: every array has one entry (or MCF_VAL_KINDS) per instance; the rows are in the view
+struct UniformCheck {
+    const int32_t *status;                               // the solution: [count], [count]
+    const int64_t *total_cost;
+    int32_t *valid, *errors, *first;                     // the answers, any may be null: [count], [count * MCF_VAL_KINDS] twice
+    int64_t *objective, *dual_cost;                      // [count]
+    int64_t *summary;                                    // [2]: invalid instances, the lowest invalid index (INT64_MAX while there is none)
+};
+
+// Instance i placed: its graph, its rows of the caller's arrays, its workspace, its output rows.  All the steps below see of a batch.
+struct InstanceView {
+    int64_t i;                                           // its entry of the per-instance arrays (status[i], changed[i], ...)
+    int32_t n, m, supply_type, trace_cap;
+    const int32_t *source, *target;                      // [m], validated at create
+    const int32_t *inc_start, *inc;                      // the graph's incidence lists [n + 1], [2m]: uniform_validate only
+    const int64_t *lower, *upper, *cost, *supply;        // the instance's rows; null: 0 / uncapacitated / 0 / 0
+    unsigned char *home;                                 // its workspace = slab + workspace
+    uint64_t workspace, trace;                           // what its slot says of where workspace and trace lie
+    int64_t *flows, *potentials;                         // output rows [m], [n], null = not asked for
+    int32_t *trace_row;                                  // [trace_cap]
+    const int64_t *check_flows, *check_potentials;       // uniform_validate: the rows of the solution to check
+};
+
+// ---- a set of graphs, every instance one of them (mcf_rbatch_*).  The tables lie where the step runs.
+struct RaggedGraph {
+    int32_t n, m, tmpl, reserved;                        // tmpl: its slot template
+    int64_t ends, inc_start, inc;                        // where its end points ([m]) and its incidence lists ([n + 1], [2m]) begin
+};
+struct RaggedProblem {
+    int32_t supply_type, trace_cap;
+    const int32_t *graph_of;                             // [count]
+    const RaggedGraph *graphs;
+    const int64_t *arc_row, *node_row;                   // [count + 1]: running sums of m and n
+    const uint64_t *workspace;                           // [count]: running sums of layout_of(m + 2n, n + 1).bytes
+    const int32_t *source, *target, *inc_start, *inc;    // every graph's, concatenated
+    const int64_t *lower, *upper, *cost, *supply;        // [arc_row[count]] three times, [node_row[count]]; null as in the view
+    const uint8_t *changed;                              // re-solve: [count], null = all
 };
 
 // ---- what the lanes share (device: all 64 lanes of the wave call these together; host: one lane, the identity)
@@ -78,6 +120,56 @@ MCF_HD inline void lanes_add_i64(int64_t *p, int64_t v)
 }
 
 MCF_HD inline const int64_t *uniform_row(const int64_t *base, int64_t stride, int64_t i) { return base ? base + i * stride : nullptr; }
+MCF_HD inline int64_t *output_row(int64_t *base, int64_t offset) { return base ? base + offset : nullptr; }
+// o: where a solve writes, c + solution rows + lists: what a validation reads; either may be absent
+MCF_HD inline InstanceView uniform_view(const UniformProblem &p, const UniformOutputs *o, int64_t i, unsigned char *slab)
+{
+    InstanceView v{};
+    v.i = i; v.n = p.n; v.m = p.m; v.supply_type = p.supply_type; v.trace_cap = p.trace_cap;
+    v.source = p.source; v.target = p.target;
+    v.lower = uniform_row(p.lower, p.lower_stride, i); v.upper = uniform_row(p.upper, p.upper_stride, i);
+    v.cost = uniform_row(p.cost, p.cost_stride, i); v.supply = uniform_row(p.supply, p.supply_stride, i);
+    v.workspace = (uint64_t)i * p.stride; v.trace = (uint64_t)i * (uint64_t)p.trace_cap;
+    v.home = slab ? slab + v.workspace : nullptr;
+    if (o) {
+        v.flows = output_row(o->flows, i * (int64_t)p.m); v.potentials = output_row(o->potentials, i * (int64_t)p.n);
+        v.trace_row = o->trace ? o->trace + i * (int64_t)p.trace_cap : nullptr;
+    }
+    return v;
+}
+MCF_HD inline InstanceView uniform_check_view(const UniformProblem &p, const int32_t *inc_start, const int32_t *inc, const int64_t *flows, const int64_t *potentials, int64_t i)
+{
+    InstanceView v = uniform_view(p, nullptr, i, nullptr);
+    v.inc_start = inc_start; v.inc = inc;
+    v.check_flows = flows + i * (int64_t)p.m; v.check_potentials = potentials + i * (int64_t)p.n;
+    return v;
+}
+// the tables say where everything of instance i lies; *tmpl = the index of its graph's slot template
+MCF_HD inline InstanceView ragged_view(const RaggedProblem &r, const UniformOutputs *o, int64_t i, unsigned char *slab, int32_t *tmpl)
+{
+    const RaggedGraph &g = r.graphs[r.graph_of[i]];
+    const int64_t arcs = r.arc_row[i], nodes = r.node_row[i];
+    InstanceView v{};
+    v.i = i; v.n = g.n; v.m = g.m; v.supply_type = r.supply_type; v.trace_cap = r.trace_cap;
+    v.source = r.source + g.ends; v.target = r.target + g.ends;
+    v.inc_start = r.inc_start + g.inc_start; v.inc = r.inc + g.inc;
+    v.lower = r.lower ? r.lower + arcs : nullptr; v.upper = r.upper ? r.upper + arcs : nullptr;
+    v.cost = r.cost ? r.cost + arcs : nullptr; v.supply = r.supply ? r.supply + nodes : nullptr;
+    if (slab) { v.workspace = r.workspace[i]; v.home = slab + v.workspace; }
+    v.trace = (uint64_t)i * (uint64_t)r.trace_cap;
+    if (o) {
+        v.flows = output_row(o->flows, arcs); v.potentials = output_row(o->potentials, nodes);
+        v.trace_row = o->trace ? o->trace + i * (int64_t)r.trace_cap : nullptr;
+    }
+    if (tmpl) *tmpl = g.tmpl;
+    return v;
+}
+MCF_HD inline InstanceView ragged_check_view(const RaggedProblem &r, const int64_t *flows, const int64_t *potentials, int64_t i)
+{
+    InstanceView v = ragged_view(r, nullptr, i, nullptr, nullptr);
+    v.check_flows = flows + r.arc_row[i]; v.check_potentials = potentials + r.node_row[i];
+    return v;
+}
 MCF_HD inline int64_t uniform_upper(const int64_t *upper, int e) { return !upper || upper[e] == MCF_INF_CAP ? kInf : upper[e]; }       // core_set_problem
 MCF_HD inline int64_t uniform_art_cost(const int64_t *cost, int n, int m, int lane, int lanes)     // art_cost_of
 {
@@ -90,27 +182,27 @@ MCF_HD inline int64_t uniform_art_cost(const int64_t *cost, int n, int m, int la
     return (lanes_max_i64(biggest) + 1) * (int64_t)n;
 }
 // the slot of instance i at the start of a solve: the handle's template, placed
-MCF_HD inline void uniform_place_slot(BatchSlot &slot, const BatchSlot &tmpl, const UniformProblem &p, int64_t i, int32_t all_arcs, int32_t run)
+MCF_HD inline void uniform_place_slot(BatchSlot &slot, const BatchSlot &tmpl, const InstanceView &p, int32_t all_arcs, int32_t run)
 {
     slot = tmpl;
     slot.all_arcs = all_arcs;
-    slot.workspace = (uint64_t)i * p.stride;
-    slot.trace = (uint64_t)i * (uint64_t)p.trace_cap;
+    slot.workspace = p.workspace;
+    slot.trace = p.trace;
     slot.run = run;
 }
 
-// ---- core_begin for instance i on its workspace `home`.  The slot says afterwards whether there is anything to run.
-MCF_HD inline void uniform_begin(const UniformProblem &p, int64_t i, const BatchSlot &tmpl, BatchSlot &slot, unsigned char *home, int lane, int lanes)
+// ---- core_begin for the instance p on its workspace.  The slot says afterwards whether there is anything to run.
+MCF_HD inline void uniform_begin(const InstanceView &p, const BatchSlot &tmpl, BatchSlot &slot, int lane, int lanes)
 {
     const int n = p.n, m = p.m, root = n;
-    const int64_t *const lower = uniform_row(p.lower, p.lower_stride, i), *const upper = uniform_row(p.upper, p.upper_stride, i);
-    const int64_t *const cost = uniform_row(p.cost, p.cost_stride, i), *const supply = uniform_row(p.supply, p.supply_stride, i);
+    unsigned char *const home = p.home;
+    const int64_t *const lower = p.lower, *const upper = p.upper, *const cost = p.cost, *const supply = p.supply;
     // NS.cs:227-231
     bool inverted = false;
     for (int e = lane; e < m; e += lanes) inverted |= uniform_upper(upper, e) < (lower ? lower[e] : 0);
     if (lanes_any(inverted)) {
         lanes_sync();
-        if (lane == 0) uniform_place_slot(slot, tmpl, p, i, m + n, kBatchByBounds);
+        if (lane == 0) uniform_place_slot(slot, tmpl, p, m + n, kBatchByBounds);
         return;
     }
     // to_standard_form.  The supplies are not part of the workspace and all_arcs -- with it, where every array lies -- is known only once they
@@ -202,20 +294,21 @@ MCF_HD inline void uniform_begin(const UniformProblem &p, int64_t i, const Batch
     if (lane == 0) {
         par[root] = -1; par_arc[root] = -1; nxt[root] = n > 0 ? 0 : root; prv[root] = n > 0 ? n - 1 : root;
         sub[root] = n + 1; fin[root] = n - 1; par_dir[root] = 0; pi[root] = 0;
-        uniform_place_slot(slot, tmpl, p, i, all_arcs, kBatchRunning);
+        uniform_place_slot(slot, tmpl, p, all_arcs, kBatchRunning);
     }
     lanes_sync();
 }
 
 // ---- finish_instance + core_finish + core_total_cost for instance i, into the caller's rows.  The flows in the workspace stay in standard
 // form: the lower bounds are added into the output row only, so a re-solve goes on from the workspace as it is.
-MCF_HD inline void uniform_finish(const UniformProblem &p, const UniformOutputs &o, int64_t i, const BatchSlot &slot, const unsigned char *home,
-                                  const int32_t *traces, int lane, int lanes)
+MCF_HD inline void uniform_finish(const InstanceView &p, const UniformOutputs &o, const BatchSlot &slot, const int32_t *traces, int lane, int lanes)
 {
     const int n = p.n, m = p.m;
+    const int64_t i = p.i;
+    const unsigned char *const home = p.home;
     const Layout l = layout_of((uint32_t)slot.all_arcs, (uint32_t)n + 1u);
     const int64_t *const flow = (const int64_t *)(home + l.flow), *const pi = (const int64_t *)(home + l.pi), *const cost = (const int64_t *)(home + l.cost);
-    const int64_t *const lower = uniform_row(p.lower, p.lower_stride, i);
+    const int64_t *const lower = p.lower;
     int32_t status = MCF_NOT_SOLVED;                                    // the pivot limit
     switch (slot.run) {
     case kBatchNoEntering: {
@@ -232,7 +325,7 @@ MCF_HD inline void uniform_finish(const UniformProblem &p, const UniformOutputs 
     const int64_t pivots = slot.run == kBatchByBounds ? 0 : slot.pivots;
     const bool optimal = status == MCF_OPTIMAL;
     uint64_t total = 0;
-    int64_t *const flows = o.flows ? o.flows + i * (int64_t)m : nullptr, *const potentials = o.potentials ? o.potentials + i * (int64_t)n : nullptr;
+    int64_t *const flows = p.flows, *const potentials = p.potentials;
     for (int e = lane; e < m; e += lanes) {
         const int64_t f = optimal ? (int64_t)((uint64_t)flow[e] + (uint64_t)(lower ? lower[e] : 0)) : 0;      // NS.cs:364-388
         if (optimal) total += (uint64_t)f * (uint64_t)cost[e];                                                // NS.cs:459-464, wrapping
@@ -241,9 +334,9 @@ MCF_HD inline void uniform_finish(const UniformProblem &p, const UniformOutputs 
     total = lanes_sum_u64(total);
     if (potentials)
         for (int v = lane; v < n; v += lanes) potentials[v] = optimal ? pi[v] : 0;
-    if (o.trace) {
+    if (p.trace_row) {
         const int64_t cap = p.trace_cap, len = pivots < cap ? pivots : cap;
-        int32_t *const row = o.trace + i * cap;
+        int32_t *const row = p.trace_row;
         for (int64_t k = lane; k < cap; k += lanes) row[k] = k < len ? traces[slot.trace + (uint64_t)k] : 0;
     }
     if (lane == 0) {
@@ -254,9 +347,10 @@ MCF_HD inline void uniform_finish(const UniformProblem &p, const UniformOutputs 
 }
 
 // ---- prepare_resolve for instance i with the costs in p.  Warm as there: the last solve ended Optimal with no flow on an artificial arc.
-MCF_HD inline void uniform_recost(const UniformProblem &p, int64_t i, const BatchSlot &tmpl, BatchSlot &slot, unsigned char *home, int lane, int lanes)
+MCF_HD inline void uniform_recost(const InstanceView &p, const BatchSlot &tmpl, BatchSlot &slot, int lane, int lanes)
 {
     const int n = p.n, m = p.m;
+    unsigned char *const home = p.home;
     const int32_t all_arcs = slot.all_arcs;
     bool warm = slot.run == kBatchNoEntering;
     if (warm) {
@@ -266,17 +360,17 @@ MCF_HD inline void uniform_recost(const UniformProblem &p, int64_t i, const Batc
         for (int e = m + lane; e < all_arcs; e += lanes) left |= flow[e] != 0;
         warm = !lanes_any(left);
     }
-    if (!warm) { uniform_begin(p, i, tmpl, slot, home, lane, lanes); return; }
+    if (!warm) { uniform_begin(p, tmpl, slot, lane, lanes); return; }
     // core_recost: cost[0, m), art_cost as to_standard_form derives it, the artificial arcs; the root links keep 0
     const Layout l = layout_of((uint32_t)all_arcs, (uint32_t)n + 1u);
     int64_t *const cost_w = (int64_t *)(home + l.cost);
-    const int64_t *const cost = uniform_row(p.cost, p.cost_stride, i);
+    const int64_t *const cost = p.cost;
     const int64_t art_cost = uniform_art_cost(cost, n, m, lane, lanes);
     for (int e = lane; e < m; e += lanes) cost_w[e] = cost ? cost[e] : 0;
     for (int e = m + n + lane; e < all_arcs; e += lanes) cost_w[e] = art_cost;
     lanes_sync();
     if (lane == 0) {                    // the rule starts as at a cold start, the count and the trace start again
-        uniform_place_slot(slot, tmpl, p, i, all_arcs, kBatchRunning);
+        uniform_place_slot(slot, tmpl, p, all_arcs, kBatchRunning);
         slot.reprice = 1;
     }
     lanes_sync();
@@ -285,17 +379,10 @@ MCF_HD inline void uniform_recost(const UniformProblem &p, int64_t i, const Batc
 // ---- the reference's SolutionValidator (SolutionValidator.cs, restated in oracle/validator.py) for instance i of a solution that lies in
 // rows as uniform_finish writes them.  It belongs to no solve: it reads the problem, the solution and the handle's incidence lists, and
 // writes the instance's row of answers; slab and slots are not its business.
-// The incidence lists (built once per handle, mcf_ubatch_create): node v's entries are inc[inc_start[v], inc_start[v + 1]), each
+// The incidence lists (built once per graph at create): node v's entries are inc[inc_start[v], inc_start[v + 1]), each
 // arc << 1 | (v is the arc's target), arc ids ascending.  With them a node sums its own arcs: no atomics, no scratch per instance.
 // Every sum is an unsigned 64-bit add (C# long, unchecked), so one lane and 64 lanes give the same bits; `first` is a minimum.
-struct UniformCheck {
-    const int32_t *inc_start, *inc;                      // [n + 1], [2m]
-    const int32_t *status;                               // the solution: [count], [count], [count * m], [count * n]
-    const int64_t *total_cost, *flows, *potentials;
-    int32_t *valid, *errors, *first;                     // the answers, any may be null: [count], [count * MCF_VAL_KINDS] twice
-    int64_t *objective, *dual_cost;                      // [count]
-    int64_t *summary;                                    // [2]: invalid instances, the lowest invalid index (INT64_MAX while there is none)
-};
+
 // the two words every invalid instance meets on
 MCF_HD inline void uniform_report_invalid(int64_t *summary, int64_t i)
 {
@@ -308,9 +395,10 @@ MCF_HD inline void uniform_report_invalid(int64_t *summary, int64_t i)
 #endif
 }
 
-MCF_HD inline void uniform_validate(const UniformProblem &p, const UniformCheck &c, int64_t i, int lane, int lanes)
+MCF_HD inline void uniform_validate(const InstanceView &p, const UniformCheck &c, int lane, int lanes)
 {
     const int n = p.n, m = p.m;
+    const int64_t i = p.i;
     uint64_t count[MCF_VAL_KINDS] = {};                  // this lane's share, folded below
     uint32_t first[MCF_VAL_KINDS];
     for (int k = 0; k < MCF_VAL_KINDS; ++k) first[k] = kNoPos;              // (int32_t)kNoPos = -1
@@ -320,9 +408,8 @@ MCF_HD inline void uniform_validate(const UniformProblem &p, const UniformCheck 
         count[MCF_VAL_STATUS] = 1;
         first[MCF_VAL_STATUS] = 0;
     } else {
-        const int64_t *const lower = uniform_row(p.lower, p.lower_stride, i), *const upper = uniform_row(p.upper, p.upper_stride, i);
-        const int64_t *const cost = uniform_row(p.cost, p.cost_stride, i), *const supply = uniform_row(p.supply, p.supply_stride, i);
-        const int64_t *const flow = c.flows + i * (int64_t)m, *const pi = c.potentials + i * (int64_t)n;
+        const int64_t *const lower = p.lower, *const upper = p.upper, *const cost = p.cost, *const supply = p.supply;
+        const int64_t *const flow = p.check_flows, *const pi = p.check_potentials;
         const auto note = [&](int kind, bool failed, int id) {
             if (!failed) return;
             ++count[kind];
@@ -343,8 +430,8 @@ MCF_HD inline void uniform_validate(const UniformProblem &p, const UniformCheck 
         // the nodes: :62-99, :193-227 and the node terms of :276-331.  One lane per node walks the node's own arcs.
         for (int v = lane; v < n; v += lanes) {
             uint64_t net = 0, adj = 0;                   // flow out - flow in; the lower bounds' shift of the supply
-            for (int32_t k = c.inc_start[v]; k < c.inc_start[v + 1]; ++k) {
-                const int32_t entry = c.inc[k], e = entry >> 1;
+            for (int32_t k = p.inc_start[v]; k < p.inc_start[v + 1]; ++k) {
+                const int32_t entry = p.inc[k], e = entry >> 1;
                 const bool incoming = (entry & 1) != 0;
                 const uint64_t f = (uint64_t)flow[e], lo = lower ? (uint64_t)lower[e] : 0;
                 net = incoming ? net - f : net + f;

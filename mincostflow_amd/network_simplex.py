@@ -624,6 +624,213 @@ class UniformBatch:
         return self._validate(L.lib().mcf_ubatch_validate_on_host, result_or_rows, cost, supply, lower, upper, supply_type, numpy_only=True)
 
 
+class RaggedResult(UniformResult):
+    """What RaggedBatch.solve / .resolve return: UniformResult's fields with flows and potentials FLAT -- instance i's arcs are
+    flows[arc_rows[i]:arc_rows[i + 1]], its nodes potentials[node_rows[i]:node_rows[i + 1]]; arcs(i) and nodes(i) return those slices
+    (views, numpy or tensor like the arrays).  status, pivots and total_cost are [count], trace is [count, record_trace]."""
+    __slots__ = ("arc_rows", "node_rows")
+
+    def __init__(self, arc_rows, node_rows, **arrays):
+        super().__init__(**arrays)
+        self.arc_rows, self.node_rows = arc_rows, node_rows
+
+    def arcs(self, i: int):
+        return self.flows[int(self.arc_rows[i]):int(self.arc_rows[i + 1])]
+
+    def nodes(self, i: int):
+        return self.potentials[int(self.node_rows[i]):int(self.node_rows[i + 1])]
+
+
+class RaggedBatch:
+    """Instances of a SET of graphs in one handle, solved on the device from arrays that already are there (mcf_rbatch_*, DESIGN.md 3.14
+    "Ragged batch").  graphs: a sequence of (node_count, source, target); graph_of[i] names the graph of instance i (None: instance i is
+    graph i).  Problem data and results are flat: cost, lower, upper and flows have arc_rows[-1] elements, instance i's at
+    [arc_rows[i], arc_rows[i + 1]); supply and potentials have node_rows[-1], likewise.  Calls take either flat numpy arrays (copied up
+    and down) or flat torch tensors on the handle's device (read and written in place) -- never a mix; int64, contiguous.  Results equal
+    BatchSolver's for the same instances bit for bit, and UniformBatch's where there is one graph.  run_on_host() / rerun_on_host() /
+    validate_on_host() are test hooks (numpy only)."""
+
+    def __init__(self, graphs, graph_of=None, rule=PivotRule.BlockSearch, pivot_limit=0, record_trace=0, device=0, pivots_per_launch=0,
+                 semantics=L.SEM_PLAIN, flags=0):
+        graphs = [(int(n), _i32(src), _i32(tgt)) for n, src, tgt in graphs]
+        for _, src, tgt in graphs:
+            if src.ndim != 1 or src.shape != tgt.shape:
+                raise ValueError("source and target must be one-dimensional and of equal length")
+        self.graph_count, self.device, self.record_trace = len(graphs), int(device), int(record_trace)
+        node_count = np.array([n for n, _, _ in graphs], np.int32)
+        arc_start = np.zeros(self.graph_count + 1, np.int64)
+        np.cumsum([len(src) for _, src, _ in graphs], out=arc_start[1:])
+        source = np.concatenate([src for _, src, _ in graphs]) if graphs else np.zeros(0, np.int32)
+        target = np.concatenate([tgt for _, _, tgt in graphs]) if graphs else np.zeros(0, np.int32)
+        of = None if graph_of is None else _i32(graph_of)
+        if of is not None and of.ndim != 1:
+            raise ValueError("graph_of must be one-dimensional")
+        self.count = self.graph_count if of is None else int(of.shape[0])
+        self._h = C.c_void_p()
+        self._last = None               # the last RaggedResult: a masked resolve() starts from its rows
+        d = L.RBatchDesc(self.device, int(rule), int(semantics), 0, int(pivot_limit), int(pivots_per_launch), self.record_trace, int(flags),
+                         self.graph_count, self.count, node_count.ctypes.data, arc_start.ctypes.data, source.ctypes.data, target.ctypes.data,
+                         None if of is None else of.ctypes.data)
+        L.check(L.lib().mcf_rbatch_create(C.byref(self._h), C.byref(d)))
+        self.arc_rows, self.node_rows = np.zeros(self.count + 1, np.int64), np.zeros(self.count + 1, np.int64)
+        L.check(L.lib().mcf_rbatch_get_rows(self._h, self.arc_rows.ctypes.data, self.node_rows.ctypes.data))
+        self.arc_total, self.node_total = int(self.arc_rows[-1]), int(self.node_rows[-1])
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            L.lib().mcf_rbatch_destroy(h)
+            self._h = None
+
+    def __len__(self):
+        return self.count
+
+    # ---- one flat input: (pointer, the object that keeps the memory alive); the checks of UniformBatch._input
+    def _input(self, a, name, length, tensors, dtype="int64"):
+        if a is None:
+            return None, None
+        if tensors:
+            import torch
+            if not _is_tensor(a):
+                raise ValueError(f"{name}: numpy arrays and tensors cannot be mixed in one call")
+            if a.device.type != "cuda" or (a.device.index or 0) != self.device:
+                raise ValueError(f"{name}: tensor on {a.device}, the batch runs on cuda:{self.device}")
+            if a.dtype != getattr(torch, dtype):
+                raise ValueError(f"{name}: dtype {a.dtype}, expected {dtype}")
+            shape, strides = tuple(a.shape), tuple(a.stride())
+        else:
+            if _is_tensor(a):
+                raise ValueError(f"{name}: numpy arrays and tensors cannot be mixed in one call")
+            if not isinstance(a, np.ndarray):
+                a = np.asarray(a, dtype)
+            if a.dtype != np.dtype(dtype):
+                raise ValueError(f"{name}: dtype {a.dtype}, expected {dtype}")
+            shape, strides = a.shape, tuple(s // a.itemsize for s in a.strides)
+        if shape != (length,):
+            raise ValueError(f"{name}: shape {tuple(shape)}, expected ({length},)")
+        if length > 1 and strides[-1] != 1:
+            raise ValueError(f"{name}: not contiguous")
+        return (a.data_ptr() if tensors else a.ctypes.data), a
+
+    def _lengths(self):
+        return (("cost", self.arc_total), ("supply", self.node_total), ("lower", self.arc_total), ("upper", self.arc_total))
+
+    def _outputs(self, tensors, like):
+        """Fresh rows, or copies of `like` (the last result) for a call that does not write every row."""
+        sizes = {"": (self.count,), "m": (self.arc_total,), "n": (self.node_total,), "t": (self.count, self.record_trace)}
+        out = {}
+        for name, dtype, dim in UniformResult.FIELDS:
+            if like is not None:
+                prev = getattr(like, name)
+                if _is_tensor(prev) != tensors:
+                    raise ValueError("a masked resolve() continues the last result: numpy arrays and tensors cannot be mixed")
+                out[name] = prev.clone() if tensors else prev.copy()
+            elif tensors:
+                import torch
+                out[name] = torch.empty(sizes[dim], dtype=getattr(torch, dtype), device=f"cuda:{self.device}")
+            else:
+                out[name] = np.empty(sizes[dim], dtype)
+        return out
+
+    def _call(self, fn, cost, supply, lower, upper, supply_type, changed=None, masked=False, numpy_only=False):
+        given = [a for a in (cost, supply, lower, upper, changed) if a is not None]
+        tensors = any(_is_tensor(a) for a in given)
+        if tensors and numpy_only:
+            raise ValueError("the host hooks take numpy arrays")
+        keep = []
+        io = L.RBatchIo()
+        io.memory, io.supply_type = (L.MEM_DEVICE if tensors else L.MEM_HOST), int(supply_type)
+        for (name, length), a in zip(self._lengths(), (cost, supply, lower, upper)):
+            ptr, obj = self._input(a, name, length, tensors)
+            keep.append(obj)
+            setattr(io, name, ptr)
+        if changed is not None:
+            if not tensors and not isinstance(changed, np.ndarray):
+                changed = np.asarray(changed)
+            if not tensors and changed.dtype == np.bool_:
+                changed = changed.view(np.uint8)
+            if tensors:
+                import torch
+                if changed.dtype == torch.bool:
+                    changed = changed.view(torch.uint8)
+            ptr, obj = self._input(changed, "changed", self.count, tensors, dtype="uint8")
+            keep.append(obj)
+            io.changed = ptr
+        if masked and changed is not None and self._last is None:
+            raise McfError(L.ERR_STATE, "resolve: the batch has not been solved")
+        out = self._outputs(tensors, self._last if masked and changed is not None else None)
+        for name, arr in out.items():
+            setattr(io, name, arr.data_ptr() if tensors else arr.ctypes.data)
+        L.check(fn(self._h, C.byref(io)))
+        self._last = RaggedResult(self.arc_rows, self.node_rows, **out)
+        return self._last
+
+    def solve(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> RaggedResult:
+        """A fresh solve of every instance; may be repeated with other supplies, bounds or costs."""
+        return self._call(L.lib().mcf_rbatch_solve, cost, supply, lower, upper, supply_type)
+
+    def resolve(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq, changed=None) -> RaggedResult:
+        """New costs for the instances `changed` marks ([count] bool / uint8, None = all), as UniformBatch.resolve."""
+        return self._call(L.lib().mcf_rbatch_resolve, cost, supply, lower, upper, supply_type, changed, masked=True)
+
+    def run_on_host(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> RaggedResult:
+        """Test hook: solve() with one lane on the CPU.  numpy only."""
+        return self._call(L.lib().mcf_rbatch_run_on_host, cost, supply, lower, upper, supply_type, numpy_only=True)
+
+    def rerun_on_host(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq, changed=None) -> RaggedResult:
+        """Test hook: resolve() with one lane on the CPU.  numpy only."""
+        return self._call(L.lib().mcf_rbatch_rerun_on_host, cost, supply, lower, upper, supply_type, changed, masked=True, numpy_only=True)
+
+    def stats(self) -> dict:
+        st = L.UBatchStats(); L.check(L.lib().mcf_rbatch_get_stats(self._h, C.byref(st))); return st.as_dict()
+
+    # ---- validation: the solution's rows where they lie
+    def _validate(self, fn, rows, cost, supply, lower, upper, supply_type, numpy_only=False):
+        names = tuple(name for name, _, _ in UniformBatch.SOLUTION_ROWS)
+        if isinstance(rows, dict):
+            rows = tuple(rows[name] for name in names)
+        elif hasattr(rows, "status"):
+            rows = tuple(getattr(rows, name) for name in names)
+        rows = tuple(rows)
+        if len(rows) != 4 or any(r is None for r in rows):
+            raise ValueError("the solution to check is status, total_cost, flows and potentials: a RaggedResult, a dict or the four rows")
+        tensors = any(_is_tensor(a) for a in (*rows, cost, supply, lower, upper) if a is not None)
+        if tensors and numpy_only:
+            raise ValueError("the host hooks take numpy arrays")
+        keep = []
+        io = L.RBatchCheckIo()
+        io.memory, io.supply_type = (L.MEM_DEVICE if tensors else L.MEM_HOST), int(supply_type)
+        for (name, length), a in zip(self._lengths(), (cost, supply, lower, upper)):
+            ptr, obj = self._input(a, name, length, tensors)
+            keep.append(obj)
+            setattr(io, name, ptr)
+        for (name, dtype, _), length, a in zip(UniformBatch.SOLUTION_ROWS, (self.count, self.count, self.arc_total, self.node_total), rows):
+            ptr, obj = self._input(a, name, length, tensors, dtype=dtype)
+            keep.append(obj)
+            setattr(io, name, ptr)
+        out = {}
+        for name, dtype, per_kind in UniformValidation.FIELDS:
+            shape = (self.count, len(L.VALIDATION_KINDS)) if per_kind else (self.count,)
+            if tensors:
+                import torch
+                out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{self.device}")
+            else:
+                out[name] = np.empty(shape, dtype)
+            setattr(io, name, out[name].data_ptr() if tensors else out[name].ctypes.data)
+        summary = L.UBatchCheckSummary()
+        L.check(fn(self._h, C.byref(io), C.byref(summary)))
+        return UniformValidation(summary.as_dict(), **out)
+
+    def validate(self, result_or_rows, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> UniformValidation:
+        """The reference's SolutionValidator for every instance in one launch, each against its own graph.  result_or_rows: a
+        RaggedResult, or status, total_cost, flows and potentials (flat) as a dict or in that order.  supply_type may also be 2."""
+        return self._validate(L.lib().mcf_rbatch_validate, result_or_rows, cost, supply, lower, upper, supply_type)
+
+    def validate_on_host(self, result_or_rows, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> UniformValidation:
+        """Test hook: validate() with one lane on the CPU.  numpy only."""
+        return self._validate(L.lib().mcf_rbatch_validate_on_host, result_or_rows, cost, supply, lower, upper, supply_type, numpy_only=True)
+
+
 def block_config(**kw) -> "L.BlockConfig":
     """new OptimizationConfig { ... } (OptimizationTypes.cs:24-38): the defaults, with the given fields replaced."""
     c = L.BlockConfig()
