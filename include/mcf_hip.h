@@ -745,7 +745,8 @@ typedef struct mcf_ubatch_desc {
     int32_t pivot_rule;
     int32_t semantics;
     int32_t reserved;
-    int64_t pivot_limit;
+    int64_t pivot_limit;          /* The output rows of an instance stopped by it (MCF_NOT_SOLVED) are zero.  Its trace row holds `limit`
+                                     entries (min(limit, trace_capacity)), zeros behind them.  A re-solve of a stopped instance starts cold. */
     int32_t pivots_per_launch;
     int32_t trace_capacity;
     int32_t flags;
@@ -861,7 +862,9 @@ typedef struct mcf_rbatch_desc {
     int32_t pivot_rule;
     int32_t semantics;
     int32_t reserved;
-    int64_t pivot_limit;          /* 0 = the default of each instance's own graph */
+    int64_t pivot_limit;          /* 0 = the default of each instance's own graph.  The output rows of an instance stopped by it
+                                     (MCF_NOT_SOLVED) are zero.  Its trace row holds `limit` entries (min(limit, trace_capacity)), zeros
+                                     behind them.  A re-solve of a stopped instance starts cold. */
     int32_t pivots_per_launch;
     int32_t trace_capacity;
     int32_t flags;

@@ -16,12 +16,14 @@ from mincostflow_amd import _lib as L
 from oracle import ns_oracle as O
 
 from test_batch_host import LDS_LIMITS, bound_infeasible
-from test_ragged_host import (HOST, Mix, assert_equals_oracle, check_absent_arrays, check_an_unused_graph, check_empty_handles, check_families, check_graph_of,
-                              check_nothing_runs, check_null_outputs, check_one_graph, check_resolve_chain, check_short_and_absent_traces, check_siblings, check_solve_twice,
-                              check_unchanged_costs_and_mask, corrupted_mix_cases, family_mix, footprints, mix_costs, resolve_mix, small_mix, solved_mix_cases,
-                              validate_on_host)
-from test_uniform_gpu import padded
-from test_uniform_host import ALL_RULES, Topology, answer_of, assert_equals_answers, assert_rows_equal, family, stride_of, to_numpy
+from test_ragged_host import (HOST, MIX_RESOLVE_LIMIT, Mix, assert_equals_oracle, check_absent_arrays, check_an_unused_graph, check_empty_handles, check_families,
+                              check_families_under_a_limit, check_graph_of, check_nothing_runs, check_null_outputs, check_one_graph, check_resolve_chain,
+                              check_resolve_chain_under_a_limit, check_short_and_absent_traces, check_siblings, check_solve_twice, check_unchanged_costs_and_mask,
+                              check_unchanged_costs_and_mask_under_a_limit_mix, check_validation_under_a_limit, corrupted_mix_cases, family_mix, footprints, mix_costs,
+                              resolve_mix, small_mix, solved_mix_cases, validate_on_host)
+from test_uniform_gpu import LAUNCH_BUDGETS, padded
+from test_uniform_host import (ALL_RULES, LIMIT_RUNS, NOT_SOLVED, STEPS, SUPPLY_TYPES, Rows, Topology, answer_of, assert_equals_answers, assert_rows_equal, family, limited, stride_of,
+                               to_numpy)
 from test_uniform_validate_host import OUT_NAMES, assert_same_rows
 
 pytestmark = pytest.mark.gpu
@@ -97,11 +99,16 @@ def mixed_tiers():
     return Mix(tops)
 
 
+@functools.lru_cache(maxsize=None)
+def mixed_answers(stype):
+    return tuple(answer_of(p, O.RULE_BLOCK, stype, trace_cap=MIXED_TRACE) for p in mixed_tiers().problems())
+
+
 def test_lds_and_global_tier_in_one_handle():
     mix = mixed_tiers()
     a = mix.arrays()
     for stype in (O.GEQ, O.LEQ):
-        answers = [answer_of(p, O.RULE_BLOCK, stype, trace_cap=MIXED_TRACE) for p in mix.problems()]
+        answers = mixed_answers(stype)
         assert any(x[1] > 0 for x, (g, _) in zip(answers, mix.order) if g in (0, 2)) and any(x[1] > 0 for x, (g, _) in zip(answers, mix.order) if g not in (0, 2))
         hook = HOST[0](mix.handle(record_trace=MIXED_TRACE), a, stype)
         assert_equals_answers(mix.split(hook), answers, "hook", trace_cap=MIXED_TRACE)
@@ -288,3 +295,103 @@ def test_bad_tensors_are_refused_before_anything_is_launched():
     for wrong in ((r.status.to(torch.int64),) + rows[1:], rows[:2] + (r.flows[:-1],) + rows[3:], rows[:3] + (r.potentials.cpu(),), rows[:3]):
         with pytest.raises(ValueError):
             h.validate(wrong, **good)
+
+
+# ---- 7: the pivot limit (references, floors and checkers of test_uniform_host.py and test_ragged_host.py)
+@functools.lru_cache(maxsize=None)
+def limited_hook_rows(name, rule, stype, k, cap):
+    mix = family_mix(name)
+    return to_numpy(HOST[0](mix.handle(rule, pivot_limit=k, record_trace=cap), mix.arrays(), stype))
+
+
+@pytest.mark.parametrize("k, cap", LIMIT_RUNS)
+@pytest.mark.parametrize("rule", ALL_RULES)
+@pytest.mark.parametrize("name", ["A", "B"])
+def test_families_under_a_pivot_limit_on_the_device(name, rule, k, cap):
+    mix = family_mix(name)
+    for budget in LAUNCH_BUDGETS[k]:
+        for stype, answers, h, r, st in check_families_under_a_limit(DEVICE[0], name, rule, k, cap, pivots_per_launch=budget):
+            what = (name, stype, k, cap, budget)
+            hook = Rows(limited_hook_rows(name, rule, stype, k, cap))
+            assert all(v.is_cuda for v in (r.status, r.pivots, r.total_cost, r.flows, r.potentials, r.trace))
+            assert_rows_equal(r, hook, what)
+            assert st["lds_instances"] == mix.count and st["global_instances"] == 0 and st["lds_bytes_max"] == max(stride_of(t) for t in mix.tops), st
+            if budget == k:
+                assert any(a[0] == NOT_SOLVED for a in answers) and st["launches"] >= 2, st           # the refused search is a launch of its own
+            if budget in (0, k):
+                numpy_in = DEVICE_NUMPY[0](mix.handle(rule, pivot_limit=k, record_trace=cap, pivots_per_launch=budget), mix.arrays(), stype)
+                assert isinstance(numpy_in.flows, np.ndarray) and isinstance(numpy_in.trace, np.ndarray)
+                assert_rows_equal(numpy_in, hook, (what, "numpy in"))
+
+
+def test_lds_and_global_tier_under_a_pivot_limit():
+    """One pivot_limit goes into every graph's slot template: instances of both tiers are stopped in the same round."""
+    mix = mixed_tiers()
+    a = mix.arrays()
+    k = 16
+    for stype in SUPPLY_TYPES:
+        answers = [limited(x, k) for x in mixed_answers(stype)]
+        stopped = [sum(x[0] == NOT_SOLVED for x, (g, _) in zip(answers, mix.order) if (g in (0, 2)) == in_global) for in_global in (True, False)]
+        print(f"mixed tiers under a pivot limit of {k}, supply type {stype}: stopped in the global tier {stopped[0]}, in LDS {stopped[1]}")
+        assert min(stopped) >= 1, stopped
+        hook = HOST[0](mix.handle(pivot_limit=k, record_trace=MIXED_TRACE), a, stype)
+        assert_equals_answers(mix.split(hook), answers, "hook", trace_cap=MIXED_TRACE)
+        for kw in ({}, dict(pivots_per_launch=11)):
+            h = mix.handle(pivot_limit=k, record_trace=MIXED_TRACE, **kw)
+            assert_rows_equal(DEVICE[0](h, a, stype), hook, (stype, kw))
+            st = h.stats()
+            assert st["lds_instances"] == 3 * MIXED_PER and st["global_instances"] == 2 * MIXED_PER and st["workspace_bytes"] == footprints(mix), st
+            assert st["total_pivots"] == sum(x[1] for x in answers), st
+
+
+@pytest.mark.parametrize("rule", ALL_RULES)
+def test_resolve_chain_under_a_pivot_limit_on_the_device(rule):
+    check_resolve_chain_under_a_limit(*DEVICE, rule)
+
+
+@functools.lru_cache(maxsize=None)
+def limited_hook_chain(rule, stype):
+    """the hook's rows under the rule's limit of MIX_RESOLVE_LIMIT: after the first solve and after each of the four re-solves"""
+    mix = resolve_mix()
+    a = mix.arrays()
+    h = mix.handle(rule, pivot_limit=MIX_RESOLVE_LIMIT[rule])
+    return (to_numpy(HOST[0](h, a, stype)),) + tuple(to_numpy(HOST[1](h, dict(a, cost=mix_costs(mix, step)), stype)) for step in range(STEPS))
+
+
+@pytest.mark.parametrize("slices", [0, 3])
+@pytest.mark.parametrize("rule", ALL_RULES)
+def test_resolve_chain_and_mask_under_a_pivot_limit_equal_the_hook(rule, slices):
+    mix = resolve_mix()
+    a = mix.arrays()
+    for stype in SUPPLY_TYPES:
+        rows = limited_hook_chain(rule, stype)
+        h = mix.handle(rule, pivot_limit=MIX_RESOLVE_LIMIT[rule], pivots_per_launch=slices)
+        assert_rows_equal(DEVICE[0](h, a, stype), Rows(rows[0]), (stype, "first solve"))
+        for step in range(STEPS):
+            assert_rows_equal(DEVICE[1](h, dict(a, cost=mix_costs(mix, step)), stype), Rows(rows[step + 1]), (stype, step))
+    check_unchanged_costs_and_mask_under_a_limit_mix(*DEVICE, rule, pivots_per_launch=slices)
+
+
+@pytest.mark.parametrize("rule", ALL_RULES)
+def test_the_device_equals_the_hook_in_any_order_under_a_pivot_limit(rule):
+    """The orders of test_the_device_equals_the_hook_in_any_order: slab and slots of limit-stopped instances move whole between host and device."""
+    mix = resolve_mix()
+    a = mix.arrays()
+    costs = [dict(a, cost=mix_costs(mix, step)) for step in range(2)]
+    for stype in SUPPLY_TYPES:
+        rows = limited_hook_chain(rule, stype)
+        assert (rows[0]["status"] == NOT_SOLVED).any() and (rows[1]["status"] == NOT_SOLVED).any()
+        for order in ((DEVICE[0], DEVICE[1], DEVICE[1]), (HOST[0], DEVICE[1], DEVICE[1]), (DEVICE[0], HOST[1], DEVICE[1]), (DEVICE_NUMPY[0], DEVICE[1], HOST[1])):
+            h = mix.handle(rule, pivot_limit=MIX_RESOLVE_LIMIT[rule])
+            assert_rows_equal(order[0](h, a, stype), Rows(rows[0]), stype)
+            assert_rows_equal(order[1](h, costs[0], stype), Rows(rows[1]), stype)
+            assert_rows_equal(order[2](h, costs[1], stype), Rows(rows[2]), stype)
+
+
+def test_validation_of_limit_stopped_results_as_they_lie():
+    """solve()'s tensors under a limit go into validate() as they are: 16 bytes up (the two summary words) and 16 down."""
+    def validate(h, r, a, stype):
+        assert r.status.is_cuda and r.flows.is_cuda
+        return h.validate(r, supply_type=stype, **tensors(a))
+    for c, v in check_validation_under_a_limit(DEVICE[0], validate, DEVICE[1]):
+        assert v.valid.is_cuda and v.errors.is_cuda and v.summary["bytes_up"] == 16 and v.summary["bytes_down"] == 16, v.summary

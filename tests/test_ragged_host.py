@@ -22,8 +22,9 @@ from oracle import validator as V
 
 from test_batch_host import ROOT, RULES, bound_infeasible
 from test_batch_resolve_host import cold_reference, with_cost
-from test_uniform_host import (ALL_RULES, KINDS, STEPS, SUPPLY_TYPES, TRACE, answer_of, assert_equals_answers, assert_matches_cold, assert_rows_equal, batch_answers,
-                               draw_topology, family, reference, resolve_family, step_costs, stride_of, to_numpy, uniform_of)
+from test_uniform_host import (ALL_RULES, CLASSES, KINDS, LIMIT_RUNS, NOT_SOLVED, STEPS, SUPPLY_TYPES, TRACE, answer_of, assert_equals_answers, assert_limit_floors,
+                               assert_matches_cold, assert_rows_equal, batch_answers, check_chain_under_a_limit, check_unchanged_costs_and_mask_under_a_limit, draw_topology,
+                               family, limited_chain, limited_reference, limited_validation_cases, reference, resolve_family, step_costs, stride_of, to_numpy, uniform_of)
 from test_uniform_validate_host import EQ, OUT_NAMES, PROBLEM_NAMES, ROW_NAMES, corrupted_cases, rows_of, solved_cases
 
 
@@ -728,3 +729,115 @@ def test_solve_without_a_device_leaves_the_handle_as_it_was():
     v = mix.handle()
     assert_rows_equal(v.run_on_host(**a), before)
     assert_rows_equal(h.rerun_on_host(**dict(a, cost=cost)), v.rerun_on_host(**dict(a, cost=cost)))
+
+
+# ---- 7: the pivot limit (the references, floors and checkers of test_uniform_host.py on one handle)
+def check_families_under_a_limit(run, name, rule, k, cap, **kw):
+    """run(handle, arrays, stype) -> result.  Every row against the oracle's limited answer; the limit changes nothing of the statistics
+    but the pivots."""
+    mix = family_mix(name)
+    a = mix.arrays()
+    for stype in SUPPLY_TYPES:
+        answers = mix.pick(limited_reference(name, rule, stype, k))
+        h = mix.handle(rule, pivot_limit=k, record_trace=cap, **kw)
+        r = run(h, a, stype)
+        assert to_numpy(r)["trace"].shape == (mix.count, cap)
+        assert_equals_answers(mix.split(r), answers, (f"family {name}, supply type {stype}, limit {k}, trace capacity {cap}", kw), trace_cap=cap)
+        st = h.stats()
+        assert st["instances"] == mix.count and st["total_pivots"] == sum(x[1] for x in answers) and st["workspace_bytes"] == footprints(mix), st
+        yield stype, answers, h, r, st
+
+
+@pytest.mark.parametrize("k, cap", LIMIT_RUNS)
+@pytest.mark.parametrize("rule", ALL_RULES)
+@pytest.mark.parametrize("name", ["A", "B"])
+def test_families_under_a_pivot_limit_on_the_host(name, rule, k, cap):
+    for stype, answers, h, r, st in check_families_under_a_limit(HOST[0], name, rule, k, cap):
+        assert st["launches"] == st["bytes_up"] == st["bytes_down"] == st["lds_instances"] == st["global_instances"] == 0
+
+
+MIX_RESOLVE_LIMIT = {O.RULE_BLOCK: 16, O.RULE_BEST: 10, O.RULE_FIRST: 23}     # per rule the smallest limit in 8..64 at which mix_limited_chain_reference() meets every class
+
+
+def mix_cost_rows(mix, step):
+    cost = mix_costs(mix, step)
+    return cost, tuple(cost[lo:hi] for lo, hi in zip(mix.arc_rows[:-1], mix.arc_rows[1:]))
+
+
+@functools.lru_cache(maxsize=None)
+def mix_limited_chain_reference(rule):
+    """per supply type: (the flat cost array and the cost rows of every step, limited_chain() of resolve_mix()).  Asserted on the references
+    alone: summed over both supply types every class of CLASSES occurs."""
+    mix = resolve_mix()
+    k = MIX_RESOLVE_LIMIT[rule]
+    costs = tuple(mix_cost_rows(mix, step) for step in range(STEPS))
+    out = tuple((costs, limited_chain(mix.problems(), stype, rule, k, [rows for _, rows in costs])) for stype in SUPPLY_TYPES)
+    classes = sum(ref[2] for _, ref in out)
+    print(f"ragged re-solve chain under a pivot limit of {k}, rule {rule}: {dict(zip(CLASSES, classes.tolist()))}")
+    assert classes.min() >= 1, classes
+    return out
+
+
+def check_resolve_chain_under_a_limit(first, again, rule, **kw):
+    mix = resolve_mix()
+    a = mix.arrays()
+    k = MIX_RESOLVE_LIMIT[rule]
+    for stype, (costs, ref) in zip(SUPPLY_TYPES, mix_limited_chain_reference(rule)):
+        h = mix.handle(rule, pivot_limit=k, **kw)
+        check_chain_under_a_limit(ref, mix.problems(), stype, k, [rows for _, rows in costs], lambda: first(h, a, stype), lambda step: again(h, dict(a, cost=costs[step][0]), stype),
+                                  lambda: first(mix.handle(rule, pivot_limit=k, **kw), dict(a, cost=costs[-1][0]), stype), mix.split, (f"supply type {stype}", kw))
+
+
+@pytest.mark.parametrize("rule", ALL_RULES)
+def test_resolve_chain_under_a_pivot_limit_on_the_host(rule):
+    check_resolve_chain_under_a_limit(*HOST, rule)
+
+
+def check_unchanged_costs_and_mask_under_a_limit_mix(first, again, rule, **kw):
+    mix = resolve_mix()
+    a = mix.arrays()
+    k = MIX_RESOLVE_LIMIT[rule]
+    seen = [check_unchanged_costs_and_mask_under_a_limit(
+        mix.problems(), stype, rule, k, lambda: mix.handle(rule, pivot_limit=k, **kw), lambda h: first(h, a, stype),
+        lambda h, cost, changed: again(h, a if cost is None else dict(a, cost=cost), stype, **({} if changed is None else dict(changed=changed))),
+        mix_costs(mix, 1), mix.split, (f"supply type {stype}", kw)) for stype in SUPPLY_TYPES]
+    assert_limit_floors(seen, f"ragged handle under a pivot limit of {k}, rule {rule}")
+
+
+@pytest.mark.parametrize("rule", ALL_RULES)
+def test_unchanged_costs_and_the_changed_mask_under_a_pivot_limit_on_the_host(rule):
+    check_unchanged_costs_and_mask_under_a_limit_mix(*HOST, rule)
+
+
+@functools.lru_cache(maxsize=None)
+def limited_mix_cases(name, k=16):
+    """per supply type: limited_validation_cases() of the whole family -- the oracle's answers under the limit as solution rows -- interleaved"""
+    cases = limited_validation_cases(name, k)
+    G = len(family(name))
+    return tuple(MixCase(cases[j * G:(j + 1) * G]) for j in range(2))
+
+
+def check_validation_under_a_limit(first, validate, again, name="B", k=16):
+    """first(h, arrays, stype), validate(h, result, arrays, stype), again(h, arrays, stype).  The result goes into the validation as it lies;
+    the re-solve behind it equals one that no validation preceded.  Yields (case, validation)."""
+    mix = family_mix(name)
+    a = mix.arrays()
+    for c in limited_mix_cases(name, k):
+        h, w = mix.handle(pivot_limit=k), mix.handle(pivot_limit=k)
+        r = first(h, a, c.stype)
+        rows = to_numpy(r)
+        for field in ROW_NAMES:                         # the rows under validation are this handle's own
+            assert np.array_equal(rows[field], c.rows[field]), (c.label, field)
+        assert (rows["status"] == NOT_SOLVED).sum() >= 10
+        stats = h.stats()
+        v = validate(h, r, a, c.stype)
+        assert_equals_oracle(v, c)
+        assert h.stats() == stats
+        yield c, v
+        HOST[0](w, a, c.stype)
+        assert_rows_equal(again(h, a, c.stype), HOST[1](w, a, c.stype), (c.label, "the validation left the state alone"))
+
+
+def test_validation_of_limit_stopped_results_on_the_host():
+    for c, v in check_validation_under_a_limit(HOST[0], lambda h, r, a, stype: h.validate_on_host(r, supply_type=stype, **a), HOST[1]):
+        assert isinstance(v.valid, np.ndarray) and v.summary["bytes_up"] == v.summary["bytes_down"] == 0

@@ -15,9 +15,11 @@ from mincostflow_amd import _lib as L
 from oracle import ns_oracle as O
 
 from test_batch_host import LDS_LIMITS, PADDED_NODES, bound_infeasible
-from test_uniform_host import (ALL_RULES, HOST, PER, STEPS, SUPPLY_TYPES, Topology, answer_of, assert_equals_answers, assert_rows_equal, check_changed_mask,
-                               check_empty_batch, check_nothing_runs, check_resolve_chain, check_short_and_absent_traces, check_solve_twice,
-                               check_unchanged_costs, family, picked, reference, resolve_family, step_costs, stride_of, to_numpy, uniform_of)
+from test_uniform_host import (ALL_RULES, HOST, LIMIT_RUNS, NOT_SOLVED, PER, RESOLVE_LIMIT, STEPS, SUPPLY_TYPES, Topology, answer_of, assert_equals_answers, assert_rows_equal,
+                               check_changed_mask, check_empty_batch, check_families_under_a_limit, check_nothing_runs, check_resolve_chain,
+                               check_resolve_chain_under_a_limit, check_short_and_absent_traces, check_solve_twice, check_unchanged_costs,
+                               check_unchanged_costs_and_mask_under_a_limit_uniform, check_validation_under_a_limit, family, limited, picked, reference, resolve_family,
+                               step_costs, stride_of, to_numpy, uniform_of)
 
 pytestmark = pytest.mark.gpu
 SLOT_BYTES = 104 + C.sizeof(L.BlockConfig)           # BatchSlot of csrc/batch_layout.hip.h, which has no padding
@@ -253,3 +255,109 @@ def test_bad_tensors_are_refused_before_anything_is_launched():
     shared = uniform_of(t, O.RULE_BLOCK).run_on_host(**dict(a, cost=a["cost"][2]))
     assert_rows_equal(u.solve(**dict(good, cost=good["cost"][2])), shared)
     assert_rows_equal(u.solve(**dict(good, cost=good["cost"][2].expand(t.count, t.m))), shared)
+
+
+# ---- 7: the pivot limit.  On the device the search that meets the limit may be the first thing of a launch of its own, on a slot read
+# back with pivots == limit, and the entering arc it found lies in the device's trace buffer behind the `limit` kept ones
+LAUNCH_BUDGETS = {1: (0, 1), 16: (0, 1, 4, 16, 17)}      # pivots_per_launch per limit: the default, 1, a divisor of the limit, the limit, one more
+
+
+@functools.lru_cache(maxsize=None)
+def limited_hook_results(name, rule, stype, k, cap):
+    return tuple(to_numpy(uniform_of(t, rule, pivot_limit=k, record_trace=cap).run_on_host(supply_type=stype, **t.arrays())) for t in family(name))
+
+
+@pytest.mark.parametrize("k, cap", LIMIT_RUNS)
+@pytest.mark.parametrize("rule", ALL_RULES)
+@pytest.mark.parametrize("name", ["A", "B"])
+def test_families_under_a_pivot_limit_on_the_device(name, rule, k, cap):
+    tops = family(name)
+    for budget in LAUNCH_BUDGETS[k]:
+        for t, stype, answers, u, r, st in check_families_under_a_limit(DEVICE[0], name, rule, k, cap, pivots_per_launch=budget):
+            what = (name, t.n, t.m, stype, k, cap, budget)
+            hook = Rows(limited_hook_results(name, rule, stype, k, cap)[tops.index(t)])
+            assert all(v.is_cuda for v in (r.status, r.pivots, r.total_cost, r.flows, r.potentials, r.trace))
+            assert_rows_equal(r, hook, what)
+            assert st["lds_instances"] == t.count and st["global_instances"] == 0 and st["lds_bytes_max"] == (stride_of(t) if st["launches"] else 0), st
+            if budget == k and any(a[0] == NOT_SOLVED for a in answers):
+                assert st["launches"] >= 2, st          # the refused search is a launch of its own
+            if budget in (0, k):
+                numpy_in = DEVICE_NUMPY[0](uniform_of(t, rule, pivot_limit=k, record_trace=cap, pivots_per_launch=budget), t.arrays(), stype)
+                assert isinstance(numpy_in.flows, np.ndarray) and isinstance(numpy_in.trace, np.ndarray)
+                assert_rows_equal(numpy_in, hook, (what, "numpy in"))
+
+
+def test_global_tier_under_a_pivot_limit():
+    rule, k, cap = O.RULE_BLOCK, 16, 32
+    stopped = finished = 0
+    for q, stype, answers in padded_family(rule):
+        want = tuple(limited(a, k) for a in answers)
+        stopped += sum(a[0] == NOT_SOLVED for a in want)
+        finished += sum(a[0] != NOT_SOLVED and a[1] > 0 for a in want)
+        hook = uniform_of(q, rule, pivot_limit=k, record_trace=cap).run_on_host(supply_type=stype, **q.arrays())
+        assert_equals_answers(hook, want, "hook", trace_cap=cap)
+        for budget in LAUNCH_BUDGETS[k]:
+            u = uniform_of(q, rule, pivot_limit=k, record_trace=cap, pivots_per_launch=budget)
+            r = u.solve(supply_type=stype, **tensors(q.arrays()))
+            assert_rows_equal(r, hook, (budget, stype))
+            st = u.stats()
+            assert st["global_instances"] == q.count and st["lds_instances"] == 0 and st["lds_bytes_max"] == 0, st
+            assert st["workspace_bytes"] == q.count * stride_of(q) and st["total_pivots"] == sum(a[1] for a in want)
+            assert budget != k or not any(a[0] == NOT_SOLVED for a in want) or st["launches"] >= 2, st
+    print(f"padded family under a pivot limit of {k}: stopped {stopped}, finished after pivots {finished}")
+    assert stopped >= 2 and finished >= 2, (stopped, finished)
+
+
+@pytest.mark.parametrize("rule", ALL_RULES)
+def test_resolve_chain_under_a_pivot_limit_on_the_device(rule):
+    check_resolve_chain_under_a_limit(*DEVICE, rule)
+
+
+@functools.lru_cache(maxsize=None)
+def limited_hook_chain(rule):
+    """hook_chain() under the rule's limit of RESOLVE_LIMIT"""
+    out = []
+    for j, (t, stype) in enumerate(resolve_family()):
+        a = t.arrays()
+        u = uniform_of(t, rule, pivot_limit=RESOLVE_LIMIT[rule])
+        rows = [to_numpy(HOST[0](u, a, stype))]
+        for step in range(STEPS):
+            rows.append(to_numpy(HOST[1](u, dict(a, cost=step_costs(t, j, step)), stype)))
+        out.append(tuple(rows))
+    return tuple(out)
+
+
+@pytest.mark.parametrize("slices", [0, 3])
+@pytest.mark.parametrize("rule", ALL_RULES)
+def test_resolve_chain_and_mask_under_a_pivot_limit_equal_the_hook(rule, slices):
+    for j, ((t, stype), rows) in enumerate(zip(resolve_family(), limited_hook_chain(rule))):
+        a = t.arrays()
+        u = uniform_of(t, rule, pivot_limit=RESOLVE_LIMIT[rule], pivots_per_launch=slices)
+        assert_rows_equal(DEVICE[0](u, a, stype), Rows(rows[0]), (j, "first solve"))
+        for step in range(STEPS):
+            assert_rows_equal(DEVICE[1](u, dict(a, cost=step_costs(t, j, step)), stype), Rows(rows[step + 1]), (j, step))
+    check_unchanged_costs_and_mask_under_a_limit_uniform(*DEVICE, rule, pivots_per_launch=slices)
+
+
+@pytest.mark.parametrize("rule", ALL_RULES)
+def test_the_device_equals_the_hook_in_any_order_under_a_pivot_limit(rule):
+    """The orders of test_the_device_equals_the_hook_in_any_order: slab and slots of limit-stopped instances move whole between host and device."""
+    orders = ((DEVICE[0], DEVICE[1], DEVICE[1]), (HOST[0], DEVICE[1], DEVICE[1]), (DEVICE[0], HOST[1], DEVICE[1]), (DEVICE_NUMPY[0], DEVICE[1], HOST[1]))
+    for j, ((t, stype), rows) in enumerate(zip(resolve_family(), limited_hook_chain(rule))):
+        a = t.arrays()
+        assert (rows[0]["status"] == NOT_SOLVED).any() and (rows[1]["status"] == NOT_SOLVED).any()
+        for order in orders:
+            u = uniform_of(t, rule, pivot_limit=RESOLVE_LIMIT[rule])
+            assert_rows_equal(order[0](u, a, stype), Rows(rows[0]), j)
+            assert_rows_equal(order[1](u, dict(a, cost=step_costs(t, j, 0)), stype), Rows(rows[1]), j)
+            assert_rows_equal(order[2](u, dict(a, cost=step_costs(t, j, 1)), stype), Rows(rows[2]), j)
+
+
+@pytest.mark.parametrize("name", ["A", "B"])
+def test_validation_of_limit_stopped_results_as_they_lie(name):
+    """solve()'s tensors under a limit go into validate() as they are: 16 bytes up (the two summary words) and 16 down."""
+    def validate(u, r, a, stype):
+        assert r.status.is_cuda and r.flows.is_cuda
+        return u.validate(r, supply_type=stype, **tensors(a))
+    for c, v in check_validation_under_a_limit(DEVICE[0], validate, DEVICE[1], name):
+        assert v.valid.is_cuda and v.errors.is_cuda and v.summary["bytes_up"] == 16 and v.summary["bytes_down"] == 16, v.summary

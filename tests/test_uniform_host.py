@@ -19,7 +19,7 @@ from oracle import ns_oracle as O
 from adversarial import BIG_COST, random_problem
 from helpers import validate_solution
 from test_batch_host import ROOT, RULES, bound_infeasible, footprint, oracle_of
-from test_batch_resolve_host import cold_reference, new_cost, with_cost
+from test_batch_resolve_host import cold_reference, new_cost, warm_after, with_cost
 
 ALL_RULES = [O.RULE_BLOCK, O.RULE_BEST, O.RULE_FIRST]
 SUPPLY_TYPES = [O.GEQ, O.LEQ]
@@ -522,17 +522,23 @@ def resolve_reference(rule):
     return tuple(out)
 
 
+def assert_row_matches_cold(r, k, p, stype, ref, what):
+    """Row k of to_numpy()'s rows against cold_reference()'s tuple for the problem p (the new costs in it)."""
+    st, total, exact = ref
+    assert r["status"][k] == st, (what, k, r["status"][k], st)
+    if st == O.OPTIMAL:
+        assert r["total_cost"][k] == total, (what, k)
+        if exact is None:
+            assert validate_solution(p, r["flows"][k], r["potentials"][k], stype) == total, (what, k)
+        else:                       # cold although Optimal: the oracle's own solve, bit for bit
+            assert np.array_equal(r["flows"][k], exact[0]) and np.array_equal(r["potentials"][k], exact[1]) and r["pivots"][k] == exact[2], (what, k)
+            assert np.array_equal(r["trace"][k][:exact[2]], exact[3]), (what, k)
+
+
 def assert_matches_cold(r, t, stype, cost, refs, what):
     r = to_numpy(r)
-    for k, (p, (st, total, exact)) in enumerate(zip(t.variants, refs)):
-        assert r["status"][k] == st, (what, k, r["status"][k], st)
-        if st == O.OPTIMAL:
-            assert r["total_cost"][k] == total, (what, k)
-            if exact is None:
-                assert validate_solution(with_cost(p, cost[k]), r["flows"][k], r["potentials"][k], stype) == total, (what, k)
-            else:                       # cold although Optimal: the oracle's own solve, bit for bit
-                assert np.array_equal(r["flows"][k], exact[0]) and np.array_equal(r["potentials"][k], exact[1]) and r["pivots"][k] == exact[2], (what, k)
-                assert np.array_equal(r["trace"][k][:exact[2]], exact[3]), (what, k)
+    for k, (p, ref) in enumerate(zip(t.variants, refs)):
+        assert_row_matches_cold(r, k, with_cost(p, cost[k]), stype, ref, what)
 
 
 def check_resolve_chain(first, again, rule, **kw):
@@ -633,3 +639,297 @@ def test_solve_without_a_device_leaves_the_handle_as_it_was():
     v = uniform_of(t, O.RULE_BLOCK)
     assert_rows_equal(v.run_on_host(supply_type=stype, **a), before)
     assert_rows_equal(u.rerun_on_host(supply_type=stype, **dict(a, cost=cost)), v.rerun_on_host(supply_type=stype, **dict(a, cost=cost)))
+
+
+# ---- 13: the pivot limit.  An instance that reaches it reports NotSolved with zero rows, `limit` pivots and `limit` trace entries
+NOT_SOLVED = M.SolverStatus.NotSolved
+LIMIT_RUNS = ((1, TRACE), (16, TRACE), (16, 16), (16, 17), (16, 8))      # (pivot_limit, record_trace): at 17 the entering arc of the refused pivot would lie inside the row
+LONG_TRACE = 1 << 15     # for the oracle's solves with the re-solves' costs
+
+
+class Rows:
+    """to_numpy()'s dict with the attributes of a result, so that the checkers take it."""
+
+    def __init__(self, rows):
+        self.__dict__.update(rows)
+
+
+def limited(answer, k):
+    """answer_of()'s tuple under a pivot limit of k, derived from the unlimited answer: a solve of at most k pivots is not touched by the
+    limit; a longer one stops behind its first k pivots and reports nothing else."""
+    if answer[1] <= k:
+        return answer
+    return NOT_SOLVED, k, answer[2][:k], None, None, None
+
+
+@functools.lru_cache(maxsize=None)
+def limited_reference(name, rule, stype, k):
+    """reference() under a pivot limit of k.  The floors are asserted here, on the oracle's answers alone: at least 10 instances are stopped,
+    and at k = 16 at least 10 finish below the limit."""
+    refs = reference(name, rule, stype)
+    pivots = np.array([a[1] for row in refs for a in row])
+    stopped, below, exact = int((pivots > k).sum()), int((pivots < k).sum()), int((pivots == k).sum())
+    print(f"family {name}, rule {rule}, supply type {stype}, pivot limit {k}: stopped {stopped}, finished below the limit {below}, solves of exactly {k} pivots {exact}")
+    assert stopped >= 10 and (k != 16 or below >= 10), (stopped, below)
+    return tuple(tuple(limited(a, k) for a in row) for row in refs)
+
+
+def test_some_solves_take_exactly_the_limit():
+    """Such a solve meets the limit's test with pivots == limit and must end as if there were no limit: limited() leaves it as it is."""
+    for k in sorted({k for k, _ in LIMIT_RUNS}):
+        exact = {(name, rule, stype): sum(a[1] == k for row in reference(name, rule, stype) for a in row) for name in "AB" for rule in ALL_RULES for stype in SUPPLY_TYPES}
+        print(f"solves of exactly {k} pivots by (family, rule, supply type): {exact}")
+        assert sum(exact.values()) >= 1, k
+
+
+def check_families_under_a_limit(run, name, rule, k, cap, **kw):
+    """run(handle, arrays, stype) -> result.  Every row against the oracle's limited answer; the limit changes nothing of the statistics
+    but the pivots."""
+    for stype in SUPPLY_TYPES:
+        for t, answers in zip(family(name), limited_reference(name, rule, stype, k)):
+            u = uniform_of(t, rule, pivot_limit=k, record_trace=cap, **kw)
+            r = run(u, t.arrays(), stype)
+            assert to_numpy(r)["trace"].shape == (t.count, cap)
+            assert_equals_answers(r, answers, (f"family {name}, n {t.n}, m {t.m}, supply type {stype}, limit {k}, trace capacity {cap}", kw), trace_cap=cap)
+            st = u.stats()
+            assert st["instances"] == t.count and st["total_pivots"] == sum(a[1] for a in answers) and st["workspace_bytes"] == t.count * stride_of(t), st
+            yield t, stype, answers, u, r, st
+
+
+@pytest.mark.parametrize("k, cap", LIMIT_RUNS)
+@pytest.mark.parametrize("rule", ALL_RULES)
+@pytest.mark.parametrize("name", ["A", "B"])
+def test_families_under_a_pivot_limit_on_the_host(name, rule, k, cap):
+    for t, stype, answers, u, r, st in check_families_under_a_limit(HOST[0], name, rule, k, cap):
+        assert st["launches"] == st["bytes_up"] == st["bytes_down"] == st["lds_instances"] == st["global_instances"] == 0
+
+
+# ---- 14: re-solves round the limit
+RESOLVE_LIMIT = {O.RULE_BLOCK: 21, O.RULE_BEST: 11, O.RULE_FIRST: 23}     # per rule the smallest limit in 8..64 at which limited_chain_reference() meets every class
+CLASSES = ("stopped -> stopped", "stopped -> finished", "Optimal -> warm and finished", "Optimal -> warm and stopped", "after warm and stopped -> finished",
+           "after warm and stopped -> stopped")
+
+
+def same_answer(a, b):
+    return a[0] == b[0] and a[1] == b[1] and np.array_equal(a[2], b[2]) and (a[0] != O.OPTIMAL or (a[3] == b[3] and np.array_equal(a[4], b[4]) and np.array_equal(a[5], b[5])))
+
+
+def limited_chain(problems, stype, rule, k, costs):
+    """The reference of a chain of re-solves under a pivot limit of k; costs[step][i] is the cost row of instance i.
+    -> (first, steps, classes).  first: the limited oracle answers of the first solve.  steps: per step `expected` (an answer per instance),
+    `warm` (re-solved from the kept basis: the last solve ended Optimal and conserves flow), `stopped`, and `cold` (cold_reference() of the
+    new costs).  classes: how often each of CLASSES occurs.
+    A row re-solved cold -- its last solve was stopped, Infeasible or left a surplus -- has the oracle's cold solve under the limit as its
+    reference.  No oracle knows a warm pivot path: there the reference is BatchSolver (set_costs + rerun_on_host, the same limit), and
+    wherever the oracle speaks BatchSolver is asserted to say the same."""
+    n = len(problems)
+    b = M.BatchSolver(rule=RULES[rule], pivot_limit=k, record_trace=TRACE)
+    for p in problems:
+        b.add(p, supply_type=stype)
+    b.run_on_host()
+    last = batch_answers(b, n)
+    first = tuple(limited(answer_of(p, rule, stype), k) for p in problems)
+    assert all(same_answer(x, y) for x, y in zip(last, first))
+    conserves = [warm_after(cold_reference(p, stype, rule)) for p in problems]
+    after_warm_and_stopped = np.zeros(n, bool)
+    classes = np.zeros(len(CLASSES), np.int64)
+    steps = []
+    for cost in costs:
+        for i in range(n):
+            b.set_costs(i, cost[i])
+        b.rerun_on_host()
+        now = batch_answers(b, n)
+        was_stopped = np.array([a[0] == NOT_SOLVED for a in last])
+        warm = np.array([a[0] == O.OPTIMAL and c for a, c in zip(last, conserves)])
+        stopped = np.array([a[0] == NOT_SOLVED for a in now])
+        cold = tuple(cold_reference(with_cost(p, cost[i]), stype, rule) for i, p in enumerate(problems))
+        expected = list(now)
+        for i in np.flatnonzero(~warm):
+            expected[i] = limited(answer_of(with_cost(problems[i], cost[i]), rule, stype, trace_cap=LONG_TRACE), k)
+            assert same_answer(now[i], expected[i]), i
+        assert all(a[1] <= k for a in now) and all(a[1] == k for a in now if a[0] == NOT_SOLVED)
+        classes += [(was_stopped & stopped).sum(), (was_stopped & ~stopped).sum(), (warm & ~stopped).sum(), (warm & stopped).sum(),
+                    (after_warm_and_stopped & ~stopped).sum(), (after_warm_and_stopped & stopped).sum()]
+        steps.append(dict(expected=tuple(expected), warm=warm, stopped=stopped, cold=cold))
+        after_warm_and_stopped = warm & stopped
+        last, conserves = now, [warm_after(ref) for ref in cold]
+    return first, tuple(steps), classes
+
+
+def check_chain_under_a_limit(ref, problems, stype, k, costs, solve, resolve, fresh, rows_of, what):
+    """solve() / resolve(step) / fresh() -> result: the handle's first solve, its re-solve with costs[step], and a fresh handle's first solve
+    with the last costs.  rows_of(result): the rows per instance."""
+    first, steps, _ = ref
+    assert_equals_answers(rows_of(solve()), first, (what, "first solve"))
+    for step, s in enumerate(steps):
+        r = rows_of(resolve(step))
+        assert_equals_answers(r, s["expected"], (what, "step", step))
+        rows = to_numpy(r)
+        for i in np.flatnonzero(s["warm"]):
+            if s["stopped"][i]:                 # its workspace holds a half-repriced basis now: the next step starts it cold
+                assert rows["status"][i] == NOT_SOLVED and rows["pivots"][i] == k, (what, step, i)
+            else:
+                assert rows["pivots"][i] <= k, (what, step, i)
+                assert_row_matches_cold(rows, i, with_cost(problems[i], costs[step][i]), stype, s["cold"][i], (what, "step", step))
+    # what the last step re-solved cold is what a fresh handle gives for the same costs
+    again = to_numpy(rows_of(fresh()))
+    cold = np.flatnonzero(~steps[-1]["warm"])
+    assert len(cold)
+    for name in rows:
+        for i in cold:
+            assert np.array_equal(rows[name][i], again[name][i]), (what, "fresh handle", name, i)
+
+
+@functools.lru_cache(maxsize=None)
+def limited_chain_reference(rule):
+    """per graph of resolve_family(): (the cost rows of every step, limited_chain()).  Asserted on the references alone: over the graphs
+    every class of CLASSES occurs."""
+    k = RESOLVE_LIMIT[rule]
+    out = []
+    classes = np.zeros(len(CLASSES), np.int64)
+    for j, (t, stype) in enumerate(resolve_family()):
+        costs = tuple(step_costs(t, j, step) for step in range(STEPS))
+        ref = limited_chain(t.variants, stype, rule, k, costs)
+        classes += ref[2]
+        out.append((costs, ref))
+    print(f"re-solve chain under a pivot limit of {k}, rule {rule}: {dict(zip(CLASSES, classes.tolist()))}")
+    assert classes.min() >= 1, classes
+    return tuple(out)
+
+
+def check_resolve_chain_under_a_limit(first, again, rule, **kw):
+    k = RESOLVE_LIMIT[rule]
+    for j, ((t, stype), (costs, ref)) in enumerate(zip(resolve_family(), limited_chain_reference(rule))):
+        a = t.arrays()
+        u = uniform_of(t, rule, pivot_limit=k, **kw)
+        check_chain_under_a_limit(ref, t.variants, stype, k, costs, lambda: first(u, a, stype), lambda step: again(u, dict(a, cost=costs[step]), stype),
+                                  lambda: first(uniform_of(t, rule, pivot_limit=k, **kw), dict(a, cost=costs[-1]), stype), lambda r: r, (f"graph {j}", kw))
+
+
+@pytest.mark.parametrize("rule", ALL_RULES)
+def test_resolve_chain_under_a_pivot_limit_on_the_host(rule):
+    check_resolve_chain_under_a_limit(*HOST, rule)
+
+
+def check_unchanged_costs_and_mask_under_a_limit(problems, stype, rule, k, make, first, again, cost, rows_of, what):
+    """make() -> a fresh handle with the limit; first(handle), again(handle, cost, changed) -> result (cost None: the first costs again).
+    -> (stopped, warm, mask) per instance, from the oracle, for the caller's floors."""
+    n = len(problems)
+    answers = [limited(answer_of(p, rule, stype), k) for p in problems]
+    stopped = np.array([a[0] == NOT_SOLVED for a in answers])
+    warm = np.array([a[0] == O.OPTIMAL and warm_after(cold_reference(p, stype, rule)) for a, p in zip(answers, problems)])
+    fields = lambda r: to_numpy(rows_of(r))
+    # unchanged costs: a stopped row starts cold and is stopped again behind the same pivots; nothing is eligible where the basis was kept
+    h = make()
+    before = fields(first(h))
+    assert_equals_answers(Rows(before), answers, what)
+    after = fields(again(h, None, None))
+    for i in range(n):
+        for name in before:
+            if warm[i] and name in ("pivots", "trace"):
+                assert not np.any(after[name][i]), (what, "unchanged costs", name, i)
+            else:
+                assert np.array_equal(after[name][i], before[name][i]), (what, "unchanged costs", name, i)
+    assert np.all(after["pivots"][stopped] == k) and np.all(after["status"][stopped] == NOT_SOLVED)
+    assert h.stats()["total_pivots"] == after["pivots"].sum()
+    # the mask: rows it leaves out keep their last outputs and are not counted, the marked ones equal an unmasked re-solve's
+    mask = np.arange(n) % 3 != 1
+    h, v = make(), make()
+    first(h)
+    first(v)
+    masked, whole = fields(again(h, cost, mask)), fields(again(v, cost, None))
+    assert h.stats()["total_pivots"] == masked["pivots"][mask].sum()
+    for i in range(n):
+        for name in before:
+            assert np.array_equal(masked[name][i], (whole if mask[i] else before)[name][i]), (what, "mask", name, i)
+    # the left-out rows go on from their own last state, stopped ones included: marked alone now, with their first costs again
+    back = fields(again(h, None, ~mask))
+    assert h.stats()["total_pivots"] == back["pivots"][~mask].sum()
+    for i in range(n):
+        for name in before:
+            assert np.array_equal(back[name][i], (masked if mask[i] else after)[name][i]), (what, "mask, the rest", name, i)
+    return stopped, warm, mask
+
+
+def assert_limit_floors(seen, what):
+    """seen: check_unchanged_costs_and_mask_under_a_limit()'s returns.  Stopped rows lie on both sides of the mask, and a row is kept warm."""
+    inside, outside, warm = (sum(int(f(*s).sum()) for s in seen) for f in (lambda st, w, m: st & m, lambda st, w, m: st & ~m, lambda st, w, m: w))
+    print(f"{what}: stopped rows marked {inside}, stopped rows left out {outside}, rows kept warm {warm}")
+    assert inside >= 1 and outside >= 1 and warm >= 1, (inside, outside, warm)
+
+
+def check_unchanged_costs_and_mask_under_a_limit_uniform(first, again, rule, **kw):
+    k = RESOLVE_LIMIT[rule]
+    seen = []
+    for j, (t, stype) in enumerate(resolve_family()):
+        a = t.arrays()
+        seen.append(check_unchanged_costs_and_mask_under_a_limit(
+            t.variants, stype, rule, k, lambda: uniform_of(t, rule, pivot_limit=k, **kw), lambda u: first(u, a, stype),
+            lambda u, cost, changed: again(u, a if cost is None else dict(a, cost=cost), stype, **({} if changed is None else dict(changed=changed))),
+            step_costs(t, j, 1), lambda r: r, (f"graph {j}", kw)))
+    assert_limit_floors(seen, f"uniform handles under a pivot limit of {k}, rule {rule}")
+
+
+@pytest.mark.parametrize("rule", ALL_RULES)
+def test_unchanged_costs_and_the_changed_mask_under_a_pivot_limit_on_the_host(rule):
+    check_unchanged_costs_and_mask_under_a_limit_uniform(*HOST, rule)
+
+
+# ---- 15: the validation of limit-stopped results
+def rows_from_answers(answers, m, n):
+    """The four rows a validation reads, as the answers say them: zeros where an instance is not Optimal."""
+    zeros = lambda length: np.zeros(length, np.int64)
+    return dict(status=np.array([a[0] for a in answers], np.int32), total_cost=np.array([a[3] or 0 for a in answers], np.int64),
+                flows=np.stack([zeros(m) if a[4] is None else np.asarray(a[4], np.int64) for a in answers]),
+                potentials=np.stack([zeros(n) if a[5] is None else np.asarray(a[5], np.int64) for a in answers]))
+
+
+@functools.lru_cache(maxsize=None)
+def limited_validation_cases(name, k=16):
+    """per supply type, per graph of family(name): the Case of test_uniform_validate_host.py whose solution rows are the oracle's answers under
+    a pivot limit of k (Block Search), its expected rows the oracle validator's.  Asserted on those alone: a stopped row has the status error
+    and nothing else, objective and dual cost 0."""
+    from test_uniform_validate_host import KINDS, Case, K
+    out = []
+    stopped = 0
+    for stype in SUPPLY_TYPES:
+        for t, answers in zip(family(name), limited_reference(name, O.RULE_BLOCK, stype, k)):
+            c = Case(f"family {name}, n {t.n}, m {t.m}, supply type {stype}, pivot limit {k}", t.n, t.src, t.tgt, t.arrays(), rows_from_answers(answers, t.m, t.n), stype)
+            bad = c.rows["status"] == NOT_SOLVED
+            stopped += int(bad.sum())
+            e = c.expected
+            assert np.all(e["errors"][bad, K["status"]] == 1) and np.all(e["errors"][bad].sum(axis=1) == 1) and not e["valid"][bad].any()
+            assert not e["objective"][bad].any() and not e["dual_cost"][bad].any() and e["errors"].shape[1] == len(KINDS)
+            out.append(c)
+    valid = sum(int(c.expected["valid"].sum()) for c in out)
+    print(f"family {name} under a pivot limit of {k}: stopped rows {stopped}, valid rows {valid}")
+    assert stopped >= 10 and valid >= 10, (stopped, valid)
+    return tuple(out)
+
+
+def check_validation_under_a_limit(first, validate, again, name, k=16):
+    """first(u, arrays, stype), validate(u, result, arrays, stype), again(u, arrays, stype).  The result goes into the validation as it lies;
+    the re-solve behind it equals one that no validation preceded.  Yields (case, validation)."""
+    from test_uniform_validate_host import ROW_NAMES, assert_equals_oracle
+    tops = family(name)
+    for j, c in enumerate(limited_validation_cases(name, k)):
+        t = tops[j % len(tops)]
+        a = t.arrays()
+        u, w = uniform_of(t, O.RULE_BLOCK, pivot_limit=k), uniform_of(t, O.RULE_BLOCK, pivot_limit=k)
+        r = first(u, a, c.stype)
+        rows = to_numpy(r)
+        for field in ROW_NAMES:                         # the rows under validation are this handle's own
+            assert np.array_equal(rows[field], c.rows[field]), (c.label, field)
+        stats = u.stats()
+        v = validate(u, r, a, c.stype)
+        assert_equals_oracle(v, c)
+        assert u.stats() == stats
+        yield c, v
+        HOST[0](w, a, c.stype)
+        assert_rows_equal(again(u, a, c.stype), HOST[1](w, a, c.stype), (c.label, "the validation left the state alone"))
+
+
+@pytest.mark.parametrize("name", ["A", "B"])
+def test_validation_of_limit_stopped_results_on_the_host(name):
+    for c, v in check_validation_under_a_limit(HOST[0], lambda u, r, a, stype: u.validate_on_host(r, supply_type=stype, **a), HOST[1], name):
+        assert isinstance(v.valid, np.ndarray) and v.summary["bytes_up"] == v.summary["bytes_down"] == 0
