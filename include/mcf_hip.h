@@ -523,6 +523,10 @@ MCF_API int mcf_ns_finish(mcf_ns *s, int32_t *status);           /* CheckFeasibi
  * the nodes in thread order whenever the walks since the last relabelling covered that many times the node count).  Fills the metrics'
  * tree_update_us / potential_update_us / loop_us (setup_us = time spent relabelling).  Node ids are the caller's again when it returns. */
 MCF_API int mcf_ns_replay(mcf_ns *s, const int32_t *arcs, int64_t count, int32_t smaller_side, double renumber_every);
+/* debug aid: after the first relabelling the driver keeps one bit per node, set where the thread list leaves the id order (Thread[a] != a + 1),
+ * and its walks take their run ends from it.  Recomputes every bit from the thread list and counts the differences (0 = the bitmap is
+ * current; also 0 while there is no bitmap yet). */
+MCF_API int mcf_ns_check_thread_breaks(mcf_ns *s, int64_t *mismatches);
 /* views of the internal SoA after mcf_ns_begin (valid until destroy); sizes: arc_capacity / node_count + 1 */
 MCF_API int mcf_ns_internal(mcf_ns *s, int32_t *search_arc_num, int32_t *arc_capacity, const int32_t **source,
                             const int32_t **target, const int64_t **cost, const int8_t **state, const int64_t **pi);

@@ -321,6 +321,7 @@ SIGNATURES = {
     "mcf_ns_apply_pivot": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int32)]),
     "mcf_ns_finish": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "mcf_ns_replay": (C.c_int, [C.c_void_p, _i32p, C.c_int64, C.c_int32, C.c_double]),
+    "mcf_ns_check_thread_breaks": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "mcf_ns_internal": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_int32), _P(_P(C.c_int32)), _P(_P(C.c_int32)),
                                   _P(_P(C.c_int64)), _P(_P(C.c_int8)), _P(_P(C.c_int64))]),
     "mcf_ns_tree": (C.c_int, [C.c_void_p, _P(_P(C.c_int32)), _P(_P(C.c_int32)), _P(_P(C.c_int32)), _P(_P(C.c_int8)), _P(_P(C.c_int64)), _P(_P(C.c_int64))]),

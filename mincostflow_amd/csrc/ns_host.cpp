@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "ns_core.h"
+#include "thread_breaks.h"
 
 struct mcf_ns : mcf::NsCore {                                         // the problem, the flows and the tree: ns_core.h
     int rule = MCF_RULE_BLOCK_SEARCH;                                  // NS.cs:77
@@ -46,6 +47,9 @@ struct mcf_ns : mcf::NsCore {                                         // the pro
     int32_t st_arc[2] = {0, 0};
     int8_t st_val[2] = {0, 0};
     mcf::hvec<int32_t> follow;      // prefetch hints of shift_potentials
+    // one bit per node, set where nxt[a] != a + 1 (thread_breaks.h): empty before the first relabelling, rebuilt by every relabelling and kept
+    // current by the re-hanging from then on
+    std::vector<uint64_t> breaks;
     mcf::hvec<int32_t> moved;       // capacity n+1, the first moved_n entries are valid
     mcf::hvec<int64_t> moved_val;   // their new potentials
     int moved_n = 0;
@@ -219,53 +223,27 @@ void decide_states(mcf_ns *s)
 //    prefetches the lines it will need kWalkAhead steps from now; a stale hint costs a useless prefetch, nothing else.
 // The order of the resulting list is irrelevant to the engine (final values).
 constexpr int kWalkAhead = 8, kWalkHintMin = 48;
-constexpr double kJumpNs = 24.0;   // what a step of a walk that leaves the id order costs (a mispredicted branch and a miss; measured 23 - 25 ns)
+// What a step of a walk that leaves the id order is charged when the next relabelling is scheduled.  It was the scalar run loop's cost of a
+// jump (a mispredicted branch and then a miss, 23 - 25 ns); the walker of thread_breaks.h overlaps its jumps' misses and pays less than half of
+// that, but a jump is also one more run for the engines to take, and the budget did not follow the walk down: charged 9 ns (2.7 times the
+// budget) config 3 was 1 - 7 % slower in 6 of 6 alternations, with or without an earlier first relabelling.
+constexpr double kJumpNs = 24.0;
 constexpr int kRunsMin = 512;      // walks of this many nodes and more hand over runs of consecutive ids (after a relabelling)
 constexpr int kWalkPiece = 2048;   // a big walk hands its nodes to the engine in pieces of this size (mcf_engine_append_potential);
                                    // 1024 .. 8192 measure alike on config 3, no hand-over at all costs 0.9 us per pivot
 
-// ---- runs of consecutive ids (after a relabelling in thread order the successor of node a is a + 1 almost everywhere).  Inside a run the
-// next address does not depend on the loaded successor (the exit test is a predicted branch, not a data dependency), so the loads of
-// consecutive nodes overlap and the hardware prefetcher sees a linear stream; a jump costs one mispredicted branch and a miss: 23-25 ns on the
-// hosts measured, which is what such a walk costs -- 2 400 jumps in a walk of 40 000 nodes after some 30 000 pivots.  (Measured and dropped:
-// eight successors compared per AVX2 step, run by run or fused with the update -- 2x faster on runs of 100 nodes, 1.4-2x SLOWER on the runs of
-// 16 that the solves have: the scalar loop's one branch per node predicts better than a vector loop's exit.)
-// the nodes first .. (count of them, in thread order) move by sigma, run by run; nodes (optional) receives them; returns the number of runs
-// that ended in a jump.  `next` receives the node behind the last one visited.
-int64_t walk_runs(mcf_ns *s, int first, int count, int64_t sigma, int32_t *nodes, int *next)
+// ---- runs of consecutive ids (after a relabelling in thread order the successor of node a is a + 1 almost everywhere).  Every walk of
+// kWalkHintMin nodes and more goes through ONE walker then (mcf::BreakWalk, thread_breaks.h): the end of a run comes from the bitmap of
+// thread breaks, not from comparing each loaded successor, so no branch depends on a load of nxt; the load of the jump's target is issued
+// before the run's potentials are added, and the hints in follow[] (run start -> the run start kJumpAhead jumps later) have the misses of
+// several jumps in flight at once.  (Measured and dropped: eight successors compared per AVX2 step -- slower on the runs of 16 that the solves
+// have; the bitmap without hints, and hints on the scalar loop without the bitmap -- neither gains on a cold cache)
+mcf::BreakWalk break_walk(mcf_ns *s, int first, int64_t sigma)
 {
-    int64_t *const pi = s->pi.data();
-    const int32_t *const nxt = s->nxt.data();
-    int64_t jumps = 0;
-    int i = 0, a = first;
-    if (nodes) {
-        while (i < count) {
-            int nx;
-            do {
-                nodes[i] = a;
-                pi[a] += sigma;
-                nx = nxt[a];
-                ++i;
-                if (nx != a + 1) { ++jumps; break; }
-                ++a;
-            } while (i < count);
-            a = nx;
-        }
-    } else {
-        while (i < count) {
-            int nx;
-            do {
-                pi[a] += sigma;
-                nx = nxt[a];
-                ++i;
-                if (nx != a + 1) { ++jumps; break; }
-                ++a;
-            } while (i < count);
-            a = nx;
-        }
-    }
-    *next = a;
-    return jumps;
+    mcf::BreakWalk w;
+    w.pi = s->pi.data(); w.nxt = s->nxt.data(); w.follow = s->follow.data(); w.bits = s->breaks.data();
+    w.sigma = sigma; w.a = first;
+    return w;
 }
 
 void shift_potentials(mcf_ns *s)
@@ -299,8 +277,9 @@ void shift_potentials(mcf_ns *s)
         int64_t *const pi = s->pi.data();
         const int32_t *const nxt = s->nxt.data();
         if (s->renumbers > 0) {
-            int behind = 0;
-            s->jumps_since_renumber += walk_runs(s, first, count, sigma, nullptr, &behind);
+            mcf::BreakWalk w = break_walk(s, first, sigma);
+            w.advance(count, [](int, int) {});
+            s->jumps_since_renumber += w.jumps;
             s->moved_as_reload = true;
             s->moved_sent = count;
             if (s->dbg.on) s->dbg.reload_walks += 1;
@@ -346,25 +325,13 @@ void shift_potentials(mcf_ns *s)
             // RUNS: one {first id, length} pair per run instead of the nodes -- the walk stores nothing per node but the potential itself, and the
             // engines get a list an order of magnitude shorter (the register-resident candidate grid takes the pairs as they are)
             int32_t *const rf = s->run_first.data(), *const rl = s->run_len.data();
-            int i = 0, a = first, nr = 0;
-            int64_t jumps = 0;
+            int i = 0, nr = 0;
+            mcf::BreakWalk w = break_walk(s, first, sigma);
             s->moved_as_runs = true;
             s->runs_sent = 0;
             while (i < count) {
                 const int stop = s->hand_over && count - (s->moved_sent + kWalkPiece) >= kWalkPiece / 2 ? std::max(i, s->moved_sent + kWalkPiece) : count;
-                while (i < stop) {
-                    const int start = a;
-                    int len = 0;
-                    for (;;) {
-                        pi[a] += sigma;
-                        const int nx = nxt[a];
-                        ++i; ++len;
-                        if (nx != a + 1) { a = nx; ++jumps; break; }
-                        ++a;
-                        if (i >= stop) break;
-                    }
-                    rf[nr] = start; rl[nr] = len; ++nr;
-                }
+                if (stop > i) { w.advance(stop - i, [&](int start, int len) { rf[nr] = start; rl[nr] = len; ++nr; }); i = stop; }
                 if (i < count) {
                     const double tp = ticks();
                     if (!s->engine_rc) s->engine_rc = engines_shift_runs(s, nr - s->runs_sent, rf + s->runs_sent, rl + s->runs_sent);
@@ -374,16 +341,20 @@ void shift_potentials(mcf_ns *s)
                 }
             }
             s->runs_n = nr;
-            s->jumps_since_renumber += jumps;
+            s->jumps_since_renumber += w.jumps;
             return;
         }
         // The engines have _pi bound (mcf_engine_bind_potentials): the list goes without values.
-        int i = 0, a = first;
-        int64_t jumps = 0;
+        int i = 0;
+        mcf::BreakWalk w = break_walk(s, first, sigma);
         s->moved_without_values = true;
         while (i < count) {
             const int stop = s->hand_over && count - (s->moved_sent + kWalkPiece) >= kWalkPiece / 2 ? std::max(i, s->moved_sent + kWalkPiece) : count;
-            if (stop > i) { jumps += walk_runs(s, a, stop - i, sigma, nodes + i, &a); i = stop; }
+            if (stop > i) {
+                int32_t *out = nodes + i;
+                w.advance(stop - i, [&](int start, int len) { for (int k = 0; k < len; ++k) out[k] = start + k; out += len; });
+                i = stop;
+            }
             if (i < count) {
                 const double tp = ticks();
                 if (!s->engine_rc) s->engine_rc = engines_append_potential(s, i - s->moved_sent, nodes + s->moved_sent, nullptr);
@@ -391,7 +362,7 @@ void shift_potentials(mcf_ns *s)
                 s->moved_sent = i;
             }
         }
-        s->jumps_since_renumber += jumps;
+        s->jumps_since_renumber += w.jumps;
         return;
     }
     int32_t *const follow = s->follow.data();
@@ -493,6 +464,8 @@ void renumber_nodes(mcf_ns *s, std::vector<int32_t> *perm_out)
     auto tr1 = [&](int32_t &x) { if (x >= 0) x = to[x]; };
     tr1(s->pv.join); tr1(s->pv.u_in); tr1(s->pv.v_in); tr1(s->pv.u_out); tr1(s->pv.v_out);
     s->walked_since_renumber = 0; s->jumps_since_renumber = 0; s->renumbers += 1;
+    s->breaks.resize(mcf::breaks_words(n));
+    mcf::breaks_rebuild(s->breaks.data(), s->nxt.data(), n);
     if (perm_out) perm_out->swap(to);
 }
 
@@ -515,6 +488,8 @@ void restore_node_ids(mcf_ns *s)
     const size_t A = s->tail.size();
     for (size_t e = 0; e < A; ++e) { s->tail[e] = back[s->tail[e]]; s->head[e] = back[s->head[e]]; }
     s->new_of.clear(); s->orig_of.clear();
+    // walks after this (the stepwise API) still go run by run, over the caller's ids: the bitmap follows
+    if (!s->breaks.empty()) mcf::breaks_rebuild(s->breaks.data(), s->nxt.data(), s->n);
 }
 
 // One pivot with a given entering arc, in two halves.  pivot_front does what the next search depends on -- the cycle, the State[] writes and
@@ -546,7 +521,8 @@ void pivot_back(mcf_ns *s, double *t_tree)
     mcf::push_flow(s->tv, s->pv);
     if (s->pv.change) {
         const double t0 = ticks();
-        mcf::rehang_subtree(s->tv, s->pv);
+        if (s->breaks.empty()) mcf::rehang_subtree(s->tv, s->pv);
+        else mcf::rehang_subtree(s->tv, s->pv, mcf::BreakNote{s->breaks.data(), s->nxt.data()});
         if (t_tree) *t_tree += ticks() - t0;
     }
 }
@@ -931,6 +907,13 @@ int mcf_ns_replay(mcf_ns *s, const int32_t *arcs, int64_t count, int32_t smaller
     return MCF_OK;
 }
 
+int mcf_ns_check_thread_breaks(mcf_ns *s, int64_t *mismatches)
+{
+    if (!s || !mismatches) return mcf::fail(MCF_ERR_INVALID, "null argument");
+    *mismatches = s->breaks.empty() ? 0 : mcf::breaks_mismatches(s->breaks.data(), s->nxt.data(), s->n);
+    return MCF_OK;
+}
+
 int mcf_ns_finish(mcf_ns *s, int32_t *status)
 {
     if (!s) return mcf::fail(MCF_ERR_INVALID, "null solver");
@@ -1151,7 +1134,7 @@ int mcf_ns_solve(mcf_ns *s, int32_t *status)
         if (s->pivot_limit && it > s->pivot_limit) { --it; limited = true; break; }
         // When to relabel.  The first time: when the walks have covered renumber_every times the node count, or a quarter of n pivots have passed
         // (the cycle searches and the candidate cache's re-evaluation of the moved nodes' arcs chase the same ids).  After that the walks count
-        // their JUMPS -- the steps that leave the id order, 23 - 25 ns each, which is what a relabelling buys back -- and the next relabelling
+        // their JUMPS -- the steps that leave the id order, charged kJumpNs each, which is what a relabelling buys back -- and the next relabelling
         // comes when the jumps since the last one have cost five times what that one took (2.9 ms with 400 k arcs, 0.3 s with 9 M: the engines
         // rebuild their per-node tables).  Config 5, whole solve: 28.9 s with the 4 relabellings of the first policy (a fixed interval, and never
         // before 25 times the last one's duration), 26.7 with 6, 27.9 with 12; config 3: flat between 6 and 13.  MCF_NS_RENUMBER=x forces an interval.

@@ -141,9 +141,15 @@ MCF_HD inline void push_flow(const TreeView &t, const Pivot &p)
     for (int u = head; u != p.join; u = par[u]) flow[parc[u]] += pdir[u] * val;
 }
 
+// what rehang_subtree tells about its Thread writes when nobody listens
+struct NoThreadNote { MCF_HD void operator()(int) const {} };
+
 // ---- NS.cs:1042-1183.  The subtree of u_out is cut off v_out, re-rooted at u_in and hung below v_in; the preorder
 // (thread) list is spliced accordingly and SuccNum / LastSucc are repaired along the two root paths.  Only for p.change.
-MCF_HD inline void rehang_subtree(const TreeView &t, const Pivot &p)
+// note(a) is called after every write of nxt[a] (the host driver keeps its bitmap of thread breaks current with it, thread_breaks.h;
+// the batch solver passes nothing and gets the code it had).
+template <class Note = NoThreadNote>
+MCF_HD inline void rehang_subtree(const TreeView &t, const Pivot &p, const Note &note = Note())
 {
     int32_t *const par = t.par, *const parc = t.par_arc, *const nxt = t.nxt, *const prv = t.prv, *const sub = t.sub, *const fin = t.fin;
     int32_t *const dirty = t.scratch;
@@ -157,24 +163,24 @@ MCF_HD inline void rehang_subtree(const TreeView &t, const Pivot &p)
         par[u_in] = v_in; parc[u_in] = in_arc; pdir[u_in] = dir_in;
         if (nxt[v_in] != u_out) {
             int after = nxt[fin_out_old];
-            nxt[before_out] = after; prv[after] = before_out;          // unlink [u_out .. fin_out_old]
+            nxt[before_out] = after; note(before_out); prv[after] = before_out;          // unlink [u_out .. fin_out_old]
             after = nxt[v_in];
-            nxt[v_in] = u_out; prv[u_out] = v_in;                       // relink right behind v_in
-            nxt[fin_out_old] = after; prv[after] = fin_out_old;
+            nxt[v_in] = u_out; note(v_in); prv[u_out] = v_in;                       // relink right behind v_in
+            nxt[fin_out_old] = after; note(fin_out_old); prv[after] = fin_out_old;
         }
     } else {
         // before_out == v_in also means join == v_out
         const int resume = before_out == v_in ? nxt[fin_out_old] : nxt[v_in];
         int stem = u_in, new_par = v_in, last = fin[u_in], after = nxt[last];
-        nxt[v_in] = u_in;
+        nxt[v_in] = u_in; note(v_in);
         int n_dirty = 0;
         dirty[n_dirty++] = v_in;
         while (stem != u_out) {
             const int up = par[stem];
-            nxt[last] = up;                       // the next stem node follows this stem's subtree
+            nxt[last] = up; note(last);           // the next stem node follows this stem's subtree
             dirty[n_dirty++] = last;
             const int before = prv[stem];         // drop the stem's subtree from its old place
-            nxt[before] = after; prv[after] = before;
+            nxt[before] = after; note(before); prv[after] = before;
             par[stem] = new_par;
             new_par = stem;
             stem = up;
@@ -182,9 +188,9 @@ MCF_HD inline void rehang_subtree(const TreeView &t, const Pivot &p)
             after = nxt[last];
         }
         par[u_out] = new_par;
-        nxt[last] = resume; prv[resume] = last;
+        nxt[last] = resume; note(last); prv[resume] = last;
         fin[u_out] = last;
-        if (before_out != v_in) { nxt[before_out] = after; prv[after] = before_out; }
+        if (before_out != v_in) { nxt[before_out] = after; note(before_out); prv[after] = before_out; }
         for (int i = 0; i < n_dirty; ++i) { const int u = dirty[i]; prv[nxt[u]] = u; }
         // reverse the parent arcs along the stem, rebuild sizes
         int acc = 0;

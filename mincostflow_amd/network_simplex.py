@@ -285,6 +285,10 @@ class NetworkSimplex:
         self.replay_relabellings = int(m.reserved)          # how often the nodes were relabelled (mcf_ns_metrics.reserved after a replay)
         return self
 
+    def check_thread_breaks(self) -> int:
+        """mcf_ns_check_thread_breaks: bits of the driver's thread-break bitmap that differ from a recomputation (0 without a bitmap)."""
+        m = C.c_int64(); L.check(L.lib().mcf_ns_check_thread_breaks(self._h, C.byref(m))); return m.value
+
     def internal(self) -> dict:
         ms, cap = C.c_int32(), C.c_int32()
         ps, pt = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()

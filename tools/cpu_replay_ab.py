@@ -3,6 +3,7 @@ sequence through mcf_ns_replay with the walk aids mcf_ns_solve starts with (smal
 
     python tools/cpu_replay_ab.py trace c3_trace.npy                    # once: the oracle's trace (a minute or two)
     python tools/cpu_replay_ab.py ab c3_trace.npy /path/to/base.so [5]  # base and new alternating, each in a process of its own
+    python tools/cpu_replay_ab.py ab c3_trace.npy /path/to/base/checkout [5]   # the same, the base (built) with its own Python side
 
 The trace is the oracle's, which the GPU parity test asserts is also the product's; both builds get the same array.  Per pivot: tree_update_us
 (the re-hanging), potential_update_us (the walk) and the rest of loop_us (cycle search, State[], flows, relabellings).  A CPU timing of CPU
@@ -51,8 +52,11 @@ def main():
         base, reps = sys.argv[3], int(sys.argv[4]) if len(sys.argv) > 4 else 5
         rows = {"base": [], "new": []}
         for _ in range(reps):
-            for name, env in (("base", {"MCF_AB_LIB": os.path.abspath(base)}), ("new", {})):
-                out = subprocess.run([sys.executable, __file__, "one", path], env=dict(os.environ, **env), check=True, capture_output=True, text=True).stdout.split()
+            # base: another build of the library under this tree's Python, or (a directory) another checkout, run with its own Python side --
+            # needed when this tree's bindings name a symbol that the base build does not export
+            base_script = os.path.join(base, "tools", os.path.basename(__file__)) if os.path.isdir(base) else __file__
+            for name, script, env in (("base", base_script, {} if os.path.isdir(base) else {"MCF_AB_LIB": os.path.abspath(base)}), ("new", __file__, {})):
+                out = subprocess.run([sys.executable, script, "one", os.path.abspath(path)], env=dict(os.environ, **env), check=True, capture_output=True, text=True).stdout.split()
                 rows[name].append([float(x) for x in out[:4]] + [int(out[4])])
                 print(name, *out, flush=True)
         assert len({r[4] for rs in rows.values() for r in rs}) == 1, "total costs differ"
