@@ -865,36 +865,56 @@ int mcf_batch_get_stats(mcf_batch *b, mcf_batch_stats *out)
 }  // extern "C"
 
 // ================================================================================================
-// mcf_ubatch_*: one topology, problem data in and results out where they are ("Uniform batch")
+// mcf_ubatch_* and mcf_rbatch_*: problem data in and results out where they are ("Uniform batch", "Ragged batch").
+// One handle body (PlacedBatch) and one set of drivers for both.  What differs between one topology at a fixed stride and a set of
+// graphs at running sums -- sizes, tables, how a problem value and a view are formed, which kernels -- is a placement:
+// UniformPlacement and RaggedPlacement, static members of the same names, chosen at compile time by the entry points.
 // ================================================================================================
-struct mcf_ubatch {
-    mcf_ubatch_desc d{};
-    std::vector<int32_t> source, target;
-    std::vector<int32_t> inc_start, inc; // per node its arcs, arc << 1 | (the node is the target): what mcf_ubatch_validate walks
-    BatchSlot tmpl{};                   // everything of a slot that the topology and the descriptor decide (configure_slot), filled once
-    uint32_t stride = 0;                // bytes between workspaces
+namespace {
+
+struct PlacedBatch {
     enum Where { kNowhere, kOnHost, kOnDevice } where = kNowhere;      // who holds the state the last solve of either kind left
     mcf_ubatch_stats stats{};
     int lds_max = 0;
-    DeviceBuffers dev;                  // slab (count * stride), slots, ids, traces
-    BatchSlot *d_tmpl = nullptr;
-    int32_t *d_source = nullptr, *d_target = nullptr, *d_inc_start = nullptr, *d_inc = nullptr;
-    int64_t *d_summary = nullptr;       // mcf_ubatch_validate: invalid instances, the lowest invalid index
+    DeviceBuffers dev;                  // slab, slots, ids, traces
+    unsigned char *d_tables = nullptr;  // the topology, its incidence lists and the placement's tables: one allocation, up once per handle
+    BatchSlot *d_tmpl = nullptr;        // the placement's slot templates, sent with every solve call
+    int64_t *d_summary = nullptr;       // validation: invalid instances, the lowest invalid index.  Allocated last: it says the tables are up
     unsigned char *d_io = nullptr;      // MCF_MEM_HOST: the caller's arrays on their way up and down
     size_t d_io_bytes = 0;
     std::vector<unsigned char> h_slab;  // the host hooks' slab, slots and traces: the device's layout
     std::vector<BatchSlot> h_slots;
     std::vector<int32_t> h_traces;
-    ~mcf_ubatch()
+    ~PlacedBatch()
     {
+        if (d_tables) (void)hipFree(d_tables);
         if (d_tmpl) (void)hipFree(d_tmpl);
-        if (d_source) (void)hipFree(d_source);
-        if (d_target) (void)hipFree(d_target);
-        if (d_inc_start) (void)hipFree(d_inc_start);
-        if (d_inc) (void)hipFree(d_inc);
         if (d_summary) (void)hipFree(d_summary);
         if (d_io) (void)hipFree(d_io);
     }
+};
+
+}  // namespace
+
+struct mcf_ubatch : PlacedBatch {
+    mcf_ubatch_desc d{};
+    std::vector<int32_t> source, target;
+    std::vector<int32_t> inc_start, inc; // per node its arcs, arc << 1 | (the node is the target): what mcf_ubatch_validate walks
+    BatchSlot tmpl{};                   // everything of a slot that the topology and the descriptor decide (configure_slot), filled once
+    uint32_t stride = 0;                // bytes between workspaces
+    const int32_t *d_source = nullptr, *d_target = nullptr, *d_inc_start = nullptr, *d_inc = nullptr;     // into d_tables
+};
+
+struct mcf_rbatch : PlacedBatch {
+    mcf_rbatch_desc d{};
+    // the tables of ragged_view, as the host hooks read them; the device gets one copy of all of them (d_tables)
+    std::vector<int32_t> source, target, inc_start, inc, graph_of;
+    std::vector<mcf::RaggedGraph> graphs;
+    std::vector<int64_t> arc_row, node_row;     // [count + 1]
+    std::vector<uint64_t> workspace;            // [count + 1]: the last entry is the slab's size
+    std::vector<uint32_t> footprint;            // [count]: layout_of(m + 2n, n + 1).bytes of the instance's graph
+    std::vector<BatchSlot> tmpl;                // one per graph (configure_slot): search_arcs, block configuration and limits go by n and m
+    mcf::RaggedProblem dt{};                    // the pointers into d_tables
 };
 
 namespace {
@@ -906,67 +926,283 @@ struct DeviceGuard {
     ~DeviceGuard() { if (previous >= 0) (void)hipSetDevice(previous); }
 };
 
-int check_io(const mcf_ubatch *b, const mcf_ubatch_io *io, const char *what, bool host_only, bool resolve)
+// The arrays of a solve call or of a validation call, whichever of the four public structs they came in (io_of, at the entry points).
+struct BatchIo {
+    bool given, check;                  // given: the caller's pointer was not null.  check: a validation call
+    int32_t memory, supply_type;
+    const int64_t *lower, *upper, *cost, *supply;
+    int64_t lower_stride, upper_stride, cost_stride, supply_stride;     // the uniform structs'; 0 from a ragged one
+    const uint8_t *changed;             // re-solves only
+    int32_t *status;                    // the solution: a solve call writes it; a validation call only reads it, and has no pivots or trace
+    int64_t *pivots, *total_cost, *flows, *potentials;
+    int32_t *trace;
+    int32_t *valid, *errors, *first;    // a validation's answers
+    int64_t *objective, *dual_cost;
+};
+template <class Io>
+BatchIo problem_io(const Io *io, bool check)           // what all four structs have
 {
-    if (!b || !io) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
-    if (io->memory != MCF_MEM_HOST && io->memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io->memory);
-    if (host_only && io->memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
-    if (io->supply_type != MCF_SUPPLY_GEQ && io->supply_type != MCF_SUPPLY_LEQ) return mcf::fail(MCF_ERR_INVALID, "Invalid supply type");
-    if (io->lower_stride < 0 || io->upper_stride < 0 || io->cost_stride < 0 || io->supply_stride < 0)
-        return mcf::fail(MCF_ERR_INVALID, "%s: negative stride", what);
-    if (resolve && b->where == mcf_ubatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
+    BatchIo x{};
+    if (!io) return x;
+    x.given = true; x.check = check; x.memory = io->memory; x.supply_type = io->supply_type;
+    x.lower = io->lower; x.upper = io->upper; x.cost = io->cost; x.supply = io->supply;
+    return x;
+}
+template <class Io>
+BatchIo solve_io(const Io *io)
+{
+    BatchIo x = problem_io(io, false);
+    if (!io) return x;
+    x.changed = io->changed;
+    x.status = io->status; x.pivots = io->pivots; x.total_cost = io->total_cost; x.flows = io->flows; x.potentials = io->potentials; x.trace = io->trace;
+    return x;
+}
+template <class Io>
+BatchIo check_io(const Io *io)
+{
+    BatchIo x = problem_io(io, true);
+    if (!io) return x;
+    x.status = const_cast<int32_t *>(io->status); x.total_cost = const_cast<int64_t *>(io->total_cost);
+    x.flows = const_cast<int64_t *>(io->flows); x.potentials = const_cast<int64_t *>(io->potentials);
+    x.valid = io->valid; x.errors = io->errors; x.first = io->first; x.objective = io->objective; x.dual_cost = io->dual_cost;
+    return x;
+}
+template <class Io>
+BatchIo with_strides(BatchIo x, const Io *io)
+{
+    if (io) { x.lower_stride = io->lower_stride; x.upper_stride = io->upper_stride; x.cost_stride = io->cost_stride; x.supply_stride = io->supply_stride; }
+    return x;
+}
+BatchIo io_of(const mcf_ubatch_io *io) { return with_strides(solve_io(io), io); }
+BatchIo io_of(const mcf_rbatch_io *io) { return solve_io(io); }
+BatchIo io_of(const mcf_ubatch_check_io *io) { return with_strides(check_io(io), io); }
+BatchIo io_of(const mcf_rbatch_check_io *io) { return check_io(io); }
+
+mcf::UniformOutputs outputs_of(const BatchIo &io)
+{
+    return mcf::UniformOutputs{io.status, io.pivots, io.total_cost, io.flows, io.potentials, io.trace};
+}
+mcf::UniformCheck check_of(const BatchIo &io, int64_t *summary)
+{
+    return mcf::UniformCheck{io.status, io.total_cost, io.valid, io.errors, io.first, io.objective, io.dual_cost, summary};
+}
+void summary_of(const int64_t words[2], int64_t count, mcf_ubatch_check_summary *out)
+{
+    out->instances = count;
+    out->invalid = words[0];
+    out->first_invalid = words[0] ? words[1] : -1;
+}
+int solution_missing(const char *what)
+{
+    return mcf::fail(MCF_ERR_INVALID, "%s: status, total_cost, flows and potentials are the solution to check, all four are required", what);
+}
+
+// the byte lengths of the caller's arrays that go by arcs and nodes; everything else is one entry (or trace_capacity, or MCF_VAL_KINDS) per instance
+struct RowBytes {
+    size_t lower, upper, cost, supply, flows, potentials;
+};
+size_t input_elements(size_t count, int64_t stride, size_t length) { return count ? (count - 1) * (size_t)stride + length : 0; }
+
+// tables in one image, each part on a 16-byte boundary, in one allocation and one copy; parts[k].at = where part k lies in d_tables
+struct TablePart {
+    const void *host;
+    size_t bytes, at;
+};
+int upload_image(PlacedBatch *b, TablePart *parts, size_t part_count)
+{
+    size_t total = 0;
+    for (size_t k = 0; k < part_count; ++k) { parts[k].at = total; total += (parts[k].bytes + 15) & ~(size_t)15; }
+    std::vector<unsigned char> image(total, 0);
+    for (size_t k = 0; k < part_count; ++k)
+        if (parts[k].bytes) memcpy(image.data() + parts[k].at, parts[k].host, parts[k].bytes);
+    // a call that failed half way left what it had allocated: that is kept and filled again, not allocated twice
+    if (!b->d_tables) HIP_TRY(hipMalloc((void **)&b->d_tables, std::max<size_t>(total, 16)));
+    if (total) HIP_TRY(hipMemcpy(b->d_tables, image.data(), total, hipMemcpyHostToDevice));
     return MCF_OK;
 }
 
-mcf::UniformProblem problem_of(const mcf_ubatch *b, const mcf_ubatch_io *io, const int32_t *source, const int32_t *target, bool resolve)
+// ---- one topology, instance i at i * stride: rows by the caller's strides, one slot template
+struct UniformPlacement {
+    using Handle = mcf_ubatch;
+    using Problem = mcf::UniformProblem;
+    static constexpr auto begin_kernel = uniform_begin_kernel;
+    static constexpr auto recost_kernel = uniform_recost_kernel;
+    static constexpr auto finish_kernel = uniform_finish_kernel;
+    static void launch_validate(const Handle *b, const Problem &p, const mcf::UniformCheck &c, const BatchIo &io)
+    {
+        hipLaunchKernelGGL(uniform_validate_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, p, c, b->d_inc_start, b->d_inc, io.flows, io.potentials);
+    }
+    static size_t slab_bytes(const Handle *b) { return (size_t)b->d.count * (size_t)b->stride; }
+    static LaunchPlan plan(Handle *b) { return LaunchPlan{&b->dev, b->lds_max, b->d.pivots_per_launch, nullptr, b->stride}; }     // one class for all
+    static const BatchSlot *templates(const Handle *b) { return &b->tmpl; }
+    static size_t template_count(const Handle *) { return 1; }
+    static RowBytes row_bytes(const Handle *b, const BatchIo &io)
+    {
+        const size_t count = (size_t)b->d.count, n = (size_t)b->d.node_count, m = (size_t)b->d.arc_count;
+        return RowBytes{8 * input_elements(count, io.lower_stride, m), 8 * input_elements(count, io.upper_stride, m), 8 * input_elements(count, io.cost_stride, m),
+                        8 * input_elements(count, io.supply_stride, n), 8 * count * m, 8 * count * n};
+    }
+    static int check_rows(const Handle *b, const BatchIo &io, const char *what)
+    {
+        if (io.lower_stride < 0 || io.upper_stride < 0 || io.cost_stride < 0 || io.supply_stride < 0) return mcf::fail(MCF_ERR_INVALID, "%s: negative stride", what);
+        if (io.check && b->d.count > 0 && (!io.status || !io.total_cost || !io.flows || !io.potentials)) return solution_missing(what);     // an empty tensor has no address
+        return MCF_OK;
+    }
+    // the topology and its incidence lists
+    static int upload_tables(Handle *b)
+    {
+        TablePart parts[] = {{b->source.data(), b->source.size() * sizeof(int32_t), 0},
+                             {b->target.data(), b->target.size() * sizeof(int32_t), 0},
+                             {b->inc_start.data(), b->inc_start.size() * sizeof(int32_t), 0},
+                             {b->inc.data(), b->inc.size() * sizeof(int32_t), 0}};
+        if (const int rc = upload_image(b, parts, 4)) return rc;
+        const unsigned char *const base = b->d_tables;
+        b->d_source = (const int32_t *)(base + parts[0].at); b->d_target = (const int32_t *)(base + parts[1].at);
+        b->d_inc_start = (const int32_t *)(base + parts[2].at); b->d_inc = (const int32_t *)(base + parts[3].at);
+        return MCF_OK;
+    }
+    // the problem where the steps run: the topology in device memory or the host's, with the rows of io
+    static Problem problem(const Handle *b, const BatchIo &io, bool on_device)
+    {
+        Problem p{};
+        p.n = b->d.node_count; p.m = b->d.arc_count; p.supply_type = io.supply_type; p.trace_cap = b->d.trace_capacity;
+        p.source = on_device ? b->d_source : b->source.data(); p.target = on_device ? b->d_target : b->target.data();
+        p.lower = io.lower; p.upper = io.upper; p.cost = io.cost; p.supply = io.supply;
+        p.lower_stride = io.lower_stride; p.upper_stride = io.upper_stride; p.cost_stride = io.cost_stride; p.supply_stride = io.supply_stride;
+        p.stride = b->stride;
+        p.changed = io.changed;
+        return p;
+    }
+    static mcf::InstanceView view(const Handle *b, const Problem &p, const mcf::UniformOutputs &o, int64_t i, unsigned char *slab, const BatchSlot **tmpl)
+    {
+        *tmpl = &b->tmpl;
+        return mcf::uniform_view(p, &o, i, slab);
+    }
+    static mcf::InstanceView check_view(const Handle *b, const Problem &p, const BatchIo &io, int64_t i)
+    {
+        return mcf::uniform_check_view(p, b->inc_start.data(), b->inc.data(), io.flows, io.potentials, i);
+    }
+};
+
+// ---- a set of graphs, instance i's rows and workspace at running sums: tables say where, one slot template per graph
+struct RaggedPlacement {
+    using Handle = mcf_rbatch;
+    using Problem = mcf::RaggedProblem;
+    static constexpr auto begin_kernel = ragged_begin_kernel;
+    static constexpr auto recost_kernel = ragged_recost_kernel;
+    static constexpr auto finish_kernel = ragged_finish_kernel;
+    static void launch_validate(const Handle *b, const Problem &r, const mcf::UniformCheck &c, const BatchIo &io)
+    {
+        hipLaunchKernelGGL(ragged_validate_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, r, c, io.flows, io.potentials);
+    }
+    static size_t slab_bytes(const Handle *b) { return (size_t)b->workspace[(size_t)b->d.count]; }
+    static LaunchPlan plan(Handle *b) { return LaunchPlan{&b->dev, b->lds_max, b->d.pivots_per_launch, b->footprint.data(), 0}; }  // a class per instance
+    static const BatchSlot *templates(const Handle *b) { return b->tmpl.data(); }
+    static size_t template_count(const Handle *b) { return b->tmpl.size(); }
+    static RowBytes row_bytes(const Handle *b, const BatchIo &)
+    {
+        const size_t arcs = 8 * (size_t)b->arc_row[(size_t)b->d.count], nodes = 8 * (size_t)b->node_row[(size_t)b->d.count];
+        return RowBytes{arcs, arcs, arcs, nodes, arcs, nodes};
+    }
+    static int check_rows(const Handle *b, const BatchIo &io, const char *what)
+    {
+        const size_t count = (size_t)b->d.count;
+        if (io.check && count > 0 && (!io.status || !io.total_cost || (b->arc_row[count] && !io.flows) || (b->node_row[count] && !io.potentials)))    // an empty tensor has no address
+            return solution_missing(what);
+        return MCF_OK;
+    }
+    // the tables, the topology and its incidence lists
+    static int upload_tables(Handle *b)
+    {
+        const size_t count = (size_t)b->d.count;
+        TablePart parts[] = {{b->graph_of.data(), count * sizeof(int32_t), 0},
+                             {b->graphs.data(), b->graphs.size() * sizeof(mcf::RaggedGraph), 0},
+                             {b->arc_row.data(), (count + 1) * sizeof(int64_t), 0},
+                             {b->node_row.data(), (count + 1) * sizeof(int64_t), 0},
+                             {b->workspace.data(), count * sizeof(uint64_t), 0},
+                             {b->source.data(), b->source.size() * sizeof(int32_t), 0},
+                             {b->target.data(), b->target.size() * sizeof(int32_t), 0},
+                             {b->inc_start.data(), b->inc_start.size() * sizeof(int32_t), 0},
+                             {b->inc.data(), b->inc.size() * sizeof(int32_t), 0}};
+        if (const int rc = upload_image(b, parts, 9)) return rc;
+        const unsigned char *const base = b->d_tables;
+        Problem &r = b->dt;
+        r = Problem{};
+        r.graph_of = (const int32_t *)(base + parts[0].at); r.graphs = (const mcf::RaggedGraph *)(base + parts[1].at);
+        r.arc_row = (const int64_t *)(base + parts[2].at); r.node_row = (const int64_t *)(base + parts[3].at);
+        r.workspace = (const uint64_t *)(base + parts[4].at);
+        r.source = (const int32_t *)(base + parts[5].at); r.target = (const int32_t *)(base + parts[6].at);
+        r.inc_start = (const int32_t *)(base + parts[7].at); r.inc = (const int32_t *)(base + parts[8].at);
+        return MCF_OK;
+    }
+    // the tables where the steps run, with the rows of io
+    static Problem problem(const Handle *b, const BatchIo &io, bool on_device)
+    {
+        Problem r = b->dt;
+        if (!on_device) {
+            r.graph_of = b->graph_of.data(); r.graphs = b->graphs.data();
+            r.arc_row = b->arc_row.data(); r.node_row = b->node_row.data(); r.workspace = b->workspace.data();
+            r.source = b->source.data(); r.target = b->target.data(); r.inc_start = b->inc_start.data(); r.inc = b->inc.data();
+        }
+        r.supply_type = io.supply_type; r.trace_cap = b->d.trace_capacity;
+        r.lower = io.lower; r.upper = io.upper; r.cost = io.cost; r.supply = io.supply;
+        r.changed = io.changed;
+        return r;
+    }
+    static mcf::InstanceView view(const Handle *b, const Problem &r, const mcf::UniformOutputs &o, int64_t i, unsigned char *slab, const BatchSlot **tmpl)
+    {
+        int32_t t = 0;
+        const mcf::InstanceView v = mcf::ragged_view(r, &o, i, slab, &t);
+        *tmpl = &b->tmpl[(size_t)t];
+        return v;
+    }
+    static mcf::InstanceView check_view(const Handle *, const Problem &r, const BatchIo &io, int64_t i) { return mcf::ragged_check_view(r, io.flows, io.potentials, i); }
+};
+
+// what every call refuses before it touches the handle.  Solve calls take MCF_SUPPLY_GEQ / _LEQ, validation calls MCF_SUPPLY_EQ too
+template <class P>
+int check_call(const typename P::Handle *b, const BatchIo &io, const char *what, bool host_only, bool resolve)
 {
-    mcf::UniformProblem p{};
-    p.n = b->d.node_count; p.m = b->d.arc_count; p.supply_type = io->supply_type; p.trace_cap = b->d.trace_capacity;
-    p.source = source; p.target = target;
-    p.lower = io->lower; p.upper = io->upper; p.cost = io->cost; p.supply = io->supply;
-    p.lower_stride = io->lower_stride; p.upper_stride = io->upper_stride; p.cost_stride = io->cost_stride; p.supply_stride = io->supply_stride;
-    p.stride = b->stride;
-    p.changed = resolve ? io->changed : nullptr;
-    return p;
-}
-mcf::UniformOutputs outputs_of(const mcf_ubatch_io *io)
-{
-    return mcf::UniformOutputs{io->status, io->pivots, io->total_cost, io->flows, io->potentials, io->trace};
+    if (!b || !io.given) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
+    if (io.memory != MCF_MEM_HOST && io.memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io.memory);
+    if (host_only && io.memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
+    if (!io.check) {
+        if (io.supply_type != MCF_SUPPLY_GEQ && io.supply_type != MCF_SUPPLY_LEQ) return mcf::fail(MCF_ERR_INVALID, "Invalid supply type");
+    } else if (io.supply_type < MCF_SUPPLY_GEQ || io.supply_type > MCF_SUPPLY_EQ) {
+        return mcf::fail(MCF_ERR_INVALID, "%s: supply type %d", what, io.supply_type);
+    }
+    if (const int rc = P::check_rows(b, io, what)) return rc;
+    if (resolve && b->where == PlacedBatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
+    return MCF_OK;
 }
 
-// the topology and its incidence lists go up once per handle, with its first device call of any kind
-int ensure_topology(mcf_ubatch *b)
+// the placement's tables go up once per handle, with its first device call of any kind
+template <class P>
+int ensure_tables(typename P::Handle *b)
 {
     if (b->d_summary) return MCF_OK;
-    const size_t n = (size_t)b->d.node_count, m = (size_t)b->d.arc_count;
-    HIP_TRY(hipMalloc((void **)&b->d_source, std::max<size_t>(m, 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void **)&b->d_target, std::max<size_t>(m, 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void **)&b->d_inc_start, (n + 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void **)&b->d_inc, std::max<size_t>(2 * m, 1) * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(b->d_inc_start, b->inc_start.data(), (n + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (m) {
-        HIP_TRY(hipMemcpy(b->d_source, b->source.data(), m * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b->d_target, b->target.data(), m * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b->d_inc, b->inc.data(), 2 * m * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
+    if (const int rc = P::upload_tables(b)) return rc;
     HIP_TRY(hipMalloc((void **)&b->d_summary, 2 * sizeof(int64_t)));          // last: it says the rest is there
     return MCF_OK;
 }
 
-int ensure_device_buffers(mcf_ubatch *b)
+template <class P>
+int ensure_device_buffers(typename P::Handle *b)
 {
-    if (const int rc = ensure_topology(b)) return rc;
-    if (b->dev.slab) return MCF_OK;
+    if (const int rc = ensure_tables<P>(b)) return rc;
+    DeviceBuffers &dev = b->dev;
+    if (dev.slab) return MCF_OK;
     const size_t count = (size_t)b->d.count;
-    HIP_TRY(hipMalloc((void **)&b->dev.slab, count * (size_t)b->stride));
-    HIP_TRY(hipMalloc((void **)&b->dev.slots, count * sizeof(BatchSlot)));
-    HIP_TRY(hipMalloc((void **)&b->dev.ids, count * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void **)&b->dev.traces, std::max<size_t>(count * (size_t)b->d.trace_capacity, 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void **)&b->d_tmpl, sizeof(BatchSlot)));
+    // a call that failed half way left what it had allocated: those are kept.  The slab comes last and says the rest is there
+    if (!dev.slots) HIP_TRY(hipMalloc((void **)&dev.slots, count * sizeof(BatchSlot)));
+    if (!dev.ids) HIP_TRY(hipMalloc((void **)&dev.ids, count * sizeof(int32_t)));
+    if (!dev.traces) HIP_TRY(hipMalloc((void **)&dev.traces, std::max<size_t>(count * (size_t)b->d.trace_capacity, 1) * sizeof(int32_t)));
+    if (!b->d_tmpl) HIP_TRY(hipMalloc((void **)&b->d_tmpl, std::max<size_t>(P::template_count(b), 1) * sizeof(BatchSlot)));
+    HIP_TRY(hipMalloc((void **)&dev.slab, std::max<size_t>(P::slab_bytes(b), 16)));
     return MCF_OK;
 }
 
-// MCF_MEM_HOST: one copy up per input array and one down per output array, through one device buffer
+// MCF_MEM_HOST: one copy up per array the call reads and one down per array it writes, through one device buffer
 struct Staged {
     struct Piece { const void *host_in; void *host_out; size_t offset, bytes; };
     std::vector<Piece> pieces;
@@ -980,52 +1216,53 @@ struct Staged {
         return at;
     }
 };
-size_t input_elements(size_t count, int64_t stride, size_t length) { return count ? (count - 1) * (size_t)stride + length : 0; }
-// the staging buffer holds st, and what st brings from the host is in it
-template <class Handle>
-int stage_send(Handle *b, const Staged &st, int64_t *bytes_up)
+
+// The caller's io as the kernels see it: itself for MCF_MEM_DEVICE; for MCF_MEM_HOST every array of *io that is there becomes its staged
+// copy, and what the call reads is uploaded here.  A solve call reads the problem and writes the solution; where it will not write every
+// row (a masked re-solve) the solution goes up too.  A validation call reads both and writes the answers.
+template <class P>
+int stage_up(typename P::Handle *b, BatchIo *io, Staged *st, int64_t *bytes_up)
 {
-    if (b->d_io_bytes < st.total) {
+    if (io->memory == MCF_MEM_DEVICE) return MCF_OK;
+    const size_t count = (size_t)b->d.count, cap = (size_t)b->d.trace_capacity;
+    const RowBytes rows = P::row_bytes(b, *io);
+    const bool solution_up = io->check || io->changed, solution_down = !io->check;
+    struct Array { void **slot; size_t bytes; bool up, down; };
+    const Array arrays[] = {{(void **)&io->lower, rows.lower, true, false},
+                            {(void **)&io->upper, rows.upper, true, false},
+                            {(void **)&io->cost, rows.cost, true, false},
+                            {(void **)&io->supply, rows.supply, true, false},
+                            {(void **)&io->changed, count, true, false},
+                            {(void **)&io->status, 4 * count, solution_up, solution_down},
+                            {(void **)&io->pivots, 8 * count, solution_up, solution_down},
+                            {(void **)&io->total_cost, 8 * count, solution_up, solution_down},
+                            {(void **)&io->flows, rows.flows, solution_up, solution_down},
+                            {(void **)&io->potentials, rows.potentials, solution_up, solution_down},
+                            {(void **)&io->trace, 4 * count * cap, solution_up, solution_down},
+                            {(void **)&io->valid, 4 * count, false, true},
+                            {(void **)&io->errors, 4 * count * MCF_VAL_KINDS, false, true},
+                            {(void **)&io->first, 4 * count * MCF_VAL_KINDS, false, true},
+                            {(void **)&io->objective, 8 * count, false, true},
+                            {(void **)&io->dual_cost, 8 * count, false, true}};
+    constexpr int kArrays = (int)(sizeof(arrays) / sizeof(arrays[0]));
+    size_t at[kArrays] = {};
+    for (int k = 0; k < kArrays; ++k)
+        if (void *const host = *arrays[k].slot) at[k] = st->add(arrays[k].up ? host : nullptr, arrays[k].down ? host : nullptr, arrays[k].bytes);
+    if (b->d_io_bytes < st->total) {
         if (b->d_io) { HIP_TRY(hipFree(b->d_io)); b->d_io = nullptr; b->d_io_bytes = 0; }
-        HIP_TRY(hipMalloc((void **)&b->d_io, st.total));
-        b->d_io_bytes = st.total;
+        HIP_TRY(hipMalloc((void **)&b->d_io, st->total));
+        b->d_io_bytes = st->total;
     }
-    for (const Staged::Piece &pc : st.pieces)
+    for (const Staged::Piece &pc : st->pieces)
         if (pc.host_in && pc.bytes) {
             HIP_TRY(hipMemcpy(b->d_io + pc.offset, pc.host_in, pc.bytes, hipMemcpyHostToDevice));
             *bytes_up += (int64_t)pc.bytes;
         }
+    for (int k = 0; k < kArrays; ++k)
+        if (*arrays[k].slot) *arrays[k].slot = b->d_io + at[k];
     return MCF_OK;
 }
-
-// the caller's io as the kernels see it: itself for MCF_MEM_DEVICE, staged copies for MCF_MEM_HOST (uploaded here).  keep_rows: the
-// output arrays go up too, because the call will not write every row (a masked re-solve)
-int stage_up(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve, mcf_ubatch_io *dio, Staged *st)
-{
-    *dio = *io;
-    if (io->memory == MCF_MEM_DEVICE) return MCF_OK;
-    const size_t count = (size_t)b->d.count, n = (size_t)b->d.node_count, m = (size_t)b->d.arc_count, cap = (size_t)b->d.trace_capacity;
-    const bool keep_rows = resolve && io->changed;
-    struct In { const void *p; size_t bytes; const void **slot; };
-    const In ins[] = {{io->lower, 8 * input_elements(count, io->lower_stride, m), (const void **)&dio->lower},
-                      {io->upper, 8 * input_elements(count, io->upper_stride, m), (const void **)&dio->upper},
-                      {io->cost, 8 * input_elements(count, io->cost_stride, m), (const void **)&dio->cost},
-                      {io->supply, 8 * input_elements(count, io->supply_stride, n), (const void **)&dio->supply},
-                      {resolve ? io->changed : nullptr, count, (const void **)&dio->changed}};
-    struct Out { void *p; size_t bytes; void **slot; };
-    const Out outs[] = {{io->status, 4 * count, (void **)&dio->status},       {io->pivots, 8 * count, (void **)&dio->pivots},
-                        {io->total_cost, 8 * count, (void **)&dio->total_cost}, {io->flows, 8 * count * m, (void **)&dio->flows},
-                        {io->potentials, 8 * count * n, (void **)&dio->potentials}, {io->trace, 4 * count * cap, (void **)&dio->trace}};
-    size_t at_in[5], at_out[6];
-    for (int k = 0; k < 5; ++k) at_in[k] = ins[k].p ? st->add(ins[k].p, nullptr, ins[k].bytes) : 0;
-    for (int k = 0; k < 6; ++k) at_out[k] = outs[k].p ? st->add(keep_rows ? outs[k].p : nullptr, outs[k].p, outs[k].bytes) : 0;
-    if (const int rc = stage_send(b, *st, &b->stats.bytes_up)) return rc;
-    for (int k = 0; k < 5; ++k) *ins[k].slot = ins[k].p ? b->d_io + at_in[k] : nullptr;
-    for (int k = 0; k < 6; ++k) *outs[k].slot = outs[k].p ? b->d_io + at_out[k] : nullptr;
-    return MCF_OK;
-}
-template <class Handle>
-int stage_down(Handle *b, const Staged &st, int64_t *bytes_down)
+int stage_down(PlacedBatch *b, const Staged &st, int64_t *bytes_down)
 {
     for (const Staged::Piece &pc : st.pieces)
         if (pc.host_out && pc.bytes) {
@@ -1035,41 +1272,42 @@ int stage_down(Handle *b, const Staged &st, int64_t *bytes_down)
     return MCF_OK;
 }
 
-// mcf_ubatch_solve and mcf_ubatch_resolve: set-up (or re-cost) launch, the launch loop of mcf_batch_solve, finish launch
-int ubatch_on_device(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve)
+// mcf_*batch_solve and _resolve: set-up (or re-cost) launch, the launch loop of mcf_batch_solve, finish launch
+template <class P>
+int solve_on_device(typename P::Handle *b, BatchIo io, bool resolve, const char *what)
 {
-    const char *const what = resolve ? "mcf_ubatch_resolve" : "mcf_ubatch_solve";
-    if (const int rc = check_io(b, io, what, false, resolve)) return rc;
+    if (const int rc = check_call<P>(b, io, what, false, resolve)) return rc;
     if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
     const double t_start = mcf::now_ns();
     const DeviceGuard guard;
     if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
     const size_t count = (size_t)b->d.count;
-    const bool in_lds = class_of(b->lds_max, b->stride) != kClasses - 1;
+    const LaunchPlan plan = P::plan(b);
     b->stats = mcf_ubatch_stats{};
     b->stats.instances = (int64_t)count;
-    (in_lds ? b->stats.lds_instances : b->stats.global_instances) = (int64_t)count;
-    b->stats.workspace_bytes = (int64_t)(count * (size_t)b->stride);
-    if (!count) { b->where = mcf_ubatch::kOnDevice; b->stats.host_ns = mcf::now_ns() - t_start; return MCF_OK; }
-    if (const int rc = ensure_device_buffers(b)) return rc;
+    for (size_t i = 0; i < count; ++i)
+        (class_of(b->lds_max, plan.bytes((int32_t)i)) != kClasses - 1 ? b->stats.lds_instances : b->stats.global_instances)++;
+    b->stats.workspace_bytes = (int64_t)P::slab_bytes(b);
+    if (!count) { b->where = PlacedBatch::kOnDevice; b->stats.host_ns = mcf::now_ns() - t_start; return MCF_OK; }
+    if (const int rc = ensure_device_buffers<P>(b)) return rc;
     DeviceBuffers &dev = b->dev;
-    if (resolve && b->where == mcf_ubatch::kOnHost) {                       // the last solve was a host hook's: its state goes up whole
-        HIP_TRY(hipMemcpy(dev.slab, b->h_slab.data(), b->h_slab.size(), hipMemcpyHostToDevice));
+    if (resolve && b->where == PlacedBatch::kOnHost) {                      // the last solve was a host hook's: its state goes up whole
+        if (!b->h_slab.empty()) HIP_TRY(hipMemcpy(dev.slab, b->h_slab.data(), b->h_slab.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dev.slots, b->h_slots.data(), count * sizeof(BatchSlot), hipMemcpyHostToDevice));
         b->stats.bytes_up += (int64_t)(b->h_slab.size() + count * sizeof(BatchSlot));
     }
-    mcf_ubatch_io dio;
+    if (!resolve) io.changed = nullptr;
     Staged staged;
-    if (const int rc = stage_up(b, io, resolve, &dio, &staged)) return rc;
-    const mcf::UniformProblem p = problem_of(b, &dio, b->d_source, b->d_target, resolve);
+    if (const int rc = stage_up<P>(b, &io, &staged, &b->stats.bytes_up)) return rc;
+    const typename P::Problem p = P::problem(b, io, true);
 
     const double t_begin = mcf::now_ns();
-    HIP_TRY(hipMemcpy(b->d_tmpl, &b->tmpl, sizeof(BatchSlot), hipMemcpyHostToDevice));
-    b->stats.bytes_up += (int64_t)sizeof(BatchSlot);
-    if (resolve) hipLaunchKernelGGL(uniform_recost_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
-    else hipLaunchKernelGGL(uniform_begin_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
+    HIP_TRY(hipMemcpy(b->d_tmpl, P::templates(b), P::template_count(b) * sizeof(BatchSlot), hipMemcpyHostToDevice));
+    b->stats.bytes_up += (int64_t)(P::template_count(b) * sizeof(BatchSlot));
+    const auto begin_kernel = resolve ? P::recost_kernel : P::begin_kernel;
+    hipLaunchKernelGGL(begin_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
     HIP_TRY(hipGetLastError());
-    b->where = mcf_ubatch::kOnDevice;
+    b->where = PlacedBatch::kOnDevice;
     std::vector<BatchSlot> slots(count);
     HIP_TRY(hipMemcpy(slots.data(), dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));      // waits for the launch; says who runs
     b->stats.bytes_down += (int64_t)(count * sizeof(BatchSlot));
@@ -1079,7 +1317,7 @@ int ubatch_on_device(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve)
     for (size_t i = 0; i < count; ++i)
         if (slots[i].run == mcf::kBatchRunning) run.push_back((int32_t)i);   // a re-solve's unmarked instances ended their last solve: not running
     LaunchTotals t;
-    if (const int rc = run_launches(LaunchPlan{&dev, b->lds_max, b->d.pivots_per_launch, nullptr, b->stride}, slots, run, &t)) return rc;
+    if (const int rc = run_launches(plan, slots, run, &t)) return rc;
     for (int32_t i : run) b->stats.total_pivots += slots[(size_t)i].pivots;
     b->stats.launches = t.launches;
     b->stats.lds_bytes_max = t.lds_bytes_max;
@@ -1088,7 +1326,7 @@ int ubatch_on_device(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve)
     b->stats.kernel_ns = t.kernel_ns;
 
     const double t_finish = mcf::now_ns();
-    hipLaunchKernelGGL(uniform_finish_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, outputs_of(&dio), dev.slots, dev.slab, dev.traces);
+    hipLaunchKernelGGL(P::finish_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, outputs_of(io), dev.slots, dev.slab, dev.traces);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     b->stats.finish_ns = mcf::now_ns() - t_finish;
@@ -1098,37 +1336,38 @@ int ubatch_on_device(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve)
 }
 
 // the host hooks: the three steps and batch_run with one lane, on a host slab of the device's layout
-int ubatch_on_host(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve)
+template <class P>
+int solve_on_host(typename P::Handle *b, BatchIo io, bool resolve, const char *what)
 {
-    const char *const what = resolve ? "mcf_ubatch_rerun_on_host" : "mcf_ubatch_run_on_host";
-    if (const int rc = check_io(b, io, what, true, resolve)) return rc;
+    if (const int rc = check_call<P>(b, io, what, true, resolve)) return rc;
     const double t_start = mcf::now_ns();
     const size_t count = (size_t)b->d.count;
-    b->h_slab.resize(count * (size_t)b->stride);
+    b->h_slab.resize(P::slab_bytes(b));
     b->h_slots.resize(count);
     b->h_traces.resize(std::max<size_t>(count * (size_t)b->d.trace_capacity, 1));
-    if (resolve && b->where == mcf_ubatch::kOnDevice && count) {            // the last solve was the device's: its state comes down whole
+    if (resolve && b->where == PlacedBatch::kOnDevice && count) {           // the last solve was the device's: its state comes down whole
         const DeviceGuard guard;
         HIP_TRY(hipSetDevice(b->d.device));
-        HIP_TRY(hipMemcpy(b->h_slab.data(), b->dev.slab, b->h_slab.size(), hipMemcpyDeviceToHost));
+        if (!b->h_slab.empty()) HIP_TRY(hipMemcpy(b->h_slab.data(), b->dev.slab, b->h_slab.size(), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(b->h_slots.data(), b->dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));
     }
     b->stats = mcf_ubatch_stats{};
     b->stats.instances = (int64_t)count;
     b->stats.workspace_bytes = (int64_t)b->h_slab.size();
-    const mcf::UniformProblem p = problem_of(b, io, b->source.data(), b->target.data(), resolve);
+    if (!resolve) io.changed = nullptr;
+    const typename P::Problem p = P::problem(b, io, false);
     const mcf::UniformOutputs o = outputs_of(io);
     for (size_t i = 0; i < count; ++i) {
-        if (p.changed && !p.changed[i]) continue;
+        if (io.changed && !io.changed[i]) continue;
         BatchSlot &slot = b->h_slots[i];
-        const mcf::InstanceView v = mcf::uniform_view(p, &o, (int64_t)i, b->h_slab.data());
-        unsigned char *const home = v.home;
-        if (resolve) mcf::uniform_recost(v, b->tmpl, slot, 0, 1);
-        else mcf::uniform_begin(v, b->tmpl, slot, 0, 1);
+        const BatchSlot *tmpl = nullptr;
+        const mcf::InstanceView v = P::view(b, p, o, (int64_t)i, b->h_slab.data(), &tmpl);
+        if (resolve) mcf::uniform_recost(v, *tmpl, slot, 0, 1);
+        else mcf::uniform_begin(v, *tmpl, slot, 0, 1);
         if (slot.run == mcf::kBatchRunning) {
             mcf::BatchWork w{};
             load_slot(w, slot, b->h_traces.data());
-            bind(w, home, layout_of((uint32_t)slot.all_arcs, (uint32_t)slot.n + 1u));
+            bind(w, v.home, layout_of((uint32_t)slot.all_arcs, (uint32_t)slot.n + 1u));
             if (slot.reprice) mcf::batch_reprice(w, 0, 1);
             mcf::batch_run(w, 0, 1, INT64_MAX);
             store_slot(slot, w);
@@ -1136,88 +1375,32 @@ int ubatch_on_host(mcf_ubatch *b, const mcf_ubatch_io *io, bool resolve)
         }
         mcf::uniform_finish(v, o, slot, b->h_traces.data(), 0, 1);
     }
-    b->where = mcf_ubatch::kOnHost;
+    b->where = PlacedBatch::kOnHost;
     b->stats.host_ns = mcf::now_ns() - t_start;
     return MCF_OK;
 }
 
-// ---- mcf_ubatch_validate / _validate_on_host: uniform_validate for every instance; independent of the solve state
-int check_check_io(const mcf_ubatch *b, const mcf_ubatch_check_io *io, const mcf_ubatch_check_summary *out, const char *what, bool host_only)
+// ---- mcf_*batch_validate / _validate_on_host: uniform_validate for every instance; independent of the solve state
+template <class P>
+int validate_on_device(typename P::Handle *b, BatchIo io, mcf_ubatch_check_summary *out, const char *what)
 {
-    if (!b || !io || !out) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
-    if (io->memory != MCF_MEM_HOST && io->memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io->memory);
-    if (host_only && io->memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
-    if (io->supply_type < MCF_SUPPLY_GEQ || io->supply_type > MCF_SUPPLY_EQ) return mcf::fail(MCF_ERR_INVALID, "%s: supply type %d", what, io->supply_type);
-    if (io->lower_stride < 0 || io->upper_stride < 0 || io->cost_stride < 0 || io->supply_stride < 0)
-        return mcf::fail(MCF_ERR_INVALID, "%s: negative stride", what);
-    if (b->d.count > 0 && (!io->status || !io->total_cost || !io->flows || !io->potentials))    // an empty tensor has no address
-        return mcf::fail(MCF_ERR_INVALID, "%s: status, total_cost, flows and potentials are the solution to check, all four are required", what);
-    return MCF_OK;
-}
-
-mcf::UniformProblem problem_of(const mcf_ubatch *b, const mcf_ubatch_check_io *io, const int32_t *source, const int32_t *target)
-{
-    mcf::UniformProblem p{};
-    p.n = b->d.node_count; p.m = b->d.arc_count; p.supply_type = io->supply_type;
-    p.source = source; p.target = target;
-    p.lower = io->lower; p.upper = io->upper; p.cost = io->cost; p.supply = io->supply;
-    p.lower_stride = io->lower_stride; p.upper_stride = io->upper_stride; p.cost_stride = io->cost_stride; p.supply_stride = io->supply_stride;
-    return p;
-}
-template <class CheckIo>
-mcf::UniformCheck check_of(const CheckIo *io, int64_t *summary)
-{
-    return mcf::UniformCheck{io->status, io->total_cost, io->valid, io->errors, io->first, io->objective, io->dual_cost, summary};
-}
-void summary_of(const int64_t words[2], int64_t count, mcf_ubatch_check_summary *out)
-{
-    out->instances = count;
-    out->invalid = words[0];
-    out->first_invalid = words[0] ? words[1] : -1;
-}
-
-int validate_on_device(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_check_summary *out)
-{
-    const char *const what = "mcf_ubatch_validate";
-    if (const int rc = check_check_io(b, io, out, what, false)) return rc;
+    if (!out) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_call<P>(b, io, what, false, false)) return rc;
     if (const int rc = have_device(b->d.device, what)) return rc;
     *out = mcf_ubatch_check_summary{};
     out->first_invalid = -1;
-    const size_t count = (size_t)b->d.count, n = (size_t)b->d.node_count, m = (size_t)b->d.arc_count;
+    const size_t count = (size_t)b->d.count;
     if (!count) return MCF_OK;
     const DeviceGuard guard;
     HIP_TRY(hipSetDevice(b->d.device));
-    if (const int rc = ensure_topology(b)) return rc;
-    // MCF_MEM_HOST: the arrays go through the staging buffer of mcf_ubatch_solve
-    mcf_ubatch_check_io dio = *io;
-    Staged staged;
-    if (io->memory == MCF_MEM_HOST) {
-        struct Piece { const void *in; void *out; size_t bytes; const void **slot; };
-        const Piece pieces[] = {{io->lower, nullptr, 8 * input_elements(count, io->lower_stride, m), (const void **)&dio.lower},
-                                {io->upper, nullptr, 8 * input_elements(count, io->upper_stride, m), (const void **)&dio.upper},
-                                {io->cost, nullptr, 8 * input_elements(count, io->cost_stride, m), (const void **)&dio.cost},
-                                {io->supply, nullptr, 8 * input_elements(count, io->supply_stride, n), (const void **)&dio.supply},
-                                {io->status, nullptr, 4 * count, (const void **)&dio.status},
-                                {io->total_cost, nullptr, 8 * count, (const void **)&dio.total_cost},
-                                {io->flows, nullptr, 8 * count * m, (const void **)&dio.flows},
-                                {io->potentials, nullptr, 8 * count * n, (const void **)&dio.potentials},
-                                {nullptr, io->valid, 4 * count, (const void **)&dio.valid},
-                                {nullptr, io->errors, 4 * count * MCF_VAL_KINDS, (const void **)&dio.errors},
-                                {nullptr, io->first, 4 * count * MCF_VAL_KINDS, (const void **)&dio.first},
-                                {nullptr, io->objective, 8 * count, (const void **)&dio.objective},
-                                {nullptr, io->dual_cost, 8 * count, (const void **)&dio.dual_cost}};
-        constexpr int kPieces = (int)(sizeof(pieces) / sizeof(pieces[0]));
-        size_t at[kPieces];
-        for (int k = 0; k < kPieces; ++k) at[k] = pieces[k].in || pieces[k].out ? staged.add(pieces[k].in, pieces[k].out, pieces[k].bytes) : 0;
-        if (const int rc = stage_send(b, staged, &out->bytes_up)) return rc;
-        for (int k = 0; k < kPieces; ++k) *pieces[k].slot = pieces[k].in || pieces[k].out ? b->d_io + at[k] : nullptr;
-    }
+    if (const int rc = ensure_tables<P>(b)) return rc;
+    Staged staged;                                                          // MCF_MEM_HOST: the arrays go through the staging buffer of the solve calls
+    if (const int rc = stage_up<P>(b, &io, &staged, &out->bytes_up)) return rc;
     int64_t words[2] = {0, INT64_MAX};
     HIP_TRY(hipMemcpy(b->d_summary, words, sizeof(words), hipMemcpyHostToDevice));
     out->bytes_up += (int64_t)sizeof(words);
     const double t_launch = mcf::now_ns();
-    hipLaunchKernelGGL(uniform_validate_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, problem_of(b, &dio, b->d_source, b->d_target),
-                       check_of(&dio, b->d_summary), b->d_inc_start, b->d_inc, dio.flows, dio.potentials);
+    P::launch_validate(b, P::problem(b, io, true), check_of(io, b->d_summary), io);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     out->kernel_ns = mcf::now_ns() - t_launch;
@@ -1228,18 +1411,26 @@ int validate_on_device(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_
     return MCF_OK;
 }
 
-int validate_on_host(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_check_summary *out)
+template <class P>
+int validate_on_host(typename P::Handle *b, const BatchIo &io, mcf_ubatch_check_summary *out, const char *what)
 {
-    if (const int rc = check_check_io(b, io, out, "mcf_ubatch_validate_on_host", true)) return rc;
+    if (!out) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_call<P>(b, io, what, true, false)) return rc;
     *out = mcf_ubatch_check_summary{};
     int64_t words[2] = {0, INT64_MAX};
-    const mcf::UniformProblem p = problem_of(b, io, b->source.data(), b->target.data());
+    const typename P::Problem p = P::problem(b, io, false);
     const mcf::UniformCheck c = check_of(io, words);
     const double t_start = mcf::now_ns();
-    for (int64_t i = 0; i < (int64_t)b->d.count; ++i)
-        mcf::uniform_validate(mcf::uniform_check_view(p, b->inc_start.data(), b->inc.data(), io->flows, io->potentials, i), c, 0, 1);
+    for (int64_t i = 0; i < (int64_t)b->d.count; ++i) mcf::uniform_validate(P::check_view(b, p, io, i), c, 0, 1);
     out->kernel_ns = mcf::now_ns() - t_start;
     summary_of(words, (int64_t)b->d.count, out);
+    return MCF_OK;
+}
+
+int get_stats(const PlacedBatch *b, mcf_ubatch_stats *out)
+{
+    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
+    *out = b->stats;
     return MCF_OK;
 }
 
@@ -1273,357 +1464,6 @@ int mcf_ubatch_create(mcf_ubatch **out, const mcf_ubatch_desc *desc)
     *out = b;
     return MCF_OK;
 }
-
-void mcf_ubatch_destroy(mcf_ubatch *b) { delete b; }
-int mcf_ubatch_solve(mcf_ubatch *b, const mcf_ubatch_io *io) { return ubatch_on_device(b, io, false); }
-int mcf_ubatch_resolve(mcf_ubatch *b, const mcf_ubatch_io *io) { return ubatch_on_device(b, io, true); }
-int mcf_ubatch_run_on_host(mcf_ubatch *b, const mcf_ubatch_io *io) { return ubatch_on_host(b, io, false); }
-int mcf_ubatch_rerun_on_host(mcf_ubatch *b, const mcf_ubatch_io *io) { return ubatch_on_host(b, io, true); }
-int mcf_ubatch_validate(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_check_summary *out) { return validate_on_device(b, io, out); }
-int mcf_ubatch_validate_on_host(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_check_summary *out) { return validate_on_host(b, io, out); }
-int mcf_ubatch_get_stats(mcf_ubatch *b, mcf_ubatch_stats *out)
-{
-    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
-    *out = b->stats;
-    return MCF_OK;
-}
-
-}  // extern "C"
-
-// ================================================================================================
-// mcf_rbatch_*: a set of graphs, every instance names its own; ragged rows in, ragged rows out ("Ragged batch")
-// ================================================================================================
-struct mcf_rbatch {
-    mcf_rbatch_desc d{};
-    // the tables of ragged_view, as the host hooks read them; the device gets one copy of all of them (d_tables)
-    std::vector<int32_t> source, target, inc_start, inc, graph_of;
-    std::vector<mcf::RaggedGraph> graphs;
-    std::vector<int64_t> arc_row, node_row;     // [count + 1]
-    std::vector<uint64_t> workspace;            // [count + 1]: the last entry is the slab's size
-    std::vector<uint32_t> footprint;            // [count]: layout_of(m + 2n, n + 1).bytes of the instance's graph
-    std::vector<BatchSlot> tmpl;                // one per graph (configure_slot): search_arcs, block configuration and limits go by n and m
-    enum Where { kNowhere, kOnHost, kOnDevice } where = kNowhere;
-    mcf_ubatch_stats stats{};
-    int lds_max = 0;
-    DeviceBuffers dev;                          // slab, slots, ids, traces
-    unsigned char *d_tables = nullptr;          // every table and the topology in one allocation; dt = the pointers into it
-    mcf::RaggedProblem dt{};
-    BatchSlot *d_tmpl = nullptr;                // [graph_count], sent with every solve call
-    int64_t *d_summary = nullptr;
-    unsigned char *d_io = nullptr;              // MCF_MEM_HOST: the caller's arrays on their way up and down
-    size_t d_io_bytes = 0;
-    std::vector<unsigned char> h_slab;          // the host hooks' slab, slots and traces: the device's layout
-    std::vector<BatchSlot> h_slots;
-    std::vector<int32_t> h_traces;
-    ~mcf_rbatch()
-    {
-        if (d_tables) (void)hipFree(d_tables);
-        if (d_tmpl) (void)hipFree(d_tmpl);
-        if (d_summary) (void)hipFree(d_summary);
-        if (d_io) (void)hipFree(d_io);
-    }
-};
-
-namespace {
-
-template <class Io>
-int check_ragged_io(const mcf_rbatch *b, const Io *io, const char *what, bool host_only, bool solve_call)
-{
-    if (!b || !io) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
-    if (io->memory != MCF_MEM_HOST && io->memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io->memory);
-    if (host_only && io->memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
-    if (solve_call) {
-        if (io->supply_type != MCF_SUPPLY_GEQ && io->supply_type != MCF_SUPPLY_LEQ) return mcf::fail(MCF_ERR_INVALID, "Invalid supply type");
-    } else if (io->supply_type < MCF_SUPPLY_GEQ || io->supply_type > MCF_SUPPLY_EQ) {
-        return mcf::fail(MCF_ERR_INVALID, "%s: supply type %d", what, io->supply_type);
-    }
-    return MCF_OK;
-}
-
-// the tables where the host hooks read them, with the rows of io
-template <class Io>
-mcf::RaggedProblem ragged_problem(const mcf_rbatch *b, const mcf::RaggedProblem &tables, const Io *io, const uint8_t *changed)
-{
-    mcf::RaggedProblem r = tables;
-    r.supply_type = io->supply_type; r.trace_cap = b->d.trace_capacity;
-    r.lower = io->lower; r.upper = io->upper; r.cost = io->cost; r.supply = io->supply;
-    r.changed = changed;
-    return r;
-}
-mcf::RaggedProblem host_tables(const mcf_rbatch *b)
-{
-    mcf::RaggedProblem r{};
-    r.graph_of = b->graph_of.data(); r.graphs = b->graphs.data();
-    r.arc_row = b->arc_row.data(); r.node_row = b->node_row.data(); r.workspace = b->workspace.data();
-    r.source = b->source.data(); r.target = b->target.data(); r.inc_start = b->inc_start.data(); r.inc = b->inc.data();
-    return r;
-}
-
-// the tables, the topology and its incidence lists go up once per handle, in one copy, with its first device call of any kind
-int ensure_tables(mcf_rbatch *b)
-{
-    if (b->d_summary) return MCF_OK;
-    struct Part { const void *host; size_t bytes; size_t at; };
-    const size_t count = (size_t)b->d.count;
-    Part parts[] = {{b->graph_of.data(), count * sizeof(int32_t), 0},
-                    {b->graphs.data(), b->graphs.size() * sizeof(mcf::RaggedGraph), 0},
-                    {b->arc_row.data(), (count + 1) * sizeof(int64_t), 0},
-                    {b->node_row.data(), (count + 1) * sizeof(int64_t), 0},
-                    {b->workspace.data(), count * sizeof(uint64_t), 0},
-                    {b->source.data(), b->source.size() * sizeof(int32_t), 0},
-                    {b->target.data(), b->target.size() * sizeof(int32_t), 0},
-                    {b->inc_start.data(), b->inc_start.size() * sizeof(int32_t), 0},
-                    {b->inc.data(), b->inc.size() * sizeof(int32_t), 0}};
-    size_t total = 0;
-    for (Part &pt : parts) { pt.at = total; total += (pt.bytes + 15) & ~(size_t)15; }
-    std::vector<unsigned char> image(total, 0);
-    for (const Part &pt : parts)
-        if (pt.bytes) memcpy(image.data() + pt.at, pt.host, pt.bytes);
-    // a call that failed half way left what it had allocated: those are kept and filled again, not allocated twice
-    if (!b->d_tables) HIP_TRY(hipMalloc((void **)&b->d_tables, std::max<size_t>(total, 16)));
-    if (total) HIP_TRY(hipMemcpy(b->d_tables, image.data(), total, hipMemcpyHostToDevice));
-    if (!b->d_tmpl) HIP_TRY(hipMalloc((void **)&b->d_tmpl, std::max<size_t>(b->tmpl.size(), 1) * sizeof(BatchSlot)));
-    unsigned char *const base = b->d_tables;
-    mcf::RaggedProblem &r = b->dt;
-    r = mcf::RaggedProblem{};
-    r.graph_of = (const int32_t *)(base + parts[0].at); r.graphs = (const mcf::RaggedGraph *)(base + parts[1].at);
-    r.arc_row = (const int64_t *)(base + parts[2].at); r.node_row = (const int64_t *)(base + parts[3].at);
-    r.workspace = (const uint64_t *)(base + parts[4].at);
-    r.source = (const int32_t *)(base + parts[5].at); r.target = (const int32_t *)(base + parts[6].at);
-    r.inc_start = (const int32_t *)(base + parts[7].at); r.inc = (const int32_t *)(base + parts[8].at);
-    HIP_TRY(hipMalloc((void **)&b->d_summary, 2 * sizeof(int64_t)));          // last: it says the rest is there
-    return MCF_OK;
-}
-
-int ensure_device_buffers(mcf_rbatch *b)
-{
-    if (const int rc = ensure_tables(b)) return rc;
-    if (b->dev.slab) return MCF_OK;
-    const size_t count = (size_t)b->d.count;
-    HIP_TRY(hipMalloc((void **)&b->dev.slab, std::max<size_t>((size_t)b->workspace[count], 16)));
-    HIP_TRY(hipMalloc((void **)&b->dev.slots, count * sizeof(BatchSlot)));
-    HIP_TRY(hipMalloc((void **)&b->dev.ids, count * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void **)&b->dev.traces, std::max<size_t>(count * (size_t)b->d.trace_capacity, 1) * sizeof(int32_t)));
-    return MCF_OK;
-}
-
-// MCF_MEM_HOST: as stage_up for the uniform batch, with the ragged totals for lengths
-int ragged_stage_up(mcf_rbatch *b, const mcf_rbatch_io *io, bool resolve, mcf_rbatch_io *dio, Staged *st)
-{
-    *dio = *io;
-    if (io->memory == MCF_MEM_DEVICE) return MCF_OK;
-    const size_t count = (size_t)b->d.count, arcs = (size_t)b->arc_row[count], nodes = (size_t)b->node_row[count], cap = (size_t)b->d.trace_capacity;
-    const bool keep_rows = resolve && io->changed;
-    struct In { const void *p; size_t bytes; const void **slot; };
-    const In ins[] = {{io->lower, 8 * arcs, (const void **)&dio->lower}, {io->upper, 8 * arcs, (const void **)&dio->upper},
-                      {io->cost, 8 * arcs, (const void **)&dio->cost},   {io->supply, 8 * nodes, (const void **)&dio->supply},
-                      {resolve ? io->changed : nullptr, count, (const void **)&dio->changed}};
-    struct Out { void *p; size_t bytes; void **slot; };
-    const Out outs[] = {{io->status, 4 * count, (void **)&dio->status},       {io->pivots, 8 * count, (void **)&dio->pivots},
-                        {io->total_cost, 8 * count, (void **)&dio->total_cost}, {io->flows, 8 * arcs, (void **)&dio->flows},
-                        {io->potentials, 8 * nodes, (void **)&dio->potentials}, {io->trace, 4 * count * cap, (void **)&dio->trace}};
-    size_t at_in[5], at_out[6];
-    for (int k = 0; k < 5; ++k) at_in[k] = ins[k].p ? st->add(ins[k].p, nullptr, ins[k].bytes) : 0;
-    for (int k = 0; k < 6; ++k) at_out[k] = outs[k].p ? st->add(keep_rows ? outs[k].p : nullptr, outs[k].p, outs[k].bytes) : 0;
-    if (const int rc = stage_send(b, *st, &b->stats.bytes_up)) return rc;
-    for (int k = 0; k < 5; ++k) *ins[k].slot = ins[k].p ? b->d_io + at_in[k] : nullptr;
-    for (int k = 0; k < 6; ++k) *outs[k].slot = outs[k].p ? b->d_io + at_out[k] : nullptr;
-    return MCF_OK;
-}
-
-mcf::UniformOutputs outputs_of(const mcf_rbatch_io *io)
-{
-    return mcf::UniformOutputs{io->status, io->pivots, io->total_cost, io->flows, io->potentials, io->trace};
-}
-
-// mcf_rbatch_solve and mcf_rbatch_resolve: ubatch_on_device with the ragged kernels round the same launch loop; the footprint per
-// instance decides each instance's class
-int rbatch_on_device(mcf_rbatch *b, const mcf_rbatch_io *io, bool resolve)
-{
-    const char *const what = resolve ? "mcf_rbatch_resolve" : "mcf_rbatch_solve";
-    if (const int rc = check_ragged_io(b, io, what, false, true)) return rc;
-    if (resolve && b->where == mcf_rbatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
-    if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
-    const double t_start = mcf::now_ns();
-    const DeviceGuard guard;
-    if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
-    const size_t count = (size_t)b->d.count;
-    b->stats = mcf_ubatch_stats{};
-    b->stats.instances = (int64_t)count;
-    for (size_t i = 0; i < count; ++i)
-        (class_of(b->lds_max, b->footprint[i]) != kClasses - 1 ? b->stats.lds_instances : b->stats.global_instances)++;
-    b->stats.workspace_bytes = (int64_t)b->workspace[count];
-    if (!count) { b->where = mcf_rbatch::kOnDevice; b->stats.host_ns = mcf::now_ns() - t_start; return MCF_OK; }
-    if (const int rc = ensure_device_buffers(b)) return rc;
-    DeviceBuffers &dev = b->dev;
-    if (resolve && b->where == mcf_rbatch::kOnHost) {                       // the last solve was a host hook's: its state goes up whole
-        if (!b->h_slab.empty()) HIP_TRY(hipMemcpy(dev.slab, b->h_slab.data(), b->h_slab.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dev.slots, b->h_slots.data(), count * sizeof(BatchSlot), hipMemcpyHostToDevice));
-        b->stats.bytes_up += (int64_t)(b->h_slab.size() + count * sizeof(BatchSlot));
-    }
-    mcf_rbatch_io dio;
-    Staged staged;
-    if (const int rc = ragged_stage_up(b, io, resolve, &dio, &staged)) return rc;
-    const mcf::RaggedProblem r = ragged_problem(b, b->dt, &dio, resolve ? dio.changed : nullptr);
-
-    const double t_begin = mcf::now_ns();
-    HIP_TRY(hipMemcpy(b->d_tmpl, b->tmpl.data(), b->tmpl.size() * sizeof(BatchSlot), hipMemcpyHostToDevice));
-    b->stats.bytes_up += (int64_t)(b->tmpl.size() * sizeof(BatchSlot));
-    if (resolve) hipLaunchKernelGGL(ragged_recost_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, r, b->d_tmpl, dev.slots, dev.slab);
-    else hipLaunchKernelGGL(ragged_begin_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, r, b->d_tmpl, dev.slots, dev.slab);
-    HIP_TRY(hipGetLastError());
-    b->where = mcf_rbatch::kOnDevice;
-    std::vector<BatchSlot> slots(count);
-    HIP_TRY(hipMemcpy(slots.data(), dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));      // waits for the launch; says who runs
-    b->stats.bytes_down += (int64_t)(count * sizeof(BatchSlot));
-    b->stats.begin_ns = mcf::now_ns() - t_begin;
-
-    std::vector<int32_t> run;
-    for (size_t i = 0; i < count; ++i)
-        if (slots[i].run == mcf::kBatchRunning) run.push_back((int32_t)i);
-    LaunchTotals t;
-    if (const int rc = run_launches(LaunchPlan{&dev, b->lds_max, b->d.pivots_per_launch, b->footprint.data(), 0}, slots, run, &t)) return rc;
-    for (int32_t i : run) b->stats.total_pivots += slots[(size_t)i].pivots;
-    b->stats.launches = t.launches;
-    b->stats.lds_bytes_max = t.lds_bytes_max;
-    b->stats.bytes_up += t.bytes_up;
-    b->stats.bytes_down += t.bytes_down;
-    b->stats.kernel_ns = t.kernel_ns;
-
-    const double t_finish = mcf::now_ns();
-    hipLaunchKernelGGL(ragged_finish_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, r, outputs_of(&dio), dev.slots, dev.slab, dev.traces);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    b->stats.finish_ns = mcf::now_ns() - t_finish;
-    if (const int rc = stage_down(b, staged, &b->stats.bytes_down)) return rc;
-    b->stats.host_ns = mcf::now_ns() - t_start - t.kernel_ns;
-    return MCF_OK;
-}
-
-// the host hooks: the same steps and batch_run with one lane, on a host slab of the device's layout
-int rbatch_on_host(mcf_rbatch *b, const mcf_rbatch_io *io, bool resolve)
-{
-    const char *const what = resolve ? "mcf_rbatch_rerun_on_host" : "mcf_rbatch_run_on_host";
-    if (const int rc = check_ragged_io(b, io, what, true, true)) return rc;
-    if (resolve && b->where == mcf_rbatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
-    const double t_start = mcf::now_ns();
-    const size_t count = (size_t)b->d.count;
-    b->h_slab.resize((size_t)b->workspace[count]);
-    b->h_slots.resize(count);
-    b->h_traces.resize(std::max<size_t>(count * (size_t)b->d.trace_capacity, 1));
-    if (resolve && b->where == mcf_rbatch::kOnDevice && count) {            // the last solve was the device's: its state comes down whole
-        const DeviceGuard guard;
-        HIP_TRY(hipSetDevice(b->d.device));
-        if (!b->h_slab.empty()) HIP_TRY(hipMemcpy(b->h_slab.data(), b->dev.slab, b->h_slab.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(b->h_slots.data(), b->dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));
-    }
-    b->stats = mcf_ubatch_stats{};
-    b->stats.instances = (int64_t)count;
-    b->stats.workspace_bytes = (int64_t)b->h_slab.size();
-    const mcf::RaggedProblem r = ragged_problem(b, host_tables(b), io, resolve ? io->changed : nullptr);
-    const mcf::UniformOutputs o = outputs_of(io);
-    for (size_t i = 0; i < count; ++i) {
-        if (r.changed && !r.changed[i]) continue;
-        BatchSlot &slot = b->h_slots[i];
-        int32_t t = 0;
-        const mcf::InstanceView v = mcf::ragged_view(r, &o, (int64_t)i, b->h_slab.data(), &t);
-        if (resolve) mcf::uniform_recost(v, b->tmpl[(size_t)t], slot, 0, 1);
-        else mcf::uniform_begin(v, b->tmpl[(size_t)t], slot, 0, 1);
-        if (slot.run == mcf::kBatchRunning) {
-            mcf::BatchWork w{};
-            load_slot(w, slot, b->h_traces.data());
-            bind(w, v.home, layout_of((uint32_t)slot.all_arcs, (uint32_t)slot.n + 1u));
-            if (slot.reprice) mcf::batch_reprice(w, 0, 1);
-            mcf::batch_run(w, 0, 1, INT64_MAX);
-            store_slot(slot, w);
-            b->stats.total_pivots += slot.pivots;
-        }
-        mcf::uniform_finish(v, o, slot, b->h_traces.data(), 0, 1);
-    }
-    b->where = mcf_rbatch::kOnHost;
-    b->stats.host_ns = mcf::now_ns() - t_start;
-    return MCF_OK;
-}
-
-int check_ragged_check_io(const mcf_rbatch *b, const mcf_rbatch_check_io *io, const mcf_ubatch_check_summary *out, const char *what, bool host_only)
-{
-    if (!out) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
-    if (const int rc = check_ragged_io(b, io, what, host_only, false)) return rc;
-    const size_t count = (size_t)b->d.count;
-    if (count > 0 && (!io->status || !io->total_cost || (b->arc_row[count] && !io->flows) || (b->node_row[count] && !io->potentials)))    // an empty tensor has no address
-        return mcf::fail(MCF_ERR_INVALID, "%s: status, total_cost, flows and potentials are the solution to check, all four are required", what);
-    return MCF_OK;
-}
-
-int rbatch_validate_on_device(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out)
-{
-    const char *const what = "mcf_rbatch_validate";
-    if (const int rc = check_ragged_check_io(b, io, out, what, false)) return rc;
-    if (const int rc = have_device(b->d.device, what)) return rc;
-    *out = mcf_ubatch_check_summary{};
-    out->first_invalid = -1;
-    const size_t count = (size_t)b->d.count;
-    if (!count) return MCF_OK;
-    const size_t arcs = (size_t)b->arc_row[count], nodes = (size_t)b->node_row[count];
-    const DeviceGuard guard;
-    HIP_TRY(hipSetDevice(b->d.device));
-    if (const int rc = ensure_tables(b)) return rc;
-    mcf_rbatch_check_io dio = *io;
-    Staged staged;
-    if (io->memory == MCF_MEM_HOST) {
-        struct Piece { const void *in; void *out; size_t bytes; const void **slot; };
-        const Piece pieces[] = {{io->lower, nullptr, 8 * arcs, (const void **)&dio.lower},
-                                {io->upper, nullptr, 8 * arcs, (const void **)&dio.upper},
-                                {io->cost, nullptr, 8 * arcs, (const void **)&dio.cost},
-                                {io->supply, nullptr, 8 * nodes, (const void **)&dio.supply},
-                                {io->status, nullptr, 4 * count, (const void **)&dio.status},
-                                {io->total_cost, nullptr, 8 * count, (const void **)&dio.total_cost},
-                                {io->flows, nullptr, 8 * arcs, (const void **)&dio.flows},
-                                {io->potentials, nullptr, 8 * nodes, (const void **)&dio.potentials},
-                                {nullptr, io->valid, 4 * count, (const void **)&dio.valid},
-                                {nullptr, io->errors, 4 * count * MCF_VAL_KINDS, (const void **)&dio.errors},
-                                {nullptr, io->first, 4 * count * MCF_VAL_KINDS, (const void **)&dio.first},
-                                {nullptr, io->objective, 8 * count, (const void **)&dio.objective},
-                                {nullptr, io->dual_cost, 8 * count, (const void **)&dio.dual_cost}};
-        constexpr int kPieces = (int)(sizeof(pieces) / sizeof(pieces[0]));
-        size_t at[kPieces];
-        for (int k = 0; k < kPieces; ++k) at[k] = pieces[k].in || pieces[k].out ? staged.add(pieces[k].in, pieces[k].out, pieces[k].bytes) : 0;
-        if (const int rc = stage_send(b, staged, &out->bytes_up)) return rc;
-        for (int k = 0; k < kPieces; ++k) *pieces[k].slot = pieces[k].in || pieces[k].out ? b->d_io + at[k] : nullptr;
-    }
-    int64_t words[2] = {0, INT64_MAX};
-    HIP_TRY(hipMemcpy(b->d_summary, words, sizeof(words), hipMemcpyHostToDevice));
-    out->bytes_up += (int64_t)sizeof(words);
-    const double t_launch = mcf::now_ns();
-    hipLaunchKernelGGL(ragged_validate_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, ragged_problem(b, b->dt, &dio, nullptr),
-                       check_of(&dio, b->d_summary), dio.flows, dio.potentials);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    out->kernel_ns = mcf::now_ns() - t_launch;
-    HIP_TRY(hipMemcpy(words, b->d_summary, sizeof(words), hipMemcpyDeviceToHost));
-    out->bytes_down += (int64_t)sizeof(words);
-    if (const int rc = stage_down(b, staged, &out->bytes_down)) return rc;
-    summary_of(words, (int64_t)count, out);
-    return MCF_OK;
-}
-
-int rbatch_validate_on_host(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out)
-{
-    if (const int rc = check_ragged_check_io(b, io, out, "mcf_rbatch_validate_on_host", true)) return rc;
-    *out = mcf_ubatch_check_summary{};
-    int64_t words[2] = {0, INT64_MAX};
-    const mcf::RaggedProblem r = ragged_problem(b, host_tables(b), io, nullptr);
-    const mcf::UniformCheck c = check_of(io, words);
-    const double t_start = mcf::now_ns();
-    for (int64_t i = 0; i < (int64_t)b->d.count; ++i) mcf::uniform_validate(mcf::ragged_check_view(r, io->flows, io->potentials, i), c, 0, 1);
-    out->kernel_ns = mcf::now_ns() - t_start;
-    summary_of(words, (int64_t)b->d.count, out);
-    return MCF_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int mcf_rbatch_create(mcf_rbatch **out, const mcf_rbatch_desc *desc)
 {
@@ -1694,7 +1534,6 @@ int mcf_rbatch_create(mcf_rbatch **out, const mcf_rbatch_desc *desc)
     return MCF_OK;
 }
 
-void mcf_rbatch_destroy(mcf_rbatch *b) { delete b; }
 int mcf_rbatch_get_rows(mcf_rbatch *b, int64_t *arc_row, int64_t *node_row)
 {
     if (!b) return mcf::fail(MCF_ERR_INVALID, "null argument");
@@ -1702,17 +1541,35 @@ int mcf_rbatch_get_rows(mcf_rbatch *b, int64_t *arc_row, int64_t *node_row)
     if (node_row) std::copy(b->node_row.begin(), b->node_row.end(), node_row);
     return MCF_OK;
 }
-int mcf_rbatch_solve(mcf_rbatch *b, const mcf_rbatch_io *io) { return rbatch_on_device(b, io, false); }
-int mcf_rbatch_resolve(mcf_rbatch *b, const mcf_rbatch_io *io) { return rbatch_on_device(b, io, true); }
-int mcf_rbatch_run_on_host(mcf_rbatch *b, const mcf_rbatch_io *io) { return rbatch_on_host(b, io, false); }
-int mcf_rbatch_rerun_on_host(mcf_rbatch *b, const mcf_rbatch_io *io) { return rbatch_on_host(b, io, true); }
-int mcf_rbatch_validate(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out) { return rbatch_validate_on_device(b, io, out); }
-int mcf_rbatch_validate_on_host(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out) { return rbatch_validate_on_host(b, io, out); }
-int mcf_rbatch_get_stats(mcf_rbatch *b, mcf_ubatch_stats *out)
+
+void mcf_ubatch_destroy(mcf_ubatch *b) { delete b; }
+int mcf_ubatch_solve(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_device<UniformPlacement>(b, io_of(io), false, "mcf_ubatch_solve"); }
+int mcf_ubatch_resolve(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_device<UniformPlacement>(b, io_of(io), true, "mcf_ubatch_resolve"); }
+int mcf_ubatch_run_on_host(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_host<UniformPlacement>(b, io_of(io), false, "mcf_ubatch_run_on_host"); }
+int mcf_ubatch_rerun_on_host(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_host<UniformPlacement>(b, io_of(io), true, "mcf_ubatch_rerun_on_host"); }
+int mcf_ubatch_validate(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_check_summary *out)
 {
-    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
-    *out = b->stats;
-    return MCF_OK;
+    return validate_on_device<UniformPlacement>(b, io_of(io), out, "mcf_ubatch_validate");
 }
+int mcf_ubatch_validate_on_host(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_check_summary *out)
+{
+    return validate_on_host<UniformPlacement>(b, io_of(io), out, "mcf_ubatch_validate_on_host");
+}
+int mcf_ubatch_get_stats(mcf_ubatch *b, mcf_ubatch_stats *out) { return get_stats(b, out); }
+
+void mcf_rbatch_destroy(mcf_rbatch *b) { delete b; }
+int mcf_rbatch_solve(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_device<RaggedPlacement>(b, io_of(io), false, "mcf_rbatch_solve"); }
+int mcf_rbatch_resolve(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_device<RaggedPlacement>(b, io_of(io), true, "mcf_rbatch_resolve"); }
+int mcf_rbatch_run_on_host(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_host<RaggedPlacement>(b, io_of(io), false, "mcf_rbatch_run_on_host"); }
+int mcf_rbatch_rerun_on_host(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_host<RaggedPlacement>(b, io_of(io), true, "mcf_rbatch_rerun_on_host"); }
+int mcf_rbatch_validate(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out)
+{
+    return validate_on_device<RaggedPlacement>(b, io_of(io), out, "mcf_rbatch_validate");
+}
+int mcf_rbatch_validate_on_host(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out)
+{
+    return validate_on_host<RaggedPlacement>(b, io_of(io), out, "mcf_rbatch_validate_on_host");
+}
+int mcf_rbatch_get_stats(mcf_rbatch *b, mcf_ubatch_stats *out) { return get_stats(b, out); }
 
 }  // extern "C"

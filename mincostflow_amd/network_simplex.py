@@ -440,36 +440,49 @@ def _is_tensor(a) -> bool:
     return type(a).__module__.split(".")[0] == "torch"
 
 
-class UniformBatch:
-    """`count` instances of ONE graph, solved on the device from arrays that already are there (mcf_ubatch_*, DESIGN.md 3.14 "Uniform
-    batch").  solve() and resolve() take either numpy arrays (copied up and down, one copy per array) or torch tensors on the handle's
-    device (read and written in place: nothing that scales with the graph crosses the bus) -- never a mix; each array is [count, m]
-    ([count, n] for supply) or [m] ([n]) for one row shared by all, int64, contiguous in its last dimension.  Results equal
-    BatchSolver's for the same instances bit for bit.  run_on_host() / rerun_on_host() are test hooks (numpy only)."""
+class RaggedResult(UniformResult):
+    """What RaggedBatch.solve / .resolve return: UniformResult's fields with flows and potentials FLAT -- instance i's arcs are
+    flows[arc_rows[i]:arc_rows[i + 1]], its nodes potentials[node_rows[i]:node_rows[i + 1]]; arcs(i) and nodes(i) return those slices
+    (views, numpy or tensor like the arrays).  status, pivots and total_cost are [count], trace is [count, record_trace]."""
+    __slots__ = ("arc_rows", "node_rows")
 
-    def __init__(self, node_count, source, target, count, rule=PivotRule.BlockSearch, pivot_limit=0, record_trace=0, device=0, pivots_per_launch=0,
-                 semantics=L.SEM_PLAIN, flags=0):
-        src, tgt = _i32(source), _i32(target)
-        if src.ndim != 1 or src.shape != tgt.shape:
-            raise ValueError("source and target must be one-dimensional and of equal length")
-        self.node_count, self.arc_count, self.count, self.device, self.record_trace = int(node_count), int(src.shape[0]), int(count), int(device), int(record_trace)
-        self._h = C.c_void_p()
-        self._last = None               # the last UniformResult: a masked resolve() starts from its rows
-        d = L.UBatchDesc(self.device, int(rule), int(semantics), 0, int(pivot_limit), int(pivots_per_launch), self.record_trace, int(flags),
-                         self.node_count, self.arc_count, self.count, src.ctypes.data, tgt.ctypes.data)
-        L.check(L.lib().mcf_ubatch_create(C.byref(self._h), C.byref(d)))
+    def __init__(self, arc_rows, node_rows, **arrays):
+        super().__init__(**arrays)
+        self.arc_rows, self.node_rows = arc_rows, node_rows
+
+    def arcs(self, i: int):
+        return self.flows[int(self.arc_rows[i]):int(self.arc_rows[i + 1])]
+
+    def nodes(self, i: int):
+        return self.potentials[int(self.node_rows[i]):int(self.node_rows[i + 1])]
+
+
+class _PlacedBatch:
+    """What UniformBatch and RaggedBatch share: the checks of every array of a call, the calls and their results.  A subclass has the
+    constructor (which sets _h, _last = None, count, device, record_trace) and says what differs:
+      _PREFIX            the library's functions are <_PREFIX>_solve, _resolve, ...
+      _IO, _CHECK_IO     the ctypes structs of a solve call and of a validation call
+      _RESULT            the result class; _result(out) makes one
+      _sizes()           the shapes of the outputs by UniformResult.FIELDS' dimension key
+      _stride(...)       the expected shape of the array of a given name, its contiguity, and the stride it is passed with"""
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
-            L.lib().mcf_ubatch_destroy(h)
+            self._fn("destroy")(h)
             self._h = None
 
     def __len__(self):
         return self.count
 
+    def _fn(self, name):
+        return getattr(L.lib(), f"{self._PREFIX}_{name}")
+
+    def _result(self, out):
+        return self._RESULT(**out)
+
     # ---- one input: (pointer, stride in elements, the object that keeps the memory alive)
-    def _input(self, a, name, length, tensors, dtype="int64", rows_only=False):
+    def _input(self, a, name, tensors, dtype="int64"):
         if a is None:
             return None, 0, None
         if tensors:
@@ -488,24 +501,29 @@ class UniformBatch:
                 a = np.asarray(a, dtype)
             if a.dtype != np.dtype(dtype):
                 raise ValueError(f"{name}: dtype {a.dtype}, expected {dtype}")
-            shape, strides = a.shape, tuple(s // a.itemsize for s in a.strides)
-        if rows_only:
-            ok = shape == (self.count,)
-        else:
-            ok = shape in ((length,), (self.count, length))
-        if not ok:
-            raise ValueError(f"{name}: shape {tuple(shape)}, expected ({length},) or ({self.count}, {length})" if not rows_only else f"{name}: shape {tuple(shape)}, expected ({self.count},)")
-        if self.count > 0 and shape[-1] > 1 and strides[-1] != 1:
-            raise ValueError(f"{name}: not contiguous in its last dimension")
-        stride = 0 if len(shape) == 1 or rows_only else (strides[0] if self.count > 1 else 0)
-        if stride < 0 or (len(shape) == 2 and self.count > 1 and 0 < stride < length):
-            raise ValueError(f"{name}: rows overlap")
-        ptr = a.data_ptr() if tensors else a.ctypes.data
-        return ptr, int(stride), a
+            shape, strides = tuple(a.shape), tuple(s // a.itemsize for s in a.strides)
+        stride = self._stride(name, shape, strides)
+        return (a.data_ptr() if tensors else a.ctypes.data), int(stride), a
+
+    def _problem(self, io, arrays, tensors, keep):
+        """cost, supply, lower, upper into io"""
+        io.memory = L.MEM_DEVICE if tensors else L.MEM_HOST
+        for name, a in zip(("cost", "supply", "lower", "upper"), arrays):
+            ptr, stride, obj = self._input(a, name, tensors)
+            keep.append(obj)
+            setattr(io, name, ptr)
+            if hasattr(io, name + "_stride"):
+                setattr(io, name + "_stride", stride)
+
+    def _empty(self, shape, dtype, tensors):
+        if tensors:
+            import torch
+            return torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{self.device}")
+        return np.empty(shape, dtype)
 
     def _outputs(self, tensors, like):
         """Fresh rows, or copies of `like` (the last result) for a call that does not write every row."""
-        sizes = {"": (self.count,), "m": (self.count, self.arc_count), "n": (self.count, self.node_count), "t": (self.count, self.record_trace)}
+        sizes = self._sizes()
         out = {}
         for name, dtype, dim in UniformResult.FIELDS:
             if like is not None:
@@ -513,11 +531,8 @@ class UniformBatch:
                 if _is_tensor(prev) != tensors:
                     raise ValueError("a masked resolve() continues the last result: numpy arrays and tensors cannot be mixed")
                 out[name] = prev.clone() if tensors else prev.copy()
-            elif tensors:
-                import torch
-                out[name] = torch.empty(sizes[dim], dtype=getattr(torch, dtype), device=f"cuda:{self.device}")
             else:
-                out[name] = np.empty(sizes[dim], dtype)
+                out[name] = self._empty(sizes[dim], dtype, tensors)
         return out
 
     def _call(self, fn, cost, supply, lower, upper, supply_type, changed=None, masked=False, numpy_only=False):
@@ -526,13 +541,9 @@ class UniformBatch:
         if tensors and numpy_only:
             raise ValueError("the host hooks take numpy arrays")
         keep = []
-        io = L.UBatchIo()
-        io.memory, io.supply_type = (L.MEM_DEVICE if tensors else L.MEM_HOST), int(supply_type)
-        for name, a, length in (("cost", cost, self.arc_count), ("supply", supply, self.node_count), ("lower", lower, self.arc_count), ("upper", upper, self.arc_count)):
-            ptr, stride, obj = self._input(a, name, length, tensors)
-            keep.append(obj)
-            setattr(io, name, ptr)
-            setattr(io, name + "_stride", stride)
+        io = self._IO()
+        io.supply_type = int(supply_type)
+        self._problem(io, (cost, supply, lower, upper), tensors, keep)
         if changed is not None:
             if not tensors and not isinstance(changed, np.ndarray):
                 changed = np.asarray(changed)
@@ -542,7 +553,7 @@ class UniformBatch:
                 import torch
                 if changed.dtype == torch.bool:
                     changed = changed.view(torch.uint8)
-            ptr, _, obj = self._input(changed, "changed", self.count, tensors, dtype="uint8", rows_only=True)
+            ptr, _, obj = self._input(changed, "changed", tensors, dtype="uint8")
             keep.append(obj)
             io.changed = ptr
         if masked and changed is not None and self._last is None:
@@ -550,30 +561,30 @@ class UniformBatch:
         out = self._outputs(tensors, self._last if masked and changed is not None else None)
         for name, arr in out.items():
             setattr(io, name, arr.data_ptr() if tensors else arr.ctypes.data)
-        L.check(fn(self._h, C.byref(io)))
-        self._last = UniformResult(**out)
+        L.check(self._fn(fn)(self._h, C.byref(io)))
+        self._last = self._result(out)
         return self._last
 
     def solve(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> UniformResult:
         """A fresh solve of every instance; may be repeated with other supplies, bounds or costs."""
-        return self._call(L.lib().mcf_ubatch_solve, cost, supply, lower, upper, supply_type)
+        return self._call("solve", cost, supply, lower, upper, supply_type)
 
     def resolve(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq, changed=None) -> UniformResult:
         """New costs for the instances `changed` marks ([count] bool / uint8, None = all): each goes on from the basis its last solve left
         where that ended Optimal.  supply, lower, upper and supply_type must be what the last solve() was given.  Rows of unmarked
         instances are the last result's."""
-        return self._call(L.lib().mcf_ubatch_resolve, cost, supply, lower, upper, supply_type, changed, masked=True)
+        return self._call("resolve", cost, supply, lower, upper, supply_type, changed, masked=True)
 
     def run_on_host(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> UniformResult:
         """Test hook: solve() with one lane on the CPU.  numpy only."""
-        return self._call(L.lib().mcf_ubatch_run_on_host, cost, supply, lower, upper, supply_type, numpy_only=True)
+        return self._call("run_on_host", cost, supply, lower, upper, supply_type, numpy_only=True)
 
     def rerun_on_host(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq, changed=None) -> UniformResult:
         """Test hook: resolve() with one lane on the CPU.  numpy only."""
-        return self._call(L.lib().mcf_ubatch_rerun_on_host, cost, supply, lower, upper, supply_type, changed, masked=True, numpy_only=True)
+        return self._call("rerun_on_host", cost, supply, lower, upper, supply_type, changed, masked=True, numpy_only=True)
 
     def stats(self) -> dict:
-        st = L.UBatchStats(); L.check(L.lib().mcf_ubatch_get_stats(self._h, C.byref(st))); return st.as_dict()
+        st = L.UBatchStats(); L.check(self._fn("get_stats")(self._h, C.byref(st))); return st.as_dict()
 
     # ---- validation: the solution's rows where they lie
     SOLUTION_ROWS = (("status", "int32", None), ("total_cost", "int64", None), ("flows", "int64", "arc_count"), ("potentials", "int64", "node_count"))
@@ -585,67 +596,83 @@ class UniformBatch:
             rows = tuple(getattr(rows, name) for name, _, _ in self.SOLUTION_ROWS)
         rows = tuple(rows)
         if len(rows) != 4 or any(r is None for r in rows):
-            raise ValueError("the solution to check is status, total_cost, flows and potentials: a UniformResult, a dict or the four rows")
+            raise ValueError(f"the solution to check is status, total_cost, flows and potentials: a {self._RESULT.__name__}, a dict or the four rows")
         tensors = any(_is_tensor(a) for a in (*rows, cost, supply, lower, upper) if a is not None)
         if tensors and numpy_only:
             raise ValueError("the host hooks take numpy arrays")
         keep = []
-        io = L.UBatchCheckIo()
-        io.memory, io.supply_type = (L.MEM_DEVICE if tensors else L.MEM_HOST), int(supply_type)
-        for name, a, length in (("cost", cost, self.arc_count), ("supply", supply, self.node_count), ("lower", lower, self.arc_count), ("upper", upper, self.arc_count)):
-            ptr, stride, obj = self._input(a, name, length, tensors)
-            keep.append(obj)
-            setattr(io, name, ptr)
-            setattr(io, name + "_stride", stride)
-        for (name, dtype, dim), a in zip(self.SOLUTION_ROWS, rows):
-            length = getattr(self, dim) if dim else None
-            ptr, stride, obj = self._input(a, name, length, tensors, dtype=dtype, rows_only=dim is None)
-            if dim and (len(obj.shape) != 2 or (self.count > 1 and stride != length)):
-                raise ValueError(f"{name}: expected dense rows of shape ({self.count}, {length})")
+        io = self._CHECK_IO()
+        io.supply_type = int(supply_type)
+        self._problem(io, (cost, supply, lower, upper), tensors, keep)
+        for (name, dtype, _), a in zip(self.SOLUTION_ROWS, rows):
+            ptr, _, obj = self._input(a, name, tensors, dtype=dtype)
             keep.append(obj)
             setattr(io, name, ptr)
         out = {}
         for name, dtype, per_kind in UniformValidation.FIELDS:
-            shape = (self.count, len(L.VALIDATION_KINDS)) if per_kind else (self.count,)
-            if tensors:
-                import torch
-                out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{self.device}")
-            else:
-                out[name] = np.empty(shape, dtype)
+            out[name] = self._empty((self.count, len(L.VALIDATION_KINDS)) if per_kind else (self.count,), dtype, tensors)
             setattr(io, name, out[name].data_ptr() if tensors else out[name].ctypes.data)
         summary = L.UBatchCheckSummary()
-        L.check(fn(self._h, C.byref(io), C.byref(summary)))
+        L.check(self._fn(fn)(self._h, C.byref(io), C.byref(summary)))
         return UniformValidation(summary.as_dict(), **out)
 
     def validate(self, result_or_rows, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> UniformValidation:
-        """The reference's SolutionValidator for every instance in one launch.  result_or_rows: a UniformResult, or status, total_cost,
-        flows and potentials as a dict or in that order -- any solution of this graph, not only this handle's.  Arrays as solve() takes
-        them; with tensors nothing that scales with the graph or the batch crosses the bus.  supply_type may also be 2 (equality)."""
-        return self._validate(L.lib().mcf_ubatch_validate, result_or_rows, cost, supply, lower, upper, supply_type)
+        """The reference's SolutionValidator for every instance in one launch, each against its own graph.  result_or_rows: a result of
+        solve(), or status, total_cost, flows and potentials as a dict or in that order -- any solution of these graphs, not only this
+        handle's.  Arrays as solve() takes them; with tensors nothing that scales with the graphs or the batch crosses the bus.
+        supply_type may also be 2 (equality)."""
+        return self._validate("validate", result_or_rows, cost, supply, lower, upper, supply_type)
 
     def validate_on_host(self, result_or_rows, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> UniformValidation:
         """Test hook: validate() with one lane on the CPU.  numpy only."""
-        return self._validate(L.lib().mcf_ubatch_validate_on_host, result_or_rows, cost, supply, lower, upper, supply_type, numpy_only=True)
+        return self._validate("validate_on_host", result_or_rows, cost, supply, lower, upper, supply_type, numpy_only=True)
 
 
-class RaggedResult(UniformResult):
-    """What RaggedBatch.solve / .resolve return: UniformResult's fields with flows and potentials FLAT -- instance i's arcs are
-    flows[arc_rows[i]:arc_rows[i + 1]], its nodes potentials[node_rows[i]:node_rows[i + 1]]; arcs(i) and nodes(i) return those slices
-    (views, numpy or tensor like the arrays).  status, pivots and total_cost are [count], trace is [count, record_trace]."""
-    __slots__ = ("arc_rows", "node_rows")
+class UniformBatch(_PlacedBatch):
+    """`count` instances of ONE graph, solved on the device from arrays that already are there (mcf_ubatch_*, DESIGN.md 3.14 "Uniform
+    batch").  solve() and resolve() take either numpy arrays (copied up and down, one copy per array) or torch tensors on the handle's
+    device (read and written in place: nothing that scales with the graph crosses the bus) -- never a mix; each array is [count, m]
+    ([count, n] for supply) or [m] ([n]) for one row shared by all, int64, contiguous in its last dimension.  Results equal
+    BatchSolver's for the same instances bit for bit.  run_on_host() / rerun_on_host() are test hooks (numpy only)."""
+    _PREFIX, _IO, _CHECK_IO, _RESULT = "mcf_ubatch", L.UBatchIo, L.UBatchCheckIo, UniformResult
+    _ROW = {"cost": "arc_count", "lower": "arc_count", "upper": "arc_count", "flows": "arc_count", "supply": "node_count", "potentials": "node_count"}
 
-    def __init__(self, arc_rows, node_rows, **arrays):
-        super().__init__(**arrays)
-        self.arc_rows, self.node_rows = arc_rows, node_rows
+    def __init__(self, node_count, source, target, count, rule=PivotRule.BlockSearch, pivot_limit=0, record_trace=0, device=0, pivots_per_launch=0,
+                 semantics=L.SEM_PLAIN, flags=0):
+        src, tgt = _i32(source), _i32(target)
+        if src.ndim != 1 or src.shape != tgt.shape:
+            raise ValueError("source and target must be one-dimensional and of equal length")
+        self.node_count, self.arc_count, self.count, self.device, self.record_trace = int(node_count), int(src.shape[0]), int(count), int(device), int(record_trace)
+        self._h = C.c_void_p()
+        self._last = None               # the last UniformResult: a masked resolve() starts from its rows
+        d = L.UBatchDesc(self.device, int(rule), int(semantics), 0, int(pivot_limit), int(pivots_per_launch), self.record_trace, int(flags),
+                         self.node_count, self.arc_count, self.count, src.ctypes.data, tgt.ctypes.data)
+        L.check(L.lib().mcf_ubatch_create(C.byref(self._h), C.byref(d)))
 
-    def arcs(self, i: int):
-        return self.flows[int(self.arc_rows[i]):int(self.arc_rows[i + 1])]
+    def _sizes(self):
+        return {"": (self.count,), "m": (self.count, self.arc_count), "n": (self.count, self.node_count), "t": (self.count, self.record_trace)}
 
-    def nodes(self, i: int):
-        return self.potentials[int(self.node_rows[i]):int(self.node_rows[i + 1])]
+    def _stride(self, name, shape, strides):
+        """cost, lower, upper, supply: one row per instance or one row shared by all; the solution's flows and potentials: dense rows;
+        everything else: one entry per instance"""
+        row = self._ROW.get(name)
+        length = self.count if row is None else getattr(self, row)
+        if row is None:
+            if shape != (length,):
+                raise ValueError(f"{name}: shape {shape}, expected ({length},)")
+        elif shape not in ((length,), (self.count, length)):
+            raise ValueError(f"{name}: shape {shape}, expected ({length},) or ({self.count}, {length})")
+        if self.count > 0 and shape[-1] > 1 and strides[-1] != 1:
+            raise ValueError(f"{name}: not contiguous in its last dimension")
+        stride = strides[0] if len(shape) == 2 and self.count > 1 else 0
+        if stride < 0 or (len(shape) == 2 and self.count > 1 and 0 < stride < length):
+            raise ValueError(f"{name}: rows overlap")
+        if name in ("flows", "potentials") and (len(shape) != 2 or (self.count > 1 and stride != length)):
+            raise ValueError(f"{name}: expected dense rows of shape ({self.count}, {length})")
+        return stride
 
 
-class RaggedBatch:
+class RaggedBatch(_PlacedBatch):
     """Instances of a SET of graphs in one handle, solved on the device from arrays that already are there (mcf_rbatch_*, DESIGN.md 3.14
     "Ragged batch").  graphs: a sequence of (node_count, source, target); graph_of[i] names the graph of instance i (None: instance i is
     graph i).  Problem data and results are flat: cost, lower, upper and flows have arc_rows[-1] elements, instance i's at
@@ -653,6 +680,8 @@ class RaggedBatch:
     and down) or flat torch tensors on the handle's device (read and written in place) -- never a mix; int64, contiguous.  Results equal
     BatchSolver's for the same instances bit for bit, and UniformBatch's where there is one graph.  run_on_host() / rerun_on_host() /
     validate_on_host() are test hooks (numpy only)."""
+    _PREFIX, _IO, _CHECK_IO, _RESULT = "mcf_rbatch", L.RBatchIo, L.RBatchCheckIo, RaggedResult
+    _ROW = {"cost": "arc_total", "lower": "arc_total", "upper": "arc_total", "flows": "arc_total", "supply": "node_total", "potentials": "node_total"}
 
     def __init__(self, graphs, graph_of=None, rule=PivotRule.BlockSearch, pivot_limit=0, record_trace=0, device=0, pivots_per_launch=0,
                  semantics=L.SEM_PLAIN, flags=0):
@@ -680,159 +709,22 @@ class RaggedBatch:
         L.check(L.lib().mcf_rbatch_get_rows(self._h, self.arc_rows.ctypes.data, self.node_rows.ctypes.data))
         self.arc_total, self.node_total = int(self.arc_rows[-1]), int(self.node_rows[-1])
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            L.lib().mcf_rbatch_destroy(h)
-            self._h = None
+    def _result(self, out):
+        return RaggedResult(self.arc_rows, self.node_rows, **out)
 
-    def __len__(self):
-        return self.count
+    def _sizes(self):
+        return {"": (self.count,), "m": (self.arc_total,), "n": (self.node_total,), "t": (self.count, self.record_trace)}
 
-    # ---- one flat input: (pointer, the object that keeps the memory alive); the checks of UniformBatch._input
-    def _input(self, a, name, length, tensors, dtype="int64"):
-        if a is None:
-            return None, None
-        if tensors:
-            import torch
-            if not _is_tensor(a):
-                raise ValueError(f"{name}: numpy arrays and tensors cannot be mixed in one call")
-            if a.device.type != "cuda" or (a.device.index or 0) != self.device:
-                raise ValueError(f"{name}: tensor on {a.device}, the batch runs on cuda:{self.device}")
-            if a.dtype != getattr(torch, dtype):
-                raise ValueError(f"{name}: dtype {a.dtype}, expected {dtype}")
-            shape, strides = tuple(a.shape), tuple(a.stride())
-        else:
-            if _is_tensor(a):
-                raise ValueError(f"{name}: numpy arrays and tensors cannot be mixed in one call")
-            if not isinstance(a, np.ndarray):
-                a = np.asarray(a, dtype)
-            if a.dtype != np.dtype(dtype):
-                raise ValueError(f"{name}: dtype {a.dtype}, expected {dtype}")
-            shape, strides = a.shape, tuple(s // a.itemsize for s in a.strides)
+    def _stride(self, name, shape, strides):
+        """every array is flat: all instances' arcs, all instances' nodes, or one entry per instance; there are no strides"""
+        row = self._ROW.get(name)
+        length = self.count if row is None else getattr(self, row)
         if shape != (length,):
-            raise ValueError(f"{name}: shape {tuple(shape)}, expected ({length},)")
+            raise ValueError(f"{name}: shape {shape}, expected ({length},)")
         if length > 1 and strides[-1] != 1:
             raise ValueError(f"{name}: not contiguous")
-        return (a.data_ptr() if tensors else a.ctypes.data), a
+        return 0
 
-    def _lengths(self):
-        return (("cost", self.arc_total), ("supply", self.node_total), ("lower", self.arc_total), ("upper", self.arc_total))
-
-    def _outputs(self, tensors, like):
-        """Fresh rows, or copies of `like` (the last result) for a call that does not write every row."""
-        sizes = {"": (self.count,), "m": (self.arc_total,), "n": (self.node_total,), "t": (self.count, self.record_trace)}
-        out = {}
-        for name, dtype, dim in UniformResult.FIELDS:
-            if like is not None:
-                prev = getattr(like, name)
-                if _is_tensor(prev) != tensors:
-                    raise ValueError("a masked resolve() continues the last result: numpy arrays and tensors cannot be mixed")
-                out[name] = prev.clone() if tensors else prev.copy()
-            elif tensors:
-                import torch
-                out[name] = torch.empty(sizes[dim], dtype=getattr(torch, dtype), device=f"cuda:{self.device}")
-            else:
-                out[name] = np.empty(sizes[dim], dtype)
-        return out
-
-    def _call(self, fn, cost, supply, lower, upper, supply_type, changed=None, masked=False, numpy_only=False):
-        given = [a for a in (cost, supply, lower, upper, changed) if a is not None]
-        tensors = any(_is_tensor(a) for a in given)
-        if tensors and numpy_only:
-            raise ValueError("the host hooks take numpy arrays")
-        keep = []
-        io = L.RBatchIo()
-        io.memory, io.supply_type = (L.MEM_DEVICE if tensors else L.MEM_HOST), int(supply_type)
-        for (name, length), a in zip(self._lengths(), (cost, supply, lower, upper)):
-            ptr, obj = self._input(a, name, length, tensors)
-            keep.append(obj)
-            setattr(io, name, ptr)
-        if changed is not None:
-            if not tensors and not isinstance(changed, np.ndarray):
-                changed = np.asarray(changed)
-            if not tensors and changed.dtype == np.bool_:
-                changed = changed.view(np.uint8)
-            if tensors:
-                import torch
-                if changed.dtype == torch.bool:
-                    changed = changed.view(torch.uint8)
-            ptr, obj = self._input(changed, "changed", self.count, tensors, dtype="uint8")
-            keep.append(obj)
-            io.changed = ptr
-        if masked and changed is not None and self._last is None:
-            raise McfError(L.ERR_STATE, "resolve: the batch has not been solved")
-        out = self._outputs(tensors, self._last if masked and changed is not None else None)
-        for name, arr in out.items():
-            setattr(io, name, arr.data_ptr() if tensors else arr.ctypes.data)
-        L.check(fn(self._h, C.byref(io)))
-        self._last = RaggedResult(self.arc_rows, self.node_rows, **out)
-        return self._last
-
-    def solve(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> RaggedResult:
-        """A fresh solve of every instance; may be repeated with other supplies, bounds or costs."""
-        return self._call(L.lib().mcf_rbatch_solve, cost, supply, lower, upper, supply_type)
-
-    def resolve(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq, changed=None) -> RaggedResult:
-        """New costs for the instances `changed` marks ([count] bool / uint8, None = all), as UniformBatch.resolve."""
-        return self._call(L.lib().mcf_rbatch_resolve, cost, supply, lower, upper, supply_type, changed, masked=True)
-
-    def run_on_host(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> RaggedResult:
-        """Test hook: solve() with one lane on the CPU.  numpy only."""
-        return self._call(L.lib().mcf_rbatch_run_on_host, cost, supply, lower, upper, supply_type, numpy_only=True)
-
-    def rerun_on_host(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq, changed=None) -> RaggedResult:
-        """Test hook: resolve() with one lane on the CPU.  numpy only."""
-        return self._call(L.lib().mcf_rbatch_rerun_on_host, cost, supply, lower, upper, supply_type, changed, masked=True, numpy_only=True)
-
-    def stats(self) -> dict:
-        st = L.UBatchStats(); L.check(L.lib().mcf_rbatch_get_stats(self._h, C.byref(st))); return st.as_dict()
-
-    # ---- validation: the solution's rows where they lie
-    def _validate(self, fn, rows, cost, supply, lower, upper, supply_type, numpy_only=False):
-        names = tuple(name for name, _, _ in UniformBatch.SOLUTION_ROWS)
-        if isinstance(rows, dict):
-            rows = tuple(rows[name] for name in names)
-        elif hasattr(rows, "status"):
-            rows = tuple(getattr(rows, name) for name in names)
-        rows = tuple(rows)
-        if len(rows) != 4 or any(r is None for r in rows):
-            raise ValueError("the solution to check is status, total_cost, flows and potentials: a RaggedResult, a dict or the four rows")
-        tensors = any(_is_tensor(a) for a in (*rows, cost, supply, lower, upper) if a is not None)
-        if tensors and numpy_only:
-            raise ValueError("the host hooks take numpy arrays")
-        keep = []
-        io = L.RBatchCheckIo()
-        io.memory, io.supply_type = (L.MEM_DEVICE if tensors else L.MEM_HOST), int(supply_type)
-        for (name, length), a in zip(self._lengths(), (cost, supply, lower, upper)):
-            ptr, obj = self._input(a, name, length, tensors)
-            keep.append(obj)
-            setattr(io, name, ptr)
-        for (name, dtype, _), length, a in zip(UniformBatch.SOLUTION_ROWS, (self.count, self.count, self.arc_total, self.node_total), rows):
-            ptr, obj = self._input(a, name, length, tensors, dtype=dtype)
-            keep.append(obj)
-            setattr(io, name, ptr)
-        out = {}
-        for name, dtype, per_kind in UniformValidation.FIELDS:
-            shape = (self.count, len(L.VALIDATION_KINDS)) if per_kind else (self.count,)
-            if tensors:
-                import torch
-                out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{self.device}")
-            else:
-                out[name] = np.empty(shape, dtype)
-            setattr(io, name, out[name].data_ptr() if tensors else out[name].ctypes.data)
-        summary = L.UBatchCheckSummary()
-        L.check(fn(self._h, C.byref(io), C.byref(summary)))
-        return UniformValidation(summary.as_dict(), **out)
-
-    def validate(self, result_or_rows, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> UniformValidation:
-        """The reference's SolutionValidator for every instance in one launch, each against its own graph.  result_or_rows: a
-        RaggedResult, or status, total_cost, flows and potentials (flat) as a dict or in that order.  supply_type may also be 2."""
-        return self._validate(L.lib().mcf_rbatch_validate, result_or_rows, cost, supply, lower, upper, supply_type)
-
-    def validate_on_host(self, result_or_rows, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> UniformValidation:
-        """Test hook: validate() with one lane on the CPU.  numpy only."""
-        return self._validate(L.lib().mcf_rbatch_validate_on_host, result_or_rows, cost, supply, lower, upper, supply_type, numpy_only=True)
 
 
 def block_config(**kw) -> "L.BlockConfig":

@@ -1,6 +1,8 @@
-// rbatch_host_check.cpp -- the host side of the ragged batch (mcf_rbatch_create, _run_on_host, _rerun_on_host, _validate_on_host) as a
-// stand-alone program, so that it can be built together with the library's host sources under -fsanitize=address,undefined and run on a
-// CPU ("Ragged batch").  Needs no GPU and is not loaded into Python.
+// rbatch_host_check.cpp -- the host side of the placed batches as a stand-alone program, so that it can be built together with the
+// library's host sources under -fsanitize=address,undefined and run on a CPU ("Ragged batch").  It runs the ragged entry
+// points (mcf_rbatch_create, _run_on_host, _rerun_on_host, _validate_on_host) on its input, then the instances of the input's first
+// graph through the uniform ones (mcf_ubatch_*), which share the drivers, and compares every row of the two.  Needs no GPU and is not
+// loaded into Python.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -I../include \
 //         rbatch_host_check.cpp ../mincostflow_amd/csrc/{batch.hip,ns_core.cpp,ns_host.cpp,engine.hip,validate.hip,problems.cpp,util.cpp,exchange.cpp} \
@@ -28,6 +30,38 @@ static long long next(FILE *f)
         if (rc__ != MCF_OK) { fprintf(stderr, "%s: %d %s\n", #call, rc__, mcf_last_error()); return 1; } \
     } while (0)
 
+constexpr int kTrace = 64;
+
+// the rows of the instances `sel`, each `length` long and beginning at row[i] * scale in `flat`, one after the other
+template <class T>
+static std::vector<T> dense(const std::vector<T> &flat, const std::vector<int64_t> &row, int64_t scale, int64_t length, const std::vector<int> &sel)
+{
+    std::vector<T> out;
+    for (int i : sel) out.insert(out.end(), flat.begin() + row[(size_t)i] * scale, flat.begin() + row[(size_t)i] * scale + length);
+    return out;
+}
+
+// what a solve call and a validation call wrote
+struct Answers {
+    std::vector<int32_t> status, trace, valid, errors, first;
+    std::vector<int64_t> pivots, total, flows, potentials, objective, dual;
+    Answers(size_t count, size_t arcs, size_t nodes)
+        : status(count), trace(count * kTrace), valid(count), errors(count * MCF_VAL_KINDS), first(count * MCF_VAL_KINDS), pivots(count), total(count), flows(arcs),
+          potentials(nodes), objective(count), dual(count) {}
+};
+// u: the uniform batch's answers for the instances `sel`; r: the ragged batch's for all
+static bool same(const char *when, const Answers &u, const Answers &r, const std::vector<int64_t> &one, const std::vector<int64_t> &arc_row,
+                 const std::vector<int64_t> &node_row, int64_t n, int64_t m, const std::vector<int> &sel)
+{
+    const bool ok = u.status == dense(r.status, one, 1, 1, sel) && u.pivots == dense(r.pivots, one, 1, 1, sel) && u.total == dense(r.total, one, 1, 1, sel) &&
+                    u.flows == dense(r.flows, arc_row, 1, m, sel) && u.potentials == dense(r.potentials, node_row, 1, n, sel) &&
+                    u.trace == dense(r.trace, one, kTrace, kTrace, sel) && u.valid == dense(r.valid, one, 1, 1, sel) &&
+                    u.errors == dense(r.errors, one, MCF_VAL_KINDS, MCF_VAL_KINDS, sel) && u.first == dense(r.first, one, MCF_VAL_KINDS, MCF_VAL_KINDS, sel) &&
+                    u.objective == dense(r.objective, one, 1, 1, sel) && u.dual == dense(r.dual, one, 1, 1, sel);
+    if (!ok) fprintf(stderr, "%s: the uniform batch's answers differ from the ragged batch's\n", when);
+    return ok;
+}
+
 int main(int argc, char **argv)
 {
     FILE *f = argc > 1 ? fopen(argv[1], "r") : nullptr;
@@ -54,12 +88,22 @@ int main(int argc, char **argv)
         for (int64_t e = 0; e < m; ++e) cost2.push_back(next(f));
     }
     fclose(f);
+    // the uniform pass: the instances of graph 0
+    std::vector<int> sel;
+    std::vector<int64_t> one;
+    for (int i = 0; i < count; ++i) {
+        one.push_back(i);
+        if (graph_of[(size_t)i] == 0) sel.push_back(i);
+    }
+    const int64_t n0 = G ? node_count[0] : 0, m0 = G ? arc_start[1] : 0;
+    std::vector<uint8_t> changed((size_t)count);
+    for (int i = 0; i < count; ++i) changed[(size_t)i] = i % 3 != 1;
 
     int64_t pivots_total = 0, invalid_total = 0;
     for (int32_t rule : {MCF_RULE_BLOCK_SEARCH, MCF_RULE_BEST_ELIGIBLE, MCF_RULE_FIRST_ELIGIBLE})
         for (int32_t stype : {MCF_SUPPLY_GEQ, MCF_SUPPLY_LEQ}) {
             mcf_rbatch_desc d{};
-            d.pivot_rule = rule; d.semantics = MCF_SEM_PLAIN; d.trace_capacity = 64;
+            d.pivot_rule = rule; d.semantics = MCF_SEM_PLAIN; d.trace_capacity = kTrace;
             d.graph_count = G; d.count = count;
             d.node_count = node_count.data(); d.arc_start = arc_start.data(); d.source = source.data(); d.target = target.data(); d.graph_of = graph_of.data();
             mcf_rbatch *b = nullptr;
@@ -68,25 +112,21 @@ int main(int argc, char **argv)
             CHECK(mcf_rbatch_get_rows(b, arc_row.data(), node_row.data()));
             if (arc_row.back() != (int64_t)lower.size() || node_row.back() != (int64_t)supply.size()) { fprintf(stderr, "rows do not match the input\n"); return 1; }
             // exactly sized outputs: a write past a row's end is a write past the allocation for the last instance, and the sanitizer's to find
-            std::vector<int32_t> status((size_t)count), trace((size_t)count * 64);
-            std::vector<int64_t> pivots((size_t)count), total((size_t)count), flows(lower.size()), potentials(supply.size());
+            Answers r((size_t)count, lower.size(), supply.size());
             mcf_rbatch_io io{};
             io.memory = MCF_MEM_HOST; io.supply_type = stype;
             io.lower = lower.data(); io.upper = upper.data(); io.cost = cost.data(); io.supply = supply.data();
-            io.status = status.data(); io.pivots = pivots.data(); io.total_cost = total.data(); io.flows = flows.data(); io.potentials = potentials.data(); io.trace = trace.data();
+            io.status = r.status.data(); io.pivots = r.pivots.data(); io.total_cost = r.total.data(); io.flows = r.flows.data(); io.potentials = r.potentials.data(); io.trace = r.trace.data();
             CHECK(mcf_rbatch_run_on_host(b, &io));
-            std::vector<int32_t> valid((size_t)count), errors((size_t)count * MCF_VAL_KINDS), first((size_t)count * MCF_VAL_KINDS);
-            std::vector<int64_t> objective((size_t)count), dual((size_t)count);
             mcf_rbatch_check_io c{};
             c.memory = MCF_MEM_HOST; c.supply_type = stype;
             c.lower = lower.data(); c.upper = upper.data(); c.cost = cost.data(); c.supply = supply.data();
-            c.status = status.data(); c.total_cost = total.data(); c.flows = flows.data(); c.potentials = potentials.data();
-            c.valid = valid.data(); c.errors = errors.data(); c.first = first.data(); c.objective = objective.data(); c.dual_cost = dual.data();
+            c.status = r.status.data(); c.total_cost = r.total.data(); c.flows = r.flows.data(); c.potentials = r.potentials.data();
+            c.valid = r.valid.data(); c.errors = r.errors.data(); c.first = r.first.data(); c.objective = r.objective.data(); c.dual_cost = r.dual.data();
             mcf_ubatch_check_summary summary{};
             CHECK(mcf_rbatch_validate_on_host(b, &c, &summary));
             invalid_total += summary.invalid;
-            std::vector<uint8_t> changed((size_t)count);
-            for (int i = 0; i < count; ++i) changed[(size_t)i] = i % 3 != 1;
+            const Answers r_first = r;
             io.cost = cost2.data(); io.changed = changed.data();
             CHECK(mcf_rbatch_rerun_on_host(b, &io));
             io.changed = nullptr;
@@ -97,8 +137,43 @@ int main(int argc, char **argv)
             CHECK(mcf_rbatch_get_stats(b, &st));
             pivots_total += st.total_pivots;
             mcf_rbatch_destroy(b);
+            if (sel.empty()) continue;
+
+            // the same calls on the uniform handle: dense rows [instances of graph 0][m0 or n0]
+            const std::vector<int64_t> u_lower = dense(lower, arc_row, 1, m0, sel), u_upper = dense(upper, arc_row, 1, m0, sel), u_cost = dense(cost, arc_row, 1, m0, sel),
+                                       u_cost2 = dense(cost2, arc_row, 1, m0, sel), u_supply = dense(supply, node_row, 1, n0, sel);
+            const std::vector<uint8_t> u_changed = dense(changed, one, 1, 1, sel);
+            mcf_ubatch_desc ud{};
+            ud.pivot_rule = rule; ud.semantics = MCF_SEM_PLAIN; ud.trace_capacity = kTrace;
+            ud.node_count = (int32_t)n0; ud.arc_count = (int32_t)m0; ud.count = (int32_t)sel.size(); ud.source = source.data(); ud.target = target.data();
+            mcf_ubatch *ub = nullptr;
+            CHECK(mcf_ubatch_create(&ub, &ud));
+            Answers u(sel.size(), u_lower.size(), u_supply.size());
+            mcf_ubatch_io uio{};
+            uio.memory = MCF_MEM_HOST; uio.supply_type = stype;
+            uio.lower = u_lower.data(); uio.upper = u_upper.data(); uio.cost = u_cost.data(); uio.supply = u_supply.data();
+            uio.lower_stride = uio.upper_stride = uio.cost_stride = m0; uio.supply_stride = n0;
+            uio.status = u.status.data(); uio.pivots = u.pivots.data(); uio.total_cost = u.total.data(); uio.flows = u.flows.data(); uio.potentials = u.potentials.data(); uio.trace = u.trace.data();
+            CHECK(mcf_ubatch_run_on_host(ub, &uio));
+            mcf_ubatch_check_io uc{};
+            uc.memory = MCF_MEM_HOST; uc.supply_type = stype;
+            uc.lower = u_lower.data(); uc.upper = u_upper.data(); uc.cost = u_cost.data(); uc.supply = u_supply.data();
+            uc.lower_stride = uc.upper_stride = uc.cost_stride = m0; uc.supply_stride = n0;
+            uc.status = u.status.data(); uc.total_cost = u.total.data(); uc.flows = u.flows.data(); uc.potentials = u.potentials.data();
+            uc.valid = u.valid.data(); uc.errors = u.errors.data(); uc.first = u.first.data(); uc.objective = u.objective.data(); uc.dual_cost = u.dual.data();
+            CHECK(mcf_ubatch_validate_on_host(ub, &uc, &summary));
+            if (!same("first solve", u, r_first, one, arc_row, node_row, n0, m0, sel)) return 1;
+            uio.cost = u_cost2.data(); uio.changed = u_changed.data();
+            CHECK(mcf_ubatch_rerun_on_host(ub, &uio));
+            uio.changed = nullptr;
+            CHECK(mcf_ubatch_rerun_on_host(ub, &uio));
+            uc.cost = u_cost2.data();
+            CHECK(mcf_ubatch_validate_on_host(ub, &uc, &summary));
+            if (!same("re-solve", u, r, one, arc_row, node_row, n0, m0, sel)) return 1;
+            mcf_ubatch_destroy(ub);
         }
-    printf("ok: %d instances of %d graphs, 3 rules x 2 supply types; %lld pivots in the last re-solves, %lld rows flagged by the first validations\n", count, G,
-           (long long)pivots_total, (long long)invalid_total);
+    printf("ok: %d instances of %d graphs, 3 rules x 2 supply types; %lld pivots in the last re-solves, %lld rows flagged by the first validations; "
+           "the %zu instances of graph 0 as a uniform batch: every row equal\n",
+           count, G, (long long)pivots_total, (long long)invalid_total, sel.size());
     return 0;
 }
