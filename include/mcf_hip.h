@@ -537,7 +537,9 @@ MCF_API int mcf_ns_tree(mcf_ns *s, const int32_t **parent, const int32_t **pred_
                         const int64_t **flow, const int64_t **upper);
 /* test aid: mcf_engine_check_reduced_costs summed over this solver's engines (after Solve()) */
 MCF_API int mcf_ns_check_reduced_costs(mcf_ns *s, int64_t *mismatches);
-/* what the last mcf_ns_apply_pivot changed: the engine calls a host would make */
+/* what the last mcf_ns_apply_pivot changed: the engine calls a host would make.  *nodes lists the *n_nodes nodes whose potential moved by
+ * *sigma, whatever form the walk wrote them down in (runs of consecutive ids are expanded here; valid until the next pivot).  After a
+ * walk that wrote no list (a reload of _pi, inside mcf_ns_solve only) *nodes is NULL and *n_nodes still counts the nodes. */
 MCF_API int mcf_ns_last_pivot(mcf_ns *s, int32_t *n_state, int32_t arcs[2], int8_t states[2], int32_t *n_nodes,
                               const int32_t **nodes, int64_t *sigma);
 

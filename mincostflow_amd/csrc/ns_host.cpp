@@ -50,13 +50,27 @@ struct mcf_ns : mcf::NsCore {                                         // the pro
     // one bit per node, set where nxt[a] != a + 1 (thread_breaks.h): empty before the first relabelling, rebuilt by every relabelling and kept
     // current by the re-hanging from then on
     std::vector<uint64_t> breaks;
-    mcf::hvec<int32_t> moved;       // capacity n+1, the first moved_n entries are valid
-    mcf::hvec<int64_t> moved_val;   // their new potentials
-    int moved_n = 0;
+    // What the last walk produced, for whoever has to tell the engines (or a caller) which potentials moved.  pivot_front resets it, the walk of
+    // shift_potentials fills it (normalise_potentials: all nodes at once), hand_over_moved sends what the engines do not have yet.
+    struct MovedList {
+        enum Form { kNothing = 0,   // no potential moved
+                    kValues,        // nodes[] and vals[], their new potentials
+                    kIds,           // nodes[] alone: the engines read the bound _pi where they need a value
+                    kRuns,          // run_first[] / run_len[]: runs of consecutive ids (mcf_engine_shift_potential_runs), nodes[] is not written
+                    kReload };      // nothing written down: the engines reload _pi
+        Form form = kNothing;
+        int n = 0;                  // nodes the walk moves
+        int walked = 0;             // of them, moved so far (= n once the walk is over)
+        int sent = 0;               // of those, what the engines already have (handed over during the walk)
+        int runs_n = 0, runs_sent = 0;
+        mcf::hvec<int32_t> nodes;   // capacity n + 1 each
+        mcf::hvec<int64_t> vals;
+        mcf::hvec<int32_t> run_first, run_len;
+        void begin(Form f, int count) { form = f; n = count; walked = sent = runs_n = runs_sent = 0; }
+    } moved;
     bool shift_smaller_side = false;  // inside mcf_ns_solve with 64-bit engines: see shift_potentials
     int reload_min = 0;               // inside mcf_ns_solve: walks of at least this many nodes are announced as a reload of _pi (0: never)
     int reload_min_engines = 0;       // what the engines asked for (mcf_engine_reload_threshold), 0 when one of them only takes lists
-    bool moved_as_reload = false;     // the last walk wrote no node list: the engines reload _pi
     bool allow_smaller_side = false;
     // MCF_NS_DEBUG only (reset by every mcf_ns_solve): moved subtrees by log2 of their size -- how many, how many nodes, and where their pivots'
     // time went (ticks): the walk incl. hand-over, the wait for the search that follows, everything else of the pivot
@@ -65,15 +79,14 @@ struct mcf_ns : mcf::NsCore {                                         // the pro
         int64_t reload_walks = 0, over_half = 0, over_half_nodes = 0;
         int64_t n[32] = {0}, nodes[32] = {0};
         double walk[32] = {0}, wait[32] = {0}, rest[32] = {0};
+        int size_class = -1;          // of the pivot whose search is being waited for
+        double t_prev = 0;
+        struct Buckets { double search, tree, pot, hand, begin, pieces; };      // ticks of the whole solve
+        void waited(double t0, double t_got);
+        void pivoted(const mcf_ns *s, double walk_ticks, double t_got);
+        void report(const mcf_ns *s, int64_t it, const Buckets &t, double ns_per_tick, double tick_start) const;
     } dbg;
     int resident_workgroups = 0;      // mcf_ns_set_device_share: workgroups of this solver's resident grid (0 = the whole device)
-    int moved_sent = 0;               // how many of them the engine already has (handed over during the walk)
-    bool moved_without_values = false;// the walk wrote no moved_val (run walk: the engines read the bound _pi where they need a value)
-    // a big walk after a relabelling writes RUNS of consecutive ids instead of nodes (mcf_engine_shift_potential_runs): run_first / run_len,
-    // runs_n of them, runs_sent already handed over
-    bool moved_as_runs = false;
-    int runs_n = 0, runs_sent = 0;
-    mcf::hvec<int32_t> run_first, run_len;
     int engine_rc = 0;                // first error of an engine call made from inside a pivot
     double piece_ticks = 0;           // time inside the hand-over calls made during the walks (part of the potential-update bucket)
     bool hand_over = false;           // a device engine is attached: state writes and potential pieces go to it as they arise
@@ -117,36 +130,17 @@ inline double ticks() { return (double)__rdtsc(); }     // invariant TSC; scaled
 
 using mcf::kInf;     // tree_pivot.h
 
-// ---- the engine calls of a pivot, fanned out to every shard this process drives
-int engines_patch_state(mcf_ns *s, int32_t count, const int32_t *arcs, const int8_t *states)
+// ---- the engine calls of a pivot, fanned out to every shard this process drives (the first error ends the round)
+template <class Call> int engines_each(mcf_ns *s, Call call)
 {
-    int rc = mcf_engine_patch_state(s->engine, count, arcs, states);       // every engine keeps the writes that fall into its shard
-    for (size_t i = 0; i < s->peers.size() && !rc; ++i) rc = mcf_engine_patch_state(s->peers[i], count, arcs, states);
-    return rc;
-}
-int engines_append_potential(mcf_ns *s, int32_t count, const int32_t *nodes, const int64_t *values)
-{
-    int rc = mcf_engine_shift_potential(s->engine, count, nodes, values, s->sigma); // the potentials are replicated on every shard
-    for (size_t i = 0; i < s->peers.size() && !rc; ++i) rc = mcf_engine_shift_potential(s->peers[i], count, nodes, values, s->sigma);
-    return rc;
-}
-int engines_shift_runs(mcf_ns *s, int32_t n_runs, const int32_t *first, const int32_t *length)
-{
-    int rc = mcf_engine_shift_potential_runs(s->engine, n_runs, first, length, s->sigma);
-    for (size_t i = 0; i < s->peers.size() && !rc; ++i) rc = mcf_engine_shift_potential_runs(s->peers[i], n_runs, first, length, s->sigma);
-    return rc;
-}
-int engines_reload_potentials(mcf_ns *s, int32_t changed)
-{
-    int rc = mcf_engine_reload_potentials(s->engine, changed);
-    for (size_t i = 0; i < s->peers.size() && !rc; ++i) rc = mcf_engine_reload_potentials(s->peers[i], changed);
+    int rc = s->engine ? call(s->engine) : MCF_OK;
+    for (size_t i = 0; i < s->peers.size() && !rc; ++i) rc = call(s->peers[i]);
     return rc;
 }
 int engines_search_begin(mcf_ns *s)
 {
-    int rc = mcf_engine_search_begin(s->engine);     // (RCCL-sharded engines too: their exchange has a stream of its own; a dispatching one launches its scan here)
-    for (size_t i = 0; i < s->peers.size() && !rc; ++i) rc = mcf_engine_search_begin(s->peers[i]);
-    return rc;
+    // (RCCL-sharded engines too: their exchange has a stream of its own; a dispatching one launches its scan here)
+    return engines_each(s, [](mcf_engine *e) { return mcf_engine_search_begin(e); });
 }
 int engines_search_end(mcf_ns *s, int32_t *found, int32_t *arc)
 {
@@ -173,21 +167,9 @@ int engines_search_end(mcf_ns *s, int32_t *found, int32_t *arc)
     }
     }
 }
-int engines_renumber(mcf_ns *s, const int32_t *new_of)
-{
-    int rc = mcf_engine_renumber_nodes(s->engine, new_of);
-    for (size_t i = 0; i < s->peers.size() && !rc; ++i) rc = mcf_engine_renumber_nodes(s->peers[i], new_of);
-    return rc;
-}
-void engines_park(mcf_ns *s)
-{
-    if (s->engine) mcf_engine_park(s->engine);
-    for (mcf_engine *e : s->peers) mcf_engine_park(e);
-}
 void engines_destroy(mcf_ns *s)
 {
-    if (s->engine) mcf_engine_destroy(s->engine);
-    for (mcf_engine *e : s->peers) mcf_engine_destroy(e);
+    engines_each(s, [](mcf_engine *e) { mcf_engine_destroy(e); return MCF_OK; });
     s->engine = nullptr;
     s->peers.clear();
     if (s->exchange) { mcf_exchange_close(s->exchange); s->exchange = nullptr; }
@@ -212,17 +194,20 @@ void decide_states(mcf_ns *s)
     }
 }
 
-// ---- NS.cs:1185-1209: host copy of pi is kept current (sigma needs pi[v_in], pi[u_in]); the node list is what
-// mcf_engine_update_potential ships to the device.
+// ---- NS.cs:1185-1209: host copy of pi is kept current (sigma needs pi[v_in], pi[u_in]); what the walk writes down (mcf_ns::MovedList) is what
+// the engines are told.
 // The subtree of u_in is the thread segment u_in .. LastSucc[u_in], SuccNum[u_in] nodes long; NS.cs:1196-1208 walks it front to back,
 // one dependent load per node, and that latency chain is what a big subtree costs (2 % of config 3's pivots move 24 000 nodes on
-// average and carry 92 % of all moved nodes).  The same walk here, with two aids that change neither the set of nodes nor their values:
-//  * small subtrees are walked from both ends at once (Thread forwards, RevThread backwards): two independent chains;
-//  * larger ones use PREFETCH HINTS: follow[v] remembers which node came kWalkAhead steps after v the last time a walk passed v.
-//    The thread order of a subtree changes little between pivots (92 % of the hints are still right on config 3), so the walk
-//    prefetches the lines it will need kWalkAhead steps from now; a stale hint costs a useless prefetch, nothing else.
+// average and carry 92 % of all moved nodes).  The same walk here, in four steps that change neither the set of nodes nor their values:
+//  1. the SIDE: the subtree, or (inside a solve) everything else when that is smaller;
+//  2. the FORM in which the engines hear of it: nodes with values, nodes alone, runs of consecutive ids, or "reload _pi";
+//  3. the WALKER: from both ends at once below kWalkHintMin nodes (Thread forwards, RevThread backwards: two independent chains); above,
+//     mcf::HintWalk before the first relabelling and mcf::BreakWalk after it (thread_breaks.h);
+//  4. the PIECES: a long list is handed to the engines while the walk goes on (walk_in_pieces, hand_over_moved).
 // The order of the resulting list is irrelevant to the engine (final values).
-constexpr int kWalkAhead = 8, kWalkHintMin = 48;
+using mcf::kWalkAhead;
+constexpr int kWalkHintMin = 48;
+static_assert(kWalkHintMin > kWalkAhead, "a hinted walk is longer than its hints reach");
 // What a step of a walk that leaves the id order is charged when the next relabelling is scheduled.  It was the scalar run loop's cost of a
 // jump (a mispredicted branch and then a miss, 23 - 25 ns); the walker of thread_breaks.h overlaps its jumps' misses and pays less than half of
 // that, but a jump is also one more run for the engines to take, and the budget did not follow the walk down: charged 9 ns (2.7 times the
@@ -232,25 +217,68 @@ constexpr int kRunsMin = 512;      // walks of this many nodes and more hand ove
 constexpr int kWalkPiece = 2048;   // a big walk hands its nodes to the engine in pieces of this size (mcf_engine_append_potential);
                                    // 1024 .. 8192 measure alike on config 3, no hand-over at all costs 0.9 us per pivot
 
-// ---- runs of consecutive ids (after a relabelling in thread order the successor of node a is a + 1 almost everywhere).  Every walk of
-// kWalkHintMin nodes and more goes through ONE walker then (mcf::BreakWalk, thread_breaks.h): the end of a run comes from the bitmap of
-// thread breaks, not from comparing each loaded successor, so no branch depends on a load of nxt; the load of the jump's target is issued
-// before the run's potentials are added, and the hints in follow[] (run start -> the run start kJumpAhead jumps later) have the misses of
-// several jumps in flight at once.  (Measured and dropped: eight successors compared per AVX2 step -- slower on the runs of 16 that the solves
-// have; the bitmap without hints, and hints on the scalar loop without the bitmap -- neither gains on a cold cache)
-mcf::BreakWalk break_walk(mcf_ns *s, int first, int64_t sigma)
+// ---- the hand-over: what the engines do not have yet of the moved list, in the list's form.  During a walk (between pieces), once after
+// pivot_front, and for normalise_potentials.  An engine's error is kept in engine_rc, and nothing more is sent after one.
+void hand_over_moved(mcf_ns *s)
 {
-    mcf::BreakWalk w;
-    w.pi = s->pi.data(); w.nxt = s->nxt.data(); w.follow = s->follow.data(); w.bits = s->breaks.data();
-    w.sigma = sigma; w.a = first;
-    return w;
+    using M = mcf_ns::MovedList;
+    M &m = s->moved;
+    if (m.sent == m.walked) return;
+    if (!s->engine_rc) s->engine_rc = engines_each(s, [&](mcf_engine *e) {       // the potentials are replicated on every shard
+        switch (m.form) {
+        case M::kRuns: return mcf_engine_shift_potential_runs(e, m.runs_n - m.runs_sent, m.run_first.data() + m.runs_sent, m.run_len.data() + m.runs_sent, s->sigma);
+        case M::kReload: return mcf_engine_reload_potentials(e, m.n);
+        default: return mcf_engine_shift_potential(e, m.walked - m.sent, m.nodes.data() + m.sent, m.form == M::kValues ? m.vals.data() + m.sent : nullptr, s->sigma);
+        }
+    });
+    m.sent = m.walked;
+    m.runs_sent = m.runs_n;
+}
+
+// ---- the piece loop: advance(k) moves the walker over the next k nodes of the list begun in s->moved.  With engines attached, a list is handed
+// over every kWalkPiece nodes as long as at least half a piece is still to come: the grid applies the piece while the walk goes on (resident
+// mode), and the hand-over after the pivot finishes the list.  (A reload has no pieces: there is no list.)
+template <class Advance> void walk_in_pieces(mcf_ns *s, Advance advance)
+{
+    mcf_ns::MovedList &m = s->moved;
+    const bool pieces = s->hand_over && m.form != mcf_ns::MovedList::kReload;
+    while (m.walked < m.n) {
+        const int stop = pieces && m.n - (m.walked + kWalkPiece) >= kWalkPiece / 2 ? m.walked + kWalkPiece : m.n;
+        advance(stop - m.walked);
+        m.walked = stop;
+        if (stop < m.n) {
+            const double tp = ticks();
+            hand_over_moved(s);
+            s->piece_ticks += ticks() - tp;
+        }
+    }
+}
+
+// fewer than kWalkHintMin nodes: from both ends at once, nodes with values
+void walk_from_both_ends(mcf_ns *s, int first, int last, int64_t sigma)
+{
+    mcf_ns::MovedList &m = s->moved;
+    int32_t *const nodes = m.nodes.data();
+    int64_t *const vals = m.vals.data();
+    int64_t *const pi = s->pi.data();
+    const int32_t *const nxt = s->nxt.data(), *const prv = s->prv.data();
+    int lo = 0, hi = m.n - 1;
+    int a = first, b = last;
+    while (lo < hi) {
+        nodes[lo] = a; vals[lo] = (pi[a] += sigma); a = nxt[a]; ++lo;
+        nodes[hi] = b; vals[hi] = (pi[b] += sigma); b = prv[b]; --hi;
+    }
+    if (lo == hi) { nodes[lo] = a; vals[lo] = (pi[a] += sigma); }
+    m.walked = m.n;
 }
 
 void shift_potentials(mcf_ns *s)
 {
+    using M = mcf_ns::MovedList;
     // runs BEFORE the re-hanging: the nodes that move are the subtree of u_out as it hangs now, and u_in's new parent direction is known
     const int u_out = s->pv.u_out;
     s->sigma = mcf::pivot_sigma(s->pv, s->pi.data(), s->cost.data());
+    // 1. the side
     int count = s->sub[u_out];
     int first = u_out, last = s->fin[u_out];
     // (the common offset pi[root] that this builds up is bounded: past 2^60 the complement is never walked again, so it stops growing and every
@@ -267,136 +295,53 @@ void shift_potentials(mcf_ns *s)
         count = s->n + 1 - count;
     }
     const int64_t sigma = s->sigma;
-    s->moved_n = count;
-    s->moved_as_reload = false;
-    s->moved_without_values = false;
-    s->moved_as_runs = false;
-    if (s->reload_min > 0 && count >= s->reload_min) {
-        // A walk this long is cheaper for the engines as "reload _pi" than as a list (mcf_engine_reload_potentials): nothing is written down,
-        // the walk only moves the potentials.  The hints need the node kWalkAhead steps back: a ring of that many.
-        int64_t *const pi = s->pi.data();
-        const int32_t *const nxt = s->nxt.data();
-        if (s->renumbers > 0) {
-            mcf::BreakWalk w = break_walk(s, first, sigma);
-            w.advance(count, [](int, int) {});
-            s->jumps_since_renumber += w.jumps;
-            s->moved_as_reload = true;
-            s->moved_sent = count;
-            if (s->dbg.on) s->dbg.reload_walks += 1;
-            return;
-        }
-        int32_t *const follow = s->follow.data();
-        int32_t ring[kWalkAhead];
-        int a = first;
-        for (int i = 0; i < count; ++i) {
-            const int h = follow[a];
-            __builtin_prefetch(&nxt[h]);
-            __builtin_prefetch(&pi[h]);
-            __builtin_prefetch(&follow[h]);
-            pi[a] += sigma;
-            if (i >= kWalkAhead) follow[ring[i & (kWalkAhead - 1)]] = a;
-            ring[i & (kWalkAhead - 1)] = a;
-            a = nxt[a];
-        }
-        s->moved_as_reload = true;
-        s->moved_sent = count;
-        if (s->dbg.on) s->dbg.reload_walks += 1;
-        return;
-    }
-    int32_t *const nodes = s->moved.data();
-    int64_t *const vals = s->moved_val.data();
-    int64_t *const pi = s->pi.data();
-    const int32_t *const nxt = s->nxt.data(), *const prv = s->prv.data();
-    if (count < kWalkHintMin) {
-        int lo = 0, hi = count - 1;
-        int a = first, b = last;
-        while (lo < hi) {
-            nodes[lo] = a; vals[lo] = (pi[a] += sigma); a = nxt[a]; ++lo;
-            nodes[hi] = b; vals[hi] = (pi[b] += sigma); b = prv[b]; --hi;
-        }
-        if (lo == hi) { nodes[lo] = a; vals[lo] = (pi[a] += sigma); }
-        return;
-    }
-    if (s->renumbers > 0) {
-        // After a relabelling in thread order the successor of node a is a + 1 almost everywhere: walk in RUNS.  Inside a run the next
-        // address does not depend on the loaded successor (the exit test is a predicted branch, not a data dependency), so the loads of
-        // consecutive nodes overlap and the hardware prefetcher sees a linear stream; a jump costs one unpredicted miss.
-        if (s->use_runs && count >= kRunsMin) {
-            // RUNS: one {first id, length} pair per run instead of the nodes -- the walk stores nothing per node but the potential itself, and the
-            // engines get a list an order of magnitude shorter (the register-resident candidate grid takes the pairs as they are)
-            int32_t *const rf = s->run_first.data(), *const rl = s->run_len.data();
-            int i = 0, nr = 0;
-            mcf::BreakWalk w = break_walk(s, first, sigma);
-            s->moved_as_runs = true;
-            s->runs_sent = 0;
-            while (i < count) {
-                const int stop = s->hand_over && count - (s->moved_sent + kWalkPiece) >= kWalkPiece / 2 ? std::max(i, s->moved_sent + kWalkPiece) : count;
-                if (stop > i) { w.advance(stop - i, [&](int start, int len) { rf[nr] = start; rl[nr] = len; ++nr; }); i = stop; }
-                if (i < count) {
-                    const double tp = ticks();
-                    if (!s->engine_rc) s->engine_rc = engines_shift_runs(s, nr - s->runs_sent, rf + s->runs_sent, rl + s->runs_sent);
-                    s->piece_ticks += ticks() - tp;
-                    s->moved_sent = i;
-                    s->runs_sent = nr;
-                }
-            }
-            s->runs_n = nr;
-            s->jumps_since_renumber += w.jumps;
-            return;
-        }
-        // The engines have _pi bound (mcf_engine_bind_potentials): the list goes without values.
-        int i = 0;
-        mcf::BreakWalk w = break_walk(s, first, sigma);
-        s->moved_without_values = true;
-        while (i < count) {
-            const int stop = s->hand_over && count - (s->moved_sent + kWalkPiece) >= kWalkPiece / 2 ? std::max(i, s->moved_sent + kWalkPiece) : count;
-            if (stop > i) {
-                int32_t *out = nodes + i;
-                w.advance(stop - i, [&](int start, int len) { for (int k = 0; k < len; ++k) out[k] = start + k; out += len; });
-                i = stop;
-            }
-            if (i < count) {
-                const double tp = ticks();
-                if (!s->engine_rc) s->engine_rc = engines_append_potential(s, i - s->moved_sent, nodes + s->moved_sent, nullptr);
-                s->piece_ticks += ticks() - tp;
-                s->moved_sent = i;
-            }
+    // 2. the form.  A walk of reload_min nodes (never below kWalkHintMin) is cheaper for the engines as "reload _pi" than as a list: nothing is
+    // written down, the walk only moves the potentials.  After a relabelling the engines have _pi bound (mcf_engine_bind_potentials) and a list
+    // goes without values; from kRunsMin nodes on it goes as one {first id, length} pair per run -- the walk stores nothing per node but the
+    // potential itself, and the engines get a list an order of magnitude shorter (the register-resident candidate grid takes the pairs as
+    // they are).
+    const bool relabelled = s->renumbers > 0;
+    M &m = s->moved;
+    m.begin(s->reload_min > 0 && count >= s->reload_min ? M::kReload
+            : count < kWalkHintMin || !relabelled       ? M::kValues
+            : s->use_runs && count >= kRunsMin          ? M::kRuns
+                                                        : M::kIds,
+            count);
+    if (m.form == M::kReload && s->dbg.on) s->dbg.reload_walks += 1;
+    // 3. the walker, 4. in pieces
+    if (count < kWalkHintMin) { walk_from_both_ends(s, first, last, sigma); return; }
+    if (relabelled) {
+        // In thread order the successor of node a is a + 1 almost everywhere: RUNS of consecutive ids, their ends from the bitmap of thread
+        // breaks, not from comparing each loaded successor, so no branch depends on a load of nxt; the load of the jump's target is issued
+        // before the run's potentials are added, and the hints in follow[] (run start -> the run start kJumpAhead jumps later) have the misses
+        // of several jumps in flight at once.  (Measured and dropped: eight successors compared per AVX2 step -- slower on the runs of 16 that
+        // the solves have; the bitmap without hints, and hints on the scalar loop without the bitmap -- neither gains on a cold cache,
+        // DESIGN.md section 4.)
+        mcf::BreakWalk w;
+        w.pi = s->pi.data(); w.nxt = s->nxt.data(); w.follow = s->follow.data(); w.bits = s->breaks.data();
+        w.sigma = sigma; w.a = first;
+        if (m.form == M::kRuns) {
+            int32_t *const rf = m.run_first.data(), *const rl = m.run_len.data();
+            int nr = 0;
+            walk_in_pieces(s, [&](int k) { w.advance(k, [&](int start, int len) { rf[nr] = start; rl[nr] = len; ++nr; }); m.runs_n = nr; });
+        } else if (m.form == M::kIds) {
+            int32_t *out = m.nodes.data();
+            walk_in_pieces(s, [&](int k) { w.advance(k, [&](int start, int len) { for (int j = 0; j < len; ++j) out[j] = start + j; out += len; }); });
+        } else {
+            walk_in_pieces(s, [&](int k) { w.advance(k, [](int, int) {}); });
         }
         s->jumps_since_renumber += w.jumps;
-        return;
-    }
-    int32_t *const follow = s->follow.data();
-    int a = first;
-    // the first kWalkAhead nodes have no node that far behind them to leave a hint with (count >= kWalkHintMin > kWalkAhead)
-    int i = 0;
-    for (; i < kWalkAhead; ++i) {
-        const int h = follow[a];
-        __builtin_prefetch(&nxt[h]);
-        __builtin_prefetch(&pi[h]);
-        __builtin_prefetch(&follow[h]);
-        nodes[i] = a;
-        vals[i] = (pi[a] += sigma);
-        a = nxt[a];
-    }
-    while (i < count) {
-        // up to the next point where a piece may be handed over (a piece's worth of nodes since the last one, at least half a piece still to come)
-        const int stop = s->hand_over && count - (s->moved_sent + kWalkPiece) >= kWalkPiece / 2 ? std::max(i, s->moved_sent + kWalkPiece) : count;
-        for (; i < stop; ++i) {
-            const int h = follow[a];
-            __builtin_prefetch(&nxt[h]);
-            __builtin_prefetch(&pi[h]);
-            __builtin_prefetch(&follow[h]);
-            nodes[i] = a;
-            vals[i] = (pi[a] += sigma);
-            follow[nodes[i - kWalkAhead]] = a;
-            a = nxt[a];
-        }
-        if (i < count) {
-            // the grid applies this piece while the walk goes on (resident mode); the search after the pivot finishes the list
-            const double tp = ticks();
-            if (!s->engine_rc) s->engine_rc = engines_append_potential(s, i - s->moved_sent, nodes + s->moved_sent, vals + s->moved_sent);
-            s->piece_ticks += ticks() - tp;
-            s->moved_sent = i;
+    } else {
+        mcf::HintWalk w;
+        w.pi = s->pi.data(); w.nxt = s->nxt.data(); w.follow = s->follow.data();
+        w.sigma = sigma; w.a = first;
+        if (m.form == M::kValues) {
+            int32_t *const nodes = m.nodes.data();
+            int64_t *const vals = m.vals.data();
+            int i = 0;
+            walk_in_pieces(s, [&](int k) { w.advance(k, [&](int a, int64_t v) { nodes[i] = a; vals[i] = v; ++i; }); });
+        } else {
+            walk_in_pieces(s, [&](int k) { w.advance(k, [](int, int64_t) {}); });
         }
     }
 }
@@ -413,34 +358,24 @@ int64_t zero_root_potential(mcf::NsCore *s)
 // the same at the end of a solve, where the engines hear of it: as one list of all nodes, or as a reload of _pi
 int normalise_potentials(mcf_ns *s)
 {
+    using M = mcf_ns::MovedList;
     const int64_t off = zero_root_potential(s);
     if (off == 0) return MCF_OK;
     const int total = s->n + 1;
+    M &m = s->moved;
     s->sigma = -off;
-    if (s->reload_min > 0) {
-        s->moved_n = total;
-        s->moved_sent = total;
-        return engines_reload_potentials(s, total);
-    }
-    for (int u = 0; u < total; ++u) { s->moved[u] = u; s->moved_val[u] = s->pi[u]; }
-    s->moved_n = total;
-    s->moved_sent = 0;
-    const int rc = engines_append_potential(s, total, s->moved.data(), s->moved_val.data());
-    s->moved_sent = total;
-    return rc;
+    m.begin(s->reload_min > 0 ? M::kReload : M::kValues, total);
+    if (m.form == M::kValues) for (int u = 0; u < total; ++u) { m.nodes[u] = u; m.vals[u] = s->pi[u]; }
+    m.walked = total;
+    hand_over_moved(s);
+    return s->engine_rc;
 }
 
-// Relabels the nodes so that id order = current thread order (root keeps id n).  Everything indexed by node is permuted, every arc's end
-// points are translated; arc ids, states, flows, costs stay where they are.  perm_out (optional) receives new id per CURRENT id.
-void renumber_nodes(mcf_ns *s, std::vector<int32_t> *perm_out)
+// Everything indexed by node moves to to[its id], every node id kept in those arrays and every arc's end points are translated; arc ids,
+// states, flows, costs stay where they are.
+void apply_node_permutation(mcf_ns *s, const std::vector<int32_t> &to)
 {
-    const int n = s->n, N = n + 1;
-    std::vector<int32_t> to(N);                      // current id -> new id
-    {
-        int u = s->nxt[s->root];
-        for (int k = 0; k < n; ++k) { to[u] = k; u = s->nxt[u]; }
-        to[s->root] = n;
-    }
+    const int N = s->n + 1;
     auto permute = [&](auto &vec) {                 // in place: the engines have the potentials' storage bound (and registered with HIP)
         using E = typename std::remove_reference<decltype(vec)>::type::value_type;
         std::vector<E> tmp((size_t)N);
@@ -453,6 +388,19 @@ void renumber_nodes(mcf_ns *s, std::vector<int32_t> *perm_out)
     translate(s->par); translate(s->nxt); translate(s->prv); translate(s->fin); translate(s->follow);
     const size_t A = s->tail.size();
     for (size_t e = 0; e < A; ++e) { s->tail[e] = to[s->tail[e]]; s->head[e] = to[s->head[e]]; }
+}
+
+// Relabels the nodes so that id order = current thread order (root keeps id n).  perm_out (optional) receives new id per CURRENT id.
+void renumber_nodes(mcf_ns *s, std::vector<int32_t> *perm_out)
+{
+    const int n = s->n, N = n + 1;
+    std::vector<int32_t> to(N);                      // current id -> new id
+    {
+        int u = s->nxt[s->root];
+        for (int k = 0; k < n; ++k) { to[u] = k; u = s->nxt[u]; }
+        to[s->root] = n;
+    }
+    apply_node_permutation(s, to);
     if (s->new_of.empty()) {
         s->new_of = to;
     } else {
@@ -473,23 +421,41 @@ void renumber_nodes(mcf_ns *s, std::vector<int32_t> *perm_out)
 void restore_node_ids(mcf_ns *s)
 {
     if (s->new_of.empty()) return;
-    const int N = s->n + 1;
-    const std::vector<int32_t> &back = s->orig_of;      // id in use -> caller's id
-    auto permute = [&](auto &vec) {
-        using E = typename std::remove_reference<decltype(vec)>::type::value_type;
-        std::vector<E> tmp((size_t)N);
-        for (int u = 0; u < N; ++u) tmp[back[u]] = vec[u];
-        std::copy(tmp.begin(), tmp.end(), vec.begin());
-    };
-    auto translate = [&](auto &vec) { for (int u = 0; u < N; ++u) if (vec[u] >= 0) vec[u] = back[vec[u]]; };
-    permute(s->supply); permute(s->pi); permute(s->par); permute(s->par_arc); permute(s->nxt); permute(s->prv); permute(s->sub); permute(s->fin);
-    permute(s->par_dir); permute(s->follow);
-    translate(s->par); translate(s->nxt); translate(s->prv); translate(s->fin); translate(s->follow);
-    const size_t A = s->tail.size();
-    for (size_t e = 0; e < A; ++e) { s->tail[e] = back[s->tail[e]]; s->head[e] = back[s->head[e]]; }
+    apply_node_permutation(s, s->orig_of);      // id in use -> caller's id
     s->new_of.clear(); s->orig_of.clear();
     // walks after this (the stepwise API) still go run by run, over the caller's ids: the bitmap follows
     if (!s->breaks.empty()) mcf::breaks_rebuild(s->breaks.data(), s->nxt.data(), s->n);
+}
+
+// ---- When to relabel.  The first time: when the walks have covered renumber_every times the node count, or a quarter of n pivots have passed
+// (the cycle searches and the candidate cache's re-evaluation of the moved nodes' arcs chase the same ids).  After that the walks count
+// their JUMPS -- the steps that leave the id order, charged kJumpNs each, which is what a relabelling buys back -- and the next relabelling
+// comes when the jumps since the last one have cost five times what that one took (2.9 ms with 400 k arcs, 0.3 s with 9 M: the engines
+// rebuild their per-node tables).  Config 5, whole solve: 28.9 s with the 4 relabellings of the first policy (a fixed interval, and never
+// before 25 times the last one's duration), 26.7 with 6, 27.9 with 12; config 3: flat between 6 and 13.  MCF_NS_RENUMBER=x forces an interval.
+bool relabelling_due(const mcf_ns *s, int64_t it)
+{
+    if (!s->allow_renumber) return false;
+    const bool walked_enough = (double)s->walked_since_renumber > s->renumber_every * (s->n + 1);
+    if (s->renumber_forced) return walked_enough;
+    if (s->renumbers == 0) return walked_enough || 4 * (it - s->renumber_at_pivot) > (int64_t)s->n;
+    return (double)s->jumps_since_renumber > s->renumber_jump_budget;
+}
+
+// relabels the nodes in thread order, here and in the engines, before pivot `it`; sets the jump budget up to the next time
+int relabel(mcf_ns *s, int64_t it, double t_start, double tick_start)
+{
+    const double tr0 = ticks();
+    std::vector<int32_t> perm;
+    renumber_nodes(s, &perm);
+    const int rc = engines_each(s, [&](mcf_engine *e) { return mcf_engine_renumber_nodes(e, perm.data()); });
+    s->renumber_last_ticks = ticks() - tr0;
+    s->renumber_last_at = ticks();
+    s->renumber_at_pivot = it;
+    const double ns_per_tick_now = (mcf::now_ns() - t_start) / std::max(1.0, ticks() - tick_start);
+    s->renumber_jump_budget = 5.0 * s->renumber_last_ticks * ns_per_tick_now / kJumpNs;     // jumps that cost five times this relabelling
+    s->renumber_ticks += s->renumber_last_ticks;
+    return rc;
 }
 
 // One pivot with a given entering arc, in two halves.  pivot_front does what the next search depends on -- the cycle, the State[] writes and
@@ -498,15 +464,15 @@ void restore_node_ids(mcf_ns *s)
 // while the device is already searching.
 bool pivot_front(mcf_ns *s, int arc, double *t_pot)
 {
-    s->moved_n = 0;
-    s->moved_sent = 0;
+    s->moved.begin(mcf_ns::MovedList::kNothing, 0);
     s->sigma = 0;
     s->pv = mcf::find_cycle(s->tv, arc, s->state[arc]);
     const mcf::Pivot &p = s->pv;
     if (!p.change && p.delta == 0) return true;
     decide_states(s);
     // the engine hears about the state writes before any piece of the potential list (the pieces may start travelling at once)
-    if (s->hand_over && !s->engine_rc) s->engine_rc = engines_patch_state(s, s->n_state, s->st_arc, s->st_val);
+    if (s->hand_over && !s->engine_rc)       // (every engine keeps the writes that fall into its shard)
+        s->engine_rc = engines_each(s, [&](mcf_engine *e) { return mcf_engine_patch_state(e, s->n_state, s->st_arc, s->st_val); });
     if (p.delta == 0) s->metrics.degenerate_pivots++;
     if (p.change) {
         const double t1 = ticks();
@@ -695,6 +661,44 @@ int pick_int_width(const mcf_ns *s)
 
 }  // namespace
 
+// ---- MCF_NS_DEBUG: the per-pivot bookkeeping and the report on stderr
+void mcf_ns::Debug::waited(double t0, double t_got)
+{
+    if (size_class >= 0) { wait[size_class] += t_got - t0; rest[size_class] += t0 - t_prev; }
+}
+
+void mcf_ns::Debug::pivoted(const mcf_ns *s, double walk_ticks, double t_got)
+{
+    const int moved_n = s->moved.n;
+    const int b = moved_n > 0 ? 31 - __builtin_clz((unsigned)moved_n) + 1 : 0;      // class 0: nothing moved; class b: 2^(b-1) .. 2^b - 1 nodes
+    size_class = b;
+    n[b] += 1; nodes[b] += moved_n;
+    walk[b] += walk_ticks;              // walk + hand-over + posting the search
+    t_prev = t_got + walk_ticks;        // what remains until the next wait begins is "rest" (cycle search, flows, tree)
+    if (2 * (int64_t)moved_n > s->n) { over_half += 1; over_half_nodes += moved_n; }
+}
+
+void mcf_ns::Debug::report(const mcf_ns *s, int64_t it, const Buckets &t, double ns_per_tick, double tick_start) const
+{
+    fprintf(stderr, "[ns] per pivot ns: search wait %.0f | walk %.0f | pieces handed over during walks %.0f | last hand-over %.0f | search begin %.0f | tree %.0f | everything else %.0f\n",
+            t.search * ns_per_tick / it, (t.pot - t.hand - t.begin - t.pieces) * ns_per_tick / it, t.pieces * ns_per_tick / it, t.hand * ns_per_tick / it, t.begin * ns_per_tick / it, t.tree * ns_per_tick / it,
+            ((ticks() - tick_start) - t.search - t.pot - t.tree) * ns_per_tick / it);
+    fprintf(stderr, "[ns] pivots by size of the moved subtree: nodes | pivots | share of pivots | nodes moved | us per pivot: walk+hand-over, search wait, rest | share of the solve\n");
+    const double all_ticks = std::max(1.0, ticks() - tick_start);
+    for (int b = 0; b < 32; ++b) {
+        if (!n[b]) continue;
+        const double k = (double)n[b], us = ns_per_tick / 1e3;
+        char label[48];
+        if (b == 0) snprintf(label, sizeof(label), "0");
+        else if (b == 1) snprintf(label, sizeof(label), "1");
+        else snprintf(label, sizeof(label), "%d-%d", 1 << (b - 1), (1 << b) - 1);
+        fprintf(stderr, "[ns]   %14s | %8lld | %5.1f %% | %11lld | %7.2f %7.2f %7.2f | %5.1f %%\n", label, (long long)n[b], 100.0 * k / (double)it, (long long)nodes[b],
+                walk[b] * us / k, wait[b] * us / k, rest[b] * us / k, 100.0 * (walk[b] + wait[b] + rest[b]) / all_ticks);
+    }
+    fprintf(stderr, "[ns] more than half of the %d nodes: %lld pivots / %lld nodes | walks announced as a reload of _pi (%d nodes and more): %lld | nodes relabelled in thread order %lld times, %.1f ms (%.1f %% of the steps since the last time left the id order)\n", s->n, (long long)over_half,
+            (long long)over_half_nodes, s->reload_min_engines, (long long)reload_walks, (long long)s->renumbers, s->renumber_ticks * ns_per_tick / 1e6, 100.0 * (double)s->jumps_since_renumber / std::max<double>(1.0, (double)s->walked_since_renumber));
+}
+
 extern "C" {
 
 int mcf_ns_create(mcf_ns **out, int32_t node_count, int32_t arc_count, const int32_t *source, const int32_t *target)
@@ -705,8 +709,8 @@ int mcf_ns_create(mcf_ns **out, int32_t node_count, int32_t arc_count, const int
     if (const int rc = mcf::core_create(s, node_count, arc_count, source, target)) { delete s; return rc; }
     mcf_block_config_default(&s->config);
     const size_t N = (size_t)node_count + 1;
-    s->moved.assign(N, 0); s->moved_val.assign(N, 0); s->follow.assign(N, 0);
-    s->run_first.assign(N, 0); s->run_len.assign(N, 0);
+    s->moved.nodes.assign(N, 0); s->moved.vals.assign(N, 0); s->follow.assign(N, 0);
+    s->moved.run_first.assign(N, 0); s->moved.run_len.assign(N, 0);
     *out = s;
     return MCF_OK;
 }
@@ -883,8 +887,8 @@ int mcf_ns_replay(mcf_ns *s, const int32_t *arcs, int64_t count, int32_t smaller
         const int arc = arcs[it];
         if (arc < 0 || arc >= s->search_arcs || s->state[arc] == MCF_STATE_TREE) { s->shift_smaller_side = false; return mcf::fail(MCF_ERR_INVALID, "pivot %lld: arc %d cannot enter", (long long)it, arc); }
         if (pivot(s, arc, &t_tree, &t_pot)) { s->status = MCF_UNBOUNDED; break; }
-        moved += s->moved_n;
-        s->walked_since_renumber += s->moved_n;
+        moved += s->moved.n;
+        s->walked_since_renumber += s->moved.n;
         if (renumber_every > 0 && (double)s->walked_since_renumber > renumber_every * (s->n + 1)) {
             const double t0 = ticks();
             renumber_nodes(s, nullptr);
@@ -956,8 +960,15 @@ int mcf_ns_last_pivot(mcf_ns *s, int32_t *n_state, int32_t arcs[2], int8_t state
     if (!s) return mcf::fail(MCF_ERR_INVALID, "null solver");
     if (n_state) *n_state = s->n_state;
     for (int i = 0; i < s->n_state; ++i) { if (arcs) arcs[i] = s->st_arc[i]; if (states) states[i] = s->st_val[i]; }
-    if (n_nodes) *n_nodes = (int32_t)s->moved_n;
-    if (nodes) *nodes = s->moved.data();
+    mcf_ns::MovedList &m = s->moved;
+    if (n_nodes) *n_nodes = (int32_t)m.n;
+    if (nodes) {
+        if (m.form == mcf_ns::MovedList::kRuns) {       // never inside a solve: the runs may be written out
+            int32_t *out = m.nodes.data();
+            for (int r = 0; r < m.runs_n; ++r) for (int j = 0; j < m.run_len[r]; ++j) *out++ = m.run_first[r] + j;
+        }
+        *nodes = m.form == mcf_ns::MovedList::kReload ? nullptr : m.nodes.data();
+    }
     if (sigma) *sigma = s->sigma;
     return MCF_OK;
 }
@@ -1111,8 +1122,6 @@ int mcf_ns_solve(mcf_ns *s, int32_t *status)
     s->renumber_at_pivot = 0;
     s->dbg = mcf_ns::Debug{};
     s->dbg.on = getenv("MCF_NS_DEBUG") != nullptr;
-    int dbg_class = -1;              // size class of the pivot whose search is being waited for
-    double dbg_t_prev = 0;
     // a list rule searches synchronously at the top of the loop (the host answers from its list or the device collects); nothing is posted
     s->list_stats = mcf_list_rule_stats{};
     if (s->list_rule) list_rule_init(s);
@@ -1126,47 +1135,20 @@ int mcf_ns_solve(mcf_ns *s, int32_t *status)
         rc = s->list_rule ? list_find_entering(s, &found, &arc) : engines_search_end(s, &found, &arc);
         const double t_got = ticks();
         t_search += t_got - t0;
-        if (s->dbg.on && dbg_class >= 0) { s->dbg.wait[dbg_class] += t_got - t0; s->dbg.rest[dbg_class] += (t0 - dbg_t_prev); }
+        if (s->dbg.on) s->dbg.waited(t0, t_got);
         if (rc || !found) break;
         if (s->trace && it < s->trace_cap) s->trace[it] = arc;
         ++it;
         if (it > max_iter) { s->status = MCF_INFEASIBLE; break; }                          // NS.cs:311-317
         if (s->pivot_limit && it > s->pivot_limit) { --it; limited = true; break; }
-        // When to relabel.  The first time: when the walks have covered renumber_every times the node count, or a quarter of n pivots have passed
-        // (the cycle searches and the candidate cache's re-evaluation of the moved nodes' arcs chase the same ids).  After that the walks count
-        // their JUMPS -- the steps that leave the id order, charged kJumpNs each, which is what a relabelling buys back -- and the next relabelling
-        // comes when the jumps since the last one have cost five times what that one took (2.9 ms with 400 k arcs, 0.3 s with 9 M: the engines
-        // rebuild their per-node tables).  Config 5, whole solve: 28.9 s with the 4 relabellings of the first policy (a fixed interval, and never
-        // before 25 times the last one's duration), 26.7 with 6, 27.9 with 12; config 3: flat between 6 and 13.  MCF_NS_RENUMBER=x forces an interval.
         if (s->dbg.on && (it % 100000) == 0) fprintf(stderr, "[ns] %lld pivots, %.2f s\n", (long long)it, (mcf::now_ns() - t_start) / 1e9);
-        const bool relabel_now = !s->allow_renumber ? false
-            : s->renumber_forced ? (double)s->walked_since_renumber > s->renumber_every * (s->n + 1)
-            : s->renumbers == 0 ? ((double)s->walked_since_renumber > s->renumber_every * (s->n + 1) || 4 * (it - s->renumber_at_pivot) > (int64_t)s->n)
-            : (double)s->jumps_since_renumber > s->renumber_jump_budget;
-        if (relabel_now) {
-            // no search in flight, nothing of a pivot half done: relabel the nodes in thread order, here and in the engines
-            const double tr0 = ticks();
-            std::vector<int32_t> perm;
-            renumber_nodes(s, &perm);
-            rc = engines_renumber(s, perm.data());
-            s->renumber_last_ticks = ticks() - tr0;
-            s->renumber_last_at = ticks();
-            s->renumber_at_pivot = it;
-            {   // jumps that cost five times this relabelling (kJumpNs each)
-                const double ns_per_tick_now = (mcf::now_ns() - t_start) / std::max(1.0, ticks() - tick_start);
-                s->renumber_jump_budget = 5.0 * s->renumber_last_ticks * ns_per_tick_now / kJumpNs;
-            }
-            s->renumber_ticks += s->renumber_last_ticks;
-            if (rc) break;
-        }
+        // no search in flight, nothing of a pivot half done: the place to relabel
+        if (relabelling_due(s, it)) { rc = relabel(s, it, t_start, tick_start); if (rc) break; }
         const double t_pot_before = t_pot;
         if (pivot_front(s, arc, &t_pot)) { s->status = MCF_UNBOUNDED; break; }
         const double t1 = ticks();
+        hand_over_moved(s);                // the rest of the list, or all of it
         rc = s->engine_rc;
-        if (!rc && s->moved_as_reload) rc = engines_reload_potentials(s, (int32_t)s->moved_n);
-        else if (!rc && s->moved_as_runs) { if (s->runs_n > s->runs_sent) rc = engines_shift_runs(s, s->runs_n - s->runs_sent, s->run_first.data() + s->runs_sent, s->run_len.data() + s->runs_sent); }
-        else if (!rc && s->moved_n > s->moved_sent)
-            rc = engines_append_potential(s, (int32_t)(s->moved_n - s->moved_sent), s->moved.data() + s->moved_sent, s->moved_without_values ? nullptr : s->moved_val.data() + s->moved_sent);
         const double t2 = ticks();
         if (!rc && !s->list_rule) rc = engines_search_begin(s);
         const double t3 = ticks();
@@ -1175,16 +1157,9 @@ int mcf_ns_solve(mcf_ns *s, int32_t *status)
         t_begin += t3 - t2;
         if (rc) break;                     // the pivot stays half done: the solver is unusable after an engine error, but nothing is left running
         pivot_back(s, &t_tree);
-        s->metrics.potential_nodes += (int64_t)s->moved_n;
-        s->walked_since_renumber += s->moved_n;
-        if (s->dbg.on) {
-            const int b = s->moved_n > 0 ? 31 - __builtin_clz((unsigned)s->moved_n) + 1 : 0;      // class 0: nothing moved; class b: 2^(b-1) .. 2^b - 1 nodes
-            dbg_class = b;
-            s->dbg.n[b] += 1; s->dbg.nodes[b] += s->moved_n;
-            s->dbg.walk[b] += (t_pot - t_pot_before);           // walk + hand-over + posting the search
-            dbg_t_prev = t_got + (t_pot - t_pot_before);        // what remains until the next wait begins is "rest" (cycle search, flows, tree)
-            if (2 * (int64_t)s->moved_n > s->n) { s->dbg.over_half += 1; s->dbg.over_half_nodes += s->moved_n; }
-        }
+        s->metrics.potential_nodes += (int64_t)s->moved.n;
+        s->walked_since_renumber += s->moved.n;
+        if (s->dbg.on) s->dbg.pivoted(s, t_pot - t_pot_before, t_got);
     }
     // ONE way out, error or not: no hand-over pending, no resident grid left spinning, trace length and iteration count filled in
     s->hand_over = false;
@@ -1195,7 +1170,7 @@ int mcf_ns_solve(mcf_ns *s, int32_t *status)
     restore_node_ids(s);             // the caller's node ids again (the parked engines keep the relabelled ones: Solve() is single-shot)
     const char *first_error = rc ? mcf_last_error() : nullptr;
     std::string keep_error = first_error ? first_error : "";
-    engines_park(s);                 // a resident scan grid must not outlive Solve()
+    engines_each(s, [](mcf_engine *e) { mcf_engine_park(e); return MCF_OK; });     // a resident scan grid must not outlive Solve()
     s->trace_len = std::min(it, s->trace_cap);
     s->metrics.iterations = it;
     if (!rc && s->status == MCF_NOT_SOLVED && !limited) mcf::core_finish(s);
@@ -1204,26 +1179,7 @@ int mcf_ns_solve(mcf_ns *s, int32_t *status)
     s->metrics.pivot_search_us = t_search * ns_per_tick / 1e3;
     s->metrics.tree_update_us = t_tree * ns_per_tick / 1e3;
     s->metrics.potential_update_us = t_pot * ns_per_tick / 1e3;
-    if (s->dbg.on && it > 1000)
-        fprintf(stderr, "[ns] per pivot ns: search wait %.0f | walk %.0f | pieces handed over during walks %.0f | last hand-over %.0f | search begin %.0f | tree %.0f | everything else %.0f\n",
-                t_search * ns_per_tick / it, (t_pot - t_hand - t_begin - s->piece_ticks) * ns_per_tick / it, s->piece_ticks * ns_per_tick / it, t_hand * ns_per_tick / it, t_begin * ns_per_tick / it, t_tree * ns_per_tick / it,
-                ((ticks() - tick_start) - t_search - t_pot - t_tree) * ns_per_tick / it);
-    if (s->dbg.on && it > 1000) {
-        fprintf(stderr, "[ns] pivots by size of the moved subtree: nodes | pivots | share of pivots | nodes moved | us per pivot: walk+hand-over, search wait, rest | share of the solve\n");
-        const double all_ticks = std::max(1.0, ticks() - tick_start);
-        for (int b = 0; b < 32; ++b) {
-            if (!s->dbg.n[b]) continue;
-            const double k = (double)s->dbg.n[b], us = ns_per_tick / 1e3;
-            char label[48];
-            if (b == 0) snprintf(label, sizeof(label), "0");
-            else if (b == 1) snprintf(label, sizeof(label), "1");
-            else snprintf(label, sizeof(label), "%d-%d", 1 << (b - 1), (1 << b) - 1);
-            fprintf(stderr, "[ns]   %14s | %8lld | %5.1f %% | %11lld | %7.2f %7.2f %7.2f | %5.1f %%\n", label, (long long)s->dbg.n[b], 100.0 * k / (double)it, (long long)s->dbg.nodes[b],
-                    s->dbg.walk[b] * us / k, s->dbg.wait[b] * us / k, s->dbg.rest[b] * us / k, 100.0 * (s->dbg.walk[b] + s->dbg.wait[b] + s->dbg.rest[b]) / all_ticks);
-        }
-        fprintf(stderr, "[ns] more than half of the %d nodes: %lld pivots / %lld nodes | walks announced as a reload of _pi (%d nodes and more): %lld | nodes relabelled in thread order %lld times, %.1f ms (%.1f %% of the steps since the last time left the id order)\n", s->n, (long long)s->dbg.over_half,
-                (long long)s->dbg.over_half_nodes, s->reload_min_engines, (long long)s->dbg.reload_walks, (long long)s->renumbers, s->renumber_ticks * ns_per_tick / 1e6, 100.0 * (double)s->jumps_since_renumber / std::max<double>(1.0, (double)s->walked_since_renumber));
-    }
+    if (s->dbg.on && it > 1000) s->dbg.report(s, it, {t_search, t_tree, t_pot, t_hand, t_begin, s->piece_ticks}, ns_per_tick, tick_start);
     mcf_engine_get_stats(s->engine, &s->metrics.engine);
     // the rest of SolverMetrics: NS.cs:262-270 (initial block size), :276 (expected iterations), :344-357
     const bool plain_block = !s->list_rule && s->rule == MCF_RULE_BLOCK_SEARCH && !s->optimized_pivot;
@@ -1322,12 +1278,12 @@ int mcf_ns_check_reduced_costs(mcf_ns *s, int64_t *mismatches)
 {
     if (!s || !mismatches) return mcf::fail(MCF_ERR_INVALID, "null argument");
     *mismatches = 0;
-    if (!s->engine) return MCF_OK;
-    int64_t m = 0;
-    int rc = mcf_engine_check_reduced_costs(s->engine, &m, nullptr);
-    *mismatches += m;
-    for (size_t i = 0; i < s->peers.size() && !rc; ++i) { rc = mcf_engine_check_reduced_costs(s->peers[i], &m, nullptr); *mismatches += m; }
-    return rc;
+    return engines_each(s, [&](mcf_engine *e) {
+        int64_t m = 0;
+        const int rc = mcf_engine_check_reduced_costs(e, &m, nullptr);
+        *mismatches += m;
+        return rc;
+    });
 }
 int mcf_ns_get_metrics(mcf_ns *s, mcf_ns_metrics *out)
 {

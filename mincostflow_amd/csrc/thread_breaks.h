@@ -1,4 +1,5 @@
-// thread_breaks.h -- the walk over a moved subtree after the nodes have been relabelled in thread order, run by run.
+// thread_breaks.h -- the two walkers over a moved subtree: run by run after the nodes have been relabelled in thread order (BreakWalk, with
+// the bitmap it reads), node by node with prefetch hints before that (HintWalk, at the end of the file).
 //
 // After a relabelling the successor of node a in the thread list is a + 1 almost everywhere.  Where it is not, the list has a BREAK.  The
 // driver keeps one bit per node, set exactly where nxt[a] != a + 1, and the walk takes the end of the run it is in from that bitmap instead
@@ -116,6 +117,46 @@ struct BreakWalk {
         }
         this->a = a;
         this->at_start = at_start;
+    }
+};
+
+// ---- the walker used before the first relabelling, when the thread order has nothing to do with the id order: node by node along nxt, one
+// dependent load per node.  PREFETCH HINTS shorten that chain: follow[v] remembers which node came kWalkAhead steps after v the last time a
+// walk passed v, and its lines are prefetched when the walk reaches v.  The thread order of a subtree changes little between pivots, so most
+// hints are still right; a stale one costs a useless prefetch, nothing else.  Same shape as BreakWalk: one object per walk, advance() piece
+// by piece, cut anywhere.
+constexpr int kWalkAhead = 8;      // a power of two
+
+struct HintWalk {
+    int64_t *pi;
+    const int32_t *nxt;
+    int32_t *follow;
+    int64_t sigma;
+    int a;                      // the next node to visit
+    unsigned seen = 0;          // nodes visited so far
+    int32_t ring[kWalkAhead];   // the last kWalkAhead of them
+
+    // the next `count` nodes move by sigma; emit(node, its new potential) is called once per node in walk order
+    template <class Emit> void advance(int count, Emit emit)
+    {
+        int a = this->a;
+        unsigned i = seen;
+        const unsigned end = i + (unsigned)count;
+        auto step = [&](bool hint) {
+            const int h = follow[a];
+            __builtin_prefetch(&nxt[h]);
+            __builtin_prefetch(&pi[h]);
+            __builtin_prefetch(&follow[h]);
+            emit(a, pi[a] += sigma);
+            if (hint) follow[ring[i & (kWalkAhead - 1)]] = a;
+            ring[i & (kWalkAhead - 1)] = a;
+            a = nxt[a];
+        };
+        // the walk's first kWalkAhead nodes have no node that far behind them to leave a hint with
+        for (; i < end && i < (unsigned)kWalkAhead; ++i) step(false);
+        for (; i < end; ++i) step(true);
+        this->a = a;
+        seen = i;
     }
 };
 

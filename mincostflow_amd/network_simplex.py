@@ -309,13 +309,15 @@ class NetworkSimplex:
         return dict(parent=cp(par, n1), pred_arc=cp(pred, n1), succ_num=cp(succ, n1), pred_dir=cp(pdir, n1), flow=cp(flow, a), upper=cp(upper, a))
 
     def last_pivot(self) -> dict:
+        """mcf_ns_last_pivot: the State[] writes, sigma and the nodes whose potential moved (`count` of them; `nodes` is empty where the
+        walk wrote no list down, a reload inside Solve())."""
         ns, nn, sigma = C.c_int32(), C.c_int32(), C.c_int64()
         arcs, states = (C.c_int32 * 2)(), (C.c_int8 * 2)()
         nodes = C.POINTER(C.c_int32)()
         L.check(L.lib().mcf_ns_last_pivot(self._h, C.byref(ns), arcs, states, C.byref(nn), C.byref(nodes), C.byref(sigma)))
-        nd = np.ctypeslib.as_array(nodes, shape=(nn.value,)).copy() if nn.value else np.zeros(0, np.int32)
+        nd = np.ctypeslib.as_array(nodes, shape=(nn.value,)).copy() if nn.value and nodes else np.zeros(0, np.int32)
         return dict(state_arcs=np.array(arcs[: ns.value], np.int32), state_values=np.array(states[: ns.value], np.int8),
-                    nodes=nd, sigma=sigma.value)
+                    nodes=nd, count=nn.value, sigma=sigma.value)
 
 
 class BatchSolver:

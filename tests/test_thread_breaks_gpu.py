@@ -64,6 +64,8 @@ def test_stepwise_pivots_on_the_device_keep_the_bitmap_current():
         eng.patch_state(lp["state_arcs"], lp["state_values"])
         now = ns.internal()["pi"]
         moved = np.nonzero(now != pi)[0].astype(np.int32)
+        if lp["sigma"] != 0:
+            assert np.array_equal(np.sort(lp["nodes"]), moved), i
         if len(moved):
             eng.set_potential(moved, now[moved])
         pi = now

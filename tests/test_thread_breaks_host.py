@@ -86,3 +86,39 @@ def test_pivot_by_pivot_keeps_the_bitmap_current(n, smaller_side):
         assert not ns.apply_pivot(int(e))
         assert ns.check_thread_breaks() == 0
     _assert_equals_oracle(ns, o)
+
+
+@functools.lru_cache(maxsize=None)
+def _big_instance():
+    """3 000 nodes / 12 000 arcs, large enough for walks of 512 nodes and more (the run form): (problem, the oracle's Best Eligible trace)."""
+    g = M.netgen_like(13502460, 3000, 12000, 40, 40)
+    p = O.Problem(g.node_count, g.arc_count, g.source, g.target, g.lower, g.upper, g.cost, g.supply)
+    st, trace = O.Oracle(p, O.SEM_CSHARP_OPT, O.RULE_BEST).solve(trace_cap=1 << 20)
+    assert st == O.OPTIMAL
+    return p, np.asarray(trace, np.int32)
+
+
+@pytest.mark.parametrize("renumber_every", [0.1, 0.0], ids=["relabelled", "control"])
+def test_last_pivot_lists_the_nodes_that_moved(renumber_every):
+    """mcf_ns_last_pivot after a replayed first half (32 relabellings at renumber_every=0.1, so the second half's walks of 512 nodes and more
+    are written down as runs of consecutive ids): after every pivot of the second half the returned list is exactly the set of nodes whose
+    potential changed, and each of them changed by sigma.  The control never relabels (no bitmap, no runs)."""
+    p, trace = _big_instance()
+    ns = _solver(p)
+    k = len(trace) // 2
+    ns.replay(trace[:k], smaller_side=False, renumber_every=renumber_every)
+    assert (ns.replay_relabellings >= 10) if renumber_every else (ns.replay_relabellings == 0)
+    pi = ns.internal()["pi"]
+    big = 0
+    for i, e in enumerate(trace[k:]):
+        assert not ns.apply_pivot(int(e))
+        lp, now = ns.last_pivot(), ns.internal()["pi"]
+        if lp["sigma"] != 0:
+            changed = np.nonzero(now != pi)[0]
+            assert lp["count"] == len(changed), i
+            assert np.array_equal(np.sort(lp["nodes"]), changed), (i, len(changed))
+            assert np.all(now[changed] - pi[changed] == lp["sigma"]), i
+            big += len(changed) >= 512
+        pi = now
+    assert big >= 100, big
+    assert ns.finish() == O.OPTIMAL

@@ -1,4 +1,4 @@
-// thread_breaks_check.cpp -- the thread-break bitmap and the run walker of the host driver (mincostflow_amd/csrc/thread_breaks.h) together
+// thread_breaks_check.cpp -- the thread-break bitmap and the two walkers of the host driver (mincostflow_amd/csrc/thread_breaks.h) together
 // with rehang_subtree's note hook (tree_pivot.h) as a stand-alone program, to be built under -fsanitize=address,undefined and run on a CPU
 // (DESIGN.md section 4).  Needs no GPU, no HIP and is not loaded into Python.
 //
@@ -10,7 +10,9 @@
 //   * the bitmap kept by the hook equals a recomputation from the thread list,
 //   * a walk over a random subtree or over its complement (through the root), cut into pieces of odd sizes, visits exactly the nodes of a plain
 //     thread walk, in the same order, adds sigma to exactly their potentials, emits only runs of consecutive ids and counts the breaks it
-//     crossed.
+//     crossed,
+//   * the hinted walker (the one the driver uses before its first relabelling) over another such segment, cut the same way, visits the same
+//     nodes as a plain thread walk in the same order and emits their new potentials, and follow[] holds node ids only.
 // All arrays are sized exactly, so a read or write past node n is the sanitizer's to find.
 #include <cstdint>
 #include <cstdio>
@@ -103,22 +105,66 @@ void check_tree(const Tree &t, int n, long pivot)
     }
 }
 
-long walks = 0, runs_seen = 0, cut_runs = 0;
+long walks = 0, hint_walks = 0, runs_seen = 0, cut_runs = 0;
+
+// a subtree, or everything but a subtree (from the node behind its last one round through the root to the node before it), walked plainly
+struct Segment {
+    int first, count, behind;
+    int64_t sigma, breaks = 0;
+    std::vector<int32_t> plain;
+    std::vector<int64_t> want;      // every potential after the walk
+    explicit Segment(const Tree &t) : want(t.pi)
+    {
+        const int n = t.n, top = (int)rnd((uint32_t)n);
+        first = top; count = t.sub[(size_t)top];
+        if (rnd(3) == 0 && count <= n) { first = t.nxt[(size_t)t.fin[(size_t)top]]; count = n + 1 - count; }
+        sigma = (int64_t)rnd(1000) - 500;
+        int u = first;
+        for (int k = 0; k < count; ++k) { plain.push_back(u); want[(size_t)u] += sigma; breaks += t.nxt[(size_t)u] != u + 1; u = t.nxt[(size_t)u]; }
+        behind = u;
+    }
+    // odd sizes, many of them inside a run
+    int piece(int done) const
+    {
+        int k = 1 + 2 * (int)rnd(12);
+        if (rnd(4) == 0) k = count;
+        return k > count - done ? count - done : k;
+    }
+};
+
+void check_hint_walk(Tree &t, long pivot)
+{
+    const int n = t.n;
+    const Segment sg(t);
+    mcf::HintWalk w;
+    w.pi = t.pi.data(); w.nxt = t.nxt.data(); w.follow = t.follow.data();
+    w.sigma = sg.sigma; w.a = sg.first;
+    std::vector<int32_t> got;
+    for (int done = 0; done < sg.count;) {
+        const int piece = sg.piece(done);
+        const size_t before = got.size();
+        w.advance(piece, [&](int a, int64_t v) {
+            REQUIRE(a >= 0 && a <= n && v == sg.want[(size_t)a], "n %d pivot %ld: hinted walk emits node %d with %lld", n, pivot, a, (long long)v);
+            got.push_back(a);
+        });
+        REQUIRE(got.size() - before == (size_t)piece, "n %d pivot %ld: a hinted piece of %d nodes emitted %zu", n, pivot, piece, got.size() - before);
+        done += piece;
+    }
+    REQUIRE(got == sg.plain, "n %d pivot %ld: the hinted walk from %d over %d nodes visits other nodes than the thread list", n, pivot, sg.first, sg.count);
+    REQUIRE(t.pi == sg.want, "n %d pivot %ld: potentials after the hinted walk from %d over %d nodes", n, pivot, sg.first, sg.count);
+    REQUIRE(w.a == sg.behind && w.seen == (unsigned)sg.count, "n %d pivot %ld: the hinted walk stopped before %d after %u nodes", n, pivot, w.a, w.seen);
+    for (int x = 0; x <= n; ++x) REQUIRE(t.follow[(size_t)x] >= 0 && t.follow[(size_t)x] <= n, "n %d pivot %ld: hint of %d", n, pivot, x);
+    ++hint_walks;
+}
 
 void check_walk(Tree &t, long pivot)
 {
     const int n = t.n;
-    // a subtree, or everything but a subtree (from the node behind its last one round through the root to the node before it)
-    const int top = (int)rnd((uint32_t)n);
-    int first = top, count = t.sub[(size_t)top];
-    if (rnd(3) == 0 && count <= n) { first = t.nxt[(size_t)t.fin[(size_t)top]]; count = n + 1 - count; }
-    const int64_t sigma = (int64_t)rnd(1000) - 500;
-    std::vector<int32_t> plain;
-    std::vector<int64_t> want = t.pi;
-    int u = first;
-    int64_t breaks = 0;
-    for (int k = 0; k < count; ++k) { plain.push_back(u); want[(size_t)u] += sigma; breaks += t.nxt[(size_t)u] != u + 1; u = t.nxt[(size_t)u]; }
-    const int behind = u;
+    const Segment sg(t);
+    const int first = sg.first, count = sg.count, behind = sg.behind;
+    const int64_t sigma = sg.sigma, breaks = sg.breaks;
+    const std::vector<int32_t> &plain = sg.plain;
+    const std::vector<int64_t> &want = sg.want;
 
     mcf::BreakWalk w;
     w.pi = t.pi.data(); w.nxt = t.nxt.data(); w.follow = t.follow.data(); w.bits = t.bits.data();
@@ -126,9 +172,7 @@ void check_walk(Tree &t, long pivot)
     std::vector<int32_t> got;
     int done = 0;
     while (done < count) {
-        int piece = 1 + 2 * (int)rnd(12);                 // odd sizes, many of them inside a run
-        if (rnd(4) == 0) piece = count;
-        if (piece > count - done) piece = count - done;
+        const int piece = sg.piece(done);
         int in_piece = 0;
         w.advance(piece, [&](int start, int len) {
             REQUIRE(len >= 1 && start >= 0 && start + len - 1 <= n, "n %d pivot %ld: run %d+%d", n, pivot, start, len);
@@ -179,6 +223,7 @@ int main(int argc, char **argv)
             const int64_t bad = mcf::breaks_mismatches(t.bits.data(), t.nxt.data(), n);
             REQUIRE(bad == 0, "n %d pivot %ld: %lld bits of the bitmap differ from the thread list", n, k, (long long)bad);
             check_walk(t, k);
+            check_hint_walk(t, k);
             if (rnd(40) == 0) {
                 t.relabel();
                 check_tree(t, n, k);
@@ -187,7 +232,7 @@ int main(int argc, char **argv)
             }
         }
     }
-    printf("ok: %ld pivots on trees of 63 .. 130 nodes (%ld moved a subtree as it was), %ld walks, %ld runs emitted, %ld pieces ended inside a run\n",
-           total, whole_moves, walks, runs_seen, cut_runs);
+    printf("ok: %ld pivots on trees of 63 .. 130 nodes (%ld moved a subtree as it was), %ld run walks, %ld runs emitted, %ld pieces ended inside a run, %ld hinted walks\n",
+           total, whole_moves, walks, runs_seen, cut_runs, hint_walks);
     return 0;
 }
