@@ -687,8 +687,10 @@ MCF_API int mcf_batch_get_stats(mcf_batch *b, mcf_batch_stats *out);
 /* ---- Re-solving a solved batch with new arc costs ("Re-solve").
  * After a cost change the basis a solve ended with is still primal feasible: only the potentials and the optimality test change.  The
  * batch keeps every instance's state in device memory until mcf_batch_destroy, so a re-solve moves the new costs, not the instances.
- * Supplies, bounds and topology cannot be changed: those need a new basis, that is a new batch.  mcf_batch_solve, mcf_batch_run_on_host
- * and mcf_batch_add on a solved batch stay MCF_ERR_STATE.
+ * mcf_batch_* takes new costs only: it sets every instance up on the host, and new supplies, bounds or topology need a new batch there
+ * (deliberately: the handles whose data live on the device, mcf_ubatch_* and mcf_rbatch_*, re-solve with new supplies and bounds from the
+ * kept basis too, see mcf_ubatch_resolve_data; the topology is fixed per handle everywhere).  mcf_batch_solve, mcf_batch_run_on_host and
+ * mcf_batch_add on a solved batch stay MCF_ERR_STATE.
  *
  * Per instance whose costs were set since the last solve:
  *   - infeasible by its bounds (it never reached the device): stays MCF_INFEASIBLE with 0 pivots;
@@ -798,7 +800,7 @@ typedef struct mcf_ubatch_stats { /* of the last solve call of any kind; the fir
 MCF_API int mcf_ubatch_create(mcf_ubatch **out, const mcf_ubatch_desc *desc);
 MCF_API void mcf_ubatch_destroy(mcf_ubatch *b);
 /* Solves all `count` instances on the device, on the null stream; returns synchronised.  May be called again: every call is a fresh solve
- * on the same buffers, and it is how supplies or bounds change.  MCF_ERR_NO_DEVICE without a GPU; the handle is left as it was. */
+ * on the same buffers (new supplies or bounds alone are cheaper through mcf_ubatch_resolve_data).  MCF_ERR_NO_DEVICE without a GPU; the handle is left as it was. */
 MCF_API int mcf_ubatch_solve(mcf_ubatch *b, const mcf_ubatch_io *io);
 /* Re-solves the instances `changed` marks with the costs in io, as mcf_batch_resolve does: from the kept basis where the instance's last
  * solve ended MCF_OPTIMAL with no flow on an artificial arc, from the start basis otherwise (the limit stated there holds here too).
@@ -811,6 +813,43 @@ MCF_API int mcf_ubatch_resolve(mcf_ubatch *b, const mcf_ubatch_io *io);
 MCF_API int mcf_ubatch_run_on_host(mcf_ubatch *b, const mcf_ubatch_io *io);
 MCF_API int mcf_ubatch_rerun_on_host(mcf_ubatch *b, const mcf_ubatch_io *io);
 MCF_API int mcf_ubatch_get_stats(mcf_ubatch *b, mcf_ubatch_stats *out);
+
+/* ---- Re-solving with new supplies and bounds from the kept basis ("Re-solve with new data").
+ * The other half of mcf_ubatch_resolve: there the costs change and lower / upper / supply must stay, here lower, upper and supply change
+ * and io->cost and io->supply_type MUST be what the last solve call of any kind was given (a supply type other than the last call's is
+ * refused with MCF_ERR_INVALID; the costs cannot be checked and are the caller's word).  After such a change the kept basis is still
+ * dual feasible -- costs and potentials are untouched -- while its tree flows may leave their bounds.  Per marked instance:
+ *   - an upper bound below its lower bound: MCF_INFEASIBLE with 0 pivots, as in a solve;
+ *   - WARM where the last solve ended MCF_OPTIMAL with no flow on an artificial arc, no non-tree arc at its upper bound has become
+ *     uncapacitated, and the new supplies sum to zero.  The new capacities go in, the non-tree flows follow their state, the tree flows
+ *     are recomputed, and DUAL pivots run first: the tree arc with the largest bound violation leaves (lowest node among equals), the
+ *     arc across its cut with the smallest reduced cost enters (lowest arc among equals).  When nothing is violated the primal pivots
+ *     take over and find nothing to do.  pivots counts both kinds, the trace records every entering arc, the pivot limit applies to the
+ *     sum (MCF_NOT_SOLVED, rows zero, cold next time);
+ *   - COLD by rule otherwise, and COLD by fallback where a warm attempt did not end with no violation, no entering arc and no flow on a
+ *     root link or an artificial arc (the new data are infeasible over the searched arcs, or Unbounded): the instance is set up again
+ *     and solved in the same call.  A cold instance's rows are a fresh mcf_ubatch_solve's bit for bit, trace included.
+ * A warm instance's status and total cost are those of a fresh solve under the limit stated at mcf_batch_resolve (finite, positive
+ * capacities); its flows and potentials are an optimal pair, not necessarily the fresh solve's.  Rows of unmarked instances are not
+ * written.  May be mixed with every other solve call and hook in any order: the results are the same.  MCF_ERR_STATE before a solve of
+ * either kind; MCF_ERR_NO_DEVICE without a GPU leaves the handle as it was.  With MCF_MEM_DEVICE nothing that scales with the arcs or the
+ * nodes crosses the bus: the slot templates and the ids of every round go up; the slots come down after the re-data launch, after every
+ * round and once more after the warm attempts are judged, and a `changed` mask comes down as one byte per instance. */
+typedef struct mcf_ubatch_redata_stats { /* of the last mcf_*batch_resolve_data / _rerun_data_on_host (all zero before one) */
+    int64_t warm_instances;       /* marked and warm by the rule above: re-solved from the kept basis (fallback_instances are among them) */
+    int64_t cold_instances;       /* marked and cold by rule (incl. the ones infeasible by their bounds) */
+    int64_t fallback_instances;   /* warm attempts that did not stand and were solved again cold in the same call */
+    int64_t untouched_instances;  /* not marked */
+    int64_t dual_pivots;          /* of all warm attempts, the given-up ones included */
+    int64_t primal_pivots;        /* of the cold solves, the fallbacks' and whatever a warm attempt needed after its dual phase */
+    int64_t launches;             /* batch kernel launches */
+    int64_t bytes_up, bytes_down; /* as mcf_ubatch_stats */
+    double kernel_ns, host_ns, begin_ns, finish_ns;    /* as mcf_ubatch_stats; begin_ns is round the re-data launch */
+} mcf_ubatch_redata_stats;
+MCF_API int mcf_ubatch_resolve_data(mcf_ubatch *b, const mcf_ubatch_io *io);
+/* TEST HOOK like mcf_ubatch_rerun_on_host: the same steps (uniform_redata, batch_dual_run) with one lane on the CPU, MCF_MEM_HOST only. */
+MCF_API int mcf_ubatch_rerun_data_on_host(mcf_ubatch *b, const mcf_ubatch_io *io);
+MCF_API int mcf_ubatch_get_redata_stats(mcf_ubatch *b, mcf_ubatch_redata_stats *out);
 
 /* ---- Validating a uniform batch where it lies ("Uniform batch: validation").  The checks of section (3) above -- the
  * reference's SolutionValidator -- for every instance in ONE launch: block i checks instance i, reading problem and solution as
@@ -923,6 +962,10 @@ MCF_API int mcf_rbatch_rerun_on_host(mcf_rbatch *b, const mcf_rbatch_io *io);
 /* mcf_ubatch_stats of the last solve call of any kind.  Here lds_instances and global_instances may both be non-zero: the tier goes by
  * each instance's own footprint; workspace_bytes is the sum of the footprints. */
 MCF_API int mcf_rbatch_get_stats(mcf_rbatch *b, mcf_ubatch_stats *out);
+/* mcf_ubatch_resolve_data, its hook and its statistics for ragged rows, contract for contract. */
+MCF_API int mcf_rbatch_resolve_data(mcf_rbatch *b, const mcf_rbatch_io *io);
+MCF_API int mcf_rbatch_rerun_data_on_host(mcf_rbatch *b, const mcf_rbatch_io *io);
+MCF_API int mcf_rbatch_get_redata_stats(mcf_rbatch *b, mcf_ubatch_redata_stats *out);
 /* mcf_ubatch_validate for ragged rows: block i checks instance i against its own graph's incidence lists. */
 MCF_API int mcf_rbatch_validate(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out);
 MCF_API int mcf_rbatch_validate_on_host(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out);

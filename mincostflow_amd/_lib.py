@@ -170,6 +170,16 @@ class UBatchStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class UBatchRedataStats(C.Structure):
+    """mcf_ubatch_redata_stats"""
+    _fields_ = [(name, C.c_int64) for name in ("warm_instances", "cold_instances", "fallback_instances", "untouched_instances", "dual_pivots", "primal_pivots",
+                                               "launches", "bytes_up", "bytes_down")] + \
+               [(name, C.c_double) for name in ("kernel_ns", "host_ns", "begin_ns", "finish_ns")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class UBatchCheckIo(C.Structure):
     """mcf_ubatch_check_io"""
     _fields_ = [("memory", C.c_int32), ("supply_type", C.c_int32), ("lower", C.c_void_p), ("upper", C.c_void_p), ("cost", C.c_void_p), ("supply", C.c_void_p),
@@ -355,6 +365,9 @@ SIGNATURES = {
     "mcf_ubatch_run_on_host": (C.c_int, [C.c_void_p, _P(UBatchIo)]),
     "mcf_ubatch_rerun_on_host": (C.c_int, [C.c_void_p, _P(UBatchIo)]),
     "mcf_ubatch_get_stats": (C.c_int, [C.c_void_p, _P(UBatchStats)]),
+    "mcf_ubatch_resolve_data": (C.c_int, [C.c_void_p, _P(UBatchIo)]),
+    "mcf_ubatch_rerun_data_on_host": (C.c_int, [C.c_void_p, _P(UBatchIo)]),
+    "mcf_ubatch_get_redata_stats": (C.c_int, [C.c_void_p, _P(UBatchRedataStats)]),
     "mcf_ubatch_validate": (C.c_int, [C.c_void_p, _P(UBatchCheckIo), _P(UBatchCheckSummary)]),
     "mcf_ubatch_validate_on_host": (C.c_int, [C.c_void_p, _P(UBatchCheckIo), _P(UBatchCheckSummary)]),
     "mcf_rbatch_create": (C.c_int, [_P(C.c_void_p), _P(RBatchDesc)]),
@@ -365,6 +378,9 @@ SIGNATURES = {
     "mcf_rbatch_run_on_host": (C.c_int, [C.c_void_p, _P(RBatchIo)]),
     "mcf_rbatch_rerun_on_host": (C.c_int, [C.c_void_p, _P(RBatchIo)]),
     "mcf_rbatch_get_stats": (C.c_int, [C.c_void_p, _P(UBatchStats)]),
+    "mcf_rbatch_resolve_data": (C.c_int, [C.c_void_p, _P(RBatchIo)]),
+    "mcf_rbatch_rerun_data_on_host": (C.c_int, [C.c_void_p, _P(RBatchIo)]),
+    "mcf_rbatch_get_redata_stats": (C.c_int, [C.c_void_p, _P(UBatchRedataStats)]),
     "mcf_rbatch_validate": (C.c_int, [C.c_void_p, _P(RBatchCheckIo), _P(UBatchCheckSummary)]),
     "mcf_rbatch_validate_on_host": (C.c_int, [C.c_void_p, _P(RBatchCheckIo), _P(UBatchCheckSummary)]),
     "mcf_problem_free": (None, [_P(ProblemStruct)]),

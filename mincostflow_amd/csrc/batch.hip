@@ -10,6 +10,8 @@
 //   * re-solves: the slab, the slots and the trace buffer live as long as the batch.  mcf_batch_set_costs + mcf_batch_resolve run the changed
 //     instances again: from the basis they ended with where that ended Optimal (new cost[] up, batch_reprice on the device, changing part
 //     down), from the start basis otherwise.
+//   * re-solves with new supplies and bounds (mcf_ubatch_resolve_data, mcf_rbatch_resolve_data): batch_dual_kernel runs the dual pivots of
+//     batch_step.hip.h in front of the primal ones, between a re-data launch and a settle launch (uniform_step.hip.h).
 // Device code does no bounds checks: mcf_batch_add validates every end point (core_create), and every index the kernel follows after
 // that was written by start_basis or by the pivot itself.
 #include <hip/hip_runtime.h>
@@ -76,6 +78,45 @@ __global__ __launch_bounds__(kBatchThreads) void batch_kernel(BatchSlot *slots, 
     if (lane == 0) store_slot(slot, w);
 }
 
+// batch_kernel for a re-solve with new supplies or bounds (mcf_*batch_resolve_data): the dual phase of an instance that is in it goes
+// first, the primal pivots follow within the same budget.  A kernel of its own, so that batch_kernel keeps its code and its registers
+// for the solves that never enter a dual phase.  The dual pivot count travels in slot.staged_out, which only mcf_batch_resolve uses
+// otherwise, and reprice == 2 (a warm attempt, for uniform_redata_settle) outlives the launch.
+template <bool kLds>
+__global__ __launch_bounds__(kBatchThreads) void batch_dual_kernel(BatchSlot *slots, const int32_t *ids, unsigned char *slab, int32_t *traces, int32_t budget)
+{
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int lane = (int)threadIdx.x;
+    BatchSlot &slot = slots[ids[blockIdx.x]];
+    const int32_t attempt = slot.reprice;
+    const Layout l = layout_of((uint32_t)slot.all_arcs, (uint32_t)slot.n + 1u);
+    unsigned char *const home = slab + slot.workspace;
+    mcf::BatchWork w;
+    load_slot(w, slot, traces);
+    w.dual_pivots = (int64_t)slot.staged_out;
+    if (kLds) {
+        const uint4 *src = (const uint4 *)home;
+        uint4 *dst = (uint4 *)lds;
+        for (uint32_t i = (uint32_t)lane; i < l.bytes / 16; i += kBatchThreads) dst[i] = src[i];
+        bind(w, lds, l);
+    } else {
+        bind(w, home, l);
+    }
+    __syncthreads();
+    mcf::batch_run_after_dual(w, lane, kBatchThreads, (int64_t)budget);
+    __syncthreads();
+    if (kLds) {
+        const uint4 *src = (const uint4 *)lds;
+        uint4 *dst = (uint4 *)home;
+        for (uint32_t i = l.changing / 16 + (uint32_t)lane; i < l.bytes / 16; i += kBatchThreads) dst[i] = src[i];
+    }
+    if (lane == 0) {
+        store_slot(slot, w);
+        slot.staged_out = (uint64_t)w.dual_pivots;
+        slot.reprice = attempt == 2 ? 2 : 0;
+    }
+}
+
 // A re-solve moves only what changed.  Block k serves instance ids[k].  kIn: its new cost[0, all_arcs) (rounded up to 16 bytes, as the
 // layout is) from the staging buffer into its workspace; else: the changing part of its workspace into the staging buffer, from where
 // one copy takes every instance's home.  Both offsets are in the slot; the host sizes the staging buffer for the larger of the two sums.
@@ -107,6 +148,18 @@ __global__ __launch_bounds__(kBatchThreads) void uniform_recost_kernel(mcf::Unif
     const int64_t i = (int64_t)blockIdx.x;
     if (p.changed && !p.changed[i]) return;
     mcf::uniform_recost(mcf::uniform_view(p, nullptr, i, slab), *tmpl, slots[i], (int)threadIdx.x, kBatchThreads);
+}
+__global__ __launch_bounds__(kBatchThreads) void uniform_redata_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
+{
+    const int64_t i = (int64_t)blockIdx.x;
+    if (p.changed && !p.changed[i]) return;
+    mcf::uniform_redata(mcf::uniform_view(p, nullptr, i, slab), *tmpl, slots[i], (int)threadIdx.x, kBatchThreads);
+}
+__global__ __launch_bounds__(kBatchThreads) void uniform_settle_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
+{
+    const int64_t i = (int64_t)blockIdx.x;
+    if (p.changed && !p.changed[i]) return;
+    mcf::uniform_redata_settle(mcf::uniform_view(p, nullptr, i, slab), *tmpl, slots[i], (int)threadIdx.x, kBatchThreads);
 }
 __global__ __launch_bounds__(kBatchThreads) void uniform_finish_kernel(mcf::UniformProblem p, mcf::UniformOutputs o, const BatchSlot *slots, unsigned char *slab,
                                                                        const int32_t *traces)
@@ -140,6 +193,22 @@ __global__ __launch_bounds__(kBatchThreads) void ragged_recost_kernel(mcf::Ragge
     int32_t t;
     const mcf::InstanceView v = mcf::ragged_view(r, nullptr, i, slab, &t);
     mcf::uniform_recost(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
+}
+__global__ __launch_bounds__(kBatchThreads) void ragged_redata_kernel(mcf::RaggedProblem r, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
+{
+    const int64_t i = (int64_t)blockIdx.x;
+    if (r.changed && !r.changed[i]) return;
+    int32_t t;
+    const mcf::InstanceView v = mcf::ragged_view(r, nullptr, i, slab, &t);
+    mcf::uniform_redata(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
+}
+__global__ __launch_bounds__(kBatchThreads) void ragged_settle_kernel(mcf::RaggedProblem r, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
+{
+    const int64_t i = (int64_t)blockIdx.x;
+    if (r.changed && !r.changed[i]) return;
+    int32_t t;
+    const mcf::InstanceView v = mcf::ragged_view(r, nullptr, i, slab, &t);
+    mcf::uniform_redata_settle(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
 }
 __global__ __launch_bounds__(kBatchThreads) void ragged_finish_kernel(mcf::RaggedProblem r, mcf::UniformOutputs o, const BatchSlot *slots, unsigned char *slab,
                                                                       const int32_t *traces)
@@ -382,6 +451,10 @@ int open_device(int32_t device, int *lds_max_out)
         (void)hipGetLastError();
         lds_max = std::min(lds_max, 64 << 10);
     }
+    if (hipFuncSetAttribute((const void *)batch_dual_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) {
+        (void)hipGetLastError();
+        lds_max = std::min(lds_max, 64 << 10);
+    }
     *lds_max_out = lds_max;
     return MCF_OK;
 }
@@ -429,6 +502,7 @@ struct LaunchPlan {
     int32_t pivots_per_launch;          // the descriptor's: 0 = the default
     const uint32_t *footprint;          // per instance, or null:
     uint32_t footprint_all;
+    bool dual = false;                  // a re-solve with new supplies or bounds: batch_dual_kernel, and kBatchDual runs on like kBatchRunning
     uint32_t bytes(int32_t i) const { return footprint ? footprint[(size_t)i] : footprint_all; }
 };
 
@@ -450,7 +524,7 @@ int run_launches(const LaunchPlan &plan, std::vector<BatchSlot> &slots, const st
         for (int g = 0; g < kClasses; ++g) {
             Launch L{(int)ids.size(), 0, 0, g != kClasses - 1};
             for (int32_t i : group[g]) {
-                if (slots[(size_t)i].run != mcf::kBatchRunning) continue;
+                if (slots[(size_t)i].run != mcf::kBatchRunning && slots[(size_t)i].run != mcf::kBatchDual) continue;
                 ids.push_back(i);
                 L.n++;
                 L.lds = std::max(L.lds, plan.bytes(i));
@@ -462,12 +536,9 @@ int run_launches(const LaunchPlan &plan, std::vector<BatchSlot> &slots, const st
         HIP_TRY(hipMemcpy(dev.ids, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         t->bytes_up += (int64_t)(ids.size() * sizeof(int32_t));
         for (const Launch &L : launches) {
-            if (L.in_lds) {
-                hipLaunchKernelGGL(batch_kernel<true>, dim3((unsigned)L.n), dim3(kBatchThreads), L.lds, 0, dev.slots, dev.ids + L.first, dev.slab, dev.traces, budget);
-                t->lds_bytes_max = std::max<int64_t>(t->lds_bytes_max, L.lds);
-            } else {
-                hipLaunchKernelGGL(batch_kernel<false>, dim3((unsigned)L.n), dim3(kBatchThreads), 0, 0, dev.slots, dev.ids + L.first, dev.slab, dev.traces, budget);
-            }
+            const auto kernel = L.in_lds ? (plan.dual ? batch_dual_kernel<true> : batch_kernel<true>) : (plan.dual ? batch_dual_kernel<false> : batch_kernel<false>);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)L.n), dim3(kBatchThreads), L.in_lds ? L.lds : 0, 0, dev.slots, dev.ids + L.first, dev.slab, dev.traces, budget);
+            if (L.in_lds) t->lds_bytes_max = std::max<int64_t>(t->lds_bytes_max, L.lds);
             HIP_TRY(hipGetLastError());
             t->launches++;
         }
@@ -875,6 +946,8 @@ namespace {
 struct PlacedBatch {
     enum Where { kNowhere, kOnHost, kOnDevice } where = kNowhere;      // who holds the state the last solve of either kind left
     mcf_ubatch_stats stats{};
+    mcf_ubatch_redata_stats redata_stats{};     // of the last re-solve with new supplies or bounds
+    int32_t supply_type = -1;           // of the last solve call of any kind: a re-solve with new data must name the same
     int lds_max = 0;
     DeviceBuffers dev;                  // slab, slots, ids, traces
     unsigned char *d_tables = nullptr;  // the topology, its incidence lists and the placement's tables: one allocation, up once per handle
@@ -1027,6 +1100,8 @@ struct UniformPlacement {
     using Problem = mcf::UniformProblem;
     static constexpr auto begin_kernel = uniform_begin_kernel;
     static constexpr auto recost_kernel = uniform_recost_kernel;
+    static constexpr auto redata_kernel = uniform_redata_kernel;
+    static constexpr auto settle_kernel = uniform_settle_kernel;
     static constexpr auto finish_kernel = uniform_finish_kernel;
     static void launch_validate(const Handle *b, const Problem &p, const mcf::UniformCheck &c, const BatchIo &io)
     {
@@ -1090,6 +1165,8 @@ struct RaggedPlacement {
     using Problem = mcf::RaggedProblem;
     static constexpr auto begin_kernel = ragged_begin_kernel;
     static constexpr auto recost_kernel = ragged_recost_kernel;
+    static constexpr auto redata_kernel = ragged_redata_kernel;
+    static constexpr auto settle_kernel = ragged_settle_kernel;
     static constexpr auto finish_kernel = ragged_finish_kernel;
     static void launch_validate(const Handle *b, const Problem &r, const mcf::UniformCheck &c, const BatchIo &io)
     {
@@ -1160,9 +1237,13 @@ struct RaggedPlacement {
 };
 
 // what every call refuses before it touches the handle.  Solve calls take MCF_SUPPLY_GEQ / _LEQ, validation calls MCF_SUPPLY_EQ too
+// a solve call: fresh, a re-solve with new costs, or a re-solve with new supplies and bounds
+enum Call { kFresh, kRecost, kRedata };
+
 template <class P>
-int check_call(const typename P::Handle *b, const BatchIo &io, const char *what, bool host_only, bool resolve)
+int check_call(const typename P::Handle *b, const BatchIo &io, const char *what, bool host_only, Call call)
 {
+    const bool resolve = call != kFresh;
     if (!b || !io.given) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
     if (io.memory != MCF_MEM_HOST && io.memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io.memory);
     if (host_only && io.memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
@@ -1173,6 +1254,8 @@ int check_call(const typename P::Handle *b, const BatchIo &io, const char *what,
     }
     if (const int rc = P::check_rows(b, io, what)) return rc;
     if (resolve && b->where == PlacedBatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
+    if (call == kRedata && io.supply_type != b->supply_type)
+        return mcf::fail(MCF_ERR_INVALID, "%s: supply type %d, the last solve's was %d (the kept basis belongs to that one)", what, io.supply_type, b->supply_type);
     return MCF_OK;
 }
 
@@ -1272,23 +1355,51 @@ int stage_down(PlacedBatch *b, const Staged &st, int64_t *bytes_down)
     return MCF_OK;
 }
 
-// mcf_*batch_solve and _resolve: set-up (or re-cost) launch, the launch loop of mcf_batch_solve, finish launch
+// What a re-solve with new data counts, on the device and in the hook alike.  An instance is warm by the step's rule (uniform_redata left
+// it in the dual phase), cold by rule (marked, and started again at once) or untouched; a warm attempt that did not stand and ran again
+// cold is a fallback, and the pivots of its attempt stay counted.
+struct RedataCount {
+    mcf_ubatch_redata_stats st{};
+    void begun(const BatchSlot &s, bool marked)
+    {
+        if (!marked) st.untouched_instances++;
+        else if (s.run == mcf::kBatchDual) st.warm_instances++;
+        else st.cold_instances++;
+    }
+    void ran(const BatchSlot &s)           // a slot as the launches left it: staged_out = its dual pivots
+    {
+        st.dual_pivots += (int64_t)s.staged_out;
+        st.primal_pivots += s.pivots - (int64_t)s.staged_out;
+    }
+    void finish(const mcf_ubatch_stats &of_call)
+    {
+        st.launches = of_call.launches; st.bytes_up = of_call.bytes_up; st.bytes_down = of_call.bytes_down;
+        st.kernel_ns = of_call.kernel_ns; st.host_ns = of_call.host_ns; st.begin_ns = of_call.begin_ns; st.finish_ns = of_call.finish_ns;
+    }
+};
+
+// mcf_*batch_solve, _resolve and _resolve_data: set-up (or re-cost, or re-data) launch, the launch loop of mcf_batch_solve, finish launch.
+// A re-solve with new data has one more step between the last two: the settle launch, and the launch loop again for the warm attempts
+// that did not stand.
 template <class P>
-int solve_on_device(typename P::Handle *b, BatchIo io, bool resolve, const char *what)
+int solve_on_device(typename P::Handle *b, BatchIo io, Call call, const char *what)
 {
-    if (const int rc = check_call<P>(b, io, what, false, resolve)) return rc;
+    const bool resolve = call != kFresh;
+    if (const int rc = check_call<P>(b, io, what, false, call)) return rc;
     if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
     const double t_start = mcf::now_ns();
     const DeviceGuard guard;
     if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
     const size_t count = (size_t)b->d.count;
-    const LaunchPlan plan = P::plan(b);
+    LaunchPlan plan = P::plan(b);
+    plan.dual = call == kRedata;
     b->stats = mcf_ubatch_stats{};
     b->stats.instances = (int64_t)count;
     for (size_t i = 0; i < count; ++i)
         (class_of(b->lds_max, plan.bytes((int32_t)i)) != kClasses - 1 ? b->stats.lds_instances : b->stats.global_instances)++;
     b->stats.workspace_bytes = (int64_t)P::slab_bytes(b);
-    if (!count) { b->where = PlacedBatch::kOnDevice; b->stats.host_ns = mcf::now_ns() - t_start; return MCF_OK; }
+    if (call == kRedata) b->redata_stats = mcf_ubatch_redata_stats{};
+    if (!count) { b->where = PlacedBatch::kOnDevice; b->supply_type = io.supply_type; b->stats.host_ns = mcf::now_ns() - t_start; return MCF_OK; }
     if (const int rc = ensure_device_buffers<P>(b)) return rc;
     DeviceBuffers &dev = b->dev;
     if (resolve && b->where == PlacedBatch::kOnHost) {                      // the last solve was a host hook's: its state goes up whole
@@ -1297,6 +1408,15 @@ int solve_on_device(typename P::Handle *b, BatchIo io, bool resolve, const char 
         b->stats.bytes_up += (int64_t)(b->h_slab.size() + count * sizeof(BatchSlot));
     }
     if (!resolve) io.changed = nullptr;
+    std::vector<uint8_t> marked;                                            // a re-solve with new data counts its instances by the mask: one byte each
+    if (call == kRedata && io.changed) {
+        marked.resize(count);
+        if (io.memory == MCF_MEM_HOST) memcpy(marked.data(), io.changed, count);
+        else {
+            HIP_TRY(hipMemcpy(marked.data(), io.changed, count, hipMemcpyDeviceToHost));
+            b->stats.bytes_down += (int64_t)count;
+        }
+    }
     Staged staged;
     if (const int rc = stage_up<P>(b, &io, &staged, &b->stats.bytes_up)) return rc;
     const typename P::Problem p = P::problem(b, io, true);
@@ -1304,20 +1424,40 @@ int solve_on_device(typename P::Handle *b, BatchIo io, bool resolve, const char 
     const double t_begin = mcf::now_ns();
     HIP_TRY(hipMemcpy(b->d_tmpl, P::templates(b), P::template_count(b) * sizeof(BatchSlot), hipMemcpyHostToDevice));
     b->stats.bytes_up += (int64_t)(P::template_count(b) * sizeof(BatchSlot));
-    const auto begin_kernel = resolve ? P::recost_kernel : P::begin_kernel;
+    const auto begin_kernel = call == kFresh ? P::begin_kernel : call == kRecost ? P::recost_kernel : P::redata_kernel;
     hipLaunchKernelGGL(begin_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
     HIP_TRY(hipGetLastError());
     b->where = PlacedBatch::kOnDevice;
+    b->supply_type = io.supply_type;
     std::vector<BatchSlot> slots(count);
     HIP_TRY(hipMemcpy(slots.data(), dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));      // waits for the launch; says who runs
     b->stats.bytes_down += (int64_t)(count * sizeof(BatchSlot));
     b->stats.begin_ns = mcf::now_ns() - t_begin;
 
-    std::vector<int32_t> run;
-    for (size_t i = 0; i < count; ++i)
-        if (slots[i].run == mcf::kBatchRunning) run.push_back((int32_t)i);   // a re-solve's unmarked instances ended their last solve: not running
+    std::vector<int32_t> run, attempts;
+    RedataCount redata;
+    for (size_t i = 0; i < count; ++i) {
+        if (call == kRedata) redata.begun(slots[i], marked.empty() || marked[i]);
+        if (slots[i].run == mcf::kBatchDual) attempts.push_back((int32_t)i);
+        if (slots[i].run == mcf::kBatchRunning || slots[i].run == mcf::kBatchDual) run.push_back((int32_t)i);   // a re-solve's unmarked instances ended their last solve: not running
+    }
     LaunchTotals t;
     if (const int rc = run_launches(plan, slots, run, &t)) return rc;
+    if (call == kRedata)
+        for (int32_t i : run) redata.ran(slots[(size_t)i]);
+    if (!attempts.empty()) {
+        // the warm attempts are judged where they lie; the ones that did not stand have been set up again and run like a fresh solve's
+        hipLaunchKernelGGL(P::settle_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(slots.data(), dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));
+        b->stats.bytes_down += (int64_t)(count * sizeof(BatchSlot));
+        std::vector<int32_t> again;
+        for (int32_t i : attempts)
+            if (slots[(size_t)i].run == mcf::kBatchRunning) again.push_back(i);
+        redata.st.fallback_instances = (int64_t)again.size();
+        if (const int rc = run_launches(plan, slots, again, &t)) return rc;
+        for (int32_t i : again) redata.ran(slots[(size_t)i]);
+    }
     for (int32_t i : run) b->stats.total_pivots += slots[(size_t)i].pivots;
     b->stats.launches = t.launches;
     b->stats.lds_bytes_max = t.lds_bytes_max;
@@ -1332,14 +1472,31 @@ int solve_on_device(typename P::Handle *b, BatchIo io, bool resolve, const char 
     b->stats.finish_ns = mcf::now_ns() - t_finish;
     if (const int rc = stage_down(b, staged, &b->stats.bytes_down)) return rc;
     b->stats.host_ns = mcf::now_ns() - t_start - t.kernel_ns;
+    if (call == kRedata) { redata.finish(b->stats); b->redata_stats = redata.st; }
     return MCF_OK;
 }
 
-// the host hooks: the three steps and batch_run with one lane, on a host slab of the device's layout
-template <class P>
-int solve_on_host(typename P::Handle *b, BatchIo io, bool resolve, const char *what)
+// the pivots of one placed instance with one lane, from its slot and back into it: what a launch loop does for it on the device
+void run_slot_on_host(BatchSlot &slot, unsigned char *home, int32_t *traces)
 {
-    if (const int rc = check_call<P>(b, io, what, true, resolve)) return rc;
+    const int32_t attempt = slot.reprice;
+    mcf::BatchWork w{};
+    load_slot(w, slot, traces);
+    w.dual_pivots = (int64_t)slot.staged_out;
+    bind(w, home, layout_of((uint32_t)slot.all_arcs, (uint32_t)slot.n + 1u));
+    if (attempt == 1) mcf::batch_reprice(w, 0, 1);
+    mcf::batch_run_after_dual(w, 0, 1, INT64_MAX);
+    store_slot(slot, w);
+    slot.staged_out = (uint64_t)w.dual_pivots;
+    slot.reprice = attempt == 2 ? 2 : 0;
+}
+
+// the host hooks: the steps and the pivots with one lane, on a host slab of the device's layout
+template <class P>
+int solve_on_host(typename P::Handle *b, BatchIo io, Call call, const char *what)
+{
+    const bool resolve = call != kFresh;
+    if (const int rc = check_call<P>(b, io, what, true, call)) return rc;
     const double t_start = mcf::now_ns();
     const size_t count = (size_t)b->d.count;
     b->h_slab.resize(P::slab_bytes(b));
@@ -1357,26 +1514,36 @@ int solve_on_host(typename P::Handle *b, BatchIo io, bool resolve, const char *w
     if (!resolve) io.changed = nullptr;
     const typename P::Problem p = P::problem(b, io, false);
     const mcf::UniformOutputs o = outputs_of(io);
+    RedataCount redata;
     for (size_t i = 0; i < count; ++i) {
-        if (io.changed && !io.changed[i]) continue;
         BatchSlot &slot = b->h_slots[i];
+        if (io.changed && !io.changed[i]) { redata.begun(slot, false); continue; }
         const BatchSlot *tmpl = nullptr;
         const mcf::InstanceView v = P::view(b, p, o, (int64_t)i, b->h_slab.data(), &tmpl);
-        if (resolve) mcf::uniform_recost(v, *tmpl, slot, 0, 1);
-        else mcf::uniform_begin(v, *tmpl, slot, 0, 1);
-        if (slot.run == mcf::kBatchRunning) {
-            mcf::BatchWork w{};
-            load_slot(w, slot, b->h_traces.data());
-            bind(w, v.home, layout_of((uint32_t)slot.all_arcs, (uint32_t)slot.n + 1u));
-            if (slot.reprice) mcf::batch_reprice(w, 0, 1);
-            mcf::batch_run(w, 0, 1, INT64_MAX);
-            store_slot(slot, w);
+        if (call == kFresh) mcf::uniform_begin(v, *tmpl, slot, 0, 1);
+        else if (call == kRecost) mcf::uniform_recost(v, *tmpl, slot, 0, 1);
+        else mcf::uniform_redata(v, *tmpl, slot, 0, 1);
+        redata.begun(slot, true);
+        const bool ran = slot.run == mcf::kBatchRunning || slot.run == mcf::kBatchDual;
+        if (ran) {
+            run_slot_on_host(slot, v.home, b->h_traces.data());
+            redata.ran(slot);
+            if (slot.reprice == 2) {                                        // a warm attempt: judged, and run again cold where it did not stand
+                mcf::uniform_redata_settle(v, *tmpl, slot, 0, 1);
+                if (slot.run == mcf::kBatchRunning) {
+                    redata.st.fallback_instances++;
+                    run_slot_on_host(slot, v.home, b->h_traces.data());
+                    redata.ran(slot);
+                }
+            }
             b->stats.total_pivots += slot.pivots;
         }
         mcf::uniform_finish(v, o, slot, b->h_traces.data(), 0, 1);
     }
     b->where = PlacedBatch::kOnHost;
+    b->supply_type = io.supply_type;
     b->stats.host_ns = mcf::now_ns() - t_start;
+    if (call == kRedata) { redata.finish(b->stats); b->redata_stats = redata.st; }
     return MCF_OK;
 }
 
@@ -1385,7 +1552,7 @@ template <class P>
 int validate_on_device(typename P::Handle *b, BatchIo io, mcf_ubatch_check_summary *out, const char *what)
 {
     if (!out) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
-    if (const int rc = check_call<P>(b, io, what, false, false)) return rc;
+    if (const int rc = check_call<P>(b, io, what, false, kFresh)) return rc;
     if (const int rc = have_device(b->d.device, what)) return rc;
     *out = mcf_ubatch_check_summary{};
     out->first_invalid = -1;
@@ -1415,7 +1582,7 @@ template <class P>
 int validate_on_host(typename P::Handle *b, const BatchIo &io, mcf_ubatch_check_summary *out, const char *what)
 {
     if (!out) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
-    if (const int rc = check_call<P>(b, io, what, true, false)) return rc;
+    if (const int rc = check_call<P>(b, io, what, true, kFresh)) return rc;
     *out = mcf_ubatch_check_summary{};
     int64_t words[2] = {0, INT64_MAX};
     const typename P::Problem p = P::problem(b, io, false);
@@ -1431,6 +1598,12 @@ int get_stats(const PlacedBatch *b, mcf_ubatch_stats *out)
 {
     if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
     *out = b->stats;
+    return MCF_OK;
+}
+int get_redata_stats(const PlacedBatch *b, mcf_ubatch_redata_stats *out)
+{
+    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
+    *out = b->redata_stats;
     return MCF_OK;
 }
 
@@ -1543,10 +1716,12 @@ int mcf_rbatch_get_rows(mcf_rbatch *b, int64_t *arc_row, int64_t *node_row)
 }
 
 void mcf_ubatch_destroy(mcf_ubatch *b) { delete b; }
-int mcf_ubatch_solve(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_device<UniformPlacement>(b, io_of(io), false, "mcf_ubatch_solve"); }
-int mcf_ubatch_resolve(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_device<UniformPlacement>(b, io_of(io), true, "mcf_ubatch_resolve"); }
-int mcf_ubatch_run_on_host(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_host<UniformPlacement>(b, io_of(io), false, "mcf_ubatch_run_on_host"); }
-int mcf_ubatch_rerun_on_host(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_host<UniformPlacement>(b, io_of(io), true, "mcf_ubatch_rerun_on_host"); }
+int mcf_ubatch_solve(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_device<UniformPlacement>(b, io_of(io), kFresh, "mcf_ubatch_solve"); }
+int mcf_ubatch_resolve(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_device<UniformPlacement>(b, io_of(io), kRecost, "mcf_ubatch_resolve"); }
+int mcf_ubatch_resolve_data(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_device<UniformPlacement>(b, io_of(io), kRedata, "mcf_ubatch_resolve_data"); }
+int mcf_ubatch_run_on_host(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_host<UniformPlacement>(b, io_of(io), kFresh, "mcf_ubatch_run_on_host"); }
+int mcf_ubatch_rerun_on_host(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_host<UniformPlacement>(b, io_of(io), kRecost, "mcf_ubatch_rerun_on_host"); }
+int mcf_ubatch_rerun_data_on_host(mcf_ubatch *b, const mcf_ubatch_io *io) { return solve_on_host<UniformPlacement>(b, io_of(io), kRedata, "mcf_ubatch_rerun_data_on_host"); }
 int mcf_ubatch_validate(mcf_ubatch *b, const mcf_ubatch_check_io *io, mcf_ubatch_check_summary *out)
 {
     return validate_on_device<UniformPlacement>(b, io_of(io), out, "mcf_ubatch_validate");
@@ -1556,12 +1731,15 @@ int mcf_ubatch_validate_on_host(mcf_ubatch *b, const mcf_ubatch_check_io *io, mc
     return validate_on_host<UniformPlacement>(b, io_of(io), out, "mcf_ubatch_validate_on_host");
 }
 int mcf_ubatch_get_stats(mcf_ubatch *b, mcf_ubatch_stats *out) { return get_stats(b, out); }
+int mcf_ubatch_get_redata_stats(mcf_ubatch *b, mcf_ubatch_redata_stats *out) { return get_redata_stats(b, out); }
 
 void mcf_rbatch_destroy(mcf_rbatch *b) { delete b; }
-int mcf_rbatch_solve(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_device<RaggedPlacement>(b, io_of(io), false, "mcf_rbatch_solve"); }
-int mcf_rbatch_resolve(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_device<RaggedPlacement>(b, io_of(io), true, "mcf_rbatch_resolve"); }
-int mcf_rbatch_run_on_host(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_host<RaggedPlacement>(b, io_of(io), false, "mcf_rbatch_run_on_host"); }
-int mcf_rbatch_rerun_on_host(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_host<RaggedPlacement>(b, io_of(io), true, "mcf_rbatch_rerun_on_host"); }
+int mcf_rbatch_solve(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_device<RaggedPlacement>(b, io_of(io), kFresh, "mcf_rbatch_solve"); }
+int mcf_rbatch_resolve(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_device<RaggedPlacement>(b, io_of(io), kRecost, "mcf_rbatch_resolve"); }
+int mcf_rbatch_resolve_data(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_device<RaggedPlacement>(b, io_of(io), kRedata, "mcf_rbatch_resolve_data"); }
+int mcf_rbatch_run_on_host(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_host<RaggedPlacement>(b, io_of(io), kFresh, "mcf_rbatch_run_on_host"); }
+int mcf_rbatch_rerun_on_host(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_host<RaggedPlacement>(b, io_of(io), kRecost, "mcf_rbatch_rerun_on_host"); }
+int mcf_rbatch_rerun_data_on_host(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_host<RaggedPlacement>(b, io_of(io), kRedata, "mcf_rbatch_rerun_data_on_host"); }
 int mcf_rbatch_validate(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out)
 {
     return validate_on_device<RaggedPlacement>(b, io_of(io), out, "mcf_rbatch_validate");
@@ -1571,5 +1749,6 @@ int mcf_rbatch_validate_on_host(mcf_rbatch *b, const mcf_rbatch_check_io *io, mc
     return validate_on_host<RaggedPlacement>(b, io_of(io), out, "mcf_rbatch_validate_on_host");
 }
 int mcf_rbatch_get_stats(mcf_rbatch *b, mcf_ubatch_stats *out) { return get_stats(b, out); }
+int mcf_rbatch_get_redata_stats(mcf_rbatch *b, mcf_ubatch_redata_stats *out) { return get_redata_stats(b, out); }
 
 }  // extern "C"

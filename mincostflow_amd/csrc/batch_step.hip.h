@@ -8,6 +8,8 @@
 //     the search with the same answer and the same rule state.  Rules: First Eligible, Best Eligible and the plain Block Search of
 //     NS.cs:1292-1668 (find_first / find_best / find_block_plain of oracle/ns_oracle.c), ties broken as there: the first arc in scan
 //     order among equals.
+//     A fourth search belongs to the dual phase (batch_dual_run): the leaving arc by the largest bound violation over the nodes, then the
+//     ratio test over the arcs across the leaving arc's cut.
 //   * join node, leaving arc, State[] writes, potentials of the subtree, flows round the cycle and the tree surgery are sequential:
 //     batch_pivot calls the steps of tree_pivot.h (the ones mcf_ns calls) in the reference's order, with the plain walk over the subtree's
 //     potentials between them.  Lane 0 runs it while the others wait.
@@ -28,7 +30,9 @@ enum BatchRun : int32_t {
     kBatchUnbounded = 2,   // NS.cs:321-325
     kBatchLimit = 3,       // the instance's pivot limit
     kBatchMaxIter = 4,     // the reference's own iteration guard (NS.cs:280, :311-317): Infeasible
-    kBatchByBounds = 5     // never ran: an upper bound below its lower bound (set by uniform_begin of uniform_step.hip.h only)
+    kBatchByBounds = 5,    // never ran: an upper bound below its lower bound (set by uniform_begin of uniform_step.hip.h only)
+    kBatchDual = 6,        // a re-solve with new supplies or bounds: the dual phase is in progress (batch_dual_run): relaunch
+    kBatchDualStuck = 7    // the dual phase found a violated tree arc and no arc across its cut to enter: the warm attempt is given up
 };
 
 struct BatchWork : TreeView {
@@ -45,6 +49,7 @@ struct BatchWork : TreeView {
     mcf_block_config cfg;
     int64_t pivots, pivot_limit, max_iter, trace_cap;
     int32_t run;                       // BatchRun
+    int64_t dual_pivots;               // of `pivots`, those of the dual phase (batch_dual_run only; the slot keeps it in staged_out)
 };
 
 // ---- NS.cs:1400-1438, same doubles, same truncations (a product and a quotient each rounded once: nothing here can be contracted into an FMA)
@@ -77,6 +82,13 @@ MCF_HD inline int64_t lanes_min_i64(int64_t v)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     for (int d = 32; d > 0; d >>= 1) { const int64_t o = __shfl_xor(v, d, 64); v = o < v ? o : v; }
+#endif
+    return v;
+}
+MCF_HD inline int64_t lanes_max_i64(int64_t v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    for (int d = 32; d > 0; d >>= 1) { const int64_t o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
 #endif
     return v;
 }
@@ -233,6 +245,120 @@ MCF_HD inline void batch_reprice(BatchWork &w, int lane, int lanes)
     lanes_sync();
 }
 
+// ---- the dual phase of a re-solve with new supplies or bounds (uniform_redata of uniform_step.hip.h, DESIGN.md 3.14 "Re-solve with new
+// data").  The basis is dual feasible (costs and potentials are the last solve's) and some tree flows lie outside their bounds.  A dual
+// pivot: the tree arc with the largest violation leaves, and of the arcs across its cut that move it toward the bound it violates the one
+// with the smallest reduced cost enters.  Both searches are over (lane, lanes) like the rules above; the rest is batch_pivot's sequence on
+// a Pivot filled here instead of by find_cycle.
+
+// the tree arc above a node v < n with the largest violation max(-flow, flow - upper), the lowest node among equals; false: none is violated
+MCF_HD inline bool batch_find_violated(const BatchWork &w, int lane, int lanes, int32_t *u_out, int64_t *violation)
+{
+    int64_t mine = 0;
+    uint32_t at = kNoPos;
+    for (int v = lane; v < w.n; v += lanes) {
+        const int e = w.par_arc[v];
+        const int64_t f = w.flow[e], up = w.upper[e];
+        const int64_t below = -f, above = up >= kInf ? 0 : f - up;
+        const int64_t worst = below > above ? below : above;
+        if (worst > mine) { mine = worst; at = (uint32_t)v; }
+    }
+    const int64_t best = lanes_max_i64(mine);
+    if (best <= 0) return false;
+    *u_out = (int32_t)lanes_min_u32(mine == best ? at : kNoPos);
+    *violation = best;
+    return true;
+}
+
+// The ratio test.  mark: what scratch[] holds for the nodes below the leaving arc.  An arc leaves the marked side when its tail is marked;
+// raising the flow of an arc that crosses the cut the way the leaving arc does lowers the leaving arc's flow, and the other way round.
+// raise: the leaving arc's flow is below 0.  The minimum of batch_reduced_cost (>= 0 by dual feasibility), the lowest arc among equals.
+MCF_HD inline bool batch_find_dual_entering(const BatchWork &w, int lane, int lanes, int32_t mark, bool out_leaves, bool raise, int32_t *in_arc)
+{
+    const int m_s = w.search_arcs;
+    int64_t mine = kMax;
+    uint32_t at = kNoPos;
+    for (int e = lane; e < m_s; e += lanes) {
+        const int8_t st = w.state[e];
+        if (st == MCF_STATE_TREE) continue;
+        const bool tail_in = w.scratch[w.tail[e]] == mark, head_in = w.scratch[w.head[e]] == mark;
+        if (tail_in == head_in) continue;
+        const bool same_way = tail_in == out_leaves, grows = st == MCF_STATE_LOWER;
+        if ((grows != same_way) != raise) continue;
+        const int64_t c = batch_reduced_cost(w, e);
+        if (c < mine) { mine = c; at = (uint32_t)e; }
+    }
+    const int64_t best = lanes_min_i64(mine);
+    const uint32_t pos = lanes_min_u32(mine == best ? at : kNoPos);
+    if (pos == kNoPos) return false;
+    *in_arc = (int32_t)pos;
+    return true;
+}
+
+// the sequential half of a dual pivot: batch_pivot's steps in its order, for the leaving arc above u_out and the entering arc in_arc
+MCF_HD inline void batch_dual_pivot(BatchWork &w, int in_arc, int u_out, int64_t violation, int32_t mark)
+{
+    Pivot p;
+    p.in_arc = in_arc;
+    p.in_state = w.state[in_arc];
+    const int tail = w.tail[in_arc], head = w.head[in_arc];
+    const bool tail_in = w.scratch[tail] == mark;
+    p.u_in = tail_in ? tail : head;
+    p.v_in = tail_in ? head : tail;
+    p.dir_in = tail_in ? kUp : kDown;
+    p.u_out = u_out;
+    p.v_out = w.par[u_out];
+    p.delta = violation;
+    p.change = true;
+    p.out_on_tail_path = tail_in;         // u_out lies between u_in and the join node
+    int a = tail, b = head;               // NS.cs:925-941
+    while (a != b) {
+        if (w.sub[a] < w.sub[b]) a = w.par[a]; else b = w.par[b];
+    }
+    p.join = a;
+    const int out = w.par_arc[u_out];
+    const int8_t out_state = leaving_state(w, p);
+    w.state[in_arc] = MCF_STATE_TREE;
+    w.state[out] = out_state;
+    const int64_t sigma = pivot_sigma(p, w.pi, w.cost);
+    int u = u_out;
+    for (int i = w.sub[u_out]; i > 0; --i) { w.pi[u] += sigma; u = w.nxt[u]; }
+    push_flow(w, p);
+    rehang_subtree(w, p);
+}
+
+// At most `budget` dual pivots; returns what is left of the budget.  Ends with w.run = kBatchRunning when no tree arc is violated (the
+// primal batch_run takes over), kBatchDual when the budget ran out, else how the phase ended.  Every lane runs this like batch_run.
+// The nodes below the leaving arc are marked in scratch[] with -(dual pivots so far + 1): rehang_subtree leaves node ids (>= 0) there, an
+// earlier pivot left a larger value, and uniform_redata clears the array, so no other node carries the mark.
+MCF_HD inline int64_t batch_dual_run(BatchWork &w, int lane, int lanes, int64_t budget)
+{
+    while (budget > 0) {
+        int32_t u_out = -1, arc = -1;
+        int64_t violation = 0;
+        if (!batch_find_violated(w, lane, lanes, &u_out, &violation)) { w.run = kBatchRunning; return budget; }
+        const int32_t mark = (int32_t)-(w.dual_pivots + 1);
+        lanes_sync();
+        if (lane == 0) {
+            int u = u_out;
+            for (int i = w.sub[u_out]; i > 0; --i) { w.scratch[u] = mark; u = w.nxt[u]; }
+        }
+        lanes_sync();
+        const int out = w.par_arc[u_out];
+        if (!batch_find_dual_entering(w, lane, lanes, mark, w.par_dir[u_out] == kUp, w.flow[out] < 0, &arc)) { w.run = kBatchDualStuck; return budget; }
+        if (lane == 0 && w.trace && w.pivots < w.trace_cap) w.trace[w.pivots] = arc;
+        ++w.pivots;
+        if (w.pivots > w.max_iter) { w.run = kBatchMaxIter; return budget; }
+        if (w.pivots > w.pivot_limit) { --w.pivots; w.run = kBatchLimit; return budget; }
+        ++w.dual_pivots;
+        --budget;
+        lanes_sync();
+        if (lane == 0) batch_dual_pivot(w, arc, u_out, violation, mark);
+        lanes_sync();
+    }
+    return 0;
+}
+
 // ---- at most `budget` pivots of the main loop (NS.cs:283-336).  Every lane runs this with its own copy of the scalars in w, and they stay equal.
 MCF_HD inline void batch_run(BatchWork &w, int lane, int lanes, int64_t budget)
 {
@@ -250,6 +376,14 @@ MCF_HD inline void batch_run(BatchWork &w, int lane, int lanes, int64_t budget)
         lanes_sync();
         if (lanes_from_first(unbounded)) { w.run = kBatchUnbounded; return; }
     }
+}
+
+// ---- a slice of a re-solve with new supplies or bounds: the dual phase where the instance is in it, then the primal pivots within the
+// same budget (an instance that started again cold comes with kBatchRunning and runs as ever)
+MCF_HD inline void batch_run_after_dual(BatchWork &w, int lane, int lanes, int64_t budget)
+{
+    if (w.run == kBatchDual) budget = batch_dual_run(w, lane, lanes, budget);
+    if (w.run == kBatchRunning) batch_run(w, lane, lanes, budget);
 }
 
 }  // namespace mcf

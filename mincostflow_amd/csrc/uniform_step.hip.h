@@ -5,6 +5,8 @@
 //   uniform_begin   bounds check, standard form, art_cost, the star start basis of start_basis (ns_core.cpp) and the instance's slot;
 //   uniform_finish  the status (finish_instance + core_finish of batch.hip / ns_core.cpp) and the output rows;
 //   uniform_recost  a re-solve with new costs: from the kept basis where the last solve ended Optimal, else uniform_begin again.
+//   uniform_redata  a re-solve with new supplies and bounds: the kept basis with its tree flows recomputed, for batch_dual_run, else
+//                   uniform_begin again; uniform_redata_settle judges the warm attempt and starts it again cold where it did not hold.
 // The pivots between them are batch_run on the workspace these steps leave, unchanged.
 // A fourth step stands apart from the solve: uniform_validate checks a solution in the caller's rows (mcf_ubatch_validate).
 // Problem data are read straight from the caller's arrays, results are written straight into the caller's rows.  The steps never learn
@@ -95,13 +97,6 @@ MCF_HD inline int popcount64(uint64_t v)
 #endif
 }
 MCF_HD inline bool lanes_any(bool p) { return lanes_ballot(p) != 0; }
-MCF_HD inline int64_t lanes_max_i64(int64_t v)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    for (int d = 32; d > 0; d >>= 1) { const int64_t o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
-#endif
-    return v;
-}
 MCF_HD inline uint64_t lanes_sum_u64(uint64_t v)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -374,6 +369,103 @@ MCF_HD inline void uniform_recost(const InstanceView &p, const BatchSlot &tmpl, 
         slot.reprice = 1;
     }
     lanes_sync();
+}
+
+// ---- a re-solve with new lower, upper and supply in p (costs and supply type are the last solve's).  The kept basis stays dual feasible:
+// WARM where the last solve ended as uniform_recost asks, no non-tree arc at its upper bound has lost that bound, and the new supplies sum
+// to zero (the lower bounds' shifts cancel in the sum; a surplus is answered by an artificial arc whose place depends on the pivot path).
+// Warm: the new capacities go in, every non-tree arc's flow follows its state, and the tree flows are recomputed -- node v's excess is
+// gathered into flow[par_arc[v]] (every node below the root owns one tree arc), folded root-ward up the reverse thread list, children
+// before parents, and turned by par_dir.  The sums wrap and commute like uniform_begin's, so one lane and 64 lanes give the same bits.
+// The slot leaves with run = kBatchDual and reprice = 2: batch_dual_run goes first, and uniform_redata_settle judges the attempt.
+// Anything else: uniform_begin with the new data, a fresh solve bit for bit.
+MCF_HD inline void uniform_redata(const InstanceView &p, const BatchSlot &tmpl, BatchSlot &slot, int lane, int lanes)
+{
+    const int n = p.n, m = p.m;
+    unsigned char *const home = p.home;
+    const int64_t *const lower = p.lower, *const upper = p.upper, *const supply = p.supply;
+    const int32_t all_arcs = slot.all_arcs;
+    bool inverted = false;
+    for (int e = lane; e < m; e += lanes) inverted |= uniform_upper(upper, e) < (lower ? lower[e] : 0);
+    if (lanes_any(inverted)) { uniform_begin(p, tmpl, slot, lane, lanes); return; }         // kBatchByBounds, nothing runs
+    bool warm = slot.run == kBatchNoEntering;
+    if (warm) {
+        const Layout l = layout_of((uint32_t)all_arcs, (uint32_t)n + 1u);
+        const int64_t *const flow = (const int64_t *)(home + l.flow);
+        const int8_t *const state = (const int8_t *)(home + l.state);
+        bool cold = false;
+        for (int e = m + lane; e < all_arcs; e += lanes) cold |= flow[e] != 0;
+        for (int e = lane; e < m; e += lanes) cold |= state[e] == MCF_STATE_UPPER && uniform_upper(upper, e) >= kInf;
+        uint64_t sum = 0;
+        if (supply)
+            for (int v = lane; v < n; v += lanes) sum += (uint64_t)supply[v];
+        warm = !lanes_any(cold) && lanes_sum_u64(sum) == 0;
+    }
+    if (!warm) { uniform_begin(p, tmpl, slot, lane, lanes); return; }
+    const Layout l = layout_of((uint32_t)all_arcs, (uint32_t)n + 1u);
+    int64_t *const upper_w = (int64_t *)(home + l.upper), *const flow = (int64_t *)(home + l.flow);
+    const int32_t *const par = (const int32_t *)(home + l.par), *const par_arc = (const int32_t *)(home + l.par_arc), *const prv = (const int32_t *)(home + l.prv);
+    int32_t *const scratch = (int32_t *)(home + l.scratch);
+    const int8_t *const state = (const int8_t *)(home + l.state), *const par_dir = (const int8_t *)(home + l.par_dir);
+    // plain stores, barrier, atomic adds on the same words, barrier, plain loads: the order uniform_begin explains
+    for (int v = lane; v < n; v += lanes) flow[par_arc[v]] = supply ? supply[v] : 0;
+    for (int v = lane; v < n + 2; v += lanes) scratch[v] = 0;              // no mark of an earlier dual phase is left (batch_dual_run)
+    lanes_sync();
+    for (int e = lane; e < m; e += lanes) {
+        const int64_t lo = lower ? lower[e] : 0, cap = uniform_upper(upper, e) - lo;
+        upper_w[e] = cap;
+        int64_t carried = lo;                                               // what the arc moves from its tail to its head, decided here
+        if (state[e] != MCF_STATE_TREE) {
+            const int64_t f = state[e] == MCF_STATE_UPPER ? cap : 0;
+            flow[e] = f;
+            carried = (int64_t)((uint64_t)carried + (uint64_t)f);
+        }
+        if (carried == 0) continue;
+        lanes_add_i64(&flow[par_arc[p.source[e]]], -carried);
+        lanes_add_i64(&flow[par_arc[p.target[e]]], carried);
+    }
+    for (int e = m + lane; e < all_arcs; e += lanes)
+        if (state[e] != MCF_STATE_TREE) flow[e] = 0;
+    lanes_sync();
+    if (lane == 0) {
+        // exactly n steps by count, like batch_reprice: the reverse thread list visits every node behind all of its subtree
+        const int root = n;
+        int u = prv[root];
+        for (int i = 0; i < n && (unsigned)u < (unsigned)root; ++i) {
+            const int e = par_arc[u], up = par[u];
+            const int64_t below = flow[e];                                  // the excess of u's subtree: it leaves through u's tree arc
+            if (up != root) flow[par_arc[up]] = (int64_t)((uint64_t)flow[par_arc[up]] + (uint64_t)below);
+            flow[e] = par_dir[u] * below;
+            u = prv[u];
+        }
+        uniform_place_slot(slot, tmpl, p, all_arcs, kBatchDual);
+        slot.reprice = 2;
+    }
+    lanes_sync();
+}
+
+// ---- the end of a warm attempt of uniform_redata (slot.reprice == 2, which this clears).  It stands when the dual phase handed over,
+// the primal phase found no entering arc and no flow is left on a root link or an artificial arc; an instance stopped by the pivot limit
+// stays stopped.  Anything else -- dual stuck, Unbounded, the iteration guard, flow left on [m, all_arcs) -- starts again cold with the
+// same data: the slot says so (kBatchRunning) and the caller runs it.
+MCF_HD inline void uniform_redata_settle(const InstanceView &p, const BatchSlot &tmpl, BatchSlot &slot, int lane, int lanes)
+{
+    if (slot.reprice != 2) return;
+    const int n = p.n, m = p.m;
+    const int32_t all_arcs = slot.all_arcs, run = slot.run;
+    bool stands = run == kBatchLimit;
+    if (run == kBatchNoEntering) {
+        const int64_t *const flow = (const int64_t *)(p.home + layout_of((uint32_t)all_arcs, (uint32_t)n + 1u).flow);
+        bool left = false;
+        for (int e = m + lane; e < all_arcs; e += lanes) left |= flow[e] != 0;
+        stands = !lanes_any(left);
+    }
+    lanes_sync();
+    if (stands) {
+        if (lane == 0) slot.reprice = 0;
+        return;
+    }
+    uniform_begin(p, tmpl, slot, lane, lanes);
 }
 
 // ---- the reference's SolutionValidator (SolutionValidator.cs, restated in oracle/validator.py) for instance i of a solution that lies in

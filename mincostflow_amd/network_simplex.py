@@ -585,8 +585,23 @@ class _PlacedBatch:
         """Test hook: resolve() with one lane on the CPU.  numpy only."""
         return self._call("rerun_on_host", cost, supply, lower, upper, supply_type, changed, masked=True, numpy_only=True)
 
+    def resolve_data(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq, changed=None) -> UniformResult:
+        """New supplies and bounds for the instances `changed` marks ([count] bool / uint8, None = all): each goes on from the basis its
+        last solve left, by dual pivots, where that ended Optimal and the new supplies sum to zero; every other one, and every warm attempt
+        that does not hold, is solved again from the start in the same call.  cost and supply_type must be what the last solve call was
+        given.  Rows of unmarked instances are the last result's."""
+        return self._call("resolve_data", cost, supply, lower, upper, supply_type, changed, masked=True)
+
+    def rerun_data_on_host(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq, changed=None) -> UniformResult:
+        """Test hook: resolve_data() with one lane on the CPU.  numpy only."""
+        return self._call("rerun_data_on_host", cost, supply, lower, upper, supply_type, changed, masked=True, numpy_only=True)
+
     def stats(self) -> dict:
         st = L.UBatchStats(); L.check(self._fn("get_stats")(self._h, C.byref(st))); return st.as_dict()
+
+    def resolve_data_stats(self) -> dict:
+        """What the last resolve_data() / rerun_data_on_host() did: warm, cold, fallback and untouched instances, dual and primal pivots."""
+        st = L.UBatchRedataStats(); L.check(self._fn("get_redata_stats")(self._h, C.byref(st))); return st.as_dict()
 
     # ---- validation: the solution's rows where they lie
     SOLUTION_ROWS = (("status", "int32", None), ("total_cost", "int64", None), ("flows", "int64", "arc_count"), ("potentials", "int64", "node_count"))
