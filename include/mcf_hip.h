@@ -970,6 +970,61 @@ MCF_API int mcf_rbatch_get_redata_stats(mcf_rbatch *b, mcf_ubatch_redata_stats *
 MCF_API int mcf_rbatch_validate(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out);
 MCF_API int mcf_rbatch_validate_on_host(mcf_rbatch *b, const mcf_rbatch_check_io *io, mcf_ubatch_check_summary *out);
 
+/* ---- Cost ranges of the kept basis (DESIGN.md 3.14 "Cost ranges of the kept basis"): classic post-optimality cost ranging, computed on
+ * the device from the state every instance's last solve call left there.  An instance is RANGED when that call, of whichever kind,
+ * left it as a warm start with new costs demands: no entering arc, and no flow on a root link or an artificial arc -- Optimal, with
+ * every supply met exactly.  For a ranged instance and each of its arcs e the kept basis stays optimal exactly while the arc's cost lies
+ * in [cost[e] - cost_down[e], cost[e] + cost_up[e]] with every other cost as the last solve call was given it: a mcf_*batch_resolve with
+ * a cost inside the interval makes no pivot and returns the same flows.  Both are >= 0 and deltas, not costs; MCF_RANGE_INF = no limit
+ * on that side.  An arc at its lower bound has cost_up = MCF_RANGE_INF, one at its upper bound cost_down = MCF_RANGE_INF; a tree arc's
+ * two sides are minima over the non-tree arcs across its cut (csrc/ranges_step.hip.h).  arc_state is the basis itself as far as the
+ * caller's arcs go: MCF_STATE_LOWER / _TREE / _UPPER.  Every other instance gets ranged = 0 and zero rows.
+ * "Every other cost" includes the cost of the artificial arcs the solver adds, which a re-solve derives anew from the largest |cost| it
+ * is given, (max |cost| + 1) * node_count: a limit of about that size comes from a root link seen through an artificial arc that stayed
+ * in the tree at flow 0, and a cost moved that far moves the artificial cost along -- read it as "practically unlimited".
+ * One wave per instance; an instance is ranged in LDS exactly when it is solved there.  Contract as mcf_ubatch_validate's: null stream,
+ * returns synchronised, the handle's device is made current and the caller's restored.  The call reads the kept state and changes none
+ * of it: workspaces, slots, basis, results and the other statistics stay, and it mixes with every solve call and hook in any order (the
+ * state moves whole between host and device as it does for them).  MCF_ERR_STATE before a solve of either kind; MCF_ERR_NO_DEVICE
+ * without a GPU leaves the handle as it was; MCF_ERR_INVALID for a null argument, an unknown memory kind, or one of cost_down / cost_up
+ * without the other.  With MCF_MEM_DEVICE nothing that scales with the arcs, the nodes or the instances crosses the bus in a call (a
+ * table of one int32 per instance goes up once per handle, with the first call). */
+#define MCF_RANGE_INF INT64_MAX
+typedef struct mcf_ubatch_range_io {
+    int32_t memory;               /* MCF_MEM_HOST / MCF_MEM_DEVICE: where every pointer below points */
+    int32_t reserved;
+    /* results, any may be NULL -- but cost_down and cost_up both or neither (without them no cycle is walked) */
+    int32_t *ranged;              /* [count] 1 / 0 */
+    int8_t *arc_state;            /* [count * arc_count] */
+    int64_t *cost_down;           /* [count * arc_count] */
+    int64_t *cost_up;             /* [count * arc_count] */
+} mcf_ubatch_range_io;
+typedef struct mcf_rbatch_range_io {                   /* the same with flat rows: instance i's arcs at [arc_row[i], arc_row[i + 1]) */
+    int32_t memory;
+    int32_t reserved;
+    int32_t *ranged;              /* [count] */
+    int8_t *arc_state;            /* [arc_row[count]] */
+    int64_t *cost_down;           /* [arc_row[count]] */
+    int64_t *cost_up;             /* [arc_row[count]] */
+} mcf_rbatch_range_io;
+typedef struct mcf_ubatch_range_stats { /* of the last mcf_*batch_cost_ranges / _on_host (all zero before one) */
+    int64_t instances;
+    int64_t ranged;               /* instances with ranged = 1 */
+    int64_t lds_instances;        /* of `instances`, by the tier they are solved in; 0 and 0 from the host hook */
+    int64_t global_instances;
+    int64_t tree_arcs;            /* the ranged instances' tree arcs among the caller's arcs: the rows that took a walk to fill */
+    int64_t cycle_hops;           /* steps of all cycle walks: one dependent load chain link each.  Both 0 without cost_down / cost_up */
+    double kernel_ns;             /* round the launches, synchronised */
+    int64_t bytes_up, bytes_down; /* MCF_MEM_DEVICE: the three summary words; MCF_MEM_HOST adds the arrays */
+} mcf_ubatch_range_stats;
+MCF_API int mcf_ubatch_cost_ranges(mcf_ubatch *b, const mcf_ubatch_range_io *io);
+/* TEST HOOK: the same step (uniform_ranges, csrc/ranges_step.hip.h) with one lane on the CPU.  io->memory must be MCF_MEM_HOST. */
+MCF_API int mcf_ubatch_cost_ranges_on_host(mcf_ubatch *b, const mcf_ubatch_range_io *io);
+MCF_API int mcf_ubatch_get_range_stats(mcf_ubatch *b, mcf_ubatch_range_stats *out);
+MCF_API int mcf_rbatch_cost_ranges(mcf_rbatch *b, const mcf_rbatch_range_io *io);
+MCF_API int mcf_rbatch_cost_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_range_io *io);
+MCF_API int mcf_rbatch_get_range_stats(mcf_rbatch *b, mcf_ubatch_range_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,28 @@ class RBatchCheckIo(C.Structure):
                 ("valid", C.c_void_p), ("errors", C.c_void_p), ("first", C.c_void_p), ("objective", C.c_void_p), ("dual_cost", C.c_void_p)]
 
 
+RANGE_INF = (1 << 63) - 1      # MCF_RANGE_INF
+
+
+class UBatchRangeIo(C.Structure):
+    """mcf_ubatch_range_io"""
+    _fields_ = [("memory", C.c_int32), ("reserved", C.c_int32), ("ranged", C.c_void_p), ("arc_state", C.c_void_p), ("cost_down", C.c_void_p), ("cost_up", C.c_void_p)]
+
+
+class RBatchRangeIo(C.Structure):
+    """mcf_rbatch_range_io"""
+    _fields_ = UBatchRangeIo._fields_
+
+
+class UBatchRangeStats(C.Structure):
+    """mcf_ubatch_range_stats"""
+    _fields_ = [(name, C.c_int64) for name in ("instances", "ranged", "lds_instances", "global_instances", "tree_arcs", "cycle_hops")] + \
+               [("kernel_ns", C.c_double), ("bytes_up", C.c_int64), ("bytes_down", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class ProblemStruct(C.Structure):
     _fields_ = [("node_count", C.c_int32), ("arc_count", C.c_int32), ("source", C.POINTER(C.c_int32)),
                 ("target", C.POINTER(C.c_int32)), ("lower", C.POINTER(C.c_int64)), ("upper", C.POINTER(C.c_int64)),
@@ -370,6 +392,9 @@ SIGNATURES = {
     "mcf_ubatch_get_redata_stats": (C.c_int, [C.c_void_p, _P(UBatchRedataStats)]),
     "mcf_ubatch_validate": (C.c_int, [C.c_void_p, _P(UBatchCheckIo), _P(UBatchCheckSummary)]),
     "mcf_ubatch_validate_on_host": (C.c_int, [C.c_void_p, _P(UBatchCheckIo), _P(UBatchCheckSummary)]),
+    "mcf_ubatch_cost_ranges": (C.c_int, [C.c_void_p, _P(UBatchRangeIo)]),
+    "mcf_ubatch_cost_ranges_on_host": (C.c_int, [C.c_void_p, _P(UBatchRangeIo)]),
+    "mcf_ubatch_get_range_stats": (C.c_int, [C.c_void_p, _P(UBatchRangeStats)]),
     "mcf_rbatch_create": (C.c_int, [_P(C.c_void_p), _P(RBatchDesc)]),
     "mcf_rbatch_destroy": (None, [C.c_void_p]),
     "mcf_rbatch_get_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -383,6 +408,9 @@ SIGNATURES = {
     "mcf_rbatch_get_redata_stats": (C.c_int, [C.c_void_p, _P(UBatchRedataStats)]),
     "mcf_rbatch_validate": (C.c_int, [C.c_void_p, _P(RBatchCheckIo), _P(UBatchCheckSummary)]),
     "mcf_rbatch_validate_on_host": (C.c_int, [C.c_void_p, _P(RBatchCheckIo), _P(UBatchCheckSummary)]),
+    "mcf_rbatch_cost_ranges": (C.c_int, [C.c_void_p, _P(RBatchRangeIo)]),
+    "mcf_rbatch_cost_ranges_on_host": (C.c_int, [C.c_void_p, _P(RBatchRangeIo)]),
+    "mcf_rbatch_get_range_stats": (C.c_int, [C.c_void_p, _P(UBatchRangeStats)]),
     "mcf_problem_free": (None, [_P(ProblemStruct)]),
     "mcf_gen_netgen_like": (C.c_int, [_P(ProblemStruct), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64]),

@@ -12,6 +12,8 @@
 //     down), from the start basis otherwise.
 //   * re-solves with new supplies and bounds (mcf_ubatch_resolve_data, mcf_rbatch_resolve_data): batch_dual_kernel runs the dual pivots of
 //     batch_step.hip.h in front of the primal ones, between a re-data launch and a settle launch (uniform_step.hip.h).
+//   * cost ranges of the kept basis (mcf_ubatch_cost_ranges, mcf_rbatch_cost_ranges): the ranges kernels run ranges_step.hip.h on the
+//     workspaces as the last solve call left them, and write nothing there.
 // Device code does no bounds checks: mcf_batch_add validates every end point (core_create), and every index the kernel follows after
 // that was written by start_basis or by the pivot itself.
 #include <hip/hip_runtime.h>
@@ -24,6 +26,7 @@
 #include "batch_step.hip.h"
 #include "common.h"
 #include "ns_core.h"
+#include "ranges_step.hip.h"
 #include "uniform_step.hip.h"
 
 namespace {
@@ -220,6 +223,27 @@ __global__ __launch_bounds__(kBatchThreads) void ragged_finish_kernel(mcf::Ragge
 __global__ __launch_bounds__(kBatchThreads) void ragged_validate_kernel(mcf::RaggedProblem r, mcf::UniformCheck c, const int64_t *flows, const int64_t *potentials)
 {
     mcf::uniform_validate(mcf::ragged_check_view(r, flows, potentials, (int64_t)blockIdx.x), c, (int)threadIdx.x, kBatchThreads);
+}
+
+// mcf_*batch_cost_ranges: block k serves instance ids[k] (the handle's table of the instances by tier and footprint class, up once per
+// handle).  One wave, like every kernel here: the minima of one instance meet in its own rows or its own LDS, and the barriers between
+// the passes are the workgroup's.  kLds: dynamic LDS holds what the step reads and the two accumulators (the host launches with at least
+// range_layout_of(m + 2n, n + 1, m).bytes); otherwise the walks run on the workspace and the minima are taken in the caller's rows.
+template <bool kLds>
+__global__ __launch_bounds__(kBatchThreads) void uniform_ranges_kernel(mcf::UniformProblem p, mcf::RangeOutputs o, const BatchSlot *slots, unsigned char *slab,
+                                                                       const int32_t *ids)
+{
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int64_t i = (int64_t)ids[blockIdx.x];
+    mcf::uniform_ranges<kLds>(mcf::uniform_view(p, nullptr, i, slab), o, slots[i], lds, (int)threadIdx.x, kBatchThreads);
+}
+template <bool kLds>
+__global__ __launch_bounds__(kBatchThreads) void ragged_ranges_kernel(mcf::RaggedProblem r, mcf::RangeOutputs o, const BatchSlot *slots, unsigned char *slab,
+                                                                      const int32_t *ids)
+{
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int64_t i = (int64_t)ids[blockIdx.x];
+    mcf::uniform_ranges<kLds>(mcf::ragged_view(r, nullptr, i, slab, nullptr), o, slots[i], lds, (int)threadIdx.x, kBatchThreads);
 }
 
 struct Instance {
@@ -955,6 +979,13 @@ struct PlacedBatch {
     int64_t *d_summary = nullptr;       // validation: invalid instances, the lowest invalid index.  Allocated last: it says the tables are up
     unsigned char *d_io = nullptr;      // MCF_MEM_HOST: the caller's arrays on their way up and down
     size_t d_io_bytes = 0;
+    // cost ranges: the instances by tier and footprint class (planned for lds_max = range_lds_max, up once), the summary words, the last call's statistics
+    struct RangeLaunch { int first, n; uint32_t lds; bool in_lds; };
+    std::vector<RangeLaunch> range_launches;
+    int32_t *d_range_ids = nullptr;
+    int64_t *d_range_summary = nullptr;
+    int range_lds_max = -1;
+    mcf_ubatch_range_stats range_stats{};
     std::vector<unsigned char> h_slab;  // the host hooks' slab, slots and traces: the device's layout
     std::vector<BatchSlot> h_slots;
     std::vector<int32_t> h_traces;
@@ -964,6 +995,8 @@ struct PlacedBatch {
         if (d_tmpl) (void)hipFree(d_tmpl);
         if (d_summary) (void)hipFree(d_summary);
         if (d_io) (void)hipFree(d_io);
+        if (d_range_ids) (void)hipFree(d_range_ids);
+        if (d_range_summary) (void)hipFree(d_range_summary);
     }
 };
 
@@ -1103,10 +1136,18 @@ struct UniformPlacement {
     static constexpr auto redata_kernel = uniform_redata_kernel;
     static constexpr auto settle_kernel = uniform_settle_kernel;
     static constexpr auto finish_kernel = uniform_finish_kernel;
+    static constexpr auto ranges_kernel_in_lds = uniform_ranges_kernel<true>;
     static void launch_validate(const Handle *b, const Problem &p, const mcf::UniformCheck &c, const BatchIo &io)
     {
         hipLaunchKernelGGL(uniform_validate_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, p, c, b->d_inc_start, b->d_inc, io.flows, io.potentials);
     }
+    static void launch_ranges(const Handle *, bool in_lds, unsigned blocks, uint32_t lds, const Problem &p, const mcf::RangeOutputs &o, const BatchSlot *slots,
+                              unsigned char *slab, const int32_t *ids)
+    {
+        hipLaunchKernelGGL(in_lds ? ranges_kernel_in_lds : uniform_ranges_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, p, o, slots, slab, ids);
+    }
+    static void sizes(const Handle *b, size_t, int32_t *n, int32_t *m) { *n = b->d.node_count; *m = b->d.arc_count; }
+    static size_t arc_rows(const Handle *b) { return (size_t)b->d.count * (size_t)b->d.arc_count; }
     static size_t slab_bytes(const Handle *b) { return (size_t)b->d.count * (size_t)b->stride; }
     static LaunchPlan plan(Handle *b) { return LaunchPlan{&b->dev, b->lds_max, b->d.pivots_per_launch, nullptr, b->stride}; }     // one class for all
     static const BatchSlot *templates(const Handle *b) { return &b->tmpl; }
@@ -1168,10 +1209,18 @@ struct RaggedPlacement {
     static constexpr auto redata_kernel = ragged_redata_kernel;
     static constexpr auto settle_kernel = ragged_settle_kernel;
     static constexpr auto finish_kernel = ragged_finish_kernel;
+    static constexpr auto ranges_kernel_in_lds = ragged_ranges_kernel<true>;
     static void launch_validate(const Handle *b, const Problem &r, const mcf::UniformCheck &c, const BatchIo &io)
     {
         hipLaunchKernelGGL(ragged_validate_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, r, c, io.flows, io.potentials);
     }
+    static void launch_ranges(const Handle *, bool in_lds, unsigned blocks, uint32_t lds, const Problem &r, const mcf::RangeOutputs &o, const BatchSlot *slots,
+                              unsigned char *slab, const int32_t *ids)
+    {
+        hipLaunchKernelGGL(in_lds ? ranges_kernel_in_lds : ragged_ranges_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, r, o, slots, slab, ids);
+    }
+    static void sizes(const Handle *b, size_t i, int32_t *n, int32_t *m) { const mcf::RaggedGraph &g = b->graphs[(size_t)b->graph_of[i]]; *n = g.n; *m = g.m; }
+    static size_t arc_rows(const Handle *b) { return (size_t)b->arc_row[(size_t)b->d.count]; }
     static size_t slab_bytes(const Handle *b) { return (size_t)b->workspace[(size_t)b->d.count]; }
     static LaunchPlan plan(Handle *b) { return LaunchPlan{&b->dev, b->lds_max, b->d.pivots_per_launch, b->footprint.data(), 0}; }  // a class per instance
     static const BatchSlot *templates(const Handle *b) { return b->tmpl.data(); }
@@ -1300,6 +1349,36 @@ struct Staged {
     }
 };
 
+// the staging buffer of MCF_MEM_HOST calls holds at least `bytes`
+int reserve_io(PlacedBatch *b, size_t bytes)
+{
+    if (b->d_io_bytes >= bytes) return MCF_OK;
+    if (b->d_io) { HIP_TRY(hipFree(b->d_io)); b->d_io = nullptr; b->d_io_bytes = 0; }
+    HIP_TRY(hipMalloc((void **)&b->d_io, bytes));
+    b->d_io_bytes = bytes;
+    return MCF_OK;
+}
+
+// The state the last solve call left moves whole, slab and slots, to where the next call runs.  Neither changes `where`: the caller
+// does, once the state there is the one that counts.
+int state_to_device(PlacedBatch *b, size_t count, int64_t *bytes_up)     // the device's buffers are there (ensure_device_buffers)
+{
+    if (b->where != PlacedBatch::kOnHost) return MCF_OK;
+    if (!b->h_slab.empty()) HIP_TRY(hipMemcpy(b->dev.slab, b->h_slab.data(), b->h_slab.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->dev.slots, b->h_slots.data(), count * sizeof(BatchSlot), hipMemcpyHostToDevice));
+    *bytes_up += (int64_t)(b->h_slab.size() + count * sizeof(BatchSlot));
+    return MCF_OK;
+}
+int state_to_host(PlacedBatch *b, int32_t device, size_t count)          // h_slab and h_slots have their sizes
+{
+    if (b->where != PlacedBatch::kOnDevice || !count) return MCF_OK;
+    const DeviceGuard guard;
+    HIP_TRY(hipSetDevice(device));
+    if (!b->h_slab.empty()) HIP_TRY(hipMemcpy(b->h_slab.data(), b->dev.slab, b->h_slab.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b->h_slots.data(), b->dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));
+    return MCF_OK;
+}
+
 // The caller's io as the kernels see it: itself for MCF_MEM_DEVICE; for MCF_MEM_HOST every array of *io that is there becomes its staged
 // copy, and what the call reads is uploaded here.  A solve call reads the problem and writes the solution; where it will not write every
 // row (a masked re-solve) the solution goes up too.  A validation call reads both and writes the answers.
@@ -1331,11 +1410,7 @@ int stage_up(typename P::Handle *b, BatchIo *io, Staged *st, int64_t *bytes_up)
     size_t at[kArrays] = {};
     for (int k = 0; k < kArrays; ++k)
         if (void *const host = *arrays[k].slot) at[k] = st->add(arrays[k].up ? host : nullptr, arrays[k].down ? host : nullptr, arrays[k].bytes);
-    if (b->d_io_bytes < st->total) {
-        if (b->d_io) { HIP_TRY(hipFree(b->d_io)); b->d_io = nullptr; b->d_io_bytes = 0; }
-        HIP_TRY(hipMalloc((void **)&b->d_io, st->total));
-        b->d_io_bytes = st->total;
-    }
+    if (const int rc = reserve_io(b, st->total)) return rc;
     for (const Staged::Piece &pc : st->pieces)
         if (pc.host_in && pc.bytes) {
             HIP_TRY(hipMemcpy(b->d_io + pc.offset, pc.host_in, pc.bytes, hipMemcpyHostToDevice));
@@ -1402,11 +1477,8 @@ int solve_on_device(typename P::Handle *b, BatchIo io, Call call, const char *wh
     if (!count) { b->where = PlacedBatch::kOnDevice; b->supply_type = io.supply_type; b->stats.host_ns = mcf::now_ns() - t_start; return MCF_OK; }
     if (const int rc = ensure_device_buffers<P>(b)) return rc;
     DeviceBuffers &dev = b->dev;
-    if (resolve && b->where == PlacedBatch::kOnHost) {                      // the last solve was a host hook's: its state goes up whole
-        if (!b->h_slab.empty()) HIP_TRY(hipMemcpy(dev.slab, b->h_slab.data(), b->h_slab.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dev.slots, b->h_slots.data(), count * sizeof(BatchSlot), hipMemcpyHostToDevice));
-        b->stats.bytes_up += (int64_t)(b->h_slab.size() + count * sizeof(BatchSlot));
-    }
+    if (resolve)                                                            // the last solve was a host hook's: its state goes up whole
+        if (const int rc = state_to_device(b, count, &b->stats.bytes_up)) return rc;
     if (!resolve) io.changed = nullptr;
     std::vector<uint8_t> marked;                                            // a re-solve with new data counts its instances by the mask: one byte each
     if (call == kRedata && io.changed) {
@@ -1502,12 +1574,8 @@ int solve_on_host(typename P::Handle *b, BatchIo io, Call call, const char *what
     b->h_slab.resize(P::slab_bytes(b));
     b->h_slots.resize(count);
     b->h_traces.resize(std::max<size_t>(count * (size_t)b->d.trace_capacity, 1));
-    if (resolve && b->where == PlacedBatch::kOnDevice && count) {           // the last solve was the device's: its state comes down whole
-        const DeviceGuard guard;
-        HIP_TRY(hipSetDevice(b->d.device));
-        if (!b->h_slab.empty()) HIP_TRY(hipMemcpy(b->h_slab.data(), b->dev.slab, b->h_slab.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(b->h_slots.data(), b->dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));
-    }
+    if (resolve)                                                            // the last solve was the device's: its state comes down whole
+        if (const int rc = state_to_host(b, b->d.device, count)) return rc;
     b->stats = mcf_ubatch_stats{};
     b->stats.instances = (int64_t)count;
     b->stats.workspace_bytes = (int64_t)b->h_slab.size();
@@ -1591,6 +1659,151 @@ int validate_on_host(typename P::Handle *b, const BatchIo &io, mcf_ubatch_check_
     for (int64_t i = 0; i < (int64_t)b->d.count; ++i) mcf::uniform_validate(P::check_view(b, p, io, i), c, 0, 1);
     out->kernel_ns = mcf::now_ns() - t_start;
     summary_of(words, (int64_t)b->d.count, out);
+    return MCF_OK;
+}
+
+// ---- mcf_*batch_cost_ranges / _on_host: uniform_ranges for every instance, on the state the last solve call left; it is only read
+struct RangeIo {
+    bool given;
+    int32_t memory;
+    int32_t *ranged;
+    int8_t *arc_state;
+    int64_t *cost_down, *cost_up;
+};
+template <class Io>
+RangeIo range_io_of(const Io *io)
+{
+    if (!io) return RangeIo{};
+    return RangeIo{true, io->memory, io->ranged, io->arc_state, io->cost_down, io->cost_up};
+}
+
+int check_range_call(const PlacedBatch *b, const RangeIo &io, const char *what, bool host_only)
+{
+    if (!b || !io.given) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
+    if (io.memory != MCF_MEM_HOST && io.memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io.memory);
+    if (host_only && io.memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
+    if (!io.cost_down != !io.cost_up) return mcf::fail(MCF_ERR_INVALID, "%s: cost_down and cost_up come together or not at all", what);
+    if (b->where == PlacedBatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
+    return MCF_OK;
+}
+
+// the instances by tier and, in the LDS tier, by the class of what the ranges kernel keeps there; the table goes up once per handle
+// (again only if the device's LDS limit were another).  An instance is ranged in LDS exactly when it is solved there.
+template <class P>
+int ensure_range_plan(typename P::Handle *b)
+{
+    if (b->d_range_ids && b->range_lds_max == b->lds_max) return MCF_OK;
+    const size_t count = (size_t)b->d.count;
+    const LaunchPlan plan = P::plan(b);
+    std::vector<int32_t> group[kClasses];
+    std::vector<uint32_t> bytes(count);
+    for (size_t i = 0; i < count; ++i) {
+        int32_t n = 0, m = 0;
+        P::sizes(b, i, &n, &m);
+        bytes[i] = mcf::range_layout_of((uint32_t)(m + 2 * n), (uint32_t)n + 1u, (uint32_t)m).bytes;       // no more than plan.bytes(i)
+        const bool in_lds = class_of(b->lds_max, plan.bytes((int32_t)i)) != kClasses - 1;
+        group[in_lds ? class_of(b->lds_max, bytes[i]) : kClasses - 1].push_back((int32_t)i);
+    }
+    std::vector<int32_t> ids;
+    b->range_launches.clear();
+    for (int g = 0; g < kClasses; ++g) {
+        if (group[g].empty()) continue;
+        PlacedBatch::RangeLaunch L{(int)ids.size(), (int)group[g].size(), 0, g != kClasses - 1};
+        for (int32_t i : group[g]) {
+            ids.push_back(i);
+            if (L.in_lds) L.lds = std::max(L.lds, bytes[(size_t)i]);
+        }
+        b->range_launches.push_back(L);
+    }
+    if (!b->d_range_ids) HIP_TRY(hipMalloc((void **)&b->d_range_ids, count * sizeof(int32_t)));
+    if (!b->d_range_summary) HIP_TRY(hipMalloc((void **)&b->d_range_summary, 3 * sizeof(int64_t)));
+    HIP_TRY(hipMemcpy(b->d_range_ids, ids.data(), count * sizeof(int32_t), hipMemcpyHostToDevice));
+    b->range_lds_max = b->lds_max;
+    return MCF_OK;
+}
+
+template <class P>
+int ranges_on_device(typename P::Handle *b, RangeIo io, const char *what)
+{
+    if (const int rc = check_range_call(b, io, what, false)) return rc;
+    if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
+    const DeviceGuard guard;
+    if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
+    const size_t count = (size_t)b->d.count;
+    mcf_ubatch_range_stats st{};
+    st.instances = (int64_t)count;
+    if (!count) { b->range_stats = st; return MCF_OK; }
+    if (b->lds_max > (64 << 10))                                            // the opt-in open_device got for the solve's kernels
+        HIP_TRY(hipFuncSetAttribute((const void *)P::ranges_kernel_in_lds, hipFuncAttributeMaxDynamicSharedMemorySize, b->lds_max));
+    if (const int rc = ensure_device_buffers<P>(b)) return rc;
+    const bool first = !b->d_range_ids;
+    if (const int rc = ensure_range_plan<P>(b)) return rc;
+    if (first) st.bytes_up += (int64_t)(count * sizeof(int32_t));
+    if (const int rc = state_to_device(b, count, &st.bytes_up)) return rc;
+    b->where = PlacedBatch::kOnDevice;                                      // the same state, now there too
+    Staged staged;                                                          // MCF_MEM_HOST: the rows come down through the staging buffer of the solve calls
+    if (io.memory == MCF_MEM_HOST) {
+        const size_t arcs = P::arc_rows(b);
+        size_t at[4] = {};
+        if (io.ranged) at[0] = staged.add(nullptr, io.ranged, 4 * count);
+        if (io.arc_state) at[1] = staged.add(nullptr, io.arc_state, arcs);
+        if (io.cost_down) { at[2] = staged.add(nullptr, io.cost_down, 8 * arcs); at[3] = staged.add(nullptr, io.cost_up, 8 * arcs); }
+        if (const int rc = reserve_io(b, std::max<size_t>(staged.total, 16))) return rc;
+        if (io.ranged) io.ranged = (int32_t *)(b->d_io + at[0]);
+        if (io.arc_state) io.arc_state = (int8_t *)(b->d_io + at[1]);
+        if (io.cost_down) { io.cost_down = (int64_t *)(b->d_io + at[2]); io.cost_up = (int64_t *)(b->d_io + at[3]); }
+    }
+    int64_t words[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpy(b->d_range_summary, words, sizeof(words), hipMemcpyHostToDevice));
+    st.bytes_up += (int64_t)sizeof(words);
+    const mcf::RangeOutputs o{io.ranged, io.arc_state, io.cost_down, io.cost_up, b->d_range_summary};
+    const typename P::Problem p = P::problem(b, BatchIo{}, true);
+    const double t_launch = mcf::now_ns();
+    for (const PlacedBatch::RangeLaunch &L : b->range_launches) {
+        P::launch_ranges(b, L.in_lds, (unsigned)L.n, L.lds, p, o, b->dev.slots, b->dev.slab, b->d_range_ids + L.first);
+        HIP_TRY(hipGetLastError());
+        (L.in_lds ? st.lds_instances : st.global_instances) += L.n;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    st.kernel_ns = mcf::now_ns() - t_launch;
+    HIP_TRY(hipMemcpy(words, b->d_range_summary, sizeof(words), hipMemcpyDeviceToHost));
+    st.bytes_down += (int64_t)sizeof(words);
+    if (const int rc = stage_down(b, staged, &st.bytes_down)) return rc;
+    st.ranged = words[0]; st.tree_arcs = words[1]; st.cycle_hops = words[2];
+    b->range_stats = st;
+    return MCF_OK;
+}
+
+template <class P>
+int ranges_on_host(typename P::Handle *b, const RangeIo &io, const char *what)
+{
+    if (const int rc = check_range_call(b, io, what, true)) return rc;
+    const size_t count = (size_t)b->d.count;
+    b->h_slab.resize(P::slab_bytes(b));
+    b->h_slots.resize(count);
+    if (const int rc = state_to_host(b, b->d.device, count)) return rc;
+    b->where = PlacedBatch::kOnHost;                                        // the same state, now here too
+    mcf_ubatch_range_stats st{};
+    st.instances = (int64_t)count;
+    int64_t words[3] = {0, 0, 0};
+    const mcf::RangeOutputs o{io.ranged, io.arc_state, io.cost_down, io.cost_up, words};
+    const typename P::Problem p = P::problem(b, BatchIo{}, false);
+    const mcf::UniformOutputs none{};
+    const double t_start = mcf::now_ns();
+    for (size_t i = 0; i < count; ++i) {
+        const BatchSlot *tmpl = nullptr;
+        mcf::uniform_ranges<false>(P::view(b, p, none, (int64_t)i, b->h_slab.data(), &tmpl), o, b->h_slots[i], nullptr, 0, 1);
+    }
+    st.kernel_ns = mcf::now_ns() - t_start;
+    st.ranged = words[0]; st.tree_arcs = words[1]; st.cycle_hops = words[2];
+    b->range_stats = st;
+    return MCF_OK;
+}
+
+int get_range_stats(const PlacedBatch *b, mcf_ubatch_range_stats *out)
+{
+    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
+    *out = b->range_stats;
     return MCF_OK;
 }
 
@@ -1732,6 +1945,9 @@ int mcf_ubatch_validate_on_host(mcf_ubatch *b, const mcf_ubatch_check_io *io, mc
 }
 int mcf_ubatch_get_stats(mcf_ubatch *b, mcf_ubatch_stats *out) { return get_stats(b, out); }
 int mcf_ubatch_get_redata_stats(mcf_ubatch *b, mcf_ubatch_redata_stats *out) { return get_redata_stats(b, out); }
+int mcf_ubatch_cost_ranges(mcf_ubatch *b, const mcf_ubatch_range_io *io) { return ranges_on_device<UniformPlacement>(b, range_io_of(io), "mcf_ubatch_cost_ranges"); }
+int mcf_ubatch_cost_ranges_on_host(mcf_ubatch *b, const mcf_ubatch_range_io *io) { return ranges_on_host<UniformPlacement>(b, range_io_of(io), "mcf_ubatch_cost_ranges_on_host"); }
+int mcf_ubatch_get_range_stats(mcf_ubatch *b, mcf_ubatch_range_stats *out) { return get_range_stats(b, out); }
 
 void mcf_rbatch_destroy(mcf_rbatch *b) { delete b; }
 int mcf_rbatch_solve(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_device<RaggedPlacement>(b, io_of(io), kFresh, "mcf_rbatch_solve"); }
@@ -1750,5 +1966,8 @@ int mcf_rbatch_validate_on_host(mcf_rbatch *b, const mcf_rbatch_check_io *io, mc
 }
 int mcf_rbatch_get_stats(mcf_rbatch *b, mcf_ubatch_stats *out) { return get_stats(b, out); }
 int mcf_rbatch_get_redata_stats(mcf_rbatch *b, mcf_ubatch_redata_stats *out) { return get_redata_stats(b, out); }
+int mcf_rbatch_cost_ranges(mcf_rbatch *b, const mcf_rbatch_range_io *io) { return ranges_on_device<RaggedPlacement>(b, range_io_of(io), "mcf_rbatch_cost_ranges"); }
+int mcf_rbatch_cost_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_range_io *io) { return ranges_on_host<RaggedPlacement>(b, range_io_of(io), "mcf_rbatch_cost_ranges_on_host"); }
+int mcf_rbatch_get_range_stats(mcf_rbatch *b, mcf_ubatch_range_stats *out) { return get_range_stats(b, out); }
 
 }  // extern "C"

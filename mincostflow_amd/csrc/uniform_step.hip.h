@@ -52,6 +52,7 @@ struct UniformCheck {
 // Instance i placed: its graph, its rows of the caller's arrays, its workspace, its output rows.  All the steps below see of a batch.
 struct InstanceView {
     int64_t i;                                           // its entry of the per-instance arrays (status[i], changed[i], ...)
+    int64_t arc_row;                                     // where its rows of the per-arc arrays begin, in elements
     int32_t n, m, supply_type, trace_cap;
     const int32_t *source, *target;                      // [m], validated at create
     const int32_t *inc_start, *inc;                      // the graph's incidence lists [n + 1], [2m]: uniform_validate only
@@ -124,6 +125,7 @@ MCF_HD inline InstanceView uniform_view(const UniformProblem &p, const UniformOu
     v.source = p.source; v.target = p.target;
     v.lower = uniform_row(p.lower, p.lower_stride, i); v.upper = uniform_row(p.upper, p.upper_stride, i);
     v.cost = uniform_row(p.cost, p.cost_stride, i); v.supply = uniform_row(p.supply, p.supply_stride, i);
+    v.arc_row = i * (int64_t)p.m;
     v.workspace = (uint64_t)i * p.stride; v.trace = (uint64_t)i * (uint64_t)p.trace_cap;
     v.home = slab ? slab + v.workspace : nullptr;
     if (o) {
@@ -145,7 +147,7 @@ MCF_HD inline InstanceView ragged_view(const RaggedProblem &r, const UniformOutp
     const RaggedGraph &g = r.graphs[r.graph_of[i]];
     const int64_t arcs = r.arc_row[i], nodes = r.node_row[i];
     InstanceView v{};
-    v.i = i; v.n = g.n; v.m = g.m; v.supply_type = r.supply_type; v.trace_cap = r.trace_cap;
+    v.i = i; v.arc_row = arcs; v.n = g.n; v.m = g.m; v.supply_type = r.supply_type; v.trace_cap = r.trace_cap;
     v.source = r.source + g.ends; v.target = r.target + g.ends;
     v.inc_start = r.inc_start + g.inc_start; v.inc = r.inc + g.inc;
     v.lower = r.lower ? r.lower + arcs : nullptr; v.upper = r.upper ? r.upper + arcs : nullptr;
@@ -341,21 +343,26 @@ MCF_HD inline void uniform_finish(const InstanceView &p, const UniformOutputs &o
     }
 }
 
+// ---- whether the last solve call of any kind left instance p with an optimal basis that is worth keeping: no entering arc, and no flow
+// on a root link (Infeasible) or on an artificial arc (Optimal with a surplus whose place depends on the pivot path).  What a warm start
+// with new costs demands (uniform_recost) and what makes the basis' cost ranges mean something (uniform_ranges of ranges_step.hip.h).
+MCF_HD inline bool uniform_kept_optimal(const InstanceView &p, const BatchSlot &slot, int lane, int lanes)
+{
+    if (slot.run != kBatchNoEntering) return false;
+    const int32_t all_arcs = slot.all_arcs;
+    const int64_t *const flow = (const int64_t *)(p.home + layout_of((uint32_t)all_arcs, (uint32_t)p.n + 1u).flow);
+    bool left = false;
+    for (int e = p.m + lane; e < all_arcs; e += lanes) left |= flow[e] != 0;
+    return !lanes_any(left);
+}
+
 // ---- prepare_resolve for instance i with the costs in p.  Warm as there: the last solve ended Optimal with no flow on an artificial arc.
 MCF_HD inline void uniform_recost(const InstanceView &p, const BatchSlot &tmpl, BatchSlot &slot, int lane, int lanes)
 {
     const int n = p.n, m = p.m;
     unsigned char *const home = p.home;
     const int32_t all_arcs = slot.all_arcs;
-    bool warm = slot.run == kBatchNoEntering;
-    if (warm) {
-        const Layout l = layout_of((uint32_t)all_arcs, (uint32_t)n + 1u);
-        const int64_t *const flow = (const int64_t *)(home + l.flow);
-        bool left = false;              // on a root link: Infeasible; on an artificial arc: Optimal with a surplus whose place depends on the pivot path
-        for (int e = m + lane; e < all_arcs; e += lanes) left |= flow[e] != 0;
-        warm = !lanes_any(left);
-    }
-    if (!warm) { uniform_begin(p, tmpl, slot, lane, lanes); return; }
+    if (!uniform_kept_optimal(p, slot, lane, lanes)) { uniform_begin(p, tmpl, slot, lane, lanes); return; }
     // core_recost: cost[0, m), art_cost as to_standard_form derives it, the artificial arcs; the root links keep 0
     const Layout l = layout_of((uint32_t)all_arcs, (uint32_t)n + 1u);
     int64_t *const cost_w = (int64_t *)(home + l.cost);

@@ -459,11 +459,41 @@ class RaggedResult(UniformResult):
         return self.potentials[int(self.node_rows[i]):int(self.node_rows[i + 1])]
 
 
+class UniformRanges:
+    """What UniformBatch.cost_ranges returns: one row per instance, numpy arrays or tensors.  ranged[i] = instance i's last solve call left
+    an optimal basis with every supply met exactly; for such an instance the kept basis stays optimal exactly while arc e's cost lies in
+    [cost - cost_down[i, e], cost + cost_up[i, e]], every other cost fixed (RANGE_INF = no limit on that side), and arc_state[i, e] is the
+    arc's place in the basis: 1 at its lower bound, 0 in the tree, -1 at its upper bound.  Rows of every other instance are zero.
+    cost_down and cost_up are None where they were not asked for."""
+    __slots__ = ("ranged", "arc_state", "cost_down", "cost_up")
+    FIELDS = (("ranged", "int32", ""), ("arc_state", "int8", "m"), ("cost_down", "int64", "m"), ("cost_up", "int64", "m"))
+    RANGE_INF = L.RANGE_INF
+
+    def __init__(self, **arrays):
+        for name, _, _ in self.FIELDS:
+            setattr(self, name, arrays.get(name))
+
+
+class RaggedRanges(UniformRanges):
+    """What RaggedBatch.cost_ranges returns: UniformRanges' fields with the per-arc rows FLAT -- instance i's arcs are
+    [arc_rows[i], arc_rows[i + 1]); arcs(i) returns (arc_state, cost_down, cost_up) of instance i as views."""
+    __slots__ = ("arc_rows",)
+
+    def __init__(self, arc_rows, **arrays):
+        super().__init__(**arrays)
+        self.arc_rows = arc_rows
+
+    def arcs(self, i: int):
+        lo, hi = int(self.arc_rows[i]), int(self.arc_rows[i + 1])
+        return tuple(None if a is None else a[lo:hi] for a in (self.arc_state, self.cost_down, self.cost_up))
+
+
 class _PlacedBatch:
     """What UniformBatch and RaggedBatch share: the checks of every array of a call, the calls and their results.  A subclass has the
     constructor (which sets _h, _last = None, count, device, record_trace) and says what differs:
       _PREFIX            the library's functions are <_PREFIX>_solve, _resolve, ...
       _IO, _CHECK_IO     the ctypes structs of a solve call and of a validation call
+      _RANGE_IO          the ctypes struct of a cost-ranges call; _ranges(out) makes its result
       _RESULT            the result class; _result(out) makes one
       _sizes()           the shapes of the outputs by UniformResult.FIELDS' dimension key
       _stride(...)       the expected shape of the array of a given name, its contiguity, and the stride it is passed with"""
@@ -603,6 +633,40 @@ class _PlacedBatch:
         """What the last resolve_data() / rerun_data_on_host() did: warm, cold, fallback and untouched instances, dual and primal pivots."""
         st = L.UBatchRedataStats(); L.check(self._fn("get_redata_stats")(self._h, C.byref(st))); return st.as_dict()
 
+    # ---- cost ranges of the kept basis
+    def _ranges(self, out):
+        return UniformRanges(**out)
+
+    def _cost_ranges(self, fn, tensors, costs):
+        if tensors is None:
+            tensors = self._last is not None and _is_tensor(self._last.status)
+        sizes = self._sizes()
+        io = self._RANGE_IO()
+        io.memory = L.MEM_DEVICE if tensors else L.MEM_HOST
+        out = {}
+        for name, dtype, dim in UniformRanges.FIELDS:
+            if not costs and name in ("cost_down", "cost_up"):
+                continue
+            out[name] = self._empty(sizes[dim], dtype, tensors)
+            setattr(io, name, out[name].data_ptr() if tensors else out[name].ctypes.data)
+        L.check(self._fn(fn)(self._h, C.byref(io)))
+        return self._ranges(out)
+
+    def cost_ranges(self, tensors=None, costs=True):
+        """Post-optimality cost ranging of the basis every instance's last solve call left, on the device: a UniformRanges /
+        RaggedRanges.  tensors: True = tensors on the handle's device (nothing that scales with the batch crosses the bus), False = numpy
+        arrays, None = like the last result.  costs=False leaves cost_down and cost_up out (ranged and arc_state only: no cycle is
+        walked).  The kept state is read, never changed: solve calls and this one mix in any order."""
+        return self._cost_ranges("cost_ranges", tensors, costs)
+
+    def cost_ranges_on_host(self, costs=True):
+        """Test hook: cost_ranges() with one lane on the CPU.  numpy only."""
+        return self._cost_ranges("cost_ranges_on_host", False, costs)
+
+    def range_stats(self) -> dict:
+        """What the last cost_ranges() / cost_ranges_on_host() did: instances, ranged ones, tiers, tree arcs ranged, cycle hops, kernel time."""
+        st = L.UBatchRangeStats(); L.check(self._fn("get_range_stats")(self._h, C.byref(st))); return st.as_dict()
+
     # ---- validation: the solution's rows where they lie
     SOLUTION_ROWS = (("status", "int32", None), ("total_cost", "int64", None), ("flows", "int64", "arc_count"), ("potentials", "int64", "node_count"))
 
@@ -651,7 +715,7 @@ class UniformBatch(_PlacedBatch):
     device (read and written in place: nothing that scales with the graph crosses the bus) -- never a mix; each array is [count, m]
     ([count, n] for supply) or [m] ([n]) for one row shared by all, int64, contiguous in its last dimension.  Results equal
     BatchSolver's for the same instances bit for bit.  run_on_host() / rerun_on_host() are test hooks (numpy only)."""
-    _PREFIX, _IO, _CHECK_IO, _RESULT = "mcf_ubatch", L.UBatchIo, L.UBatchCheckIo, UniformResult
+    _PREFIX, _IO, _CHECK_IO, _RESULT, _RANGE_IO = "mcf_ubatch", L.UBatchIo, L.UBatchCheckIo, UniformResult, L.UBatchRangeIo
     _ROW = {"cost": "arc_count", "lower": "arc_count", "upper": "arc_count", "flows": "arc_count", "supply": "node_count", "potentials": "node_count"}
 
     def __init__(self, node_count, source, target, count, rule=PivotRule.BlockSearch, pivot_limit=0, record_trace=0, device=0, pivots_per_launch=0,
@@ -697,7 +761,7 @@ class RaggedBatch(_PlacedBatch):
     and down) or flat torch tensors on the handle's device (read and written in place) -- never a mix; int64, contiguous.  Results equal
     BatchSolver's for the same instances bit for bit, and UniformBatch's where there is one graph.  run_on_host() / rerun_on_host() /
     validate_on_host() are test hooks (numpy only)."""
-    _PREFIX, _IO, _CHECK_IO, _RESULT = "mcf_rbatch", L.RBatchIo, L.RBatchCheckIo, RaggedResult
+    _PREFIX, _IO, _CHECK_IO, _RESULT, _RANGE_IO = "mcf_rbatch", L.RBatchIo, L.RBatchCheckIo, RaggedResult, L.RBatchRangeIo
     _ROW = {"cost": "arc_total", "lower": "arc_total", "upper": "arc_total", "flows": "arc_total", "supply": "node_total", "potentials": "node_total"}
 
     def __init__(self, graphs, graph_of=None, rule=PivotRule.BlockSearch, pivot_limit=0, record_trace=0, device=0, pivots_per_launch=0,
@@ -728,6 +792,9 @@ class RaggedBatch(_PlacedBatch):
 
     def _result(self, out):
         return RaggedResult(self.arc_rows, self.node_rows, **out)
+
+    def _ranges(self, out):
+        return RaggedRanges(self.arc_rows, **out)
 
     def _sizes(self):
         return {"": (self.count,), "m": (self.arc_total,), "n": (self.node_total,), "t": (self.count, self.record_trace)}
