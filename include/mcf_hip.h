@@ -1025,6 +1025,67 @@ MCF_API int mcf_rbatch_cost_ranges(mcf_rbatch *b, const mcf_rbatch_range_io *io)
 MCF_API int mcf_rbatch_cost_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_range_io *io);
 MCF_API int mcf_rbatch_get_range_stats(mcf_rbatch *b, mcf_ubatch_range_stats *out);
 
+/* ---- Starting a solve from a basis the caller supplies (DESIGN.md 3.14 "Start from a given basis").  The way back in for what
+ * mcf_*batch_cost_ranges writes out as arc_state: one state per arc of the caller's, MCF_STATE_LOWER / _TREE / _UPPER, from a solve of
+ * this handle or of another, of a mcf_ubatch or of a mcf_rbatch on the same graph, from today or from a file.  A uniform handle takes one
+ * row per instance or, with state_stride 0, ONE row for the whole batch: solve a representative instance once, start the others from
+ * its basis.  The call is a solve call like mcf_ubatch_solve: allowed on a handle that has never solved and at any later time, it reads
+ * all of io and replaces the kept state of every instance; afterwards mcf_*batch_resolve, _resolve_data, _cost_ranges and _validate go on
+ * from it as from any solve.  pivots and the trace describe this call, dual and primal pivots together; mcf_*batch_get_stats too.
+ * Per instance (csrc/uniform_step.hip.h, uniform_begin_from):
+ *   - the TREE arcs of its row must form a forest on the nodes.  It is walked depth first over the handle's incidence lists (arc ids
+ *     ascending per node), components by ascending lowest node, each rooted there and hung on the artificial root by an ARTIFICIAL arc
+ *     of cost (max |cost| + 1) * node_count -- not by the node's zero-cost root link, so that all potentials lie beyond that cost as they
+ *     do after a real solve and no root link becomes eligible.  The walk is bounded by count: no row can make it spin;
+ *   - non-tree arcs carry 0 or, at UPPER, their capacity; tree flows follow from conservation, potentials from the tree's costs;
+ *   - COLD BY RULE, which means a fresh mcf_*batch_solve of the instance bit for bit, trace included: a value outside {-1, 0, 1}; a TREE
+ *     arc that closes a cycle (a self loop and the second of two parallel TREE arcs are such); UPPER on an uncapacitated arc; supplies that
+ *     do not sum to zero; a component whose supplies do not balance by themselves; a basis that is neither of the two below; an upper
+ *     bound below its lower bound (MCF_INFEASIBLE with 0 pivots, as in a solve);
+ *   - a PRIMAL START where every tree arc's flow lies within its bounds: primal pivots from there -- none at all where the basis is
+ *     optimal for the data given, as a basis exported after an Optimal solve without artificial flow is for that solve's data;
+ *   - else a DUAL START where every non-tree arc's reduced cost has the sign of its state: dual pivots first, as in
+ *     mcf_ubatch_resolve_data, then the primal ones;
+ *   - an accepted start that does not end with no entering arc and no flow on a root link or an artificial arc is set up again and solved
+ *     cold in the same call (a fallback); the pivot limit is the exception and stays MCF_NOT_SOLVED with zero rows.
+ * So every answer is a fresh solve's: status and total cost under the limit stated at mcf_batch_resolve, flows and potentials an optimal
+ * pair, not necessarily the fresh solve's.  Refusals, MCF_ERR_INVALID with a message: a null argument or a null arc_state, a basis
+ * whose `memory` differs from io->memory, a negative stride, a non-null io->changed (an unmarked instance of a fresh handle would have no
+ * state), a hook called with MCF_MEM_DEVICE.  MCF_ERR_NO_DEVICE without a GPU leaves the handle as it was.  With MCF_MEM_DEVICE nothing
+ * that scales with the arcs, the nodes or the instances' rows crosses the bus in a call: the slot templates and the ids of every round
+ * go up, the slots come down (after the start launch, after every round, after the settle launch); the incidence lists go up once per
+ * handle with the topology.  mcf_batch_* has no such call, for the reason given at mcf_ubatch_resolve_data: it sets its instances up
+ * on the host. */
+typedef struct mcf_ubatch_basis_io {
+    int32_t memory;               /* MCF_MEM_HOST / MCF_MEM_DEVICE: must equal io->memory */
+    int32_t reserved;
+    const int8_t *arc_state;      /* [arc_count] per instance */
+    int64_t state_stride;         /* elements between instances' rows; 0 = one row for all */
+} mcf_ubatch_basis_io;
+typedef struct mcf_rbatch_basis_io {
+    int32_t memory;
+    int32_t reserved;
+    const int8_t *arc_state;      /* [arc_row[count]]: instance i's arcs at [arc_row[i], arc_row[i + 1]) */
+} mcf_rbatch_basis_io;
+typedef struct mcf_ubatch_start_stats { /* of the last mcf_*batch_solve_from / _run_from_on_host (all zero before one) */
+    int64_t primal_starts;        /* accepted with every tree flow within its bounds (fallback_instances may be among them) */
+    int64_t dual_starts;          /* accepted with violated tree flows and dual-feasible reduced costs (likewise) */
+    int64_t cold_instances;       /* cold by rule */
+    int64_t fallback_instances;   /* accepted starts that did not stand and were solved again cold in the same call */
+    int64_t dual_pivots;          /* of all dual starts, the given-up ones included */
+    int64_t primal_pivots;        /* everything else: primal starts, cold solves, fallbacks, what a dual start needed afterwards */
+    int64_t launches;             /* batch kernel launches */
+    int64_t bytes_up, bytes_down; /* as mcf_ubatch_stats */
+    double kernel_ns, host_ns, begin_ns, finish_ns;    /* as mcf_ubatch_stats; begin_ns is round the start launch */
+} mcf_ubatch_start_stats;
+MCF_API int mcf_ubatch_solve_from(mcf_ubatch *b, const mcf_ubatch_io *io, const mcf_ubatch_basis_io *basis);
+/* TEST HOOK: the same steps (uniform_begin_from, batch_dual_run, batch_run) with one lane on the CPU, MCF_MEM_HOST only. */
+MCF_API int mcf_ubatch_run_from_on_host(mcf_ubatch *b, const mcf_ubatch_io *io, const mcf_ubatch_basis_io *basis);
+MCF_API int mcf_ubatch_get_start_stats(mcf_ubatch *b, mcf_ubatch_start_stats *out);
+MCF_API int mcf_rbatch_solve_from(mcf_rbatch *b, const mcf_rbatch_io *io, const mcf_rbatch_basis_io *basis);
+MCF_API int mcf_rbatch_run_from_on_host(mcf_rbatch *b, const mcf_rbatch_io *io, const mcf_rbatch_basis_io *basis);
+MCF_API int mcf_rbatch_get_start_stats(mcf_rbatch *b, mcf_ubatch_start_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

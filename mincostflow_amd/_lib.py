@@ -239,6 +239,26 @@ class UBatchRangeStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class UBatchBasisIo(C.Structure):
+    """mcf_ubatch_basis_io"""
+    _fields_ = [("memory", C.c_int32), ("reserved", C.c_int32), ("arc_state", C.c_void_p), ("state_stride", C.c_int64)]
+
+
+class RBatchBasisIo(C.Structure):
+    """mcf_rbatch_basis_io"""
+    _fields_ = [("memory", C.c_int32), ("reserved", C.c_int32), ("arc_state", C.c_void_p)]
+
+
+class UBatchStartStats(C.Structure):
+    """mcf_ubatch_start_stats"""
+    _fields_ = [(name, C.c_int64) for name in ("primal_starts", "dual_starts", "cold_instances", "fallback_instances", "dual_pivots", "primal_pivots",
+                                               "launches", "bytes_up", "bytes_down")] + \
+               [(name, C.c_double) for name in ("kernel_ns", "host_ns", "begin_ns", "finish_ns")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class ProblemStruct(C.Structure):
     _fields_ = [("node_count", C.c_int32), ("arc_count", C.c_int32), ("source", C.POINTER(C.c_int32)),
                 ("target", C.POINTER(C.c_int32)), ("lower", C.POINTER(C.c_int64)), ("upper", C.POINTER(C.c_int64)),
@@ -395,6 +415,9 @@ SIGNATURES = {
     "mcf_ubatch_cost_ranges": (C.c_int, [C.c_void_p, _P(UBatchRangeIo)]),
     "mcf_ubatch_cost_ranges_on_host": (C.c_int, [C.c_void_p, _P(UBatchRangeIo)]),
     "mcf_ubatch_get_range_stats": (C.c_int, [C.c_void_p, _P(UBatchRangeStats)]),
+    "mcf_ubatch_solve_from": (C.c_int, [C.c_void_p, _P(UBatchIo), _P(UBatchBasisIo)]),
+    "mcf_ubatch_run_from_on_host": (C.c_int, [C.c_void_p, _P(UBatchIo), _P(UBatchBasisIo)]),
+    "mcf_ubatch_get_start_stats": (C.c_int, [C.c_void_p, _P(UBatchStartStats)]),
     "mcf_rbatch_create": (C.c_int, [_P(C.c_void_p), _P(RBatchDesc)]),
     "mcf_rbatch_destroy": (None, [C.c_void_p]),
     "mcf_rbatch_get_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -411,6 +434,9 @@ SIGNATURES = {
     "mcf_rbatch_cost_ranges": (C.c_int, [C.c_void_p, _P(RBatchRangeIo)]),
     "mcf_rbatch_cost_ranges_on_host": (C.c_int, [C.c_void_p, _P(RBatchRangeIo)]),
     "mcf_rbatch_get_range_stats": (C.c_int, [C.c_void_p, _P(UBatchRangeStats)]),
+    "mcf_rbatch_solve_from": (C.c_int, [C.c_void_p, _P(RBatchIo), _P(RBatchBasisIo)]),
+    "mcf_rbatch_run_from_on_host": (C.c_int, [C.c_void_p, _P(RBatchIo), _P(RBatchBasisIo)]),
+    "mcf_rbatch_get_start_stats": (C.c_int, [C.c_void_p, _P(UBatchStartStats)]),
     "mcf_problem_free": (None, [_P(ProblemStruct)]),
     "mcf_gen_netgen_like": (C.c_int, [_P(ProblemStruct), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64]),

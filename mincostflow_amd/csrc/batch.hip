@@ -14,6 +14,8 @@
 //     batch_step.hip.h in front of the primal ones, between a re-data launch and a settle launch (uniform_step.hip.h).
 //   * cost ranges of the kept basis (mcf_ubatch_cost_ranges, mcf_rbatch_cost_ranges): the ranges kernels run ranges_step.hip.h on the
 //     workspaces as the last solve call left them, and write nothing there.
+//   * solves that start from a basis the caller supplies (mcf_ubatch_solve_from, mcf_rbatch_solve_from): the start kernels run
+//     uniform_begin_from in place of the set-up launch; rounds and settle launch are those of a re-solve with new data.
 // Device code does no bounds checks: mcf_batch_add validates every end point (core_create), and every index the kernel follows after
 // that was written by start_basis or by the pivot itself.
 #include <hip/hip_runtime.h>
@@ -158,6 +160,15 @@ __global__ __launch_bounds__(kBatchThreads) void uniform_redata_kernel(mcf::Unif
     if (p.changed && !p.changed[i]) return;
     mcf::uniform_redata(mcf::uniform_view(p, nullptr, i, slab), *tmpl, slots[i], (int)threadIdx.x, kBatchThreads);
 }
+// mcf_ubatch_solve_from: the view as the re-data kernel forms it, with the handle's incidence lists (the validation's) for the walk
+__global__ __launch_bounds__(kBatchThreads) void uniform_start_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab,
+                                                                      const int32_t *inc_start, const int32_t *inc)
+{
+    const int64_t i = (int64_t)blockIdx.x;
+    mcf::InstanceView v = mcf::uniform_view(p, nullptr, i, slab);
+    v.inc_start = inc_start; v.inc = inc;
+    mcf::uniform_begin_from(v, *tmpl, slots[i], (int)threadIdx.x, kBatchThreads);
+}
 __global__ __launch_bounds__(kBatchThreads) void uniform_settle_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
 {
     const int64_t i = (int64_t)blockIdx.x;
@@ -204,6 +215,13 @@ __global__ __launch_bounds__(kBatchThreads) void ragged_redata_kernel(mcf::Ragge
     int32_t t;
     const mcf::InstanceView v = mcf::ragged_view(r, nullptr, i, slab, &t);
     mcf::uniform_redata(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
+}
+__global__ __launch_bounds__(kBatchThreads) void ragged_start_kernel(mcf::RaggedProblem r, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
+{
+    const int64_t i = (int64_t)blockIdx.x;
+    int32_t t;
+    const mcf::InstanceView v = mcf::ragged_view(r, nullptr, i, slab, &t);
+    mcf::uniform_begin_from(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
 }
 __global__ __launch_bounds__(kBatchThreads) void ragged_settle_kernel(mcf::RaggedProblem r, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
 {
@@ -971,6 +989,7 @@ struct PlacedBatch {
     enum Where { kNowhere, kOnHost, kOnDevice } where = kNowhere;      // who holds the state the last solve of either kind left
     mcf_ubatch_stats stats{};
     mcf_ubatch_redata_stats redata_stats{};     // of the last re-solve with new supplies or bounds
+    mcf_ubatch_start_stats start_stats{};       // of the last solve from a given basis
     int32_t supply_type = -1;           // of the last solve call of any kind: a re-solve with new data must name the same
     int lds_max = 0;
     DeviceBuffers dev;                  // slab, slots, ids, traces
@@ -1039,6 +1058,10 @@ struct BatchIo {
     const int64_t *lower, *upper, *cost, *supply;
     int64_t lower_stride, upper_stride, cost_stride, supply_stride;     // the uniform structs'; 0 from a ragged one
     const uint8_t *changed;             // re-solves only
+    bool basis_given;                   // a solve from a given basis: the caller's basis io was not null ...
+    int32_t basis_memory;               // ... and what it says
+    const int8_t *start_state;
+    int64_t start_stride;               // the uniform struct's; 0 from a ragged one
     int32_t *status;                    // the solution: a solve call writes it; a validation call only reads it, and has no pivots or trace
     int64_t *pivots, *total_cost, *flows, *potentials;
     int32_t *trace;
@@ -1081,6 +1104,16 @@ BatchIo with_strides(BatchIo x, const Io *io)
 }
 BatchIo io_of(const mcf_ubatch_io *io) { return with_strides(solve_io(io), io); }
 BatchIo io_of(const mcf_rbatch_io *io) { return solve_io(io); }
+BatchIo with_basis(BatchIo x, const mcf_ubatch_basis_io *basis)
+{
+    if (basis) { x.basis_given = true; x.basis_memory = basis->memory; x.start_state = basis->arc_state; x.start_stride = basis->state_stride; }
+    return x;
+}
+BatchIo with_basis(BatchIo x, const mcf_rbatch_basis_io *basis)
+{
+    if (basis) { x.basis_given = true; x.basis_memory = basis->memory; x.start_state = basis->arc_state; }
+    return x;
+}
 BatchIo io_of(const mcf_ubatch_check_io *io) { return with_strides(check_io(io), io); }
 BatchIo io_of(const mcf_rbatch_check_io *io) { return check_io(io); }
 
@@ -1105,7 +1138,7 @@ int solution_missing(const char *what)
 
 // the byte lengths of the caller's arrays that go by arcs and nodes; everything else is one entry (or trace_capacity, or MCF_VAL_KINDS) per instance
 struct RowBytes {
-    size_t lower, upper, cost, supply, flows, potentials;
+    size_t lower, upper, cost, supply, flows, potentials, state;       // state: the rows of a given basis, one byte per arc
 };
 size_t input_elements(size_t count, int64_t stride, size_t length) { return count ? (count - 1) * (size_t)stride + length : 0; }
 
@@ -1135,6 +1168,10 @@ struct UniformPlacement {
     static constexpr auto recost_kernel = uniform_recost_kernel;
     static constexpr auto redata_kernel = uniform_redata_kernel;
     static constexpr auto settle_kernel = uniform_settle_kernel;
+    static void launch_start(const Handle *b, const Problem &p, BatchSlot *slots, unsigned char *slab)
+    {
+        hipLaunchKernelGGL(uniform_start_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, slots, slab, b->d_inc_start, b->d_inc);
+    }
     static constexpr auto finish_kernel = uniform_finish_kernel;
     static constexpr auto ranges_kernel_in_lds = uniform_ranges_kernel<true>;
     static void launch_validate(const Handle *b, const Problem &p, const mcf::UniformCheck &c, const BatchIo &io)
@@ -1156,11 +1193,11 @@ struct UniformPlacement {
     {
         const size_t count = (size_t)b->d.count, n = (size_t)b->d.node_count, m = (size_t)b->d.arc_count;
         return RowBytes{8 * input_elements(count, io.lower_stride, m), 8 * input_elements(count, io.upper_stride, m), 8 * input_elements(count, io.cost_stride, m),
-                        8 * input_elements(count, io.supply_stride, n), 8 * count * m, 8 * count * n};
+                        8 * input_elements(count, io.supply_stride, n), 8 * count * m, 8 * count * n, input_elements(count, io.start_stride, m)};
     }
     static int check_rows(const Handle *b, const BatchIo &io, const char *what)
     {
-        if (io.lower_stride < 0 || io.upper_stride < 0 || io.cost_stride < 0 || io.supply_stride < 0) return mcf::fail(MCF_ERR_INVALID, "%s: negative stride", what);
+        if (io.lower_stride < 0 || io.upper_stride < 0 || io.cost_stride < 0 || io.supply_stride < 0 || io.start_stride < 0) return mcf::fail(MCF_ERR_INVALID, "%s: negative stride", what);
         if (io.check && b->d.count > 0 && (!io.status || !io.total_cost || !io.flows || !io.potentials)) return solution_missing(what);     // an empty tensor has no address
         return MCF_OK;
     }
@@ -1187,12 +1224,15 @@ struct UniformPlacement {
         p.lower_stride = io.lower_stride; p.upper_stride = io.upper_stride; p.cost_stride = io.cost_stride; p.supply_stride = io.supply_stride;
         p.stride = b->stride;
         p.changed = io.changed;
+        p.start_state = io.start_state; p.start_stride = io.start_stride;
         return p;
     }
     static mcf::InstanceView view(const Handle *b, const Problem &p, const mcf::UniformOutputs &o, int64_t i, unsigned char *slab, const BatchSlot **tmpl)
     {
         *tmpl = &b->tmpl;
-        return mcf::uniform_view(p, &o, i, slab);
+        mcf::InstanceView v = mcf::uniform_view(p, &o, i, slab);
+        v.inc_start = b->inc_start.data(); v.inc = b->inc.data();             // the host's lists: uniform_begin_from walks them
+        return v;
     }
     static mcf::InstanceView check_view(const Handle *b, const Problem &p, const BatchIo &io, int64_t i)
     {
@@ -1208,6 +1248,10 @@ struct RaggedPlacement {
     static constexpr auto recost_kernel = ragged_recost_kernel;
     static constexpr auto redata_kernel = ragged_redata_kernel;
     static constexpr auto settle_kernel = ragged_settle_kernel;
+    static void launch_start(const Handle *b, const Problem &r, BatchSlot *slots, unsigned char *slab)
+    {
+        hipLaunchKernelGGL(ragged_start_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, r, b->d_tmpl, slots, slab);
+    }
     static constexpr auto finish_kernel = ragged_finish_kernel;
     static constexpr auto ranges_kernel_in_lds = ragged_ranges_kernel<true>;
     static void launch_validate(const Handle *b, const Problem &r, const mcf::UniformCheck &c, const BatchIo &io)
@@ -1228,7 +1272,7 @@ struct RaggedPlacement {
     static RowBytes row_bytes(const Handle *b, const BatchIo &)
     {
         const size_t arcs = 8 * (size_t)b->arc_row[(size_t)b->d.count], nodes = 8 * (size_t)b->node_row[(size_t)b->d.count];
-        return RowBytes{arcs, arcs, arcs, nodes, arcs, nodes};
+        return RowBytes{arcs, arcs, arcs, nodes, arcs, nodes, arcs / 8};
     }
     static int check_rows(const Handle *b, const BatchIo &io, const char *what)
     {
@@ -1273,6 +1317,7 @@ struct RaggedPlacement {
         r.supply_type = io.supply_type; r.trace_cap = b->d.trace_capacity;
         r.lower = io.lower; r.upper = io.upper; r.cost = io.cost; r.supply = io.supply;
         r.changed = io.changed;
+        r.start_state = io.start_state;
         return r;
     }
     static mcf::InstanceView view(const Handle *b, const Problem &r, const mcf::UniformOutputs &o, int64_t i, unsigned char *slab, const BatchSlot **tmpl)
@@ -1287,13 +1332,16 @@ struct RaggedPlacement {
 
 // what every call refuses before it touches the handle.  Solve calls take MCF_SUPPLY_GEQ / _LEQ, validation calls MCF_SUPPLY_EQ too
 // a solve call: fresh, a re-solve with new costs, or a re-solve with new supplies and bounds
-enum Call { kFresh, kRecost, kRedata };
+// or a solve that starts from a basis the caller supplies
+enum Call { kFresh, kRecost, kRedata, kStart };
+inline bool is_resolve(Call call) { return call == kRecost || call == kRedata; }        // goes on from the state the last call left
+inline bool has_attempts(Call call) { return call == kRedata || call == kStart; }       // dual phase, settle launch, fallback
 
 template <class P>
 int check_call(const typename P::Handle *b, const BatchIo &io, const char *what, bool host_only, Call call)
 {
-    const bool resolve = call != kFresh;
-    if (!b || !io.given) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
+    const bool resolve = is_resolve(call);
+    if (!b || !io.given || (call == kStart && !io.basis_given)) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
     if (io.memory != MCF_MEM_HOST && io.memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io.memory);
     if (host_only && io.memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
     if (!io.check) {
@@ -1302,6 +1350,11 @@ int check_call(const typename P::Handle *b, const BatchIo &io, const char *what,
         return mcf::fail(MCF_ERR_INVALID, "%s: supply type %d", what, io.supply_type);
     }
     if (const int rc = P::check_rows(b, io, what)) return rc;
+    if (call == kStart) {
+        if (io.basis_memory != io.memory) return mcf::fail(MCF_ERR_INVALID, "%s: the basis lies in memory kind %d, the problem in %d: one call, one kind", what, io.basis_memory, io.memory);
+        if (!io.start_state && P::arc_rows(b)) return mcf::fail(MCF_ERR_INVALID, "%s: null arc_state", what);
+        if (io.changed) return mcf::fail(MCF_ERR_INVALID, "%s: a solve from a given basis takes no `changed` mask (an unmarked instance of a fresh handle would have no state)", what);
+    }
     if (resolve && b->where == PlacedBatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
     if (call == kRedata && io.supply_type != b->supply_type)
         return mcf::fail(MCF_ERR_INVALID, "%s: supply type %d, the last solve's was %d (the kept basis belongs to that one)", what, io.supply_type, b->supply_type);
@@ -1395,6 +1448,7 @@ int stage_up(typename P::Handle *b, BatchIo *io, Staged *st, int64_t *bytes_up)
                             {(void **)&io->cost, rows.cost, true, false},
                             {(void **)&io->supply, rows.supply, true, false},
                             {(void **)&io->changed, count, true, false},
+                            {(void **)&io->start_state, rows.state, true, false},
                             {(void **)&io->status, 4 * count, solution_up, solution_down},
                             {(void **)&io->pivots, 8 * count, solution_up, solution_down},
                             {(void **)&io->total_cost, 8 * count, solution_up, solution_down},
@@ -1435,10 +1489,12 @@ int stage_down(PlacedBatch *b, const Staged &st, int64_t *bytes_down)
 // cold is a fallback, and the pivots of its attempt stay counted.
 struct RedataCount {
     mcf_ubatch_redata_stats st{};
+    int64_t primal_starts = 0;             // a solve from a given basis only: accepted with nothing violated (uniform_begin_from)
     void begun(const BatchSlot &s, bool marked)
     {
         if (!marked) st.untouched_instances++;
         else if (s.run == mcf::kBatchDual) st.warm_instances++;
+        else if (s.run == mcf::kBatchRunning && s.reprice == 2) primal_starts++;
         else st.cold_instances++;
     }
     void ran(const BatchSlot &s)           // a slot as the launches left it: staged_out = its dual pivots
@@ -1451,6 +1507,18 @@ struct RedataCount {
         st.launches = of_call.launches; st.bytes_up = of_call.bytes_up; st.bytes_down = of_call.bytes_down;
         st.kernel_ns = of_call.kernel_ns; st.host_ns = of_call.host_ns; st.begin_ns = of_call.begin_ns; st.finish_ns = of_call.finish_ns;
     }
+    mcf_ubatch_start_stats of_start() const        // after finish()
+    {
+        return mcf_ubatch_start_stats{primal_starts, st.warm_instances, st.cold_instances, st.fallback_instances, st.dual_pivots, st.primal_pivots,
+                                      st.launches, st.bytes_up, st.bytes_down, st.kernel_ns, st.host_ns, st.begin_ns, st.finish_ns};
+    }
+    // the call's statistics into the handle, by its kind
+    void record(Call call, PlacedBatch *b)
+    {
+        if (!has_attempts(call)) return;
+        finish(b->stats);
+        if (call == kRedata) b->redata_stats = st; else b->start_stats = of_start();
+    }
 };
 
 // mcf_*batch_solve, _resolve and _resolve_data: set-up (or re-cost, or re-data) launch, the launch loop of mcf_batch_solve, finish launch.
@@ -1459,7 +1527,7 @@ struct RedataCount {
 template <class P>
 int solve_on_device(typename P::Handle *b, BatchIo io, Call call, const char *what)
 {
-    const bool resolve = call != kFresh;
+    const bool resolve = is_resolve(call);
     if (const int rc = check_call<P>(b, io, what, false, call)) return rc;
     if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
     const double t_start = mcf::now_ns();
@@ -1467,13 +1535,14 @@ int solve_on_device(typename P::Handle *b, BatchIo io, Call call, const char *wh
     if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
     const size_t count = (size_t)b->d.count;
     LaunchPlan plan = P::plan(b);
-    plan.dual = call == kRedata;
+    plan.dual = has_attempts(call);
     b->stats = mcf_ubatch_stats{};
     b->stats.instances = (int64_t)count;
     for (size_t i = 0; i < count; ++i)
         (class_of(b->lds_max, plan.bytes((int32_t)i)) != kClasses - 1 ? b->stats.lds_instances : b->stats.global_instances)++;
     b->stats.workspace_bytes = (int64_t)P::slab_bytes(b);
     if (call == kRedata) b->redata_stats = mcf_ubatch_redata_stats{};
+    if (call == kStart) b->start_stats = mcf_ubatch_start_stats{};
     if (!count) { b->where = PlacedBatch::kOnDevice; b->supply_type = io.supply_type; b->stats.host_ns = mcf::now_ns() - t_start; return MCF_OK; }
     if (const int rc = ensure_device_buffers<P>(b)) return rc;
     DeviceBuffers &dev = b->dev;
@@ -1496,8 +1565,12 @@ int solve_on_device(typename P::Handle *b, BatchIo io, Call call, const char *wh
     const double t_begin = mcf::now_ns();
     HIP_TRY(hipMemcpy(b->d_tmpl, P::templates(b), P::template_count(b) * sizeof(BatchSlot), hipMemcpyHostToDevice));
     b->stats.bytes_up += (int64_t)(P::template_count(b) * sizeof(BatchSlot));
-    const auto begin_kernel = call == kFresh ? P::begin_kernel : call == kRecost ? P::recost_kernel : P::redata_kernel;
-    hipLaunchKernelGGL(begin_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
+    if (call == kStart) {
+        P::launch_start(b, p, dev.slots, dev.slab);
+    } else {
+        const auto begin_kernel = call == kFresh ? P::begin_kernel : call == kRecost ? P::recost_kernel : P::redata_kernel;
+        hipLaunchKernelGGL(begin_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
+    }
     HIP_TRY(hipGetLastError());
     b->where = PlacedBatch::kOnDevice;
     b->supply_type = io.supply_type;
@@ -1509,13 +1582,13 @@ int solve_on_device(typename P::Handle *b, BatchIo io, Call call, const char *wh
     std::vector<int32_t> run, attempts;
     RedataCount redata;
     for (size_t i = 0; i < count; ++i) {
-        if (call == kRedata) redata.begun(slots[i], marked.empty() || marked[i]);
-        if (slots[i].run == mcf::kBatchDual) attempts.push_back((int32_t)i);
+        if (has_attempts(call)) redata.begun(slots[i], marked.empty() || marked[i]);
+        if (slots[i].reprice == 2) attempts.push_back((int32_t)i);            // a warm attempt or an accepted start: kBatchDual, or kBatchRunning from a primal start
         if (slots[i].run == mcf::kBatchRunning || slots[i].run == mcf::kBatchDual) run.push_back((int32_t)i);   // a re-solve's unmarked instances ended their last solve: not running
     }
     LaunchTotals t;
     if (const int rc = run_launches(plan, slots, run, &t)) return rc;
-    if (call == kRedata)
+    if (has_attempts(call))
         for (int32_t i : run) redata.ran(slots[(size_t)i]);
     if (!attempts.empty()) {
         // the warm attempts are judged where they lie; the ones that did not stand have been set up again and run like a fresh solve's
@@ -1544,7 +1617,7 @@ int solve_on_device(typename P::Handle *b, BatchIo io, Call call, const char *wh
     b->stats.finish_ns = mcf::now_ns() - t_finish;
     if (const int rc = stage_down(b, staged, &b->stats.bytes_down)) return rc;
     b->stats.host_ns = mcf::now_ns() - t_start - t.kernel_ns;
-    if (call == kRedata) { redata.finish(b->stats); b->redata_stats = redata.st; }
+    redata.record(call, b);
     return MCF_OK;
 }
 
@@ -1567,7 +1640,7 @@ void run_slot_on_host(BatchSlot &slot, unsigned char *home, int32_t *traces)
 template <class P>
 int solve_on_host(typename P::Handle *b, BatchIo io, Call call, const char *what)
 {
-    const bool resolve = call != kFresh;
+    const bool resolve = is_resolve(call);
     if (const int rc = check_call<P>(b, io, what, true, call)) return rc;
     const double t_start = mcf::now_ns();
     const size_t count = (size_t)b->d.count;
@@ -1590,7 +1663,8 @@ int solve_on_host(typename P::Handle *b, BatchIo io, Call call, const char *what
         const mcf::InstanceView v = P::view(b, p, o, (int64_t)i, b->h_slab.data(), &tmpl);
         if (call == kFresh) mcf::uniform_begin(v, *tmpl, slot, 0, 1);
         else if (call == kRecost) mcf::uniform_recost(v, *tmpl, slot, 0, 1);
-        else mcf::uniform_redata(v, *tmpl, slot, 0, 1);
+        else if (call == kRedata) mcf::uniform_redata(v, *tmpl, slot, 0, 1);
+        else mcf::uniform_begin_from(v, *tmpl, slot, 0, 1);
         redata.begun(slot, true);
         const bool ran = slot.run == mcf::kBatchRunning || slot.run == mcf::kBatchDual;
         if (ran) {
@@ -1611,7 +1685,7 @@ int solve_on_host(typename P::Handle *b, BatchIo io, Call call, const char *what
     b->where = PlacedBatch::kOnHost;
     b->supply_type = io.supply_type;
     b->stats.host_ns = mcf::now_ns() - t_start;
-    if (call == kRedata) { redata.finish(b->stats); b->redata_stats = redata.st; }
+    redata.record(call, b);
     return MCF_OK;
 }
 
@@ -1813,6 +1887,12 @@ int get_stats(const PlacedBatch *b, mcf_ubatch_stats *out)
     *out = b->stats;
     return MCF_OK;
 }
+int get_start_stats(const PlacedBatch *b, mcf_ubatch_start_stats *out)
+{
+    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
+    *out = b->start_stats;
+    return MCF_OK;
+}
 int get_redata_stats(const PlacedBatch *b, mcf_ubatch_redata_stats *out)
 {
     if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
@@ -1945,6 +2025,15 @@ int mcf_ubatch_validate_on_host(mcf_ubatch *b, const mcf_ubatch_check_io *io, mc
 }
 int mcf_ubatch_get_stats(mcf_ubatch *b, mcf_ubatch_stats *out) { return get_stats(b, out); }
 int mcf_ubatch_get_redata_stats(mcf_ubatch *b, mcf_ubatch_redata_stats *out) { return get_redata_stats(b, out); }
+int mcf_ubatch_solve_from(mcf_ubatch *b, const mcf_ubatch_io *io, const mcf_ubatch_basis_io *basis)
+{
+    return solve_on_device<UniformPlacement>(b, with_basis(io_of(io), basis), kStart, "mcf_ubatch_solve_from");
+}
+int mcf_ubatch_run_from_on_host(mcf_ubatch *b, const mcf_ubatch_io *io, const mcf_ubatch_basis_io *basis)
+{
+    return solve_on_host<UniformPlacement>(b, with_basis(io_of(io), basis), kStart, "mcf_ubatch_run_from_on_host");
+}
+int mcf_ubatch_get_start_stats(mcf_ubatch *b, mcf_ubatch_start_stats *out) { return get_start_stats(b, out); }
 int mcf_ubatch_cost_ranges(mcf_ubatch *b, const mcf_ubatch_range_io *io) { return ranges_on_device<UniformPlacement>(b, range_io_of(io), "mcf_ubatch_cost_ranges"); }
 int mcf_ubatch_cost_ranges_on_host(mcf_ubatch *b, const mcf_ubatch_range_io *io) { return ranges_on_host<UniformPlacement>(b, range_io_of(io), "mcf_ubatch_cost_ranges_on_host"); }
 int mcf_ubatch_get_range_stats(mcf_ubatch *b, mcf_ubatch_range_stats *out) { return get_range_stats(b, out); }
@@ -1966,6 +2055,15 @@ int mcf_rbatch_validate_on_host(mcf_rbatch *b, const mcf_rbatch_check_io *io, mc
 }
 int mcf_rbatch_get_stats(mcf_rbatch *b, mcf_ubatch_stats *out) { return get_stats(b, out); }
 int mcf_rbatch_get_redata_stats(mcf_rbatch *b, mcf_ubatch_redata_stats *out) { return get_redata_stats(b, out); }
+int mcf_rbatch_solve_from(mcf_rbatch *b, const mcf_rbatch_io *io, const mcf_rbatch_basis_io *basis)
+{
+    return solve_on_device<RaggedPlacement>(b, with_basis(io_of(io), basis), kStart, "mcf_rbatch_solve_from");
+}
+int mcf_rbatch_run_from_on_host(mcf_rbatch *b, const mcf_rbatch_io *io, const mcf_rbatch_basis_io *basis)
+{
+    return solve_on_host<RaggedPlacement>(b, with_basis(io_of(io), basis), kStart, "mcf_rbatch_run_from_on_host");
+}
+int mcf_rbatch_get_start_stats(mcf_rbatch *b, mcf_ubatch_start_stats *out) { return get_start_stats(b, out); }
 int mcf_rbatch_cost_ranges(mcf_rbatch *b, const mcf_rbatch_range_io *io) { return ranges_on_device<RaggedPlacement>(b, range_io_of(io), "mcf_rbatch_cost_ranges"); }
 int mcf_rbatch_cost_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_range_io *io) { return ranges_on_host<RaggedPlacement>(b, range_io_of(io), "mcf_rbatch_cost_ranges_on_host"); }
 int mcf_rbatch_get_range_stats(mcf_rbatch *b, mcf_ubatch_range_stats *out) { return get_range_stats(b, out); }

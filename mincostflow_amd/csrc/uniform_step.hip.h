@@ -7,6 +7,8 @@
 //   uniform_recost  a re-solve with new costs: from the kept basis where the last solve ended Optimal, else uniform_begin again.
 //   uniform_redata  a re-solve with new supplies and bounds: the kept basis with its tree flows recomputed, for batch_dual_run, else
 //                   uniform_begin again; uniform_redata_settle judges the warm attempt and starts it again cold where it did not hold.
+//   uniform_begin_from  a solve that starts from a basis the caller supplies, one state per arc: the forest of its TREE arcs is walked,
+//                   hung on the root, given flows and potentials and classed; anything that is no basis: uniform_begin.
 // The pivots between them are batch_run on the workspace these steps leave, unchanged.
 // A fourth step stands apart from the solve: uniform_validate checks a solution in the caller's rows (mcf_ubatch_validate).
 // Problem data are read straight from the caller's arrays, results are written straight into the caller's rows.  The steps never learn
@@ -33,6 +35,8 @@ struct UniformProblem {
     int64_t lower_stride, upper_stride, cost_stride, supply_stride;     // elements between instances, 0 = shared
     uint64_t stride;                                     // bytes between workspaces: layout_of(m + 2n, n + 1).bytes
     const uint8_t *changed;                              // re-solve: [count], null = all
+    const int8_t *start_state;                           // uniform_begin_from: the caller's basis, [m] per instance ...
+    int64_t start_stride;                                // ... elements between instances, 0 = one row for all
 };
 struct UniformOutputs {                                  // any may be null
     int32_t *status;
@@ -55,7 +59,8 @@ struct InstanceView {
     int64_t arc_row;                                     // where its rows of the per-arc arrays begin, in elements
     int32_t n, m, supply_type, trace_cap;
     const int32_t *source, *target;                      // [m], validated at create
-    const int32_t *inc_start, *inc;                      // the graph's incidence lists [n + 1], [2m]: uniform_validate only
+    const int32_t *inc_start, *inc;                      // the graph's incidence lists [n + 1], [2m]: uniform_validate and uniform_begin_from
+    const int8_t *start_state;                           // uniform_begin_from: the instance's row of arc states [m]
     const int64_t *lower, *upper, *cost, *supply;        // the instance's rows; null: 0 / uncapacitated / 0 / 0
     unsigned char *home;                                 // its workspace = slab + workspace
     uint64_t workspace, trace;                           // what its slot says of where workspace and trace lie
@@ -78,6 +83,7 @@ struct RaggedProblem {
     const int32_t *source, *target, *inc_start, *inc;    // every graph's, concatenated
     const int64_t *lower, *upper, *cost, *supply;        // [arc_row[count]] three times, [node_row[count]]; null as in the view
     const uint8_t *changed;                              // re-solve: [count], null = all
+    const int8_t *start_state;                           // uniform_begin_from: [arc_row[count]]
 };
 
 // ---- what the lanes share (device: all 64 lanes of the wave call these together; host: one lane, the identity)
@@ -126,6 +132,7 @@ MCF_HD inline InstanceView uniform_view(const UniformProblem &p, const UniformOu
     v.lower = uniform_row(p.lower, p.lower_stride, i); v.upper = uniform_row(p.upper, p.upper_stride, i);
     v.cost = uniform_row(p.cost, p.cost_stride, i); v.supply = uniform_row(p.supply, p.supply_stride, i);
     v.arc_row = i * (int64_t)p.m;
+    v.start_state = p.start_state ? p.start_state + i * p.start_stride : nullptr;
     v.workspace = (uint64_t)i * p.stride; v.trace = (uint64_t)i * (uint64_t)p.trace_cap;
     v.home = slab ? slab + v.workspace : nullptr;
     if (o) {
@@ -152,6 +159,7 @@ MCF_HD inline InstanceView ragged_view(const RaggedProblem &r, const UniformOutp
     v.inc_start = r.inc_start + g.inc_start; v.inc = r.inc + g.inc;
     v.lower = r.lower ? r.lower + arcs : nullptr; v.upper = r.upper ? r.upper + arcs : nullptr;
     v.cost = r.cost ? r.cost + arcs : nullptr; v.supply = r.supply ? r.supply + nodes : nullptr;
+    v.start_state = r.start_state ? r.start_state + arcs : nullptr;
     if (slab) { v.workspace = r.workspace[i]; v.home = slab + v.workspace; }
     v.trace = (uint64_t)i * (uint64_t)r.trace_cap;
     if (o) {
@@ -378,37 +386,17 @@ MCF_HD inline void uniform_recost(const InstanceView &p, const BatchSlot &tmpl, 
     lanes_sync();
 }
 
-// ---- a re-solve with new lower, upper and supply in p (costs and supply type are the last solve's).  The kept basis stays dual feasible:
-// WARM where the last solve ended as uniform_recost asks, no non-tree arc at its upper bound has lost that bound, and the new supplies sum
-// to zero (the lower bounds' shifts cancel in the sum; a surplus is answered by an artificial arc whose place depends on the pivot path).
-// Warm: the new capacities go in, every non-tree arc's flow follows its state, and the tree flows are recomputed -- node v's excess is
-// gathered into flow[par_arc[v]] (every node below the root owns one tree arc), folded root-ward up the reverse thread list, children
-// before parents, and turned by par_dir.  The sums wrap and commute like uniform_begin's, so one lane and 64 lanes give the same bits.
-// The slot leaves with run = kBatchDual and reprice = 2: batch_dual_run goes first, and uniform_redata_settle judges the attempt.
-// Anything else: uniform_begin with the new data, a fresh solve bit for bit.
-MCF_HD inline void uniform_redata(const InstanceView &p, const BatchSlot &tmpl, BatchSlot &slot, int lane, int lanes)
+// ---- the flows of the basis that lies in p's workspace, under the lower, upper and supply in p: the new capacities go in, every non-tree
+// arc's flow follows its state, and the tree flows are recomputed -- node v's excess is gathered into flow[par_arc[v]] (every node below
+// the root owns one tree arc), folded root-ward up the reverse thread list, children before parents, and turned by par_dir.  The sums wrap
+// and commute like uniform_begin's, so one lane and 64 lanes give the same bits.  scratch[] is cleared: no mark of an earlier dual phase
+// is left (batch_dual_run).  Shared by uniform_redata (the kept basis) and uniform_begin_from (the caller's); lane 0 leaves with the
+// flows written, the caller's lanes_sync() publishes them.
+MCF_HD inline void uniform_tree_flows(const InstanceView &p, int32_t all_arcs, int lane, int lanes)
 {
     const int n = p.n, m = p.m;
     unsigned char *const home = p.home;
     const int64_t *const lower = p.lower, *const upper = p.upper, *const supply = p.supply;
-    const int32_t all_arcs = slot.all_arcs;
-    bool inverted = false;
-    for (int e = lane; e < m; e += lanes) inverted |= uniform_upper(upper, e) < (lower ? lower[e] : 0);
-    if (lanes_any(inverted)) { uniform_begin(p, tmpl, slot, lane, lanes); return; }         // kBatchByBounds, nothing runs
-    bool warm = slot.run == kBatchNoEntering;
-    if (warm) {
-        const Layout l = layout_of((uint32_t)all_arcs, (uint32_t)n + 1u);
-        const int64_t *const flow = (const int64_t *)(home + l.flow);
-        const int8_t *const state = (const int8_t *)(home + l.state);
-        bool cold = false;
-        for (int e = m + lane; e < all_arcs; e += lanes) cold |= flow[e] != 0;
-        for (int e = lane; e < m; e += lanes) cold |= state[e] == MCF_STATE_UPPER && uniform_upper(upper, e) >= kInf;
-        uint64_t sum = 0;
-        if (supply)
-            for (int v = lane; v < n; v += lanes) sum += (uint64_t)supply[v];
-        warm = !lanes_any(cold) && lanes_sum_u64(sum) == 0;
-    }
-    if (!warm) { uniform_begin(p, tmpl, slot, lane, lanes); return; }
     const Layout l = layout_of((uint32_t)all_arcs, (uint32_t)n + 1u);
     int64_t *const upper_w = (int64_t *)(home + l.upper), *const flow = (int64_t *)(home + l.flow);
     const int32_t *const par = (const int32_t *)(home + l.par), *const par_arc = (const int32_t *)(home + l.par_arc), *const prv = (const int32_t *)(home + l.prv);
@@ -416,7 +404,7 @@ MCF_HD inline void uniform_redata(const InstanceView &p, const BatchSlot &tmpl, 
     const int8_t *const state = (const int8_t *)(home + l.state), *const par_dir = (const int8_t *)(home + l.par_dir);
     // plain stores, barrier, atomic adds on the same words, barrier, plain loads: the order uniform_begin explains
     for (int v = lane; v < n; v += lanes) flow[par_arc[v]] = supply ? supply[v] : 0;
-    for (int v = lane; v < n + 2; v += lanes) scratch[v] = 0;              // no mark of an earlier dual phase is left (batch_dual_run)
+    for (int v = lane; v < n + 2; v += lanes) scratch[v] = 0;
     lanes_sync();
     for (int e = lane; e < m; e += lanes) {
         const int64_t lo = lower ? lower[e] : 0, cap = uniform_upper(upper, e) - lo;
@@ -445,6 +433,40 @@ MCF_HD inline void uniform_redata(const InstanceView &p, const BatchSlot &tmpl, 
             flow[e] = par_dir[u] * below;
             u = prv[u];
         }
+    }
+}
+
+// ---- a re-solve with new lower, upper and supply in p (costs and supply type are the last solve's).  The kept basis stays dual feasible:
+// WARM where the last solve ended as uniform_recost asks, no non-tree arc at its upper bound has lost that bound, and the new supplies sum
+// to zero (the lower bounds' shifts cancel in the sum; a surplus is answered by an artificial arc whose place depends on the pivot path).
+// Warm: uniform_tree_flows above.
+// The slot leaves with run = kBatchDual and reprice = 2: batch_dual_run goes first, and uniform_redata_settle judges the attempt.
+// Anything else: uniform_begin with the new data, a fresh solve bit for bit.
+MCF_HD inline void uniform_redata(const InstanceView &p, const BatchSlot &tmpl, BatchSlot &slot, int lane, int lanes)
+{
+    const int n = p.n, m = p.m;
+    unsigned char *const home = p.home;
+    const int64_t *const lower = p.lower, *const upper = p.upper, *const supply = p.supply;
+    const int32_t all_arcs = slot.all_arcs;
+    bool inverted = false;
+    for (int e = lane; e < m; e += lanes) inverted |= uniform_upper(upper, e) < (lower ? lower[e] : 0);
+    if (lanes_any(inverted)) { uniform_begin(p, tmpl, slot, lane, lanes); return; }         // kBatchByBounds, nothing runs
+    bool warm = slot.run == kBatchNoEntering;
+    if (warm) {
+        const Layout l = layout_of((uint32_t)all_arcs, (uint32_t)n + 1u);
+        const int64_t *const flow = (const int64_t *)(home + l.flow);
+        const int8_t *const state = (const int8_t *)(home + l.state);
+        bool cold = false;
+        for (int e = m + lane; e < all_arcs; e += lanes) cold |= flow[e] != 0;
+        for (int e = lane; e < m; e += lanes) cold |= state[e] == MCF_STATE_UPPER && uniform_upper(upper, e) >= kInf;
+        uint64_t sum = 0;
+        if (supply)
+            for (int v = lane; v < n; v += lanes) sum += (uint64_t)supply[v];
+        warm = !lanes_any(cold) && lanes_sum_u64(sum) == 0;
+    }
+    if (!warm) { uniform_begin(p, tmpl, slot, lane, lanes); return; }
+    uniform_tree_flows(p, all_arcs, lane, lanes);
+    if (lane == 0) {
         uniform_place_slot(slot, tmpl, p, all_arcs, kBatchDual);
         slot.reprice = 2;
     }
@@ -472,6 +494,139 @@ MCF_HD inline void uniform_redata_settle(const InstanceView &p, const BatchSlot 
         if (lane == 0) slot.reprice = 0;
         return;
     }
+    uniform_begin(p, tmpl, slot, lane, lanes);
+}
+
+// ---- a solve that starts from a basis the caller supplies (mcf_*batch_solve_from, DESIGN.md 3.14 "Start from a given basis"):
+// p.start_state holds one state per arc of the caller's, LOWER / TREE / UPPER, as uniform_ranges writes arc_state.  The TREE arcs must
+// form a forest on the n nodes.  uniform_start_try builds the basis in the workspace and says whether it is one the pivots can go on
+// from; false = COLD BY RULE, and nothing it wrote counts.  In this order:
+//   1. what uniform_begin checks and derives (bounds, art_cost), the row's values, the supplies' sum, and the number of TREE arcs T: a
+//      forest of T arcs has n - T components, which fixes all_arcs = m + n + (n - T) and with it where every array lies -- before the walk,
+//      as uniform_begin counts `hung` before it places anything;
+//   2. the arcs [0, m) in standard form with the row's states, the n root links at LOWER with flow 0;
+//   3. the forest, on lane 0: a depth-first walk over the incidence lists (arc ids ascending per node), components by ascending lowest
+//      node and rooted there.  It needs no stack: the way back is par[], and each node's cursor into its list lies in scratch[], which
+//      uniform_tree_flows clears afterwards.  par[v] = -1 marks a node not reached yet.  A TREE arc that reaches a reached node -- a cycle,
+//      the second of two parallel arcs, a self loop -- ends the walk: cold.  The walk writes par, par_arc, par_dir, nxt, prv, sub, fin in
+//      preorder and is bounded by count: each step starts a component (<= n), moves a cursor (<= 2m) or leaves a node (<= n);
+//   4. component k hangs on the root by the artificial arc m + n + k of its lowest node, directed and costed as uniform_begin's for a node
+//      that cannot use its root link.  Not by the root link: that would give the node potential 0 and make the other nodes' root links
+//      eligible, while after a real solve every potential lies beyond -/+ art_cost ("A limit that follows from the definition");
+//   5. flows by uniform_tree_flows, potentials by batch_reprice;
+//   6. the class.  Flow on an artificial arc (a component that does not balance by itself): cold.  Every caller's tree arc within its
+//      bounds: a PRIMAL start, run = kBatchRunning.  Else every non-tree arc of [0, search_arcs) with state * reduced cost >= 0: a DUAL
+//      start, run = kBatchDual.  Else cold.
+// Both accepted kinds leave reprice = 2, so batch_run_after_dual runs them and uniform_redata_settle judges them as it judges a warm
+// attempt of uniform_redata.  Cold by rule is uniform_begin on the same view: a fresh solve bit for bit.
+MCF_HD inline bool uniform_start_try(const InstanceView &p, const BatchSlot &tmpl, BatchSlot &slot, int lane, int lanes)
+{
+    const int n = p.n, m = p.m, root = n;
+    unsigned char *const home = p.home;
+    const int64_t *const lower = p.lower, *const upper = p.upper, *const cost = p.cost, *const supply = p.supply;
+    const int8_t *const row = p.start_state;
+    bool bad = false;
+    uint64_t trees = 0, sum = 0;
+    for (int e = lane; e < m; e += lanes) {
+        const int8_t st = row[e];
+        const int64_t up = uniform_upper(upper, e);
+        bad |= up < (lower ? lower[e] : 0) || st < MCF_STATE_UPPER || st > MCF_STATE_LOWER || (st == MCF_STATE_UPPER && up >= kInf);
+        trees += st == MCF_STATE_TREE;
+    }
+    if (supply)
+        for (int v = lane; v < n; v += lanes) sum += (uint64_t)supply[v];
+    trees = lanes_sum_u64(trees);
+    if (lanes_any(bad) || lanes_sum_u64(sum) != 0 || trees >= (uint64_t)n) return false;        // n = 0 too: nothing to hang
+    const int32_t comps = n - (int32_t)trees, all_arcs = m + n + comps;
+    const int64_t art_cost = uniform_art_cost(cost, n, m, lane, lanes);
+    const bool geq = p.supply_type == MCF_SUPPLY_GEQ;
+    const Layout l = layout_of((uint32_t)all_arcs, (uint32_t)n + 1u);
+    int32_t *const tail = (int32_t *)(home + l.tail), *const head = (int32_t *)(home + l.head);
+    int64_t *const cost_w = (int64_t *)(home + l.cost), *const upper_w = (int64_t *)(home + l.upper), *const flow = (int64_t *)(home + l.flow);
+    int32_t *const par = (int32_t *)(home + l.par), *const par_arc = (int32_t *)(home + l.par_arc), *const nxt = (int32_t *)(home + l.nxt);
+    int32_t *const prv = (int32_t *)(home + l.prv), *const sub = (int32_t *)(home + l.sub), *const fin = (int32_t *)(home + l.fin);
+    int32_t *const cursor = (int32_t *)(home + l.scratch);
+    int8_t *const state = (int8_t *)(home + l.state), *const par_dir = (int8_t *)(home + l.par_dir);
+    for (int e = lane; e < m; e += lanes) {
+        tail[e] = p.source[e]; head[e] = p.target[e];
+        cost_w[e] = cost ? cost[e] : 0;
+        upper_w[e] = uniform_upper(upper, e) - (lower ? lower[e] : 0);
+        flow[e] = 0;
+        state[e] = row[e];
+    }
+    for (int v = lane; v < n; v += lanes) {
+        const int link = m + v;
+        tail[link] = geq ? root : v; head[link] = geq ? v : root;   // the zero-cost link: GEQ root->v, LEQ v->root
+        upper_w[link] = kInf; cost_w[link] = 0; flow[link] = 0; state[link] = MCF_STATE_LOWER;
+        par[v] = -1; sub[v] = 1; cursor[v] = p.inc_start[v];
+    }
+    lanes_sync();
+    int32_t forest = 1;
+    if (lane == 0) {
+        int last = root, u = -1, lowest = 0;
+        int32_t k = 0;
+        int64_t steps = 2 * (int64_t)m + 2 * (int64_t)n + 1;
+        for (;;) {
+            if (steps-- <= 0) { forest = 0; break; }
+            if (u < 0) {                                            // the next component: the lowest node not reached yet
+                while (lowest < n && par[lowest] != -1) ++lowest;
+                if (lowest >= n) break;
+                if (k >= comps) { forest = 0; break; }              // more components than a forest of `trees` arcs has: there is a cycle
+                u = lowest;
+                const int extra = m + n + k++;
+                par[u] = root; par_arc[u] = extra; par_dir[u] = geq ? kUp : kDown;
+                tail[extra] = geq ? u : root; head[extra] = geq ? root : u;
+                upper_w[extra] = kInf; cost_w[extra] = art_cost; flow[extra] = 0; state[extra] = MCF_STATE_TREE;
+                nxt[last] = u; prv[u] = last; last = u;
+                continue;
+            }
+            const int32_t at = cursor[u];
+            if (at >= p.inc_start[u + 1]) {                         // u's list is done: back up
+                const int up = par[u];
+                fin[u] = last;
+                if (up != root) sub[up] += sub[u];
+                u = up != root ? up : -1;
+                continue;
+            }
+            cursor[u] = at + 1;
+            const int32_t entry = p.inc[at], e = entry >> 1;
+            if (row[e] != MCF_STATE_TREE || e == par_arc[u]) continue;
+            const bool incoming = (entry & 1) != 0;                 // u is e's target: the other end is its tail
+            const int v = incoming ? p.source[e] : p.target[e];
+            if (par[v] != -1) { forest = 0; break; }
+            par[v] = u; par_arc[v] = e; par_dir[v] = incoming ? kUp : kDown;
+            nxt[last] = v; prv[v] = last; last = v;
+            u = v;
+        }
+        if (k != comps) forest = 0;
+        nxt[last] = root; prv[root] = last;                         // last = root where nothing was reached: n > 0 rules that out
+        par[root] = -1; par_arc[root] = -1; sub[root] = n + 1; fin[root] = last; par_dir[root] = 0;
+    }
+    lanes_sync();
+    if (!lanes_from_first(forest)) return false;
+    uniform_tree_flows(p, all_arcs, lane, lanes);
+    BatchWork w{};
+    bind(w, home, l);
+    w.n = n; w.search_arcs = tmpl.search_arcs;
+    batch_reprice(w, lane, lanes);
+    bool unbalanced = false, outside = false, eligible = false;
+    for (int e = m + n + lane; e < all_arcs; e += lanes) unbalanced |= flow[e] != 0;
+    for (int e = lane; e < m; e += lanes) outside |= state[e] == MCF_STATE_TREE && (flow[e] < 0 || flow[e] > upper_w[e]);
+    for (int e = lane; e < w.search_arcs; e += lanes) eligible |= state[e] != MCF_STATE_TREE && batch_reduced_cost(w, e) < 0;
+    if (lanes_any(unbalanced)) return false;
+    const bool primal = !lanes_any(outside);
+    if (!primal && lanes_any(eligible)) return false;
+    if (lane == 0) {
+        uniform_place_slot(slot, tmpl, p, all_arcs, primal ? kBatchRunning : kBatchDual);
+        slot.reprice = 2;
+    }
+    lanes_sync();
+    return true;
+}
+MCF_HD inline void uniform_begin_from(const InstanceView &p, const BatchSlot &tmpl, BatchSlot &slot, int lane, int lanes)
+{
+    if (uniform_start_try(p, tmpl, slot, lane, lanes)) return;
+    lanes_sync();                       // what the attempt read in the workspace has been read
     uniform_begin(p, tmpl, slot, lane, lanes);
 }
 

@@ -494,6 +494,7 @@ class _PlacedBatch:
       _PREFIX            the library's functions are <_PREFIX>_solve, _resolve, ...
       _IO, _CHECK_IO     the ctypes structs of a solve call and of a validation call
       _RANGE_IO          the ctypes struct of a cost-ranges call; _ranges(out) makes its result
+      _BASIS_IO          the ctypes struct that carries a given basis into solve_from()
       _RESULT            the result class; _result(out) makes one
       _sizes()           the shapes of the outputs by UniformResult.FIELDS' dimension key
       _stride(...)       the expected shape of the array of a given name, its contiguity, and the stride it is passed with"""
@@ -567,8 +568,8 @@ class _PlacedBatch:
                 out[name] = self._empty(sizes[dim], dtype, tensors)
         return out
 
-    def _call(self, fn, cost, supply, lower, upper, supply_type, changed=None, masked=False, numpy_only=False):
-        given = [a for a in (cost, supply, lower, upper, changed) if a is not None]
+    def _call(self, fn, cost, supply, lower, upper, supply_type, changed=None, masked=False, numpy_only=False, arc_state=None):
+        given = [a for a in (cost, supply, lower, upper, changed, arc_state) if a is not None]
         tensors = any(_is_tensor(a) for a in given)
         if tensors and numpy_only:
             raise ValueError("the host hooks take numpy arrays")
@@ -593,7 +594,17 @@ class _PlacedBatch:
         out = self._outputs(tensors, self._last if masked and changed is not None else None)
         for name, arr in out.items():
             setattr(io, name, arr.data_ptr() if tensors else arr.ctypes.data)
-        L.check(self._fn(fn)(self._h, C.byref(io)))
+        extra = []
+        if arc_state is not None:           # a solve from a given basis: the row(s) of arc states, checked like every other array
+            basis = self._BASIS_IO()
+            basis.memory = io.memory
+            ptr, stride, obj = self._input(arc_state, "arc_state", tensors, dtype="int8")
+            keep.append(obj)
+            basis.arc_state = ptr
+            if hasattr(basis, "state_stride"):
+                basis.state_stride = stride
+            extra.append(C.byref(basis))
+        L.check(self._fn(fn)(self._h, C.byref(io), *extra))
         self._last = self._result(out)
         return self._last
 
@@ -625,6 +636,28 @@ class _PlacedBatch:
     def rerun_data_on_host(self, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq, changed=None) -> UniformResult:
         """Test hook: resolve_data() with one lane on the CPU.  numpy only."""
         return self._call("rerun_data_on_host", cost, supply, lower, upper, supply_type, changed, masked=True, numpy_only=True)
+
+    def solve_from(self, arc_state, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> UniformResult:
+        """A solve of every instance that starts from the basis in arc_state instead of from the start basis: int8, one state per arc
+        (1 lower bound, 0 tree, -1 upper bound) as cost_ranges() returns it -- from this handle or another, of either kind, on the same
+        graph.  UniformBatch: [arc_count] (one row for the whole batch) or [count, arc_count]; RaggedBatch: flat, arc_rows[-1] long.
+        numpy or tensors like the other arrays.  A row that is no basis the pivots can go on from (a cycle among its tree arcs, supplies
+        its components do not balance, ...) is solved from the start basis, bit for bit a solve(); every answer is a fresh solve's.
+        Allowed on a handle that has never solved; afterwards resolve(), resolve_data(), cost_ranges() and validate() go on from it."""
+        if arc_state is None:
+            raise ValueError("arc_state: a basis is required (int8, one state per arc)")
+        return self._call("solve_from", cost, supply, lower, upper, supply_type, arc_state=arc_state)
+
+    def run_from_on_host(self, arc_state, cost, supply, lower=None, upper=None, supply_type=SupplyType.Geq) -> UniformResult:
+        """Test hook: solve_from() with one lane on the CPU.  numpy only."""
+        if arc_state is None:
+            raise ValueError("arc_state: a basis is required (int8, one state per arc)")
+        return self._call("run_from_on_host", cost, supply, lower, upper, supply_type, numpy_only=True, arc_state=arc_state)
+
+    def start_stats(self) -> dict:
+        """What the last solve_from() / run_from_on_host() did: primal starts, dual starts, instances cold by rule, fallbacks, dual and
+        primal pivots."""
+        st = L.UBatchStartStats(); L.check(self._fn("get_start_stats")(self._h, C.byref(st))); return st.as_dict()
 
     def stats(self) -> dict:
         st = L.UBatchStats(); L.check(self._fn("get_stats")(self._h, C.byref(st))); return st.as_dict()
@@ -715,8 +748,9 @@ class UniformBatch(_PlacedBatch):
     device (read and written in place: nothing that scales with the graph crosses the bus) -- never a mix; each array is [count, m]
     ([count, n] for supply) or [m] ([n]) for one row shared by all, int64, contiguous in its last dimension.  Results equal
     BatchSolver's for the same instances bit for bit.  run_on_host() / rerun_on_host() are test hooks (numpy only)."""
-    _PREFIX, _IO, _CHECK_IO, _RESULT, _RANGE_IO = "mcf_ubatch", L.UBatchIo, L.UBatchCheckIo, UniformResult, L.UBatchRangeIo
-    _ROW = {"cost": "arc_count", "lower": "arc_count", "upper": "arc_count", "flows": "arc_count", "supply": "node_count", "potentials": "node_count"}
+    _PREFIX, _IO, _CHECK_IO, _RESULT, _RANGE_IO, _BASIS_IO = "mcf_ubatch", L.UBatchIo, L.UBatchCheckIo, UniformResult, L.UBatchRangeIo, L.UBatchBasisIo
+    _ROW = {"cost": "arc_count", "lower": "arc_count", "upper": "arc_count", "flows": "arc_count", "supply": "node_count", "potentials": "node_count",
+            "arc_state": "arc_count"}
 
     def __init__(self, node_count, source, target, count, rule=PivotRule.BlockSearch, pivot_limit=0, record_trace=0, device=0, pivots_per_launch=0,
                  semantics=L.SEM_PLAIN, flags=0):
@@ -761,8 +795,9 @@ class RaggedBatch(_PlacedBatch):
     and down) or flat torch tensors on the handle's device (read and written in place) -- never a mix; int64, contiguous.  Results equal
     BatchSolver's for the same instances bit for bit, and UniformBatch's where there is one graph.  run_on_host() / rerun_on_host() /
     validate_on_host() are test hooks (numpy only)."""
-    _PREFIX, _IO, _CHECK_IO, _RESULT, _RANGE_IO = "mcf_rbatch", L.RBatchIo, L.RBatchCheckIo, RaggedResult, L.RBatchRangeIo
-    _ROW = {"cost": "arc_total", "lower": "arc_total", "upper": "arc_total", "flows": "arc_total", "supply": "node_total", "potentials": "node_total"}
+    _PREFIX, _IO, _CHECK_IO, _RESULT, _RANGE_IO, _BASIS_IO = "mcf_rbatch", L.RBatchIo, L.RBatchCheckIo, RaggedResult, L.RBatchRangeIo, L.RBatchBasisIo
+    _ROW = {"cost": "arc_total", "lower": "arc_total", "upper": "arc_total", "flows": "arc_total", "supply": "node_total", "potentials": "node_total",
+            "arc_state": "arc_total"}
 
     def __init__(self, graphs, graph_of=None, rule=PivotRule.BlockSearch, pivot_limit=0, record_trace=0, device=0, pivots_per_launch=0,
                  semantics=L.SEM_PLAIN, flags=0):

@@ -1,8 +1,9 @@
 // rbatch_host_check.cpp -- the host side of the placed batches as a stand-alone program, so that it can be built together with the
 // library's host sources under -fsanitize=address,undefined and run on a CPU ("Ragged batch").  It runs the ragged entry
-// points (mcf_rbatch_create, _run_on_host, _rerun_on_host, _validate_on_host) on its input, then the instances of the input's first
-// graph through the uniform ones (mcf_ubatch_*), which share the drivers, and compares every row of the two.  Needs no GPU and is not
-// loaded into Python.
+// points (mcf_rbatch_create, _run_on_host, _rerun_on_host, _validate_on_host) on its input, exports the first solve's basis
+// (_cost_ranges_on_host) and starts a second handle from it (_run_from_on_host: the same data must give the first solve's status and
+// total cost; the second costs run for the sanitizer's sake), then the instances of the input's first graph through the uniform entry
+// points (mcf_ubatch_*), which share the drivers, and compares every row of the two.  Needs no GPU and is not loaded into Python.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -I../include \
 //         rbatch_host_check.cpp ../mincostflow_amd/csrc/{batch.hip,ns_core.cpp,ns_host.cpp,engine.hip,validate.hip,problems.cpp,util.cpp,exchange.cpp} \
@@ -99,7 +100,7 @@ int main(int argc, char **argv)
     std::vector<uint8_t> changed((size_t)count);
     for (int i = 0; i < count; ++i) changed[(size_t)i] = i % 3 != 1;
 
-    int64_t pivots_total = 0, invalid_total = 0;
+    int64_t pivots_total = 0, invalid_total = 0, started = 0;
     for (int32_t rule : {MCF_RULE_BLOCK_SEARCH, MCF_RULE_BEST_ELIGIBLE, MCF_RULE_FIRST_ELIGIBLE})
         for (int32_t stype : {MCF_SUPPLY_GEQ, MCF_SUPPLY_LEQ}) {
             mcf_rbatch_desc d{};
@@ -127,6 +128,29 @@ int main(int argc, char **argv)
             CHECK(mcf_rbatch_validate_on_host(b, &c, &summary));
             invalid_total += summary.invalid;
             const Answers r_first = r;
+            // the basis as far as the caller's arcs go, exactly sized like the outputs
+            std::vector<int8_t> arc_state(lower.size());
+            std::vector<int32_t> ranged((size_t)count);
+            mcf_rbatch_range_io rio{};
+            rio.memory = MCF_MEM_HOST; rio.ranged = ranged.data(); rio.arc_state = arc_state.data();
+            CHECK(mcf_rbatch_cost_ranges_on_host(b, &rio));
+            {
+                mcf_rbatch *from = nullptr;
+                CHECK(mcf_rbatch_create(&from, &d));
+                Answers s((size_t)count, lower.size(), supply.size());
+                mcf_rbatch_io sio = io;
+                sio.status = s.status.data(); sio.pivots = s.pivots.data(); sio.total_cost = s.total.data(); sio.flows = s.flows.data(); sio.potentials = s.potentials.data(); sio.trace = s.trace.data();
+                mcf_rbatch_basis_io basis{};
+                basis.memory = MCF_MEM_HOST; basis.arc_state = arc_state.data();
+                CHECK(mcf_rbatch_run_from_on_host(from, &sio, &basis));
+                if (s.status != r_first.status || s.total != r_first.total) { fprintf(stderr, "the start from the exported basis answers differently from the solve that left it\n"); return 1; }
+                mcf_ubatch_start_stats ss{};
+                CHECK(mcf_rbatch_get_start_stats(from, &ss));
+                started += ss.primal_starts + ss.dual_starts;
+                sio.cost = cost2.data();                                      // other costs on the kept basis: primal pivots from there, or cold
+                CHECK(mcf_rbatch_run_from_on_host(from, &sio, &basis));
+                mcf_rbatch_destroy(from);
+            }
             io.cost = cost2.data(); io.changed = changed.data();
             CHECK(mcf_rbatch_rerun_on_host(b, &io));
             io.changed = nullptr;
@@ -173,7 +197,7 @@ int main(int argc, char **argv)
             mcf_ubatch_destroy(ub);
         }
     printf("ok: %d instances of %d graphs, 3 rules x 2 supply types; %lld pivots in the last re-solves, %lld rows flagged by the first validations; "
-           "the %zu instances of graph 0 as a uniform batch: every row equal\n",
-           count, G, (long long)pivots_total, (long long)invalid_total, sel.size());
+           "%lld starts from an exported basis accepted; the %zu instances of graph 0 as a uniform batch: every row equal\n",
+           count, G, (long long)pivots_total, (long long)invalid_total, (long long)started, sel.size());
     return 0;
 }
