@@ -182,9 +182,10 @@ def redata(resolve_data):
     return between
 
 
-def check_meaning(solve, resolve, ranges, between=None, reference=None):
-    """solve / resolve(handle, arrays) -> result with one shared row per array but the costs."""
-    p, o = meaning_problem()
+def check_meaning(solve, resolve, ranges, between=None, reference=None, problem=None):
+    """solve / resolve(handle, arrays) -> result with one shared row per array but the costs.  problem: (a ranged circulation, its
+    oracle), by default meaning_problem()."""
+    p, o = problem or meaning_problem()
     m, count = p.m, 4 * p.m
     u = M.UniformBatch(p.n, p.src, p.tgt, count)
     base = {f: getattr(p, f) for f in PROBLEM_FIELDS}

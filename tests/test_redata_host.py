@@ -61,8 +61,9 @@ def cut_off(p, rng):
     return with_data(p, supply, lower, upper)
 
 
-def next_data(p, name, k, rng):
-    """The problem after the step `name` of the chain; an arc whose upper bound lies below its lower bound keeps both."""
+def next_data(p, name, k, rng, pool=None):
+    """The problem after the step `name` of the chain; an arc whose upper bound lies below its lower bound keeps both.  pool: the nodes whose
+    supplies steps b and g may redraw, by default every node."""
     supply, lower, upper = p.supply.copy(), p.lower.copy(), p.upper.copy()
     live = upper > lower
     cap = upper - lower
@@ -73,9 +74,10 @@ def next_data(p, name, k, rng):
             supply[rng.choice(pos)] -= delta
             supply[rng.choice(neg)] += delta
     elif name == "b":                   # 5 % of the supplies redrawn, at least two, their sum kept
-        hit = rng.random(p.n) < 0.05
-        hit[rng.choice(p.n, min(2, p.n), replace=False)] = True
-        at = np.flatnonzero(hit)
+        nodes = np.arange(p.n) if pool is None else np.asarray(pool)
+        hit = rng.random(len(nodes)) < 0.05
+        hit[rng.choice(len(nodes), min(2, len(nodes)), replace=False)] = True
+        at = nodes[np.flatnonzero(hit)]
         new = rng.integers(-8, 9, len(at))
         new[-1] += supply[at].sum() - new.sum()
         supply[at] = new
@@ -90,7 +92,7 @@ def next_data(p, name, k, rng):
         if k in CUT:
             return cut_off(p, rng)
     elif name == "g":                   # supplies redrawn as in b, in the variants SURPLUS with a surplus
-        supply = next_data(p, "b", k, rng).supply
+        supply = next_data(p, "b", k, rng, pool).supply
         if k in SURPLUS:
             supply[rng.integers(0, p.n)] += 3
     return with_data(p, supply, lower, upper)
@@ -281,9 +283,11 @@ def test_changed_mask_on_the_host():
 
 
 # ---- 4: mixed with re-solves with new costs
-def check_mixed_with_new_costs(first, again, recost, rule, **kw):
-    """new costs, then new data under those costs, then new costs under those data: each against the oracle's cold solve of what holds then"""
-    for j, ((t, steps), (_, stype)) in enumerate(zip(chain(), redata_family())):
+def check_mixed_with_new_costs(first, again, recost, rule, graphs=None, **kw):
+    """new costs, then new data under those costs, then new costs under those data: each against the oracle's cold solve of what holds then.
+    graphs: ((topology, its steps), supply type) per graph, by default the chain's."""
+    graphs = tuple((c, stype) for c, (_, stype) in zip(chain(), redata_family())) if graphs is None else graphs
+    for j, ((t, steps), stype) in enumerate(graphs):
         u = uniform_of(t, rule, **kw)
         first(u, t.arrays(), stype)
         cost_1, cost_2, data = step_costs(t, j, 1), step_costs(t, j, 0), steps[1]
