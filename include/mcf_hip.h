@@ -1025,6 +1025,80 @@ MCF_API int mcf_rbatch_cost_ranges(mcf_rbatch *b, const mcf_rbatch_range_io *io)
 MCF_API int mcf_rbatch_cost_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_range_io *io);
 MCF_API int mcf_rbatch_get_range_stats(mcf_rbatch *b, mcf_ubatch_range_stats *out);
 
+/* ---- Supply and bound ranges of the kept basis (DESIGN.md 3.14 "Supply and bound ranges of the kept basis"): classic right-hand-side
+ * ranging, the data side of the cost ranges above, computed on the device from the same kept state.  RANGED as there; every other
+ * instance gets ranged = 0 and zero rows.  For a ranged instance the kept basis stays primal feasible -- a mcf_*batch_resolve_data that
+ * changes this one thing counts the instance as warm, makes no dual and no primal pivot, does not fall back, and leaves it ranged with
+ * the same arc_state -- exactly while
+ *   - the flow of arc e, were it moved with every other non-tree flow fixed, falls by at most flow_down[e] or rises by at most flow_up[e].
+ *     A tree arc's two sides are its own room within its bounds; a non-tree arc's are the least room along its cycle in the tree
+ *     (csrc/data_ranges_step.hip.h) and are NOT clipped by the arc's own capacity.  An arc without an upper bound (MCF_INF_CAP) has no
+ *     limit to rise, whatever its lower bound (lower bounds below 2^61 in size);
+ *   - d units of supply move from node b to node a of a pair the caller names (supply[a] + d, supply[b] - d) with d <= ship_forth, or
+ *     from a to b with d <= ship_back.  a == b gives MCF_RANGE_INF twice; an id outside [0, node_count) gives -1 twice and reads nothing.
+ * All are >= 0 and deltas; MCF_RANGE_INF = no limit.  The ranges of the bounds follow per arc without another walk (for an uncapacitated
+ * arc MCF_RANGE_INF in the upper columns means there is no finite upper bound to move):
+ *
+ *   arc_state | lower may fall by | lower may rise by             | upper may fall by             | upper may rise by
+ *   LOWER     | flow_down         | min(flow_up, upper - lower)   | upper - lower                 | MCF_RANGE_INF
+ *   UPPER     | MCF_RANGE_INF     | upper - lower                 | min(flow_down, upper - lower) | flow_up
+ *   TREE      | MCF_RANGE_INF     | flow_down                     | flow_up                       | MCF_RANGE_INF
+ *
+ * A tree path that passes a root link or an artificial arc has no room: the re-solve lets no warm attempt stand that leaves flow there.
+ * One wave per instance; an instance is ranged in LDS exactly when it is solved there.  Contract as mcf_*batch_cost_ranges': null
+ * stream, returns synchronised, the handle's device made current and the caller's restored; the call reads the kept state and changes
+ * none of it, and mixes with every solve call and hook in any order.  The pairs lie in the memory kind of the call.  MCF_ERR_STATE
+ * before a solve of either kind; MCF_ERR_NO_DEVICE without a GPU leaves the handle as it was; MCF_ERR_INVALID for a null argument, an
+ * unknown memory kind, one of flow_down / flow_up or of ship_forth / ship_back without the other, ship rows without pairs, a negative
+ * pair count, and -- where the tables lie in host memory -- pair_row or ship_row that do not fit each other.  With MCF_MEM_DEVICE nothing
+ * that scales with the arcs, the nodes, the pairs or the instances crosses the bus in a call (a table of one int32 per instance goes up
+ * once per handle, with the first call). */
+typedef struct mcf_ubatch_data_range_io {
+    int32_t memory;               /* MCF_MEM_HOST / MCF_MEM_DEVICE: where every pointer below points */
+    int32_t reserved;
+    /* the pairs: ONE list for every instance; NULL with pair_count 0 */
+    int64_t pair_count;
+    const int32_t *pairs;         /* [pair_count][2] node ids (a, b) */
+    /* results, any may be NULL -- but flow_down and flow_up both or neither, ship_forth and ship_back both or neither */
+    int32_t *ranged;              /* [count] 1 / 0 */
+    int8_t *arc_state;            /* [count * arc_count] */
+    int64_t *flow_down;           /* [count * arc_count] */
+    int64_t *flow_up;             /* [count * arc_count] */
+    int64_t *ship_forth;          /* [count * pair_count] */
+    int64_t *ship_back;           /* [count * pair_count] */
+} mcf_ubatch_data_range_io;
+typedef struct mcf_rbatch_data_range_io {              /* flat rows: instance i's arcs at [arc_row[i], arc_row[i + 1]) */
+    int32_t memory;
+    int32_t reserved;
+    /* the pairs: one list per GRAPH, flat; graph g's are pairs[pair_row[g] .. pair_row[g + 1]), pair_row[0] = 0.  All three NULL: none */
+    const int32_t *pairs;         /* [pair_row[graph_count]][2] */
+    const int64_t *pair_row;      /* [graph_count + 1] */
+    const int64_t *ship_row;      /* [count + 1]: where instance i's answers begin in the ship rows, running sums of its graph's pair count */
+    int32_t *ranged;              /* [count] */
+    int8_t *arc_state;            /* [arc_row[count]] */
+    int64_t *flow_down;           /* [arc_row[count]] */
+    int64_t *flow_up;             /* [arc_row[count]] */
+    int64_t *ship_forth;          /* [ship_row[count]] */
+    int64_t *ship_back;           /* [ship_row[count]] */
+} mcf_rbatch_data_range_io;
+typedef struct mcf_ubatch_data_range_stats { /* of the last mcf_*batch_data_ranges / _on_host (all zero before one) */
+    int64_t instances;
+    int64_t ranged;               /* instances with ranged = 1 */
+    int64_t lds_instances;        /* of `instances`, by the tier they are solved in; 0 and 0 from the host hook */
+    int64_t global_instances;
+    int64_t walks;                /* tree paths walked: one per non-tree arc (with flow rows), one per pair with both ids in range */
+    int64_t hops;                 /* steps of all walks: one dependent load chain link each */
+    double kernel_ns;             /* round the launches, synchronised */
+    int64_t bytes_up, bytes_down; /* MCF_MEM_DEVICE: the three summary words; MCF_MEM_HOST adds the arrays */
+} mcf_ubatch_data_range_stats;
+MCF_API int mcf_ubatch_data_ranges(mcf_ubatch *b, const mcf_ubatch_data_range_io *io);
+/* TEST HOOK: the same step (uniform_data_ranges, csrc/data_ranges_step.hip.h) with one lane on the CPU.  io->memory must be MCF_MEM_HOST. */
+MCF_API int mcf_ubatch_data_ranges_on_host(mcf_ubatch *b, const mcf_ubatch_data_range_io *io);
+MCF_API int mcf_ubatch_get_data_range_stats(mcf_ubatch *b, mcf_ubatch_data_range_stats *out);
+MCF_API int mcf_rbatch_data_ranges(mcf_rbatch *b, const mcf_rbatch_data_range_io *io);
+MCF_API int mcf_rbatch_data_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_data_range_io *io);
+MCF_API int mcf_rbatch_get_data_range_stats(mcf_rbatch *b, mcf_ubatch_data_range_stats *out);
+
 /* ---- Starting a solve from a basis the caller supplies (DESIGN.md 3.14 "Start from a given basis").  The way back in for what
  * mcf_*batch_cost_ranges writes out as arc_state: one state per arc of the caller's, MCF_STATE_LOWER / _TREE / _UPPER, from a solve of
  * this handle or of another, of a mcf_ubatch or of a mcf_rbatch on the same graph, from today or from a file.  A uniform handle takes one

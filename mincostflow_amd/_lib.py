@@ -239,6 +239,27 @@ class UBatchRangeStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class UBatchDataRangeIo(C.Structure):
+    """mcf_ubatch_data_range_io"""
+    _fields_ = [("memory", C.c_int32), ("reserved", C.c_int32), ("pair_count", C.c_int64), ("pairs", C.c_void_p)] + \
+               [(name, C.c_void_p) for name in ("ranged", "arc_state", "flow_down", "flow_up", "ship_forth", "ship_back")]
+
+
+class RBatchDataRangeIo(C.Structure):
+    """mcf_rbatch_data_range_io"""
+    _fields_ = [("memory", C.c_int32), ("reserved", C.c_int32), ("pairs", C.c_void_p), ("pair_row", C.c_void_p), ("ship_row", C.c_void_p)] + \
+               [(name, C.c_void_p) for name in ("ranged", "arc_state", "flow_down", "flow_up", "ship_forth", "ship_back")]
+
+
+class UBatchDataRangeStats(C.Structure):
+    """mcf_ubatch_data_range_stats"""
+    _fields_ = [(name, C.c_int64) for name in ("instances", "ranged", "lds_instances", "global_instances", "walks", "hops")] + \
+               [("kernel_ns", C.c_double), ("bytes_up", C.c_int64), ("bytes_down", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class UBatchBasisIo(C.Structure):
     """mcf_ubatch_basis_io"""
     _fields_ = [("memory", C.c_int32), ("reserved", C.c_int32), ("arc_state", C.c_void_p), ("state_stride", C.c_int64)]
@@ -434,6 +455,12 @@ SIGNATURES = {
     "mcf_rbatch_cost_ranges": (C.c_int, [C.c_void_p, _P(RBatchRangeIo)]),
     "mcf_rbatch_cost_ranges_on_host": (C.c_int, [C.c_void_p, _P(RBatchRangeIo)]),
     "mcf_rbatch_get_range_stats": (C.c_int, [C.c_void_p, _P(UBatchRangeStats)]),
+    "mcf_ubatch_data_ranges": (C.c_int, [C.c_void_p, _P(UBatchDataRangeIo)]),
+    "mcf_ubatch_data_ranges_on_host": (C.c_int, [C.c_void_p, _P(UBatchDataRangeIo)]),
+    "mcf_ubatch_get_data_range_stats": (C.c_int, [C.c_void_p, _P(UBatchDataRangeStats)]),
+    "mcf_rbatch_data_ranges": (C.c_int, [C.c_void_p, _P(RBatchDataRangeIo)]),
+    "mcf_rbatch_data_ranges_on_host": (C.c_int, [C.c_void_p, _P(RBatchDataRangeIo)]),
+    "mcf_rbatch_get_data_range_stats": (C.c_int, [C.c_void_p, _P(UBatchDataRangeStats)]),
     "mcf_rbatch_solve_from": (C.c_int, [C.c_void_p, _P(RBatchIo), _P(RBatchBasisIo)]),
     "mcf_rbatch_run_from_on_host": (C.c_int, [C.c_void_p, _P(RBatchIo), _P(RBatchBasisIo)]),
     "mcf_rbatch_get_start_stats": (C.c_int, [C.c_void_p, _P(UBatchStartStats)]),

@@ -14,6 +14,8 @@
 //     batch_step.hip.h in front of the primal ones, between a re-data launch and a settle launch (uniform_step.hip.h).
 //   * cost ranges of the kept basis (mcf_ubatch_cost_ranges, mcf_rbatch_cost_ranges): the ranges kernels run ranges_step.hip.h on the
 //     workspaces as the last solve call left them, and write nothing there.
+//   * supply and bound ranges of the kept basis (mcf_ubatch_data_ranges, mcf_rbatch_data_ranges): the data-ranges kernels run
+//     data_ranges_step.hip.h on the same state, the same way; every walk gathers into registers, so they need no atomics.
 //   * solves that start from a basis the caller supplies (mcf_ubatch_solve_from, mcf_rbatch_solve_from): the start kernels run
 //     uniform_begin_from in place of the set-up launch; rounds and settle launch are those of a re-solve with new data.
 // Device code does no bounds checks: mcf_batch_add validates every end point (core_create), and every index the kernel follows after
@@ -27,6 +29,7 @@
 #include "batch_layout.hip.h"
 #include "batch_step.hip.h"
 #include "common.h"
+#include "data_ranges_step.hip.h"
 #include "ns_core.h"
 #include "ranges_step.hip.h"
 #include "uniform_step.hip.h"
@@ -262,6 +265,28 @@ __global__ __launch_bounds__(kBatchThreads) void ragged_ranges_kernel(mcf::Ragge
     extern __shared__ __align__(16) unsigned char lds[];
     const int64_t i = (int64_t)ids[blockIdx.x];
     mcf::uniform_ranges<kLds>(mcf::ragged_view(r, nullptr, i, slab, nullptr), o, slots[i], lds, (int)threadIdx.x, kBatchThreads);
+}
+
+// mcf_*batch_data_ranges: the same launch shape on data_ranges_step.hip.h.  Nothing of an instance is shared between lanes but the room
+// arrays of the LDS tier, written before the one barrier and read after it; the walks gather into registers and the answers go straight
+// to the caller's rows.  kLds: dynamic LDS holds what a hop reads (at least data_range_layout_of(m, n + 1).bytes); otherwise the walks
+// follow the workspace in place.  The pairs: one list for all (uniform), one per graph by the caller's tables (ragged).
+template <bool kLds>
+__global__ __launch_bounds__(kBatchThreads) void uniform_data_ranges_kernel(mcf::UniformProblem p, mcf::DataRangeOutputs o, const int32_t *pairs, int64_t pair_count,
+                                                                            const BatchSlot *slots, unsigned char *slab, const int32_t *ids)
+{
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int64_t i = (int64_t)ids[blockIdx.x];
+    mcf::uniform_data_ranges<kLds>(mcf::uniform_view(p, nullptr, i, slab), o, mcf::uniform_pairs(pairs, pair_count, i), slots[i], lds, (int)threadIdx.x, kBatchThreads);
+}
+template <bool kLds>
+__global__ __launch_bounds__(kBatchThreads) void ragged_data_ranges_kernel(mcf::RaggedProblem r, mcf::DataRangeOutputs o, const int32_t *pairs, const int64_t *pair_row,
+                                                                           const int64_t *ship_row, const BatchSlot *slots, unsigned char *slab, const int32_t *ids)
+{
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int64_t i = (int64_t)ids[blockIdx.x];
+    mcf::uniform_data_ranges<kLds>(mcf::ragged_view(r, nullptr, i, slab, nullptr), o, mcf::ragged_pairs(pairs, pair_row, ship_row, r.graph_of[i], i), slots[i], lds,
+                                   (int)threadIdx.x, kBatchThreads);
 }
 
 struct Instance {
@@ -998,13 +1023,18 @@ struct PlacedBatch {
     int64_t *d_summary = nullptr;       // validation: invalid instances, the lowest invalid index.  Allocated last: it says the tables are up
     unsigned char *d_io = nullptr;      // MCF_MEM_HOST: the caller's arrays on their way up and down
     size_t d_io_bytes = 0;
-    // cost ranges: the instances by tier and footprint class (planned for lds_max = range_lds_max, up once), the summary words, the last call's statistics
+    // cost ranges and data ranges: for each the instances by tier and footprint class (planned for the lds_max it names, up once), the
+    // summary words both use, the last calls' statistics
     struct RangeLaunch { int first, n; uint32_t lds; bool in_lds; };
-    std::vector<RangeLaunch> range_launches;
-    int32_t *d_range_ids = nullptr;
+    struct RangePlan {
+        std::vector<RangeLaunch> launches;
+        int32_t *d_ids = nullptr;
+        int lds_max = -1;
+    };
+    RangePlan range_plan, data_range_plan;
     int64_t *d_range_summary = nullptr;
-    int range_lds_max = -1;
     mcf_ubatch_range_stats range_stats{};
+    mcf_ubatch_data_range_stats data_range_stats{};
     std::vector<unsigned char> h_slab;  // the host hooks' slab, slots and traces: the device's layout
     std::vector<BatchSlot> h_slots;
     std::vector<int32_t> h_traces;
@@ -1014,7 +1044,8 @@ struct PlacedBatch {
         if (d_tmpl) (void)hipFree(d_tmpl);
         if (d_summary) (void)hipFree(d_summary);
         if (d_io) (void)hipFree(d_io);
-        if (d_range_ids) (void)hipFree(d_range_ids);
+        if (range_plan.d_ids) (void)hipFree(range_plan.d_ids);
+        if (data_range_plan.d_ids) (void)hipFree(data_range_plan.d_ids);
         if (d_range_summary) (void)hipFree(d_range_summary);
     }
 };
@@ -1117,6 +1148,34 @@ BatchIo with_basis(BatchIo x, const mcf_rbatch_basis_io *basis)
 BatchIo io_of(const mcf_ubatch_check_io *io) { return with_strides(check_io(io), io); }
 BatchIo io_of(const mcf_rbatch_check_io *io) { return check_io(io); }
 
+// The arrays of a data-ranges call, whichever of the two public structs they came in (data_range_io_of): the uniform struct's one pair
+// list or the ragged struct's tables, never both.
+struct DataRangeIo {
+    bool given;
+    int32_t memory;
+    const int32_t *pairs;
+    int64_t pair_count;                 // the uniform struct's
+    const int64_t *pair_row, *ship_row; // the ragged struct's
+    int32_t *ranged;
+    int8_t *arc_state;
+    int64_t *flow_down, *flow_up, *ship_forth, *ship_back;
+};
+DataRangeIo data_range_io_of(const mcf_ubatch_data_range_io *io)
+{
+    if (!io) return DataRangeIo{};
+    return DataRangeIo{true, io->memory, io->pairs, io->pair_count, nullptr, nullptr, io->ranged, io->arc_state, io->flow_down, io->flow_up, io->ship_forth, io->ship_back};
+}
+DataRangeIo data_range_io_of(const mcf_rbatch_data_range_io *io)
+{
+    if (!io) return DataRangeIo{};
+    return DataRangeIo{true, io->memory, io->pairs, 0, io->pair_row, io->ship_row, io->ranged, io->arc_state, io->flow_down, io->flow_up, io->ship_forth, io->ship_back};
+}
+// how many pairs and ship entries a call's arrays hold, where the host can know (the tables of a ragged MCF_MEM_DEVICE call lie on the device)
+struct PairSizes {
+    bool known;
+    size_t pairs, ships;
+};
+
 mcf::UniformOutputs outputs_of(const BatchIo &io)
 {
     return mcf::UniformOutputs{io.status, io.pivots, io.total_cost, io.flows, io.potentials, io.trace};
@@ -1183,6 +1242,23 @@ struct UniformPlacement {
     {
         hipLaunchKernelGGL(in_lds ? ranges_kernel_in_lds : uniform_ranges_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, p, o, slots, slab, ids);
     }
+    static constexpr auto data_ranges_kernel_in_lds = uniform_data_ranges_kernel<true>;
+    static void launch_data_ranges(const Handle *, bool in_lds, unsigned blocks, uint32_t lds, const Problem &p, const mcf::DataRangeOutputs &o, const DataRangeIo &io,
+                                   const BatchSlot *slots, unsigned char *slab, const int32_t *ids)
+    {
+        hipLaunchKernelGGL(in_lds ? data_ranges_kernel_in_lds : uniform_data_ranges_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, p, o, io.pairs,
+                           io.pair_count, slots, slab, ids);
+    }
+    // one list for every instance
+    static int check_pairs(const Handle *b, const DataRangeIo &io, const char *what, PairSizes *sizes)
+    {
+        if (io.pair_count < 0) return mcf::fail(MCF_ERR_INVALID, "%s: negative pair count", what);
+        if (io.pair_count > 0 && !io.pairs) return mcf::fail(MCF_ERR_INVALID, "%s: null pairs", what);
+        if (io.ship_forth && io.pair_count == 0) return mcf::fail(MCF_ERR_INVALID, "%s: ship rows without pairs", what);
+        *sizes = PairSizes{true, (size_t)io.pair_count, (size_t)b->d.count * (size_t)io.pair_count};
+        return MCF_OK;
+    }
+    static mcf::PairList pair_list(const Handle *, const DataRangeIo &io, int64_t i) { return mcf::uniform_pairs(io.pairs, io.pair_count, i); }
     static void sizes(const Handle *b, size_t, int32_t *n, int32_t *m) { *n = b->d.node_count; *m = b->d.arc_count; }
     static size_t arc_rows(const Handle *b) { return (size_t)b->d.count * (size_t)b->d.arc_count; }
     static size_t slab_bytes(const Handle *b) { return (size_t)b->d.count * (size_t)b->stride; }
@@ -1262,6 +1338,41 @@ struct RaggedPlacement {
                               unsigned char *slab, const int32_t *ids)
     {
         hipLaunchKernelGGL(in_lds ? ranges_kernel_in_lds : ragged_ranges_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, r, o, slots, slab, ids);
+    }
+    static constexpr auto data_ranges_kernel_in_lds = ragged_data_ranges_kernel<true>;
+    static void launch_data_ranges(const Handle *, bool in_lds, unsigned blocks, uint32_t lds, const Problem &r, const mcf::DataRangeOutputs &o, const DataRangeIo &io,
+                                   const BatchSlot *slots, unsigned char *slab, const int32_t *ids)
+    {
+        hipLaunchKernelGGL(in_lds ? data_ranges_kernel_in_lds : ragged_data_ranges_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, r, o, io.pairs, io.pair_row,
+                           io.ship_row, slots, slab, ids);
+    }
+    // one list per graph: pair_row says where each begins, ship_row where each instance's answers do.  Tables in host memory are checked
+    // against each other; tables in device memory are the caller's word, as the rows of every call are.
+    static int check_pairs(const Handle *b, const DataRangeIo &io, const char *what, PairSizes *sizes)
+    {
+        const size_t count = (size_t)b->d.count, G = b->graphs.size();
+        if (!io.pair_row != !io.ship_row) return mcf::fail(MCF_ERR_INVALID, "%s: pair_row and ship_row come together or not at all", what);
+        if (io.pairs && !io.pair_row) return mcf::fail(MCF_ERR_INVALID, "%s: pairs without pair_row and ship_row", what);
+        if (io.ship_forth && !io.pair_row) return mcf::fail(MCF_ERR_INVALID, "%s: ship rows without pairs", what);
+        *sizes = PairSizes{!io.pair_row, 0, 0};
+        if (!io.pair_row || io.memory != MCF_MEM_HOST) return MCF_OK;
+        if (io.pair_row[0] != 0 || io.ship_row[0] != 0) return mcf::fail(MCF_ERR_INVALID, "%s: pair_row and ship_row begin at 0", what);
+        for (size_t g = 0; g < G; ++g)
+            if (io.pair_row[g + 1] < io.pair_row[g]) return mcf::fail(MCF_ERR_INVALID, "%s: negative pair count of graph %zu", what, g);
+        for (size_t i = 0; i < count; ++i) {
+            const size_t g = (size_t)b->graph_of[i];
+            if (io.ship_row[i + 1] - io.ship_row[i] != io.pair_row[g + 1] - io.pair_row[g])
+                return mcf::fail(MCF_ERR_INVALID, "%s: ship_row gives instance %zu %lld answers, its graph has %lld pairs", what, i,
+                                 (long long)(io.ship_row[i + 1] - io.ship_row[i]), (long long)(io.pair_row[g + 1] - io.pair_row[g]));
+        }
+        if (io.pair_row[G] > 0 && !io.pairs) return mcf::fail(MCF_ERR_INVALID, "%s: null pairs", what);
+        if (io.ship_forth && io.ship_row[count] == 0 && io.pair_row[G] == 0) return mcf::fail(MCF_ERR_INVALID, "%s: ship rows without pairs", what);
+        *sizes = PairSizes{true, (size_t)io.pair_row[G], (size_t)io.ship_row[count]};
+        return MCF_OK;
+    }
+    static mcf::PairList pair_list(const Handle *b, const DataRangeIo &io, int64_t i)
+    {
+        return mcf::ragged_pairs(io.pairs, io.pair_row, io.ship_row, b->graph_of[(size_t)i], i);
     }
     static void sizes(const Handle *b, size_t i, int32_t *n, int32_t *m) { const mcf::RaggedGraph &g = b->graphs[(size_t)b->graph_of[i]]; *n = g.n; *m = g.m; }
     static size_t arc_rows(const Handle *b) { return (size_t)b->arc_row[(size_t)b->d.count]; }
@@ -1761,12 +1872,13 @@ int check_range_call(const PlacedBatch *b, const RangeIo &io, const char *what, 
     return MCF_OK;
 }
 
-// the instances by tier and, in the LDS tier, by the class of what the ranges kernel keeps there; the table goes up once per handle
-// (again only if the device's LDS limit were another).  An instance is ranged in LDS exactly when it is solved there.
-template <class P>
-int ensure_range_plan(typename P::Handle *b)
+// the instances by tier and, in the LDS tier, by the class of what a ranges kernel keeps there (footprint(n, m), never more than the
+// solve's); the table goes up once per handle and plan (again only if the device's LDS limit were another).  An instance is ranged in
+// LDS exactly when it is solved there.
+template <class P, class Footprint>
+int ensure_range_plan(typename P::Handle *b, PlacedBatch::RangePlan &rp, Footprint footprint)
 {
-    if (b->d_range_ids && b->range_lds_max == b->lds_max) return MCF_OK;
+    if (rp.d_ids && rp.lds_max == b->lds_max) return MCF_OK;
     const size_t count = (size_t)b->d.count;
     const LaunchPlan plan = P::plan(b);
     std::vector<int32_t> group[kClasses];
@@ -1774,12 +1886,12 @@ int ensure_range_plan(typename P::Handle *b)
     for (size_t i = 0; i < count; ++i) {
         int32_t n = 0, m = 0;
         P::sizes(b, i, &n, &m);
-        bytes[i] = mcf::range_layout_of((uint32_t)(m + 2 * n), (uint32_t)n + 1u, (uint32_t)m).bytes;       // no more than plan.bytes(i)
+        bytes[i] = footprint(n, m);                                         // no more than plan.bytes(i)
         const bool in_lds = class_of(b->lds_max, plan.bytes((int32_t)i)) != kClasses - 1;
         group[in_lds ? class_of(b->lds_max, bytes[i]) : kClasses - 1].push_back((int32_t)i);
     }
     std::vector<int32_t> ids;
-    b->range_launches.clear();
+    rp.launches.clear();
     for (int g = 0; g < kClasses; ++g) {
         if (group[g].empty()) continue;
         PlacedBatch::RangeLaunch L{(int)ids.size(), (int)group[g].size(), 0, g != kClasses - 1};
@@ -1787,14 +1899,16 @@ int ensure_range_plan(typename P::Handle *b)
             ids.push_back(i);
             if (L.in_lds) L.lds = std::max(L.lds, bytes[(size_t)i]);
         }
-        b->range_launches.push_back(L);
+        rp.launches.push_back(L);
     }
-    if (!b->d_range_ids) HIP_TRY(hipMalloc((void **)&b->d_range_ids, count * sizeof(int32_t)));
+    if (!rp.d_ids) HIP_TRY(hipMalloc((void **)&rp.d_ids, count * sizeof(int32_t)));
     if (!b->d_range_summary) HIP_TRY(hipMalloc((void **)&b->d_range_summary, 3 * sizeof(int64_t)));
-    HIP_TRY(hipMemcpy(b->d_range_ids, ids.data(), count * sizeof(int32_t), hipMemcpyHostToDevice));
-    b->range_lds_max = b->lds_max;
+    HIP_TRY(hipMemcpy(rp.d_ids, ids.data(), count * sizeof(int32_t), hipMemcpyHostToDevice));
+    rp.lds_max = b->lds_max;
     return MCF_OK;
 }
+inline uint32_t range_footprint(int32_t n, int32_t m) { return mcf::range_layout_of((uint32_t)(m + 2 * n), (uint32_t)n + 1u, (uint32_t)m).bytes; }
+inline uint32_t data_range_footprint(int32_t n, int32_t m) { return mcf::data_range_layout_of((uint32_t)m, (uint32_t)n + 1u).bytes; }
 
 template <class P>
 int ranges_on_device(typename P::Handle *b, RangeIo io, const char *what)
@@ -1810,8 +1924,8 @@ int ranges_on_device(typename P::Handle *b, RangeIo io, const char *what)
     if (b->lds_max > (64 << 10))                                            // the opt-in open_device got for the solve's kernels
         HIP_TRY(hipFuncSetAttribute((const void *)P::ranges_kernel_in_lds, hipFuncAttributeMaxDynamicSharedMemorySize, b->lds_max));
     if (const int rc = ensure_device_buffers<P>(b)) return rc;
-    const bool first = !b->d_range_ids;
-    if (const int rc = ensure_range_plan<P>(b)) return rc;
+    const bool first = !b->range_plan.d_ids;
+    if (const int rc = ensure_range_plan<P>(b, b->range_plan, range_footprint)) return rc;
     if (first) st.bytes_up += (int64_t)(count * sizeof(int32_t));
     if (const int rc = state_to_device(b, count, &st.bytes_up)) return rc;
     b->where = PlacedBatch::kOnDevice;                                      // the same state, now there too
@@ -1833,8 +1947,8 @@ int ranges_on_device(typename P::Handle *b, RangeIo io, const char *what)
     const mcf::RangeOutputs o{io.ranged, io.arc_state, io.cost_down, io.cost_up, b->d_range_summary};
     const typename P::Problem p = P::problem(b, BatchIo{}, true);
     const double t_launch = mcf::now_ns();
-    for (const PlacedBatch::RangeLaunch &L : b->range_launches) {
-        P::launch_ranges(b, L.in_lds, (unsigned)L.n, L.lds, p, o, b->dev.slots, b->dev.slab, b->d_range_ids + L.first);
+    for (const PlacedBatch::RangeLaunch &L : b->range_plan.launches) {
+        P::launch_ranges(b, L.in_lds, (unsigned)L.n, L.lds, p, o, b->dev.slots, b->dev.slab, b->range_plan.d_ids + L.first);
         HIP_TRY(hipGetLastError());
         (L.in_lds ? st.lds_instances : st.global_instances) += L.n;
     }
@@ -1878,6 +1992,118 @@ int get_range_stats(const PlacedBatch *b, mcf_ubatch_range_stats *out)
 {
     if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
     *out = b->range_stats;
+    return MCF_OK;
+}
+
+// ---- mcf_*batch_data_ranges / _on_host: uniform_data_ranges for every instance, on the state the last solve call left; it is only read
+template <class P>
+int check_data_range_call(const typename P::Handle *b, const DataRangeIo &io, const char *what, bool host_only, PairSizes *sizes)
+{
+    if (!b || !io.given) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
+    if (io.memory != MCF_MEM_HOST && io.memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io.memory);
+    if (host_only && io.memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
+    if (!io.flow_down != !io.flow_up) return mcf::fail(MCF_ERR_INVALID, "%s: flow_down and flow_up come together or not at all", what);
+    if (!io.ship_forth != !io.ship_back) return mcf::fail(MCF_ERR_INVALID, "%s: ship_forth and ship_back come together or not at all", what);
+    if (const int rc = P::check_pairs(b, io, what, sizes)) return rc;
+    if (b->where == PlacedBatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
+    return MCF_OK;
+}
+
+template <class P>
+int data_ranges_on_device(typename P::Handle *b, DataRangeIo io, const char *what)
+{
+    PairSizes sizes{};
+    if (const int rc = check_data_range_call<P>(b, io, what, false, &sizes)) return rc;
+    if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
+    const DeviceGuard guard;
+    if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
+    const size_t count = (size_t)b->d.count;
+    mcf_ubatch_data_range_stats st{};
+    st.instances = (int64_t)count;
+    if (!count) { b->data_range_stats = st; return MCF_OK; }
+    if (b->lds_max > (64 << 10))                                            // the opt-in open_device got for the solve's kernels
+        HIP_TRY(hipFuncSetAttribute((const void *)P::data_ranges_kernel_in_lds, hipFuncAttributeMaxDynamicSharedMemorySize, b->lds_max));
+    if (const int rc = ensure_device_buffers<P>(b)) return rc;
+    const bool first = !b->data_range_plan.d_ids;
+    if (const int rc = ensure_range_plan<P>(b, b->data_range_plan, data_range_footprint)) return rc;
+    if (first) st.bytes_up += (int64_t)(count * sizeof(int32_t));
+    if (const int rc = state_to_device(b, count, &st.bytes_up)) return rc;
+    b->where = PlacedBatch::kOnDevice;                                      // the same state, now there too
+    Staged staged;                                                          // MCF_MEM_HOST: pairs and tables go up, the rows come down, through the staging buffer of the solve calls
+    if (io.memory == MCF_MEM_HOST) {
+        const size_t arcs = P::arc_rows(b), graphs = P::template_count(b);
+        size_t at[9] = {};
+        if (io.pairs && sizes.pairs) at[0] = staged.add(io.pairs, nullptr, 8 * sizes.pairs);
+        if (io.pair_row) { at[1] = staged.add(io.pair_row, nullptr, 8 * (graphs + 1)); at[2] = staged.add(io.ship_row, nullptr, 8 * (count + 1)); }
+        if (io.ranged) at[3] = staged.add(nullptr, io.ranged, 4 * count);
+        if (io.arc_state) at[4] = staged.add(nullptr, io.arc_state, arcs);
+        if (io.flow_down) { at[5] = staged.add(nullptr, io.flow_down, 8 * arcs); at[6] = staged.add(nullptr, io.flow_up, 8 * arcs); }
+        if (io.ship_forth) { at[7] = staged.add(nullptr, io.ship_forth, 8 * sizes.ships); at[8] = staged.add(nullptr, io.ship_back, 8 * sizes.ships); }
+        if (const int rc = reserve_io(b, std::max<size_t>(staged.total, 16))) return rc;
+        for (const Staged::Piece &piece : staged.pieces)
+            if (piece.host_in && piece.bytes) {
+                HIP_TRY(hipMemcpy(b->d_io + piece.offset, piece.host_in, piece.bytes, hipMemcpyHostToDevice));
+                st.bytes_up += (int64_t)piece.bytes;
+            }
+        if (io.pairs && sizes.pairs) io.pairs = (const int32_t *)(b->d_io + at[0]); else io.pairs = nullptr;
+        if (io.pair_row) { io.pair_row = (const int64_t *)(b->d_io + at[1]); io.ship_row = (const int64_t *)(b->d_io + at[2]); }
+        if (io.ranged) io.ranged = (int32_t *)(b->d_io + at[3]);
+        if (io.arc_state) io.arc_state = (int8_t *)(b->d_io + at[4]);
+        if (io.flow_down) { io.flow_down = (int64_t *)(b->d_io + at[5]); io.flow_up = (int64_t *)(b->d_io + at[6]); }
+        if (io.ship_forth) { io.ship_forth = (int64_t *)(b->d_io + at[7]); io.ship_back = (int64_t *)(b->d_io + at[8]); }
+    }
+    int64_t words[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpy(b->d_range_summary, words, sizeof(words), hipMemcpyHostToDevice));
+    st.bytes_up += (int64_t)sizeof(words);
+    const mcf::DataRangeOutputs o{io.ranged, io.arc_state, io.flow_down, io.flow_up, io.ship_forth, io.ship_back, b->d_range_summary};
+    const typename P::Problem p = P::problem(b, BatchIo{}, true);
+    const double t_launch = mcf::now_ns();
+    for (const PlacedBatch::RangeLaunch &L : b->data_range_plan.launches) {
+        P::launch_data_ranges(b, L.in_lds, (unsigned)L.n, L.lds, p, o, io, b->dev.slots, b->dev.slab, b->data_range_plan.d_ids + L.first);
+        HIP_TRY(hipGetLastError());
+        (L.in_lds ? st.lds_instances : st.global_instances) += L.n;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    st.kernel_ns = mcf::now_ns() - t_launch;
+    HIP_TRY(hipMemcpy(words, b->d_range_summary, sizeof(words), hipMemcpyDeviceToHost));
+    st.bytes_down += (int64_t)sizeof(words);
+    if (const int rc = stage_down(b, staged, &st.bytes_down)) return rc;
+    st.ranged = words[0]; st.walks = words[1]; st.hops = words[2];
+    b->data_range_stats = st;
+    return MCF_OK;
+}
+
+template <class P>
+int data_ranges_on_host(typename P::Handle *b, const DataRangeIo &io, const char *what)
+{
+    PairSizes sizes{};
+    if (const int rc = check_data_range_call<P>(b, io, what, true, &sizes)) return rc;
+    const size_t count = (size_t)b->d.count;
+    b->h_slab.resize(P::slab_bytes(b));
+    b->h_slots.resize(count);
+    if (const int rc = state_to_host(b, b->d.device, count)) return rc;
+    b->where = PlacedBatch::kOnHost;                                        // the same state, now here too
+    mcf_ubatch_data_range_stats st{};
+    st.instances = (int64_t)count;
+    int64_t words[3] = {0, 0, 0};
+    const mcf::DataRangeOutputs o{io.ranged, io.arc_state, io.flow_down, io.flow_up, io.ship_forth, io.ship_back, words};
+    const typename P::Problem p = P::problem(b, BatchIo{}, false);
+    const mcf::UniformOutputs none{};
+    const double t_start = mcf::now_ns();
+    for (size_t i = 0; i < count; ++i) {
+        const BatchSlot *tmpl = nullptr;
+        mcf::uniform_data_ranges<false>(P::view(b, p, none, (int64_t)i, b->h_slab.data(), &tmpl), o, P::pair_list(b, io, (int64_t)i), b->h_slots[i], nullptr, 0, 1);
+    }
+    st.kernel_ns = mcf::now_ns() - t_start;
+    st.ranged = words[0]; st.walks = words[1]; st.hops = words[2];
+    b->data_range_stats = st;
+    return MCF_OK;
+}
+
+int get_data_range_stats(const PlacedBatch *b, mcf_ubatch_data_range_stats *out)
+{
+    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
+    *out = b->data_range_stats;
     return MCF_OK;
 }
 
@@ -2037,6 +2263,12 @@ int mcf_ubatch_get_start_stats(mcf_ubatch *b, mcf_ubatch_start_stats *out) { ret
 int mcf_ubatch_cost_ranges(mcf_ubatch *b, const mcf_ubatch_range_io *io) { return ranges_on_device<UniformPlacement>(b, range_io_of(io), "mcf_ubatch_cost_ranges"); }
 int mcf_ubatch_cost_ranges_on_host(mcf_ubatch *b, const mcf_ubatch_range_io *io) { return ranges_on_host<UniformPlacement>(b, range_io_of(io), "mcf_ubatch_cost_ranges_on_host"); }
 int mcf_ubatch_get_range_stats(mcf_ubatch *b, mcf_ubatch_range_stats *out) { return get_range_stats(b, out); }
+int mcf_ubatch_data_ranges(mcf_ubatch *b, const mcf_ubatch_data_range_io *io) { return data_ranges_on_device<UniformPlacement>(b, data_range_io_of(io), "mcf_ubatch_data_ranges"); }
+int mcf_ubatch_data_ranges_on_host(mcf_ubatch *b, const mcf_ubatch_data_range_io *io)
+{
+    return data_ranges_on_host<UniformPlacement>(b, data_range_io_of(io), "mcf_ubatch_data_ranges_on_host");
+}
+int mcf_ubatch_get_data_range_stats(mcf_ubatch *b, mcf_ubatch_data_range_stats *out) { return get_data_range_stats(b, out); }
 
 void mcf_rbatch_destroy(mcf_rbatch *b) { delete b; }
 int mcf_rbatch_solve(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_device<RaggedPlacement>(b, io_of(io), kFresh, "mcf_rbatch_solve"); }
@@ -2067,5 +2299,11 @@ int mcf_rbatch_get_start_stats(mcf_rbatch *b, mcf_ubatch_start_stats *out) { ret
 int mcf_rbatch_cost_ranges(mcf_rbatch *b, const mcf_rbatch_range_io *io) { return ranges_on_device<RaggedPlacement>(b, range_io_of(io), "mcf_rbatch_cost_ranges"); }
 int mcf_rbatch_cost_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_range_io *io) { return ranges_on_host<RaggedPlacement>(b, range_io_of(io), "mcf_rbatch_cost_ranges_on_host"); }
 int mcf_rbatch_get_range_stats(mcf_rbatch *b, mcf_ubatch_range_stats *out) { return get_range_stats(b, out); }
+int mcf_rbatch_data_ranges(mcf_rbatch *b, const mcf_rbatch_data_range_io *io) { return data_ranges_on_device<RaggedPlacement>(b, data_range_io_of(io), "mcf_rbatch_data_ranges"); }
+int mcf_rbatch_data_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_data_range_io *io)
+{
+    return data_ranges_on_host<RaggedPlacement>(b, data_range_io_of(io), "mcf_rbatch_data_ranges_on_host");
+}
+int mcf_rbatch_get_data_range_stats(mcf_rbatch *b, mcf_ubatch_data_range_stats *out) { return get_data_range_stats(b, out); }
 
 }  // extern "C"

@@ -488,6 +488,86 @@ class RaggedRanges(UniformRanges):
         return tuple(None if a is None else a[lo:hi] for a in (self.arc_state, self.cost_down, self.cost_up))
 
 
+class UniformDataRanges:
+    """What UniformBatch.data_ranges returns: one row per instance, numpy arrays or tensors.  ranged and arc_state as in UniformRanges.  For
+    a ranged instance the kept basis stays primal feasible -- a resolve_data() that changes this one thing makes no pivot and does not
+    fall back -- while arc e's flow, moved alone, falls by at most flow_down[i, e] or rises by at most flow_up[i, e] (a non-tree arc's are
+    not clipped by its own capacity), and while d units of supply move from node b to node a of pair k (supply[a] + d, supply[b] - d)
+    with d <= ship_forth[i, k], or the other way with d <= ship_back[i, k].  RANGE_INF = no limit; a pair (a, a) gives RANGE_INF twice, a
+    pair with an id out of range -1 twice.  Rows of every other instance are zero.  Rows that were not asked for are None.
+    bounds(lower, upper) turns the flow rows into the ranges of the bounds."""
+    __slots__ = ("ranged", "arc_state", "flow_down", "flow_up", "ship_forth", "ship_back")
+    FIELDS = (("ranged", "int32", ""), ("arc_state", "int8", "m"), ("flow_down", "int64", "m"), ("flow_up", "int64", "m"),
+              ("ship_forth", "int64", "p"), ("ship_back", "int64", "p"))
+    RANGE_INF = L.RANGE_INF
+
+    def __init__(self, **arrays):
+        for name, _, _ in self.FIELDS:
+            setattr(self, name, arrays.get(name))
+
+    def _ranged_per_arc(self, xp):
+        return self.ranged[:, None] != 0
+
+    def bounds(self, lower, upper):
+        """(lower may fall by, lower may rise by, upper may fall by, upper may rise by): four rows shaped like flow_down, from the bounds
+        the last solve call was given (lower None = 0, upper None or INF_CAP = uncapacitated; [m] rows are shared by all instances).
+
+            arc_state | lower falls | lower rises            | upper falls              | upper rises
+            LOWER  1  | flow_down   | min(flow_up, capacity) | capacity                 | RANGE_INF
+            UPPER -1  | RANGE_INF   | capacity               | min(flow_down, capacity) | flow_up
+            TREE   0  | RANGE_INF   | flow_down              | flow_up                  | RANGE_INF
+
+        capacity = upper - lower.  RANGE_INF = no limit; for an uncapacitated arc it says in the upper columns that there is no finite
+        upper bound to move.  Rows of instances that are not ranged are zero."""
+        if self.flow_down is None or self.arc_state is None:
+            raise ValueError("bounds() needs arc_state, flow_down and flow_up: data_ranges(flows=True)")
+        down, up, state = self.flow_down, self.flow_up, self.arc_state
+        tensors = _is_tensor(down)
+        if tensors:
+            import torch as xp
+            as_rows = lambda a: a if _is_tensor(a) else xp.as_tensor(np.asarray(a, np.int64), device=down.device)
+        else:
+            xp = np
+            as_rows = lambda a: np.asarray(a.cpu().numpy() if _is_tensor(a) else a, np.int64)
+        inf = xp.full_like(down, L.RANGE_INF)
+        zero = xp.zeros_like(down)
+        lo = zero if lower is None else as_rows(lower) + zero
+        hi = inf if upper is None else as_rows(upper) + zero
+        cap = xp.where(hi == L.INF_CAP, inf, hi - xp.where(hi == L.INF_CAP, zero, lo))
+        at_lower, at_upper = state == 1, state == -1
+        rows = (xp.where(at_lower, down, inf),
+                xp.where(at_lower, xp.minimum(up, cap), xp.where(at_upper, cap, down)),
+                xp.where(at_lower, cap, xp.where(at_upper, xp.minimum(down, cap), up)),
+                xp.where(at_upper, up, inf))
+        ranged = self._ranged_per_arc(xp)
+        return tuple(xp.where(ranged, r, zero) for r in rows)
+
+
+class RaggedDataRanges(UniformDataRanges):
+    """What RaggedBatch.data_ranges returns: UniformDataRanges' fields FLAT -- instance i's arcs are [arc_rows[i], arc_rows[i + 1]), its
+    answers to its graph's pairs [ship_rows[i], ship_rows[i + 1]); arcs(i) returns (arc_state, flow_down, flow_up) and ships(i)
+    (ship_forth, ship_back) of instance i as views."""
+    __slots__ = ("arc_rows", "ship_rows")
+
+    def __init__(self, arc_rows, ship_rows, **arrays):
+        super().__init__(**arrays)
+        self.arc_rows, self.ship_rows = arc_rows, ship_rows
+
+    def arcs(self, i: int):
+        lo, hi = int(self.arc_rows[i]), int(self.arc_rows[i + 1])
+        return tuple(None if a is None else a[lo:hi] for a in (self.arc_state, self.flow_down, self.flow_up))
+
+    def ships(self, i: int):
+        lo, hi = int(self.ship_rows[i]), int(self.ship_rows[i + 1])
+        return tuple(None if a is None else a[lo:hi] for a in (self.ship_forth, self.ship_back))
+
+    def _ranged_per_arc(self, xp):
+        counts = np.diff(self.arc_rows)
+        if xp is np:
+            return np.repeat(self.ranged != 0, counts)
+        return xp.repeat_interleave(self.ranged != 0, xp.as_tensor(counts, device=self.ranged.device))
+
+
 class _PlacedBatch:
     """What UniformBatch and RaggedBatch share: the checks of every array of a call, the calls and their results.  A subclass has the
     constructor (which sets _h, _last = None, count, device, record_trace) and says what differs:
@@ -700,6 +780,65 @@ class _PlacedBatch:
         """What the last cost_ranges() / cost_ranges_on_host() did: instances, ranged ones, tiers, tree arcs ranged, cycle hops, kernel time."""
         st = L.UBatchRangeStats(); L.check(self._fn("get_range_stats")(self._h, C.byref(st))); return st.as_dict()
 
+    # ---- supply and bound ranges of the kept basis
+    def _pair_array(self, pairs, tensors, name="pairs"):
+        """[k, 2] int32 node ids where the call's arrays lie"""
+        if tensors:
+            import torch
+            if not _is_tensor(pairs):
+                pairs = torch.as_tensor(np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2)), device=f"cuda:{self.device}")
+            if pairs.device.type != "cuda" or (pairs.device.index or 0) != self.device:
+                raise ValueError(f"{name}: tensor on {pairs.device}, the batch runs on cuda:{self.device}")
+            if pairs.dtype != torch.int32:
+                raise ValueError(f"{name}: dtype {pairs.dtype}, expected int32")
+            if pairs.dim() != 2 or pairs.shape[1] != 2:
+                raise ValueError(f"{name}: shape {tuple(pairs.shape)}, expected (pairs, 2)")
+            return pairs.contiguous()
+        if _is_tensor(pairs):
+            raise ValueError(f"{name}: numpy arrays and tensors cannot be mixed in one call")
+        a = np.asarray(pairs)
+        if a.size == 0:
+            a = np.zeros((0, 2), np.int32)
+        if a.dtype.kind not in "iu" or a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError(f"{name}: expected integer node ids of shape (pairs, 2), got {a.dtype} {a.shape}")
+        if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):
+            raise ValueError(f"{name}: node ids outside int32")
+        return np.ascontiguousarray(a, np.int32)
+
+    def _data_ranges(self, fn, pairs, tensors, flows):
+        if tensors is None:
+            tensors = self._last is not None and _is_tensor(self._last.status)
+        io = self._DATA_RANGE_IO()
+        io.memory = L.MEM_DEVICE if tensors else L.MEM_HOST
+        keep = []
+        ships, ship_rows = self._pairs_into(io, pairs, tensors, keep)           # the shape of the ship rows (None: no pairs)
+        sizes = dict(self._sizes(), p=ships)
+        out = {}
+        for name, dtype, dim in UniformDataRanges.FIELDS:
+            if (not flows and name in ("flow_down", "flow_up")) or (ships is None and dim == "p"):
+                continue
+            out[name] = self._empty(sizes[dim], dtype, tensors)
+            setattr(io, name, out[name].data_ptr() if tensors else out[name].ctypes.data)
+        L.check(self._fn(fn)(self._h, C.byref(io)))
+        return self._data_range_result(out, ship_rows)
+
+    def data_ranges(self, pairs=None, tensors=None, flows=True):
+        """Right-hand-side ranging of the basis every instance's last solve call left, on the device: a UniformDataRanges /
+        RaggedDataRanges.  pairs: node pairs (a, b) to ask the supply ranges of -- UniformBatch: one [k, 2] list for every instance;
+        RaggedBatch: one such list per graph.  tensors: True = tensors on the handle's device (nothing that scales with the batch crosses
+        the bus; pairs given as a tensor are read where they lie), False = numpy arrays, None = like the last result.  flows=False leaves
+        flow_down and flow_up out.  Ask before a resolve_data(): a change inside the range is answered from the kept basis with no
+        pivot.  The kept state is read, never changed: solve calls and this one mix in any order."""
+        return self._data_ranges("data_ranges", pairs, tensors, flows)
+
+    def data_ranges_on_host(self, pairs=None, flows=True):
+        """Test hook: data_ranges() with one lane on the CPU.  numpy only."""
+        return self._data_ranges("data_ranges_on_host", pairs, False, flows)
+
+    def data_range_stats(self) -> dict:
+        """What the last data_ranges() / data_ranges_on_host() did: instances, ranged ones, tiers, walks, hops, kernel time."""
+        st = L.UBatchDataRangeStats(); L.check(self._fn("get_data_range_stats")(self._h, C.byref(st))); return st.as_dict()
+
     # ---- validation: the solution's rows where they lie
     SOLUTION_ROWS = (("status", "int32", None), ("total_cost", "int64", None), ("flows", "int64", "arc_count"), ("potentials", "int64", "node_count"))
 
@@ -764,6 +903,23 @@ class UniformBatch(_PlacedBatch):
                          self.node_count, self.arc_count, self.count, src.ctypes.data, tgt.ctypes.data)
         L.check(L.lib().mcf_ubatch_create(C.byref(self._h), C.byref(d)))
 
+    _DATA_RANGE_IO = L.UBatchDataRangeIo
+
+    def _pairs_into(self, io, pairs, tensors, keep):
+        """one list for every instance: ship rows [count, k]"""
+        if pairs is None:
+            return None, None
+        a = self._pair_array(pairs, tensors)
+        if a.shape[0] == 0:
+            return None, None
+        keep.append(a)
+        io.pair_count = int(a.shape[0])
+        io.pairs = a.data_ptr() if tensors else a.ctypes.data
+        return (self.count, int(a.shape[0])), None
+
+    def _data_range_result(self, out, ship_rows):
+        return UniformDataRanges(**out)
+
     def _sizes(self):
         return {"": (self.count,), "m": (self.count, self.arc_count), "n": (self.count, self.node_count), "t": (self.count, self.record_trace)}
 
@@ -815,6 +971,7 @@ class RaggedBatch(_PlacedBatch):
         if of is not None and of.ndim != 1:
             raise ValueError("graph_of must be one-dimensional")
         self.count = self.graph_count if of is None else int(of.shape[0])
+        self._graph_of = np.arange(self.graph_count) if of is None else of.astype(np.int64)
         self._h = C.c_void_p()
         self._last = None               # the last RaggedResult: a masked resolve() starts from its rows
         d = L.RBatchDesc(self.device, int(rule), int(semantics), 0, int(pivot_limit), int(pivots_per_launch), self.record_trace, int(flags),
@@ -830,6 +987,45 @@ class RaggedBatch(_PlacedBatch):
 
     def _ranges(self, out):
         return RaggedRanges(self.arc_rows, **out)
+
+    _DATA_RANGE_IO = L.RBatchDataRangeIo
+
+    def _pairs_into(self, io, pairs, tensors, keep):
+        """one list per graph, flat, with pair_row (where each graph's begins) and ship_row (where each instance's answers do); the two
+        tables are built here and, for a call on tensors, kept on the device while the lists' lengths stay the same"""
+        if pairs is None:
+            return None, None
+        pairs = list(pairs)
+        if len(pairs) != self.graph_count:
+            raise ValueError(f"pairs: {len(pairs)} lists, the batch has {self.graph_count} graphs (one list per graph)")
+        lists = [self._pair_array(p, tensors, f"pairs[{g}]") for g, p in enumerate(pairs)]
+        lengths = tuple(int(a.shape[0]) for a in lists)
+        if sum(lengths) == 0:
+            return None, None
+        key = (lengths, bool(tensors))
+        if getattr(self, "_pair_tables", (None,))[0] != key:
+            pair_row = np.zeros(self.graph_count + 1, np.int64)
+            np.cumsum(lengths, out=pair_row[1:])
+            ship_rows = np.zeros(self.count + 1, np.int64)
+            np.cumsum(np.asarray(lengths, np.int64)[self._graph_of], out=ship_rows[1:])
+            tables = (pair_row, ship_rows)
+            if tensors:
+                import torch
+                tables = tuple(torch.as_tensor(t, device=f"cuda:{self.device}") for t in tables)
+            self._pair_tables = (key, tables, ship_rows)
+        _, tables, ship_rows = self._pair_tables
+        if tensors:
+            import torch
+            flat = torch.cat(lists).contiguous()
+        else:
+            flat = np.ascontiguousarray(np.concatenate(lists))
+        keep.extend((flat,) + tuple(tables))
+        ptr = (lambda a: a.data_ptr()) if tensors else (lambda a: a.ctypes.data)
+        io.pairs, io.pair_row, io.ship_row = ptr(flat), ptr(tables[0]), ptr(tables[1])
+        return (int(ship_rows[-1]),), ship_rows
+
+    def _data_range_result(self, out, ship_rows):
+        return RaggedDataRanges(self.arc_rows, ship_rows if ship_rows is not None else np.zeros(self.count + 1, np.int64), **out)
 
     def _sizes(self):
         return {"": (self.count,), "m": (self.arc_total,), "n": (self.node_total,), "t": (self.count, self.record_trace)}

@@ -1,7 +1,7 @@
 // rbatch_host_check.cpp -- the host side of the placed batches as a stand-alone program, so that it can be built together with the
 // library's host sources under -fsanitize=address,undefined and run on a CPU ("Ragged batch").  It runs the ragged entry
 // points (mcf_rbatch_create, _run_on_host, _rerun_on_host, _validate_on_host) on its input, exports the first solve's basis
-// (_cost_ranges_on_host) and starts a second handle from it (_run_from_on_host: the same data must give the first solve's status and
+// (_cost_ranges_on_host), asks the same basis' supply and bound ranges (_data_ranges_on_host, pairs included) and starts a second handle from it (_run_from_on_host: the same data must give the first solve's status and
 // total cost; the second costs run for the sanitizer's sake), then the instances of the input's first graph through the uniform entry
 // points (mcf_ubatch_*), which share the drivers, and compares every row of the two.  Needs no GPU and is not loaded into Python.
 //
@@ -100,7 +100,7 @@ int main(int argc, char **argv)
     std::vector<uint8_t> changed((size_t)count);
     for (int i = 0; i < count; ++i) changed[(size_t)i] = i % 3 != 1;
 
-    int64_t pivots_total = 0, invalid_total = 0, started = 0;
+    int64_t pivots_total = 0, invalid_total = 0, started = 0, data_ranged_total = 0, data_walks = 0;
     for (int32_t rule : {MCF_RULE_BLOCK_SEARCH, MCF_RULE_BEST_ELIGIBLE, MCF_RULE_FIRST_ELIGIBLE})
         for (int32_t stype : {MCF_SUPPLY_GEQ, MCF_SUPPLY_LEQ}) {
             mcf_rbatch_desc d{};
@@ -134,6 +134,52 @@ int main(int argc, char **argv)
             mcf_rbatch_range_io rio{};
             rio.memory = MCF_MEM_HOST; rio.ranged = ranged.data(); rio.arc_state = arc_state.data();
             CHECK(mcf_rbatch_cost_ranges_on_host(b, &rio));
+            {
+                // the supply and bound ranges of the same basis: per graph the two ends of every third arc, its first and last node both
+                // ways round, a pair (0, 0) and one with an id out of range; pairs, tables and every output exactly sized
+                std::vector<int32_t> pairs;
+                std::vector<int64_t> pair_row{0}, ship_row{0};
+                for (int g = 0; g < G; ++g) {
+                    const int32_t n = node_count[(size_t)g];
+                    for (int64_t e = arc_start[(size_t)g]; e < arc_start[(size_t)g + 1]; e += 3) { pairs.push_back(source[(size_t)e]); pairs.push_back(target[(size_t)e]); }
+                    for (int32_t v : {0, n - 1, n - 1, 0, 0, 0, n, 0}) pairs.push_back(v);
+                    pair_row.push_back((int64_t)pairs.size() / 2);
+                }
+                for (int i = 0; i < count; ++i) {
+                    const size_t g = (size_t)graph_of[(size_t)i];
+                    ship_row.push_back(ship_row.back() + pair_row[g + 1] - pair_row[g]);
+                }
+                std::vector<int8_t> data_state(lower.size());
+                std::vector<int32_t> data_ranged((size_t)count);
+                std::vector<int64_t> flow_down(lower.size()), flow_up(lower.size()), ship_forth((size_t)ship_row.back()), ship_back((size_t)ship_row.back());
+                mcf_rbatch_data_range_io dio{};
+                dio.memory = MCF_MEM_HOST; dio.pairs = pairs.data(); dio.pair_row = pair_row.data(); dio.ship_row = ship_row.data();
+                dio.ranged = data_ranged.data(); dio.arc_state = data_state.data(); dio.flow_down = flow_down.data(); dio.flow_up = flow_up.data();
+                dio.ship_forth = ship_forth.data(); dio.ship_back = ship_back.data();
+                CHECK(mcf_rbatch_data_ranges_on_host(b, &dio));
+                if (data_state != arc_state || data_ranged != ranged) { fprintf(stderr, "the data ranges name another basis than the cost ranges\n"); return 1; }
+                for (int i = 0; i < count; ++i) {
+                    if (!ranged[(size_t)i]) continue;
+                    const size_t g = (size_t)graph_of[(size_t)i];
+                    int64_t k = ship_row[(size_t)i];
+                    for (int64_t e = 0; e < arc_start[g + 1] - arc_start[g]; e += 3, ++k) {
+                        const size_t at = (size_t)(arc_row[(size_t)i] + e);
+                        if (arc_state[at] != MCF_STATE_TREE && (ship_forth[(size_t)k] != flow_down[at] || ship_back[(size_t)k] != flow_up[at])) {
+                            fprintf(stderr, "instance %d, arc %lld: the pair of its ends ships another amount than the arc's flow may move\n", i, (long long)e);
+                            return 1;
+                        }
+                    }
+                    if (ship_forth[(size_t)k + 2] != MCF_RANGE_INF || ship_back[(size_t)k + 2] != MCF_RANGE_INF || ship_forth[(size_t)k + 3] != -1 || ship_back[(size_t)k + 3] != -1 ||
+                        ship_forth[(size_t)k] != ship_back[(size_t)k + 1] || ship_back[(size_t)k] != ship_forth[(size_t)k + 1]) {
+                        fprintf(stderr, "instance %d: the special pairs' answers\n", i);
+                        return 1;
+                    }
+                    ++data_ranged_total;
+                }
+                mcf_ubatch_data_range_stats ds{};
+                CHECK(mcf_rbatch_get_data_range_stats(b, &ds));
+                data_walks += ds.walks;
+            }
             {
                 mcf_rbatch *from = nullptr;
                 CHECK(mcf_rbatch_create(&from, &d));
@@ -197,7 +243,8 @@ int main(int argc, char **argv)
             mcf_ubatch_destroy(ub);
         }
     printf("ok: %d instances of %d graphs, 3 rules x 2 supply types; %lld pivots in the last re-solves, %lld rows flagged by the first validations; "
-           "%lld starts from an exported basis accepted; the %zu instances of graph 0 as a uniform batch: every row equal\n",
-           count, G, (long long)pivots_total, (long long)invalid_total, (long long)started, sel.size());
+           "%lld starts from an exported basis accepted; %lld instances' supply and bound ranges over %lld walks; "
+           "the %zu instances of graph 0 as a uniform batch: every row equal\n",
+           count, G, (long long)pivots_total, (long long)invalid_total, (long long)started, (long long)data_ranged_total, (long long)data_walks, sel.size());
     return 0;
 }
