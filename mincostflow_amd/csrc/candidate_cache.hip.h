@@ -1,31 +1,23 @@
-// candidate_cache.hip.h -- host side of the exact candidate cache of the resident engine (included by engine.hip only, inside its anonymous
-// namespace, after the resident-grid helpers it posts and collects with).  DESIGN.md section 3.4.
+// candidate_cache.hip.h -- the device-facing side of the exact candidate cache of the resident engine (included by engine.hip only, inside its
+// anonymous namespace, after the resident-grid helpers it posts and collects with).  The cache's decision state and its rules -- epochs, heap,
+// list, admission, decide, install -- are candidate_state.h (plain C++, checked on a CPU by tools/candidate_state_check.cpp); here is what
+// needs the engine: what the device has not heard yet, posting a search, polling for its records.  DESIGN.md section 3.4.
 #pragma once
 
 // ------------------------------------------------------------------------------------------------ candidate cache
-// Best Eligible picks argmin (c, arc) over ALL search arcs with the CURRENT potentials (NS.cs:1644-1667).  A pivot changes the
-// potentials of one subtree and one or two states, so only arcs that touch those nodes change their key; every other arc keeps the key
-// the last device search saw.  A device search returns a sorted candidate list that is COMPLETE below a threshold (every eligible arc
-// with a smaller key is on it) as of the moment it was posted (its epoch).  The host keeps
-//   * the list, and for every node / arc the epoch of its last change: a list entry is CLEAN when nothing of it changed after the list's epoch;
-//   * a min-heap with the current keys of all arcs touched since (re-evaluated from the host mirrors when they are touched; at most
-//     kCandMaxNodes nodes' adjacency per pivot -- a bigger subtree is not evaluated here, the device searches instead).
-// Then, exactly:   min over untouched arcs = first clean list entry (all unlisted untouched arcs lie above the threshold)
-//                  min over touched arcs   = top of the heap
-// and the entering arc is the smaller of the two -- the reference's pivot, arc for arc (every parity test runs with the cache on and off).
 // The list is refreshed ASYNCHRONOUSLY: when it runs low the next device search is posted while the host keeps answering from the current
 // list; its answer is installed when it has arrived.  The host only waits for the device when it cannot decide: after a big subtree
 // moved, or when the list ran out above the threshold.
-constexpr int kCandMaxNodes = 256;              // sweep on config 3 (profiles/r03_cand_nodes_sweep.txt): 192-384 nodes evaluated on the host beat a device round trip
-constexpr int kCandRefreshLow = 12;             // entries left on the list when the next one is asked for
-constexpr int64_t kCandDegreePerNode = 8;       // adjacency entries re-evaluated per pivot at most: this many per node of kCandMaxNodes
+static_assert(kCandNone == kNone, "the state's 'no arc' is the kernels'");
+constexpr int kCandRefreshLow = 12;            // entries left on the list when the next one is asked for
 constexpr int kCandMaxAvgDegree = 24;           // denser graphs: a single moved node already touches too many arcs
 
 inline const int64_t *cand_pi(const mcf_engine *e) { return e->ext_pi ? e->ext_pi : e->pi.data(); }
-inline bool cand_key_less(const mcf_engine::CandKey &a, const mcf_engine::CandKey &b) { return a.c < b.c || (a.c == b.c && a.p < b.p); }
-struct CandHeapAfter {        // std::*_heap keep the LARGEST on top: order by "comes later"
-    bool operator()(const mcf_engine::HeapEnt &a, const mcf_engine::HeapEnt &b) const { return b.c < a.c || (b.c == a.c && b.p < a.p); }
-};
+// what the cache's evaluations read: the host mirrors as they are now
+inline CandGraph cand_graph(const mcf_engine *e)
+{
+    return CandGraph{e->adj_start.data(), e->adj.data(), e->h_src.data(), e->h_tgt.data(), e->h_cost.data(), e->h_state.data(), cand_pi(e)};
+}
 
 // a potential / state change reported by the caller (the mirrors e->pi / e->h_state already hold the new value)
 inline void cand_note_node(mcf_engine *e, int u, bool sigma_known = false, int64_t sigma = 0)
@@ -35,24 +27,11 @@ inline void cand_note_node(mcf_engine *e, int u, bool sigma_known = false, int64
         else e->rc_shift_unknown = true;
     }
     if (e->blind_count > 0 && e->blind_epoch == e->cand_now) e->blind_sets = 2;      // may repeat a node of the big list with a newer value: that list's values are read again
-    // what cand_decide verified last time stays verified until one of ITS nodes is touched (four compares here instead of six scattered loads there)
-    if ((u == e->tp_u) | (u == e->tp_v)) e->tp_ok = false;
-    if ((u == e->hd_u) | (u == e->hd_v)) e->hd_ok = false;
-    if (e->node_at[u] != e->cand_now) {
-        e->node_at[u] = e->cand_now;
-        e->sync_nodes.push_back(u);
-        if (!e->pivot_overflow) {
-            e->pivot_nodes.push_back(u);
-            e->pivot_degree += e->adj_start[u + 1] - e->adj_start[u];
-            if ((int)e->pivot_nodes.size() > kCandMaxNodes || e->pivot_degree > kCandDegreePerNode * kCandMaxNodes) e->pivot_overflow = true;
-        }
-    }
+    if (cand_state_note_node(e, u, e->adj_start.data())) e->sync_nodes.push_back(u);
 }
 inline void cand_note_arc(mcf_engine *e, int a)
 {
-    if (a == e->tp_a) e->tp_ok = false;
-    if (a == e->hd_a) e->hd_ok = false;
-    if (e->arc_at[a] != e->cand_now) { e->arc_at[a] = e->cand_now; e->sync_arcs.push_back(a); e->pivot_arcs.push_back(a); }
+    if (cand_state_note_arc(e, a)) e->sync_arcs.push_back(a);
 }
 // Long lists (a big subtree): nothing will be evaluated here -- the device searches next, and a list of its epoch or later makes the
 // touched nodes' stamps irrelevant (cand_decide) -- so the list is taken over as it is, without a look at its nodes.
@@ -133,125 +112,11 @@ inline int cand_note_nodes_blind(mcf_engine *e, int32_t count, const int32_t *no
     return MCF_OK;
 }
 
-inline bool cand_heap_current(const mcf_engine *e, const mcf_engine::HeapEnt &t)
-{
-    return ((int)(e->arc_at[t.p] <= t.at) & (int)(e->node_at[t.u] <= t.at) & (int)(e->node_at[t.v] <= t.at)) != 0;      // three independent loads: they miss together
-}
-
-inline void cand_push(mcf_engine *e, int a)
-{
-    const int st = e->h_state[a];
-    if (st == 0) return;
-    const int64_t *pi = cand_pi(e);
-    const int32_t u = e->h_src[a], v = e->h_tgt[a];
-    const int64_t d = e->h_cost[a] + pi[u] - pi[v];
-    const int64_t rc = st > 0 ? d : -d;
-    if (rc >= 0) return;
-    e->heap.push_back(mcf_engine::HeapEnt{rc, (uint32_t)a, e->cand_now, u, v});
-    std::push_heap(e->heap.begin(), e->heap.end(), CandHeapAfter());
-}
-
-// all changes of the pivot are in: bring the heap up to date (or note that it is not)
-void cand_absorb_pivot(mcf_engine *e)
-{
-    if (e->pivot_overflow) {
-        e->heap_gap = e->cand_now;
-        // arcs next to the moved nodes keep heap entries of older versions: they must not be taken for current ones
-        // (entries are only trusted for snapshots taken at or after heap_gap, and those know the arcs' present keys -- see cand_decide)
-    } else {
-        const int64_t *pi = cand_pi(e);
-        const uint32_t now = e->cand_now;
-        // first the addresses the evaluation will miss on (version counters and far potentials live in arrays of the graph's size) ...
-        for (int u : e->pivot_nodes)
-            for (int i = e->adj_start[u], hi = e->adj_start[u + 1]; i < hi; ++i) {
-                const mcf_engine::AdjEnt &x = e->adj[i];
-                __builtin_prefetch(&pi[x.other & 0x1FFFFFFFu]);
-            }
-        for (int u : e->pivot_nodes) {
-            const int64_t pu = pi[u];
-            // everything an evaluation needs sits in the entry except the other end's potential and the arc's version counter; an arc
-            // between two moved nodes is evaluated twice (the second entry outdates the first), which is cheaper than remembering it
-            for (int i = e->adj_start[u], hi = e->adj_start[u + 1]; i < hi; ++i) {
-                const mcf_engine::AdjEnt &x = e->adj[i];
-                const int st = (int)((x.other >> 29) & 3u) - 1;
-                if (st == 0) continue;
-                const int32_t other = (int32_t)(x.other & 0x1FFFFFFFu);
-                const int64_t po = pi[other];
-                const int64_t d = (x.other >> 31) ? x.cost + po - pu : x.cost + pu - po;
-                const int64_t rc = st > 0 ? d : -d;
-                if (rc >= 0) continue;
-                e->heap.push_back(mcf_engine::HeapEnt{rc, (uint32_t)x.arc, now, u, other});
-                std::push_heap(e->heap.begin(), e->heap.end(), CandHeapAfter());
-            }
-        }
-        for (int a : e->pivot_arcs) cand_push(e, a);
-    }
-    e->pivot_nodes.clear();
-    e->pivot_arcs.clear();
-    e->pivot_degree = 0;
-    e->pivot_overflow = false;
-    if (e->heap.size() > e->heap_compact_above) {          // drop what lazy deletion left behind
-        size_t keep = 0;
-        for (size_t i = 0; i < e->heap.size(); ++i)
-            if (cand_heap_current(e, e->heap[i])) e->heap[keep++] = e->heap[i];
-        e->heap.resize(keep);
-        std::make_heap(e->heap.begin(), e->heap.end(), CandHeapAfter());
-        e->st.heap_compactions += 1;
-    }
-}
-
 // true: *k holds the entering arc (or "none": the scan would find nothing either) without asking the device
 bool cand_decide(mcf_engine *e, Key *k)
 {
-    // the heap knows every change after snap_at only if none of them was skipped (heap_gap) -- and after a gap the entries of the arcs
-    // next to the skipped nodes are outdated without being marked so; a snapshot at or after the gap makes all of that irrelevant:
-    // an arc touched at or before snap_at is judged by the list (or lies above the threshold), whatever the heap says about it
-    if (!e->cand_valid || e->snap_at < e->heap_gap) return false;
-    mcf_engine::CandKey best_d{0, kNone};
-    while (!e->heap.empty()) {
-        const mcf_engine::HeapEnt &t = e->heap.front();
-        const uint32_t a = t.p;
-        // the entry that was found current last time, and none of its arc's three stamps has been touched since (cand_note_node / _arc)
-        if (e->tp_ok && (int32_t)a == e->tp_a && t.at == e->tp_at) { best_d = mcf_engine::CandKey{t.c, a}; break; }
-        // current version, and touched after the snapshot (an arc last touched before it is the list's business).  While an entry is
-        // current its own epoch is the arc's last touch: a later touch either pushed a newer entry or was a skipped one, i.e. a gap -- and
-        // no list older than a gap gets here (above), so both the entry's epoch and the true one are <= snap_at then.
-        const bool after = t.at > e->snap_at;
-        if (after && cand_heap_current(e, t)) {
-            e->tp_ok = true; e->tp_a = (int32_t)a; e->tp_at = t.at; e->tp_u = t.u; e->tp_v = t.v;
-            best_d = mcf_engine::CandKey{t.c, a};
-            break;
-        }
-        std::pop_heap(e->heap.begin(), e->heap.end(), CandHeapAfter());
-        e->heap.pop_back();
-    }
-    while (e->cand_ptr < e->cand_list.size()) {
-        if (e->hd_ok && e->hd_ptr == e->cand_ptr) break;     // verified clean last time, untouched since
-        const uint32_t a = e->cand_list[e->cand_ptr].p;
-        // three independent loads (no short circuit: they miss together), and the next entry's lines are asked for meanwhile
-        if (e->cand_ptr + 1 < e->cand_list.size()) {
-            __builtin_prefetch(&e->arc_at[e->cand_list[e->cand_ptr + 1].p]);
-            __builtin_prefetch(&e->node_at[e->cand_ends[2 * e->cand_ptr + 2]]);
-            __builtin_prefetch(&e->node_at[e->cand_ends[2 * e->cand_ptr + 3]]);
-        }
-        const uint32_t t_arc = e->arc_at[a], t_src = e->node_at[e->cand_ends[2 * e->cand_ptr]], t_tgt = e->node_at[e->cand_ends[2 * e->cand_ptr + 1]];
-        if ((t_arc <= e->snap_at) & (t_src <= e->snap_at) & (t_tgt <= e->snap_at)) {
-            e->hd_ok = true; e->hd_ptr = e->cand_ptr; e->hd_a = (int32_t)a; e->hd_u = e->cand_ends[2 * e->cand_ptr]; e->hd_v = e->cand_ends[2 * e->cand_ptr + 1];
-            break;
-        }
-        e->cand_ptr++;
-    }
-    mcf_engine::CandKey win{0, kNone};
-    if (e->cand_ptr < e->cand_list.size()) {
-        win = e->cand_list[e->cand_ptr];
-        if (best_d.p != kNone && cand_key_less(best_d, win)) win = best_d;
-    } else if (e->cand_thr.p == kNone) {
-        win = best_d;                                   // the list was complete: nothing untouched is left
-    } else if (best_d.p != kNone && cand_key_less(best_d, e->cand_thr)) {
-        win = best_d;                                   // everything untouched and unlisted lies above the threshold
-    } else {
-        return false;
-    }
+    mcf_engine::CandKey win;
+    if (!cand_decide(static_cast<CandState *>(e), &win)) return false;
     k->c = win.p == kNone ? 0 : win.c;
     k->r = 0;
     k->p = win.p;
@@ -306,8 +171,8 @@ int cand_collect(mcf_engine *e, uint32_t at)
     const double t0 = (double)__rdtsc();
     double t0_wall = 0;
     const volatile Slot *slots = e->h_slots;
-    e->cand_list.clear();
-    e->cand_thr = mcf_engine::CandKey{0, kNone};
+    e->cand_records.clear();
+    mcf_engine::CandKey thr{0, kNone};          // the smallest key that was NOT reported
     for (int g = 0; g < e->res_grid; ++g) {
         const volatile Slot *rec = slots + (size_t)g * kCandRecords;
         uint64_t spins = 0;
@@ -332,27 +197,14 @@ int cand_collect(mcf_engine *e, uint32_t at)
         }
         std::atomic_thread_fence(std::memory_order_acquire);
         for (int r = 0; r < kCandPerGroup; ++r)
-            if (rec[r].p != kNone) e->cand_list.push_back(mcf_engine::CandKey{rec[r].c, rec[r].p});
+            if (rec[r].p != kNone) e->cand_records.push_back(mcf_engine::CandKey{rec[r].c, rec[r].p});
         if (rec[kCandPerGroup].p != kNone) {
             const mcf_engine::CandKey t{rec[kCandPerGroup].c, rec[kCandPerGroup].p};
-            if (e->cand_thr.p == kNone || cand_key_less(t, e->cand_thr)) e->cand_thr = t;
+            if (thr.p == kNone || cand_key_less(t, thr)) thr = t;
         }
     }
     e->wait_ticks += (double)__rdtsc() - t0;
-    if (e->cand_thr.p != kNone) {      // keep only what is provably complete: keys below the smallest unreported key
-        size_t keep = 0;
-        for (size_t i = 0; i < e->cand_list.size(); ++i)
-            if (cand_key_less(e->cand_list[i], e->cand_thr)) e->cand_list[keep++] = e->cand_list[i];
-        e->cand_list.resize(keep);
-    }
-    std::sort(e->cand_list.begin(), e->cand_list.end(), cand_key_less);
-    e->cand_ends.resize(2 * e->cand_list.size());
-    for (size_t i = 0; i < e->cand_list.size(); ++i) { e->cand_ends[2 * i] = e->h_src[e->cand_list[i].p]; e->cand_ends[2 * i + 1] = e->h_tgt[e->cand_list[i].p]; }
-    e->cand_ptr = 0;
-    e->cand_valid = true;
-    e->hd_ok = e->tp_ok = false;          // another list, another snapshot epoch: nothing verified yet
-    e->snap_at = at;
-    e->async_posted = false;
+    cand_install(e, cand_graph(e), e->cand_records.data(), e->cand_records.size(), thr, at);
     e->tk_collect += (double)__rdtsc() - t0;
     return MCF_OK;
 }
@@ -611,15 +463,4 @@ void cand_build_adjacency(mcf_engine *e)
     }
 }
 
-// forgets the list and the heap (upload, or the device state was changed behind the cache's back)
-void cand_reset(mcf_engine *e)
-{
-    e->cand_valid = false;
-    e->cand_list.clear();
-    e->cand_ptr = 0;
-    e->hd_ok = e->tp_ok = false;
-    e->heap.clear();
-    e->pivot_nodes.clear(); e->pivot_arcs.clear(); e->pivot_degree = 0; e->pivot_overflow = false;
-    e->heap_gap = e->cand_now;
-}
 

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "common.h"
+#include "candidate_state.h"
 
 #include "kernels.hip.h"
 #include "collect.hip.h"
@@ -89,7 +90,7 @@ constexpr int kRcMaxGrid = 512;      // ... and of the dispatched RC scan
 
 // ------------------------------------------------------------------------------------------------ engine
 
-struct mcf_engine {
+struct mcf_engine : CandState {
     mcf_engine_desc d{};
     int begin = 0, end = 0;        // shard [begin, end) of the search arcs
     int count_padded = 0;
@@ -203,29 +204,13 @@ struct mcf_engine {
     uint32_t idle_ticks = 0;       // a resident grid leaves after this long without a request (kResidentIdleTicks; MCF_HIP_IDLE_MS)
     uint32_t prev_seq = 0;
     // candidate cache (Best Eligible, resident, register-resident tiles, sparse graphs): see cand_* below
-    bool cand_on = false, cand_valid = false;
+    bool cand_on = false;                       // (the decision state -- epochs, heap, list, memos -- is the CandState base: candidate_state.h)
     mcf::hvec<int32_t> h_src, h_tgt;            // host mirrors of the resident arrays (search arcs only)
     mcf::hvec<int64_t> h_cost;
     mcf::hvec<int8_t> h_state;
-    struct AdjEnt { int32_t arc; uint32_t other; int64_t cost; };  // other: the arc's second end point (bits 0-28), the arc's state + 1 (bits 29-30), bit 31 set when THIS node is the arc's target
     mcf::hvec<int32_t> adj_start;
     mcf::hvec<AdjEnt> adj;                      // arcs incident to each node, with what a re-evaluation needs next to each other
-    // every change carries the number of the search it precedes ("epoch"); a snapshot taken at epoch P knows all changes stamped <= P
-    mcf::hvec<uint32_t> node_at, arc_at;        // epoch of the node's last potential change / the arc's last state change
     mcf::hvec<int32_t> adj_pos;                 // where the two entries of an arc sit in adj (the second is -1 for a self loop): a state write reaches both
-    uint32_t cand_now = 1;                        // epoch of the changes that are arriving
-    uint32_t snap_at = 0;                         // epoch the candidate list reflects
-    uint32_t heap_gap = 0;                        // latest epoch whose changes were NOT evaluated into the heap (a subtree too big to evaluate here)
-    struct CandKey { int64_t c; uint32_t p; };
-    // c, p: the key; at: the epoch of the touch that pushed it; u, v: the arc's end points.  An entry is CURRENT while nothing of its arc was
-    // touched after `at` (arc_at[p], node_at[u], node_at[v] all <= at): a later touch either pushed a newer entry or was a skipped one, i.e. a
-    // gap -- and no list older than a gap is ever judged against the heap (cand_decide).  (Rounds 1-2 kept a version counter per arc and
-    // bumped it for every arc an evaluation looked at: 80 scattered read-modify-writes per pivot on the headline workload.)
-    struct HeapEnt { int64_t c; uint32_t p; uint32_t at; int32_t u, v; };
-    std::vector<HeapEnt> heap;                    // min-heap of the current keys of the arcs touched since (lazy deletion through arc_stamp)
-    std::vector<int32_t> pivot_nodes, pivot_arcs; // touched since the last search: evaluated when the next search begins (all values final by then)
-    int64_t pivot_degree = 0;
-    bool pivot_overflow = false;
     std::vector<int32_t> sync_nodes, sync_arcs;   // changed since the device last heard from us (values are read from the mirrors when the request is built)
     size_t blind_count = 0;                       // the same for big subtrees: node lists taken over wholesale, with their values -- they are the
                                                   // first blind_count entries of pend_node / pend_val already (and may have started travelling)
@@ -243,25 +228,14 @@ struct mcf_engine {
     bool rc_shift_unknown = false;                // ... unless some change came without its shift (mcf_engine_set_potential): then values travel
     bool call_shift_known = false;                // mcf_engine_shift_potential is calling: every node of the call moves by call_shift
     int64_t call_shift = 0;
-    std::vector<CandKey> cand_list;               // sorted; complete below cand_thr as of snap_at
-    std::vector<int32_t> cand_ends;               // the end points of the listed arcs (2 per entry), looked up once when the list is installed
-    size_t cand_ptr = 0;
-    // what cand_decide found valid last time: the heap's top entry (tp_*) and the list's first clean entry (hd_*), remembered with their arc
-    // and end points so that a touch of any of them (cand_note_node / cand_note_arc) can revoke it
-    bool tp_ok = false, hd_ok = false;
-    int32_t tp_a = -1, tp_u = -1, tp_v = -1, hd_a = -1, hd_u = -1, hd_v = -1;
-    uint32_t tp_at = 0;
-    size_t hd_ptr = 0;
-    CandKey cand_thr{0, 0xFFFFFFFFu};             // p == kNone: the list holds every eligible arc
-    bool async_posted = false;                    // a refresh is on its way while the host keeps answering from the current list
+    std::vector<CandState::CandKey> cand_records; // a device answer's records as they are read from the slots (cand_collect)
     uint32_t async_at = 0, posted_at = 0;
     int patch_capacity = 0;                       // potential patches one request / one staged update can carry (2 * node_count + 256)
     uint32_t cand_epoch0 = 1;                     // the epoch an upload starts from (MCF_HIP_CAND_EPOCH0: tests start close to the wrap)
-    size_t heap_compact_above = 1u << 18;         // heap entries above which the stale ones are swept out (MCF_HIP_CAND_HEAP_COMPACT: tests)
     bool cand_debug = false;                      // MCF_HIP_CAND_DEBUG: host-side time breakdown of the candidate cache on stderr
     // where the host's time goes in candidate mode (TSC ticks; printed by mcf_engine_destroy when cand_debug is set)
     double tk_absorb = 0, tk_decide = 0, tk_post = 0, tk_collect = 0, tk_probe = 0;
-    int64_t n_sync_posts = 0, n_async_waits = 0, n_gap_pivots = 0, n_heap_push = 0, n_heap_pop = 0, n_list_skip = 0;
+    int64_t n_sync_posts = 0, n_async_waits = 0, n_gap_pivots = 0, n_list_skip = 0;
     uint32_t *h_exit = nullptr, *d_exit = nullptr;
     int res_grid = 0, res_threads = kResidentThreads;
     hipEvent_t res_start = nullptr, res_stop = nullptr;
@@ -535,24 +509,13 @@ int search_begin(mcf_engine *e)
     const bool had = !e->pend_node.empty() || !e->pend_arc.empty();
     // a resident grid needs one of the device's slots; without one this search is served by a dispatch (the arrays are the same)
     const bool resident_now = e->resident_ok && (e->resident_running || resident_slot_acquire(e));
-    if (e->cand_on && e->cand_now >= 0xFFFFFF00u && !e->async_posted) {
-        // the epoch counter is about to wrap (four billion searches): start over with nothing known -- the device searches next
-        std::fill(e->node_at.begin(), e->node_at.end(), 0u);
-        std::fill(e->arc_at.begin(), e->arc_at.end(), 0u);
-        const bool overflow = e->pivot_overflow;
-        const std::vector<int32_t> pn = e->pivot_nodes, pa = e->pivot_arcs;
-        cand_reset(e);
-        e->cand_now = 1;
-        e->snap_at = 0;
-        e->heap_gap = 1;
-        e->pivot_overflow = overflow;                       // this pivot's changes are still to be shipped (sync lists are untouched)
-        for (int u : pn) e->node_at[u] = 1;
-        for (int a : pa) e->arc_at[a] = 1;
+    if (e->cand_on && e->cand_now >= kCandEpochWrap && !e->async_posted) {
+        cand_restart_epochs(e);
     }
     if (e->cand_on) {
         const double ta = (double)__rdtsc();
         if (e->pivot_overflow) e->n_gap_pivots += 1;
-        cand_absorb_pivot(e);
+        cand_absorb_pivot(e, cand_graph(e));
         const double tb = (double)__rdtsc();
         e->tk_absorb += tb - ta;
         if (resident_now) {
@@ -1064,10 +1027,11 @@ void mcf_engine_destroy(mcf_engine *e)
     if (e->cand_on && e->cand_debug && e->st.searches > 1000) {
         const double ns_per_tick = (mcf::now_ns() - e->cal_ns) / std::max(1.0, (double)__rdtsc() - e->cal_ticks);
         const double n = (double)e->st.searches;
-        fprintf(stderr, "[cand] searches %lld host %lld async %lld sync_posts %lld async_waits %lld gap_pivots %lld | per search ns: absorb %.0f probe %.0f decide %.0f post %.0f collect %.0f wait %.0f | heap size %zu\n",
+        fprintf(stderr, "[cand] searches %lld host %lld async %lld sync_posts %lld async_waits %lld gap_pivots %lld | per search ns: absorb %.0f probe %.0f decide %.0f post %.0f collect %.0f wait %.0f | heap size %zu pushes %lld admitted %lld pops %lld sweeps %lld\n",
                 (long long)e->st.searches, (long long)e->st.host_decided, (long long)e->st.async_refreshes, (long long)e->n_sync_posts, (long long)e->n_async_waits,
                 (long long)e->n_gap_pivots, e->tk_absorb * ns_per_tick / n, e->tk_probe * ns_per_tick / n, e->tk_decide * ns_per_tick / n, e->tk_post * ns_per_tick / n,
-                e->tk_collect * ns_per_tick / n, e->wait_ticks * ns_per_tick / n, e->heap.size());
+                e->tk_collect * ns_per_tick / n, e->wait_ticks * ns_per_tick / n, e->heap.size(), (long long)e->n_heap_push, (long long)e->n_heap_admit, (long long)e->n_heap_pop,
+                (long long)e->n_heap_sweeps);
     }
     (void)hipSetDevice(e->d.device);
     (void)resident_stop(e);
@@ -1664,13 +1628,7 @@ int mcf_engine_renumber_nodes(mcf_engine *e, const int32_t *new_of)
         const int m_s = e->d.search_arc_num;
         for (int a = 0; a < m_s; ++a) { e->h_src[a] = new_of[e->h_src[a]]; e->h_tgt[a] = new_of[e->h_tgt[a]]; }
         cand_build_adjacency(e);
-        mcf::hvec<uint32_t> at((size_t)n);
-        for (int u = 0; u < n; ++u) at[new_of[u]] = e->node_at[u];
-        std::copy(at.begin(), at.end(), e->node_at.begin());
-        for (size_t i = 0; i < e->cand_ends.size(); ++i) e->cand_ends[i] = new_of[e->cand_ends[i]];
-        for (auto &h : e->heap) { h.u = new_of[h.u]; h.v = new_of[h.v]; }
-        e->tp_ok = e->hd_ok = false;
-        for (int32_t &u : e->pivot_nodes) u = new_of[u];
+        cand_renumber(e, new_of, n);
         for (int32_t &u : e->sync_nodes) u = new_of[u];
         for (auto &x : e->rc_sync) x.node = new_of[x.node];
     }
@@ -1944,6 +1902,7 @@ int mcf_engine_get_stats(mcf_engine *e, mcf_engine_stats *out)
     e->st.host_wait_ns = e->wait_ticks * ns_per_tick;
     e->st.host_launch_ns = e->launch_ticks * ns_per_tick;
     e->st.current_block_size = e->block_size;
+    e->st.heap_compactions = e->n_heap_sweeps;
     *out = e->st;
     return MCF_OK;
 }
@@ -1956,6 +1915,7 @@ int mcf_engine_reset_stats(mcf_engine *e)
     const mcf_engine_stats keep = e->st;
     e->st = mcf_engine_stats{};
     e->wait_ticks = e->launch_ticks = 0;
+    e->n_heap_sweeps = 0;
     e->st.scan_workgroups = keep.scan_workgroups;
     e->st.scan_threads = keep.scan_threads;
     e->st.bytes_per_scan = keep.bytes_per_scan;
