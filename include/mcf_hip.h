@@ -1160,6 +1160,76 @@ MCF_API int mcf_rbatch_solve_from(mcf_rbatch *b, const mcf_rbatch_io *io, const 
 MCF_API int mcf_rbatch_run_from_on_host(mcf_rbatch *b, const mcf_rbatch_io *io, const mcf_rbatch_basis_io *basis);
 MCF_API int mcf_rbatch_get_start_stats(mcf_rbatch *b, mcf_ubatch_start_stats *out);
 
+/* ---- Why an instance is infeasible (DESIGN.md 3.14 "Why infeasible: a cut from the kept flow"): a certificate read on the device from
+ * the flow every instance's last solve call left there.  The status word mirrors the reference's test (difference D9: the n root links
+ * only) and is not mathematical feasibility: an instance can be MCF_OPTIMAL with a supply surplus left on an artificial arc, and
+ * MCF_INFEASIBLE with a flow that satisfies every constraint.  This call answers the question itself, for every instance whose last
+ * solve call ended with no entering arc (csrc/diagnose_step.hip.h):
+ *   unmet[v]   what node v could not ship: with nf(v) the net outflow of v on the caller's arcs, nf(v) = supply'(v) - unmet[v], where
+ *              supply' is the supply shifted by the lower bounds.  MCF_SUPPLY_GEQ asks nf >= supply: v is violated where unmet > 0
+ *              and has slack where unmet < 0; MCF_SUPPLY_LEQ mirrors both signs.
+ *   MCF_DIAG_FEASIBLE  no node is violated: the kept flow satisfies every constraint.  violation 0, set_size 0, side all 0.
+ *   MCF_DIAG_CUT       the instance is infeasible, and side[] names a node set S that proves it in the caller's own numbers:
+ *                        GEQ  violation = supply(S) - (upper(arcs leaving S) - lower(arcs entering S)) > 0
+ *                        LEQ  violation = (lower(arcs leaving S) - upper(arcs entering S)) - supply(S) > 0
+ *                      S is what the violated nodes reach (GEQ; LEQ: the nodes that reach them) in the residual graph of the kept flow,
+ *                      no uncapacitated arc crosses it in the bounding direction, and violation is the sum of |unmet| over S.
+ *   MCF_DIAG_OPEN      S holds a node with slack: the kept flow is not extremal and no certificate comes from it.  side[] is S,
+ *                      violation 0.  The artificial cost (max |cost| + 1) * node_count rules this out after a solve that found no
+ *                      entering arc; it is counted so that it can be seen to stay zero.
+ *   MCF_DIAG_BOUNDS    some arc has upper < lower; no cut.  Zero rows.
+ *   MCF_DIAG_NONE      the last solve call ended Unbounded or at a limit, or there was none for this instance.  Zero rows.
+ * One wave per instance; an instance is diagnosed in LDS exactly when it is solved there (16 bytes per arc of the caller's and 18 per
+ * node, below the solve's footprint); the others walk their workspace in place with marks and frontiers in a buffer of the handle's,
+ * allocated with the first call.  Contract as mcf_*batch_cost_ranges': null stream, returns synchronised, the handle's device made
+ * current and the caller's restored; the call reads the kept state and changes none of it -- workspaces, slots, basis, results and the
+ * other statistics stay -- and mixes with every solve call, range call and hook in any order.  MCF_ERR_STATE before a solve of either
+ * kind; MCF_ERR_NO_DEVICE without a GPU leaves the handle as it was; MCF_ERR_INVALID for a null argument or an unknown memory kind.
+ * With MCF_MEM_DEVICE nothing that scales with the arcs, the nodes or the instances crosses the bus in a call (a table of one int32 per
+ * instance goes up once per handle, with the first call).  Without `side` the walk still runs: the verdict needs it. */
+#define MCF_DIAG_NONE 0
+#define MCF_DIAG_FEASIBLE 1
+#define MCF_DIAG_CUT 2
+#define MCF_DIAG_OPEN 3
+#define MCF_DIAG_BOUNDS 4
+typedef struct mcf_ubatch_diagnose_io {
+    int32_t memory;               /* MCF_MEM_HOST / MCF_MEM_DEVICE: where every pointer below points */
+    int32_t reserved;
+    /* results, any may be NULL */
+    int32_t *verdict;             /* [count] MCF_DIAG_* */
+    int64_t *violation;           /* [count] */
+    int32_t *set_size;            /* [count] nodes in S */
+    int8_t *side;                 /* [count * node_count] 1 = in S */
+    int64_t *unmet;               /* [count * node_count] */
+} mcf_ubatch_diagnose_io;
+typedef struct mcf_rbatch_diagnose_io {                /* the same with flat rows: instance i's nodes at [node_row[i], node_row[i + 1]) */
+    int32_t memory;
+    int32_t reserved;
+    int32_t *verdict;             /* [count] */
+    int64_t *violation;           /* [count] */
+    int32_t *set_size;            /* [count] */
+    int8_t *side;                 /* [node_row[count]] */
+    int64_t *unmet;               /* [node_row[count]] */
+} mcf_rbatch_diagnose_io;
+typedef struct mcf_ubatch_diagnose_stats { /* of the last mcf_*batch_diagnose / _on_host (all zero before one) */
+    int64_t instances;
+    int64_t none, feasible, cut, open, bounds;          /* of `instances`, by verdict */
+    int64_t lds_instances;        /* of `instances`, by the tier they are solved in; 0 and 0 from the host hook */
+    int64_t global_instances;
+    int64_t levels;               /* levels of all walks: two barriers and one sweep over the nodes each */
+    int64_t frontier_nodes;       /* nodes of all frontiers = the sizes of all S */
+    int64_t inc_entries;          /* incidence entries read: one flow (and capacity) lookup each */
+    double kernel_ns;             /* round the launches, synchronised */
+    int64_t bytes_up, bytes_down; /* MCF_MEM_DEVICE: the summary words; MCF_MEM_HOST adds the arrays */
+} mcf_ubatch_diagnose_stats;
+MCF_API int mcf_ubatch_diagnose(mcf_ubatch *b, const mcf_ubatch_diagnose_io *io);
+/* TEST HOOK: the same step (uniform_diagnose, csrc/diagnose_step.hip.h) with one lane on the CPU.  io->memory must be MCF_MEM_HOST. */
+MCF_API int mcf_ubatch_diagnose_on_host(mcf_ubatch *b, const mcf_ubatch_diagnose_io *io);
+MCF_API int mcf_ubatch_get_diagnose_stats(mcf_ubatch *b, mcf_ubatch_diagnose_stats *out);
+MCF_API int mcf_rbatch_diagnose(mcf_rbatch *b, const mcf_rbatch_diagnose_io *io);
+MCF_API int mcf_rbatch_diagnose_on_host(mcf_rbatch *b, const mcf_rbatch_diagnose_io *io);
+MCF_API int mcf_rbatch_get_diagnose_stats(mcf_rbatch *b, mcf_ubatch_diagnose_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

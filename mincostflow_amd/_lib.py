@@ -280,6 +280,29 @@ class UBatchStartStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+DIAG_NONE, DIAG_FEASIBLE, DIAG_CUT, DIAG_OPEN, DIAG_BOUNDS = range(5)      # MCF_DIAG_*
+
+
+class UBatchDiagnoseIo(C.Structure):
+    """mcf_ubatch_diagnose_io"""
+    _fields_ = [("memory", C.c_int32), ("reserved", C.c_int32)] + [(name, C.c_void_p) for name in ("verdict", "violation", "set_size", "side", "unmet")]
+
+
+class RBatchDiagnoseIo(C.Structure):
+    """mcf_rbatch_diagnose_io"""
+    _fields_ = UBatchDiagnoseIo._fields_
+
+
+class UBatchDiagnoseStats(C.Structure):
+    """mcf_ubatch_diagnose_stats"""
+    _fields_ = [(name, C.c_int64) for name in ("instances", "none", "feasible", "cut", "open", "bounds", "lds_instances", "global_instances", "levels",
+                                               "frontier_nodes", "inc_entries")] + \
+               [("kernel_ns", C.c_double), ("bytes_up", C.c_int64), ("bytes_down", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class ProblemStruct(C.Structure):
     _fields_ = [("node_count", C.c_int32), ("arc_count", C.c_int32), ("source", C.POINTER(C.c_int32)),
                 ("target", C.POINTER(C.c_int32)), ("lower", C.POINTER(C.c_int64)), ("upper", C.POINTER(C.c_int64)),
@@ -464,6 +487,12 @@ SIGNATURES = {
     "mcf_rbatch_solve_from": (C.c_int, [C.c_void_p, _P(RBatchIo), _P(RBatchBasisIo)]),
     "mcf_rbatch_run_from_on_host": (C.c_int, [C.c_void_p, _P(RBatchIo), _P(RBatchBasisIo)]),
     "mcf_rbatch_get_start_stats": (C.c_int, [C.c_void_p, _P(UBatchStartStats)]),
+    "mcf_ubatch_diagnose": (C.c_int, [C.c_void_p, _P(UBatchDiagnoseIo)]),
+    "mcf_ubatch_diagnose_on_host": (C.c_int, [C.c_void_p, _P(UBatchDiagnoseIo)]),
+    "mcf_ubatch_get_diagnose_stats": (C.c_int, [C.c_void_p, _P(UBatchDiagnoseStats)]),
+    "mcf_rbatch_diagnose": (C.c_int, [C.c_void_p, _P(RBatchDiagnoseIo)]),
+    "mcf_rbatch_diagnose_on_host": (C.c_int, [C.c_void_p, _P(RBatchDiagnoseIo)]),
+    "mcf_rbatch_get_diagnose_stats": (C.c_int, [C.c_void_p, _P(UBatchDiagnoseStats)]),
     "mcf_problem_free": (None, [_P(ProblemStruct)]),
     "mcf_gen_netgen_like": (C.c_int, [_P(ProblemStruct), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64]),

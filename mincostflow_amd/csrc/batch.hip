@@ -16,6 +16,8 @@
 //     workspaces as the last solve call left them, and write nothing there.
 //   * supply and bound ranges of the kept basis (mcf_ubatch_data_ranges, mcf_rbatch_data_ranges): the data-ranges kernels run
 //     data_ranges_step.hip.h on the same state, the same way; every walk gathers into registers, so they need no atomics.
+//   * why an instance is infeasible (mcf_ubatch_diagnose, mcf_rbatch_diagnose): the diagnose kernels run diagnose_step.hip.h on the same
+//     state, the same way; marks and frontiers lie in LDS or, for the global tier, in a buffer of the handle's.
 //   * solves that start from a basis the caller supplies (mcf_ubatch_solve_from, mcf_rbatch_solve_from): the start kernels run
 //     uniform_begin_from in place of the set-up launch; rounds and settle launch are those of a re-solve with new data.
 // Device code does no bounds checks: mcf_batch_add validates every end point (core_create), and every index the kernel follows after
@@ -30,6 +32,7 @@
 #include "batch_step.hip.h"
 #include "common.h"
 #include "data_ranges_step.hip.h"
+#include "diagnose_step.hip.h"
 #include "ns_core.h"
 #include "ranges_step.hip.h"
 #include "uniform_step.hip.h"
@@ -287,6 +290,30 @@ __global__ __launch_bounds__(kBatchThreads) void ragged_data_ranges_kernel(mcf::
     const int64_t i = (int64_t)ids[blockIdx.x];
     mcf::uniform_data_ranges<kLds>(mcf::ragged_view(r, nullptr, i, slab, nullptr), o, mcf::ragged_pairs(pairs, pair_row, ship_row, r.graph_of[i], i), slots[i], lds,
                                    (int)threadIdx.x, kBatchThreads);
+}
+
+// mcf_*batch_diagnose: the same launch shape on diagnose_step.hip.h.  kLds: dynamic LDS holds flow and upper of the caller's arcs, unmet,
+// marks and frontiers (at least diag_layout_of(m, n + 1).bytes); otherwise block k works in work + k * work_stride, which the host sized
+// for the largest instance of the global tier, and reads flow and upper in the workspace.
+template <bool kLds>
+__global__ __launch_bounds__(kBatchThreads) void uniform_diagnose_kernel(mcf::UniformProblem p, mcf::DiagOutputs o, const BatchSlot *slots, unsigned char *slab,
+                                                                         const int32_t *ids, const int32_t *inc_start, const int32_t *inc, unsigned char *work,
+                                                                         uint64_t work_stride)
+{
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int64_t i = (int64_t)ids[blockIdx.x];
+    mcf::InstanceView v = mcf::uniform_view(p, nullptr, i, slab);
+    v.inc_start = inc_start; v.inc = inc;
+    mcf::uniform_diagnose<kLds>(v, o, slots[i], kLds ? lds : work + (uint64_t)blockIdx.x * work_stride, (int)threadIdx.x, kBatchThreads);
+}
+template <bool kLds>
+__global__ __launch_bounds__(kBatchThreads) void ragged_diagnose_kernel(mcf::RaggedProblem r, mcf::DiagOutputs o, const BatchSlot *slots, unsigned char *slab,
+                                                                        const int32_t *ids, unsigned char *work, uint64_t work_stride)
+{
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int64_t i = (int64_t)ids[blockIdx.x];
+    mcf::uniform_diagnose<kLds>(mcf::ragged_view(r, nullptr, i, slab, nullptr), o, slots[i], kLds ? lds : work + (uint64_t)blockIdx.x * work_stride, (int)threadIdx.x,
+                                kBatchThreads);
 }
 
 struct Instance {
@@ -1031,10 +1058,16 @@ struct PlacedBatch {
         int32_t *d_ids = nullptr;
         int lds_max = -1;
     };
-    RangePlan range_plan, data_range_plan;
+    RangePlan range_plan, data_range_plan, diagnose_plan;
     int64_t *d_range_summary = nullptr;
     mcf_ubatch_range_stats range_stats{};
     mcf_ubatch_data_range_stats data_range_stats{};
+    // diagnosis: its summary words, the global tier's marks and frontiers (work_stride bytes per instance of that tier, in launch order;
+    // allocated with the first call that has such instances), the last call's statistics
+    int64_t *d_diag_summary = nullptr;
+    unsigned char *d_diag_work = nullptr;
+    size_t diag_work_bytes = 0;
+    mcf_ubatch_diagnose_stats diagnose_stats{};
     std::vector<unsigned char> h_slab;  // the host hooks' slab, slots and traces: the device's layout
     std::vector<BatchSlot> h_slots;
     std::vector<int32_t> h_traces;
@@ -1046,6 +1079,9 @@ struct PlacedBatch {
         if (d_io) (void)hipFree(d_io);
         if (range_plan.d_ids) (void)hipFree(range_plan.d_ids);
         if (data_range_plan.d_ids) (void)hipFree(data_range_plan.d_ids);
+        if (diagnose_plan.d_ids) (void)hipFree(diagnose_plan.d_ids);
+        if (d_diag_summary) (void)hipFree(d_diag_summary);
+        if (d_diag_work) (void)hipFree(d_diag_work);
         if (d_range_summary) (void)hipFree(d_range_summary);
     }
 };
@@ -1249,6 +1285,13 @@ struct UniformPlacement {
         hipLaunchKernelGGL(in_lds ? data_ranges_kernel_in_lds : uniform_data_ranges_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, p, o, io.pairs,
                            io.pair_count, slots, slab, ids);
     }
+    static constexpr auto diagnose_kernel_in_lds = uniform_diagnose_kernel<true>;
+    static void launch_diagnose(const Handle *b, bool in_lds, unsigned blocks, uint32_t lds, const Problem &p, const mcf::DiagOutputs &o, const BatchSlot *slots,
+                                unsigned char *slab, const int32_t *ids, unsigned char *work, uint64_t work_stride)
+    {
+        hipLaunchKernelGGL(in_lds ? diagnose_kernel_in_lds : uniform_diagnose_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, p, o, slots, slab, ids,
+                           b->d_inc_start, b->d_inc, work, work_stride);
+    }
     // one list for every instance
     static int check_pairs(const Handle *b, const DataRangeIo &io, const char *what, PairSizes *sizes)
     {
@@ -1261,6 +1304,7 @@ struct UniformPlacement {
     static mcf::PairList pair_list(const Handle *, const DataRangeIo &io, int64_t i) { return mcf::uniform_pairs(io.pairs, io.pair_count, i); }
     static void sizes(const Handle *b, size_t, int32_t *n, int32_t *m) { *n = b->d.node_count; *m = b->d.arc_count; }
     static size_t arc_rows(const Handle *b) { return (size_t)b->d.count * (size_t)b->d.arc_count; }
+    static size_t node_rows(const Handle *b) { return (size_t)b->d.count * (size_t)b->d.node_count; }
     static size_t slab_bytes(const Handle *b) { return (size_t)b->d.count * (size_t)b->stride; }
     static LaunchPlan plan(Handle *b) { return LaunchPlan{&b->dev, b->lds_max, b->d.pivots_per_launch, nullptr, b->stride}; }     // one class for all
     static const BatchSlot *templates(const Handle *b) { return &b->tmpl; }
@@ -1346,6 +1390,13 @@ struct RaggedPlacement {
         hipLaunchKernelGGL(in_lds ? data_ranges_kernel_in_lds : ragged_data_ranges_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, r, o, io.pairs, io.pair_row,
                            io.ship_row, slots, slab, ids);
     }
+    static constexpr auto diagnose_kernel_in_lds = ragged_diagnose_kernel<true>;
+    static void launch_diagnose(const Handle *, bool in_lds, unsigned blocks, uint32_t lds, const Problem &r, const mcf::DiagOutputs &o, const BatchSlot *slots,
+                                unsigned char *slab, const int32_t *ids, unsigned char *work, uint64_t work_stride)
+    {
+        hipLaunchKernelGGL(in_lds ? diagnose_kernel_in_lds : ragged_diagnose_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, r, o, slots, slab, ids, work,
+                           work_stride);
+    }
     // one list per graph: pair_row says where each begins, ship_row where each instance's answers do.  Tables in host memory are checked
     // against each other; tables in device memory are the caller's word, as the rows of every call are.
     static int check_pairs(const Handle *b, const DataRangeIo &io, const char *what, PairSizes *sizes)
@@ -1376,6 +1427,7 @@ struct RaggedPlacement {
     }
     static void sizes(const Handle *b, size_t i, int32_t *n, int32_t *m) { const mcf::RaggedGraph &g = b->graphs[(size_t)b->graph_of[i]]; *n = g.n; *m = g.m; }
     static size_t arc_rows(const Handle *b) { return (size_t)b->arc_row[(size_t)b->d.count]; }
+    static size_t node_rows(const Handle *b) { return (size_t)b->node_row[(size_t)b->d.count]; }
     static size_t slab_bytes(const Handle *b) { return (size_t)b->workspace[(size_t)b->d.count]; }
     static LaunchPlan plan(Handle *b) { return LaunchPlan{&b->dev, b->lds_max, b->d.pivots_per_launch, b->footprint.data(), 0}; }  // a class per instance
     static const BatchSlot *templates(const Handle *b) { return b->tmpl.data(); }
@@ -2107,6 +2159,163 @@ int get_data_range_stats(const PlacedBatch *b, mcf_ubatch_data_range_stats *out)
     return MCF_OK;
 }
 
+// ---- mcf_*batch_diagnose / _on_host: uniform_diagnose for every instance, on the state the last solve call left; it is only read
+struct DiagIo {
+    bool given;
+    int32_t memory;
+    int32_t *verdict;
+    int64_t *violation;
+    int32_t *set_size;
+    int8_t *side;
+    int64_t *unmet;
+};
+template <class Io>
+DiagIo diag_io_of(const Io *io)
+{
+    if (!io) return DiagIo{};
+    return DiagIo{true, io->memory, io->verdict, io->violation, io->set_size, io->side, io->unmet};
+}
+
+int check_diagnose_call(const PlacedBatch *b, const DiagIo &io, const char *what, bool host_only)
+{
+    if (!b || !io.given) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
+    if (io.memory != MCF_MEM_HOST && io.memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io.memory);
+    if (host_only && io.memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
+    if (b->where == PlacedBatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
+    return MCF_OK;
+}
+inline uint32_t diagnose_footprint(int32_t n, int32_t m) { return mcf::diag_layout_of((uint32_t)m, (uint32_t)n + 1u).bytes; }
+void diagnose_stats_of(const int64_t words[mcf::kDiagSummaryWords], mcf_ubatch_diagnose_stats *st)
+{
+    st->none = words[MCF_DIAG_NONE]; st->feasible = words[MCF_DIAG_FEASIBLE]; st->cut = words[MCF_DIAG_CUT]; st->open = words[MCF_DIAG_OPEN];
+    st->bounds = words[MCF_DIAG_BOUNDS];
+    st->levels = words[MCF_DIAG_BOUNDS + 1]; st->frontier_nodes = words[MCF_DIAG_BOUNDS + 2]; st->inc_entries = words[MCF_DIAG_BOUNDS + 3];
+}
+// the room one instance of the global tier needs for unmet, marks and frontiers: the largest such instance's, for every block of that launch
+template <class P>
+uint64_t diagnose_work_stride(const typename P::Handle *b)
+{
+    const LaunchPlan plan = P::plan(const_cast<typename P::Handle *>(b));
+    uint32_t most = 0;
+    for (size_t i = 0; i < (size_t)b->d.count; ++i) {
+        if (class_of(b->lds_max, plan.bytes((int32_t)i)) != kClasses - 1) continue;
+        int32_t n = 0, m = 0;
+        P::sizes(b, i, &n, &m);
+        most = std::max(most, mcf::diag_layout_of(0, (uint32_t)n + 1u).bytes);
+    }
+    return most;
+}
+
+template <class P>
+int diagnose_on_device(typename P::Handle *b, DiagIo io, const char *what)
+{
+    if (const int rc = check_diagnose_call(b, io, what, false)) return rc;
+    if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
+    const DeviceGuard guard;
+    if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
+    const size_t count = (size_t)b->d.count;
+    mcf_ubatch_diagnose_stats st{};
+    st.instances = (int64_t)count;
+    if (!count) { b->diagnose_stats = st; return MCF_OK; }
+    if (b->lds_max > (64 << 10))                                            // the opt-in open_device got for the solve's kernels
+        HIP_TRY(hipFuncSetAttribute((const void *)P::diagnose_kernel_in_lds, hipFuncAttributeMaxDynamicSharedMemorySize, b->lds_max));
+    if (const int rc = ensure_device_buffers<P>(b)) return rc;
+    const bool first = !b->diagnose_plan.d_ids;
+    if (const int rc = ensure_range_plan<P>(b, b->diagnose_plan, diagnose_footprint)) return rc;
+    if (first) st.bytes_up += (int64_t)(count * sizeof(int32_t));
+    if (!b->d_diag_summary) HIP_TRY(hipMalloc((void **)&b->d_diag_summary, mcf::kDiagSummaryWords * sizeof(int64_t)));
+    uint64_t work_stride = 0;
+    for (const PlacedBatch::RangeLaunch &L : b->diagnose_plan.launches) {
+        if (L.in_lds) continue;
+        work_stride = diagnose_work_stride<P>(b);
+        const size_t need = (size_t)L.n * (size_t)work_stride;
+        if (b->diag_work_bytes < need) {
+            if (b->d_diag_work) { HIP_TRY(hipFree(b->d_diag_work)); b->d_diag_work = nullptr; b->diag_work_bytes = 0; }
+            HIP_TRY(hipMalloc((void **)&b->d_diag_work, need));
+            b->diag_work_bytes = need;
+        }
+    }
+    if (const int rc = state_to_device(b, count, &st.bytes_up)) return rc;
+    b->where = PlacedBatch::kOnDevice;                                      // the same state, now there too
+    Staged staged;                                                          // MCF_MEM_HOST: the rows come down through the staging buffer of the solve calls
+    if (io.memory == MCF_MEM_HOST) {
+        const size_t nodes = P::node_rows(b);
+        size_t at[5] = {};
+        if (io.verdict) at[0] = staged.add(nullptr, io.verdict, 4 * count);
+        if (io.violation) at[1] = staged.add(nullptr, io.violation, 8 * count);
+        if (io.set_size) at[2] = staged.add(nullptr, io.set_size, 4 * count);
+        if (io.side) at[3] = staged.add(nullptr, io.side, nodes);
+        if (io.unmet) at[4] = staged.add(nullptr, io.unmet, 8 * nodes);
+        if (const int rc = reserve_io(b, std::max<size_t>(staged.total, 16))) return rc;
+        if (io.verdict) io.verdict = (int32_t *)(b->d_io + at[0]);
+        if (io.violation) io.violation = (int64_t *)(b->d_io + at[1]);
+        if (io.set_size) io.set_size = (int32_t *)(b->d_io + at[2]);
+        if (io.side) io.side = (int8_t *)(b->d_io + at[3]);
+        if (io.unmet) io.unmet = (int64_t *)(b->d_io + at[4]);
+    }
+    int64_t words[mcf::kDiagSummaryWords] = {};
+    HIP_TRY(hipMemcpy(b->d_diag_summary, words, sizeof(words), hipMemcpyHostToDevice));
+    st.bytes_up += (int64_t)sizeof(words);
+    const mcf::DiagOutputs o{io.verdict, io.violation, io.set_size, io.side, io.unmet, b->d_diag_summary};
+    BatchIo kept{};
+    kept.supply_type = b->supply_type;                                      // the last solve call's: the kept flow belongs to that one
+    const typename P::Problem p = P::problem(b, kept, true);
+    const double t_launch = mcf::now_ns();
+    for (const PlacedBatch::RangeLaunch &L : b->diagnose_plan.launches) {
+        P::launch_diagnose(b, L.in_lds, (unsigned)L.n, L.lds, p, o, b->dev.slots, b->dev.slab, b->diagnose_plan.d_ids + L.first, b->d_diag_work, work_stride);
+        HIP_TRY(hipGetLastError());
+        (L.in_lds ? st.lds_instances : st.global_instances) += L.n;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    st.kernel_ns = mcf::now_ns() - t_launch;
+    HIP_TRY(hipMemcpy(words, b->d_diag_summary, sizeof(words), hipMemcpyDeviceToHost));
+    st.bytes_down += (int64_t)sizeof(words);
+    if (const int rc = stage_down(b, staged, &st.bytes_down)) return rc;
+    diagnose_stats_of(words, &st);
+    b->diagnose_stats = st;
+    return MCF_OK;
+}
+
+template <class P>
+int diagnose_on_host(typename P::Handle *b, const DiagIo &io, const char *what)
+{
+    if (const int rc = check_diagnose_call(b, io, what, true)) return rc;
+    const size_t count = (size_t)b->d.count;
+    b->h_slab.resize(P::slab_bytes(b));
+    b->h_slots.resize(count);
+    if (const int rc = state_to_host(b, b->d.device, count)) return rc;
+    b->where = PlacedBatch::kOnHost;                                        // the same state, now here too
+    mcf_ubatch_diagnose_stats st{};
+    st.instances = (int64_t)count;
+    int64_t words[mcf::kDiagSummaryWords] = {};
+    const mcf::DiagOutputs o{io.verdict, io.violation, io.set_size, io.side, io.unmet, words};
+    BatchIo kept{};
+    kept.supply_type = b->supply_type;
+    const typename P::Problem p = P::problem(b, kept, false);
+    const mcf::UniformOutputs none{};
+    struct alignas(16) Word { uint64_t lo, hi; };
+    std::vector<Word> room;                                                 // one instance's unmet, marks and frontiers at a time
+    const double t_start = mcf::now_ns();
+    for (size_t i = 0; i < count; ++i) {
+        const BatchSlot *tmpl = nullptr;
+        const mcf::InstanceView v = P::view(b, p, none, (int64_t)i, b->h_slab.data(), &tmpl);
+        const size_t words_needed = mcf::diag_layout_of(0, (uint32_t)v.n + 1u).bytes / sizeof(Word);
+        if (room.size() < words_needed) room.resize(words_needed);
+        mcf::uniform_diagnose<false>(v, o, b->h_slots[i], (unsigned char *)room.data(), 0, 1);
+    }
+    st.kernel_ns = mcf::now_ns() - t_start;
+    diagnose_stats_of(words, &st);
+    b->diagnose_stats = st;
+    return MCF_OK;
+}
+
+int get_diagnose_stats(const PlacedBatch *b, mcf_ubatch_diagnose_stats *out)
+{
+    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
+    *out = b->diagnose_stats;
+    return MCF_OK;
+}
+
 int get_stats(const PlacedBatch *b, mcf_ubatch_stats *out)
 {
     if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
@@ -2269,6 +2478,9 @@ int mcf_ubatch_data_ranges_on_host(mcf_ubatch *b, const mcf_ubatch_data_range_io
     return data_ranges_on_host<UniformPlacement>(b, data_range_io_of(io), "mcf_ubatch_data_ranges_on_host");
 }
 int mcf_ubatch_get_data_range_stats(mcf_ubatch *b, mcf_ubatch_data_range_stats *out) { return get_data_range_stats(b, out); }
+int mcf_ubatch_diagnose(mcf_ubatch *b, const mcf_ubatch_diagnose_io *io) { return diagnose_on_device<UniformPlacement>(b, diag_io_of(io), "mcf_ubatch_diagnose"); }
+int mcf_ubatch_diagnose_on_host(mcf_ubatch *b, const mcf_ubatch_diagnose_io *io) { return diagnose_on_host<UniformPlacement>(b, diag_io_of(io), "mcf_ubatch_diagnose_on_host"); }
+int mcf_ubatch_get_diagnose_stats(mcf_ubatch *b, mcf_ubatch_diagnose_stats *out) { return get_diagnose_stats(b, out); }
 
 void mcf_rbatch_destroy(mcf_rbatch *b) { delete b; }
 int mcf_rbatch_solve(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_device<RaggedPlacement>(b, io_of(io), kFresh, "mcf_rbatch_solve"); }
@@ -2305,5 +2517,8 @@ int mcf_rbatch_data_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_data_range_io
     return data_ranges_on_host<RaggedPlacement>(b, data_range_io_of(io), "mcf_rbatch_data_ranges_on_host");
 }
 int mcf_rbatch_get_data_range_stats(mcf_rbatch *b, mcf_ubatch_data_range_stats *out) { return get_data_range_stats(b, out); }
+int mcf_rbatch_diagnose(mcf_rbatch *b, const mcf_rbatch_diagnose_io *io) { return diagnose_on_device<RaggedPlacement>(b, diag_io_of(io), "mcf_rbatch_diagnose"); }
+int mcf_rbatch_diagnose_on_host(mcf_rbatch *b, const mcf_rbatch_diagnose_io *io) { return diagnose_on_host<RaggedPlacement>(b, diag_io_of(io), "mcf_rbatch_diagnose_on_host"); }
+int mcf_rbatch_get_diagnose_stats(mcf_rbatch *b, mcf_ubatch_diagnose_stats *out) { return get_diagnose_stats(b, out); }
 
 }  // extern "C"

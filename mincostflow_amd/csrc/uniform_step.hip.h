@@ -57,6 +57,7 @@ struct UniformCheck {
 struct InstanceView {
     int64_t i;                                           // its entry of the per-instance arrays (status[i], changed[i], ...)
     int64_t arc_row;                                     // where its rows of the per-arc arrays begin, in elements
+    int64_t node_row;                                    // ... and its rows of the per-node arrays
     int32_t n, m, supply_type, trace_cap;
     const int32_t *source, *target;                      // [m], validated at create
     const int32_t *inc_start, *inc;                      // the graph's incidence lists [n + 1], [2m]: uniform_validate and uniform_begin_from
@@ -131,7 +132,7 @@ MCF_HD inline InstanceView uniform_view(const UniformProblem &p, const UniformOu
     v.source = p.source; v.target = p.target;
     v.lower = uniform_row(p.lower, p.lower_stride, i); v.upper = uniform_row(p.upper, p.upper_stride, i);
     v.cost = uniform_row(p.cost, p.cost_stride, i); v.supply = uniform_row(p.supply, p.supply_stride, i);
-    v.arc_row = i * (int64_t)p.m;
+    v.arc_row = i * (int64_t)p.m; v.node_row = i * (int64_t)p.n;
     v.start_state = p.start_state ? p.start_state + i * p.start_stride : nullptr;
     v.workspace = (uint64_t)i * p.stride; v.trace = (uint64_t)i * (uint64_t)p.trace_cap;
     v.home = slab ? slab + v.workspace : nullptr;
@@ -154,7 +155,7 @@ MCF_HD inline InstanceView ragged_view(const RaggedProblem &r, const UniformOutp
     const RaggedGraph &g = r.graphs[r.graph_of[i]];
     const int64_t arcs = r.arc_row[i], nodes = r.node_row[i];
     InstanceView v{};
-    v.i = i; v.arc_row = arcs; v.n = g.n; v.m = g.m; v.supply_type = r.supply_type; v.trace_cap = r.trace_cap;
+    v.i = i; v.arc_row = arcs; v.node_row = nodes; v.n = g.n; v.m = g.m; v.supply_type = r.supply_type; v.trace_cap = r.trace_cap;
     v.source = r.source + g.ends; v.target = r.target + g.ends;
     v.inc_start = r.inc_start + g.inc_start; v.inc = r.inc + g.inc;
     v.lower = r.lower ? r.lower + arcs : nullptr; v.upper = r.upper ? r.upper + arcs : nullptr;

@@ -32,6 +32,10 @@ class SolverStatus:                   # Types/SolverStatus.cs
     NotSolved, Optimal, Infeasible, Unbounded, Unbalanced = 0, 1, 2, 3, 4
 
 
+class Verdict:                        # MCF_DIAG_* of include/mcf_hip.h: what diagnose() says of an instance
+    NoVerdict, Feasible, Cut, Open, Bounds = L.DIAG_NONE, L.DIAG_FEASIBLE, L.DIAG_CUT, L.DIAG_OPEN, L.DIAG_BOUNDS
+
+
 def _vector_width_abi(v: int) -> int:
     """Python side: 0 = not hardware accelerated, 2 / 4 / 8 = Vector<long>.Count (the oracle's convention).  C ABI: MCF_VECTOR_NONE = -1, 0 = default (4)."""
     if v not in (0, 2, 4, 8):
@@ -568,6 +572,36 @@ class RaggedDataRanges(UniformDataRanges):
         return xp.repeat_interleave(self.ranged != 0, xp.as_tensor(counts, device=self.ranged.device))
 
 
+class UniformDiagnosis:
+    """What UniformBatch.diagnose returns: one row per instance, numpy arrays or tensors.  verdict[i] is a Verdict.  Feasible: the flow the
+    last solve call left satisfies every constraint, whatever status says.  Cut: the instance is infeasible and side[i] marks a node set S
+    that proves it in the caller's numbers -- Geq: violation[i] = supply(S) - (upper(arcs leaving S) - lower(arcs entering S)) > 0;
+    Leq: violation[i] = (lower(arcs leaving S) - upper(arcs entering S)) - supply(S) > 0 -- with set_size[i] nodes.  unmet[i, v] is what
+    node v could not ship (Geq: > 0 violated, < 0 slack; Leq mirrored); violation is the sum of |unmet| over S.  Bounds: an upper bound
+    below its lower bound.  NoVerdict: Unbounded, a limit, never solved.  Open: no certificate (never seen; counted in diagnose_stats()).
+    Rows of Bounds and NoVerdict instances are zero.  side and unmet are None where they were not asked for."""
+    __slots__ = ("verdict", "violation", "set_size", "side", "unmet")
+    FIELDS = (("verdict", "int32", ""), ("violation", "int64", ""), ("set_size", "int32", ""), ("side", "int8", "n"), ("unmet", "int64", "n"))
+
+    def __init__(self, **arrays):
+        for name, _, _ in self.FIELDS:
+            setattr(self, name, arrays.get(name))
+
+
+class RaggedDiagnosis(UniformDiagnosis):
+    """What RaggedBatch.diagnose returns: UniformDiagnosis' fields with the per-node rows FLAT -- instance i's nodes are
+    [node_rows[i], node_rows[i + 1]); nodes(i) returns (side, unmet) of instance i as views."""
+    __slots__ = ("node_rows",)
+
+    def __init__(self, node_rows, **arrays):
+        super().__init__(**arrays)
+        self.node_rows = node_rows
+
+    def nodes(self, i: int):
+        lo, hi = int(self.node_rows[i]), int(self.node_rows[i + 1])
+        return tuple(None if a is None else a[lo:hi] for a in (self.side, self.unmet))
+
+
 class _PlacedBatch:
     """What UniformBatch and RaggedBatch share: the checks of every array of a call, the calls and their results.  A subclass has the
     constructor (which sets _h, _last = None, count, device, record_trace) and says what differs:
@@ -575,6 +609,7 @@ class _PlacedBatch:
       _IO, _CHECK_IO     the ctypes structs of a solve call and of a validation call
       _RANGE_IO          the ctypes struct of a cost-ranges call; _ranges(out) makes its result
       _BASIS_IO          the ctypes struct that carries a given basis into solve_from()
+      _DIAGNOSE_IO       the ctypes struct of a diagnose call; _diagnosis(out) makes its result
       _RESULT            the result class; _result(out) makes one
       _sizes()           the shapes of the outputs by UniformResult.FIELDS' dimension key
       _stride(...)       the expected shape of the array of a given name, its contiguity, and the stride it is passed with"""
@@ -839,6 +874,41 @@ class _PlacedBatch:
         """What the last data_ranges() / data_ranges_on_host() did: instances, ranged ones, tiers, walks, hops, kernel time."""
         st = L.UBatchDataRangeStats(); L.check(self._fn("get_data_range_stats")(self._h, C.byref(st))); return st.as_dict()
 
+    # ---- why infeasible: a cut from the kept flow
+    def _diagnosis(self, out):
+        return UniformDiagnosis(**out)
+
+    def _diagnose(self, fn, tensors, nodes):
+        if tensors is None:
+            tensors = self._last is not None and _is_tensor(self._last.status)
+        sizes = self._sizes()
+        io = self._DIAGNOSE_IO()
+        io.memory = L.MEM_DEVICE if tensors else L.MEM_HOST
+        out = {}
+        for name, dtype, dim in UniformDiagnosis.FIELDS:
+            if not nodes and dim == "n":
+                continue
+            out[name] = self._empty(sizes[dim], dtype, tensors)
+            setattr(io, name, out[name].data_ptr() if tensors else out[name].ctypes.data)
+        L.check(self._fn(fn)(self._h, C.byref(io)))
+        return self._diagnosis(out)
+
+    def diagnose(self, tensors=None, nodes=True):
+        """Whether the flow every instance's last solve call left satisfies its constraints and, where it does not, a cut that proves the
+        instance infeasible, on the device: a UniformDiagnosis / RaggedDiagnosis.  tensors: True = tensors on the handle's device (nothing
+        that scales with the batch crosses the bus), False = numpy arrays, None = like the last result.  nodes=False leaves side and unmet
+        out (the walk still runs: the verdict needs it).  The kept state is read, never changed: solve calls, range calls and this one mix
+        in any order."""
+        return self._diagnose("diagnose", tensors, nodes)
+
+    def diagnose_on_host(self, nodes=True):
+        """Test hook: diagnose() with one lane on the CPU.  numpy only."""
+        return self._diagnose("diagnose_on_host", False, nodes)
+
+    def diagnose_stats(self) -> dict:
+        """What the last diagnose() / diagnose_on_host() did: instances per verdict, tiers, levels, frontier nodes, incidence entries, kernel time."""
+        st = L.UBatchDiagnoseStats(); L.check(self._fn("get_diagnose_stats")(self._h, C.byref(st))); return st.as_dict()
+
     # ---- validation: the solution's rows where they lie
     SOLUTION_ROWS = (("status", "int32", None), ("total_cost", "int64", None), ("flows", "int64", "arc_count"), ("potentials", "int64", "node_count"))
 
@@ -904,6 +974,7 @@ class UniformBatch(_PlacedBatch):
         L.check(L.lib().mcf_ubatch_create(C.byref(self._h), C.byref(d)))
 
     _DATA_RANGE_IO = L.UBatchDataRangeIo
+    _DIAGNOSE_IO = L.UBatchDiagnoseIo
 
     def _pairs_into(self, io, pairs, tensors, keep):
         """one list for every instance: ship rows [count, k]"""
@@ -989,6 +1060,10 @@ class RaggedBatch(_PlacedBatch):
         return RaggedRanges(self.arc_rows, **out)
 
     _DATA_RANGE_IO = L.RBatchDataRangeIo
+    _DIAGNOSE_IO = L.RBatchDiagnoseIo
+
+    def _diagnosis(self, out):
+        return RaggedDiagnosis(self.node_rows, **out)
 
     def _pairs_into(self, io, pairs, tensors, keep):
         """one list per graph, flat, with pair_row (where each graph's begins) and ship_row (where each instance's answers do); the two

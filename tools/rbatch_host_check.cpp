@@ -1,7 +1,8 @@
 // rbatch_host_check.cpp -- the host side of the placed batches as a stand-alone program, so that it can be built together with the
 // library's host sources under -fsanitize=address,undefined and run on a CPU ("Ragged batch").  It runs the ragged entry
 // points (mcf_rbatch_create, _run_on_host, _rerun_on_host, _validate_on_host) on its input, exports the first solve's basis
-// (_cost_ranges_on_host), asks the same basis' supply and bound ranges (_data_ranges_on_host, pairs included) and starts a second handle from it (_run_from_on_host: the same data must give the first solve's status and
+// (_cost_ranges_on_host), asks the same basis' supply and bound ranges (_data_ranges_on_host, pairs included), diagnoses the same state
+// (_diagnose_on_host, on a ragged and a uniform handle, verdict counts printed) and starts a second handle from it (_run_from_on_host: the same data must give the first solve's status and
 // total cost; the second costs run for the sanitizer's sake), then the instances of the input's first graph through the uniform entry
 // points (mcf_ubatch_*), which share the drivers, and compares every row of the two.  Needs no GPU and is not loaded into Python.
 //
@@ -41,6 +42,14 @@ static std::vector<T> dense(const std::vector<T> &flat, const std::vector<int64_
     for (int i : sel) out.insert(out.end(), flat.begin() + row[(size_t)i] * scale, flat.begin() + row[(size_t)i] * scale + length);
     return out;
 }
+
+// what a diagnose call wrote, exactly sized
+struct Diagnosis {
+    std::vector<int32_t> verdict, set_size;
+    std::vector<int64_t> violation, unmet;
+    std::vector<int8_t> side;
+    Diagnosis(size_t count, size_t nodes) : verdict(count), set_size(count), violation(count), unmet(nodes), side(nodes) {}
+};
 
 // what a solve call and a validation call wrote
 struct Answers {
@@ -101,6 +110,7 @@ int main(int argc, char **argv)
     for (int i = 0; i < count; ++i) changed[(size_t)i] = i % 3 != 1;
 
     int64_t pivots_total = 0, invalid_total = 0, started = 0, data_ranged_total = 0, data_walks = 0;
+    int64_t verdicts[MCF_DIAG_BOUNDS + 1] = {}, uniform_verdicts[MCF_DIAG_BOUNDS + 1] = {}, diag_levels = 0;
     for (int32_t rule : {MCF_RULE_BLOCK_SEARCH, MCF_RULE_BEST_ELIGIBLE, MCF_RULE_FIRST_ELIGIBLE})
         for (int32_t stype : {MCF_SUPPLY_GEQ, MCF_SUPPLY_LEQ}) {
             mcf_rbatch_desc d{};
@@ -180,6 +190,34 @@ int main(int argc, char **argv)
                 CHECK(mcf_rbatch_get_data_range_stats(b, &ds));
                 data_walks += ds.walks;
             }
+            // why infeasible, from the same kept state: every output exactly sized; a cut's violation is the |unmet| of its side
+            Diagnosis dg((size_t)count, supply.size());
+            {
+                mcf_rbatch_diagnose_io gio{};
+                gio.memory = MCF_MEM_HOST; gio.verdict = dg.verdict.data(); gio.violation = dg.violation.data(); gio.set_size = dg.set_size.data();
+                gio.side = dg.side.data(); gio.unmet = dg.unmet.data();
+                CHECK(mcf_rbatch_diagnose_on_host(b, &gio));
+                mcf_ubatch_diagnose_stats gs{};
+                CHECK(mcf_rbatch_get_diagnose_stats(b, &gs));
+                if (gs.open != 0) { fprintf(stderr, "%lld instances without a certificate\n", (long long)gs.open); return 1; }
+                diag_levels += gs.levels;
+                for (int i = 0; i < count; ++i) {
+                    const int32_t v = dg.verdict[(size_t)i];
+                    if (v < MCF_DIAG_NONE || v > MCF_DIAG_BOUNDS) { fprintf(stderr, "instance %d: verdict %d\n", i, v); return 1; }
+                    ++verdicts[v];
+                    int64_t sum = 0, size = 0;
+                    for (int64_t k = node_row[(size_t)i]; k < node_row[(size_t)i + 1]; ++k)
+                        if (dg.side[(size_t)k]) { sum += dg.unmet[(size_t)k] < 0 ? -dg.unmet[(size_t)k] : dg.unmet[(size_t)k]; ++size; }
+                    if (size != dg.set_size[(size_t)i] || (v == MCF_DIAG_CUT) != (dg.violation[(size_t)i] > 0) || (v == MCF_DIAG_CUT && sum != dg.violation[(size_t)i])) {
+                        fprintf(stderr, "instance %d: verdict %d, violation %lld, |unmet| over the side %lld\n", i, v, (long long)dg.violation[(size_t)i], (long long)sum);
+                        return 1;
+                    }
+                }
+                gio.side = nullptr; gio.unmet = nullptr;                  // without the rows the walk still runs
+                const std::vector<int32_t> with_rows = dg.verdict;
+                CHECK(mcf_rbatch_diagnose_on_host(b, &gio));
+                if (dg.verdict != with_rows) { fprintf(stderr, "another verdict without the node rows\n"); return 1; }
+            }
             {
                 mcf_rbatch *from = nullptr;
                 CHECK(mcf_rbatch_create(&from, &d));
@@ -233,6 +271,19 @@ int main(int argc, char **argv)
             uc.valid = u.valid.data(); uc.errors = u.errors.data(); uc.first = u.first.data(); uc.objective = u.objective.data(); uc.dual_cost = u.dual.data();
             CHECK(mcf_ubatch_validate_on_host(ub, &uc, &summary));
             if (!same("first solve", u, r_first, one, arc_row, node_row, n0, m0, sel)) return 1;
+            {
+                Diagnosis ug(sel.size(), u_supply.size());
+                mcf_ubatch_diagnose_io gio{};
+                gio.memory = MCF_MEM_HOST; gio.verdict = ug.verdict.data(); gio.violation = ug.violation.data(); gio.set_size = ug.set_size.data();
+                gio.side = ug.side.data(); gio.unmet = ug.unmet.data();
+                CHECK(mcf_ubatch_diagnose_on_host(ub, &gio));
+                if (ug.verdict != dense(dg.verdict, one, 1, 1, sel) || ug.violation != dense(dg.violation, one, 1, 1, sel) || ug.set_size != dense(dg.set_size, one, 1, 1, sel) ||
+                    ug.side != dense(dg.side, node_row, 1, n0, sel) || ug.unmet != dense(dg.unmet, node_row, 1, n0, sel)) {
+                    fprintf(stderr, "the uniform batch's diagnosis differs from the ragged batch's\n");
+                    return 1;
+                }
+                for (int32_t v : ug.verdict) ++uniform_verdicts[v];
+            }
             uio.cost = u_cost2.data(); uio.changed = u_changed.data();
             CHECK(mcf_ubatch_rerun_on_host(ub, &uio));
             uio.changed = nullptr;
@@ -246,5 +297,10 @@ int main(int argc, char **argv)
            "%lld starts from an exported basis accepted; %lld instances' supply and bound ranges over %lld walks; "
            "the %zu instances of graph 0 as a uniform batch: every row equal\n",
            count, G, (long long)pivots_total, (long long)invalid_total, (long long)started, (long long)data_ranged_total, (long long)data_walks, sel.size());
+    printf("diagnosed over all handles: ragged none %lld, feasible %lld, cut %lld, open %lld, by bounds %lld (%lld levels); "
+           "uniform none %lld, feasible %lld, cut %lld, open %lld, by bounds %lld\n",
+           (long long)verdicts[MCF_DIAG_NONE], (long long)verdicts[MCF_DIAG_FEASIBLE], (long long)verdicts[MCF_DIAG_CUT], (long long)verdicts[MCF_DIAG_OPEN],
+           (long long)verdicts[MCF_DIAG_BOUNDS], (long long)diag_levels, (long long)uniform_verdicts[MCF_DIAG_NONE], (long long)uniform_verdicts[MCF_DIAG_FEASIBLE],
+           (long long)uniform_verdicts[MCF_DIAG_CUT], (long long)uniform_verdicts[MCF_DIAG_OPEN], (long long)uniform_verdicts[MCF_DIAG_BOUNDS]);
     return 0;
 }
