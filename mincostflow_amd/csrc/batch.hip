@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cstring>
 #include <vector>
 
@@ -1050,41 +1051,40 @@ struct PlacedBatch {
     int64_t *d_summary = nullptr;       // validation: invalid instances, the lowest invalid index.  Allocated last: it says the tables are up
     unsigned char *d_io = nullptr;      // MCF_MEM_HOST: the caller's arrays on their way up and down
     size_t d_io_bytes = 0;
-    // cost ranges and data ranges: for each the instances by tier and footprint class (planned for the lds_max it names, up once), the
-    // summary words both use, the last calls' statistics
-    struct RangeLaunch { int first, n; uint32_t lds; bool in_lds; };
-    struct RangePlan {
-        std::vector<RangeLaunch> launches;
+    // The queries of the kept state (cost ranges, data ranges, diagnosis): each has its own plan -- the instances by tier and by the class
+    // of ITS footprint, planned for the lds_max it names, the id table up once -- and the statistics of its last call that succeeded.
+    struct QueryLaunch { int first, n; uint32_t lds; bool in_lds; };
+    struct QueryPlan {
+        std::vector<QueryLaunch> launches;
         int32_t *d_ids = nullptr;
         int lds_max = -1;
+        ~QueryPlan() { if (d_ids) (void)hipFree(d_ids); }
     };
-    RangePlan range_plan, data_range_plan, diagnose_plan;
-    int64_t *d_range_summary = nullptr;
-    mcf_ubatch_range_stats range_stats{};
-    mcf_ubatch_data_range_stats data_range_stats{};
-    // diagnosis: its summary words, the global tier's marks and frontiers (work_stride bytes per instance of that tier, in launch order;
-    // allocated with the first call that has such instances), the last call's statistics
-    int64_t *d_diag_summary = nullptr;
+    template <class Stats>
+    struct Query {
+        QueryPlan plan;
+        Stats stats{};
+        operator const Stats &() const { return stats; }
+    };
+    Query<mcf_ubatch_range_stats> cost_ranges;
+    Query<mcf_ubatch_data_range_stats> data_ranges;
+    Query<mcf_ubatch_diagnose_stats> diagnose;
+    int64_t *d_query_summary = nullptr; // kQuerySummaryWords, whichever query runs; allocated with the first device call of any of them
+    // diagnosis, global tier: marks and frontiers, diag_work_stride bytes per instance of that tier in launch order (the last call's
+    // stride; allocated with the first call that has such instances)
     unsigned char *d_diag_work = nullptr;
     size_t diag_work_bytes = 0;
-    mcf_ubatch_diagnose_stats diagnose_stats{};
+    uint64_t diag_work_stride = 0;
     std::vector<unsigned char> h_slab;  // the host hooks' slab, slots and traces: the device's layout
     std::vector<BatchSlot> h_slots;
     std::vector<int32_t> h_traces;
     ~PlacedBatch()
     {
-        if (d_tables) (void)hipFree(d_tables);
-        if (d_tmpl) (void)hipFree(d_tmpl);
-        if (d_summary) (void)hipFree(d_summary);
-        if (d_io) (void)hipFree(d_io);
-        if (range_plan.d_ids) (void)hipFree(range_plan.d_ids);
-        if (data_range_plan.d_ids) (void)hipFree(data_range_plan.d_ids);
-        if (diagnose_plan.d_ids) (void)hipFree(diagnose_plan.d_ids);
-        if (d_diag_summary) (void)hipFree(d_diag_summary);
-        if (d_diag_work) (void)hipFree(d_diag_work);
-        if (d_range_summary) (void)hipFree(d_range_summary);
+        for (void *p : {(void *)d_tables, (void *)d_tmpl, (void *)d_summary, (void *)d_io, (void *)d_query_summary, (void *)d_diag_work})
+            if (p) (void)hipFree(p);
     }
 };
+constexpr int kQuerySummaryWords = mcf::kDiagSummaryWords > 3 ? mcf::kDiagSummaryWords : 3;    // the most any query has
 
 }  // namespace
 
@@ -1184,32 +1184,195 @@ BatchIo with_basis(BatchIo x, const mcf_rbatch_basis_io *basis)
 BatchIo io_of(const mcf_ubatch_check_io *io) { return with_strides(check_io(io), io); }
 BatchIo io_of(const mcf_rbatch_check_io *io) { return check_io(io); }
 
-// The arrays of a data-ranges call, whichever of the two public structs they came in (data_range_io_of): the uniform struct's one pair
-// list or the ragged struct's tables, never both.
-struct DataRangeIo {
-    bool given;
-    int32_t memory;
-    const int32_t *pairs;
-    int64_t pair_count;                 // the uniform struct's
-    const int64_t *pair_row, *ship_row; // the ragged struct's
-    int32_t *ranged;
-    int8_t *arc_state;
-    int64_t *flow_down, *flow_up, *ship_forth, *ship_back;
+// One array of the caller's on its way through the staging buffer of a MCF_MEM_HOST call (stage_arrays): where the call keeps its
+// pointer, its true length, whether the call reads it and whether it writes it.
+struct StagedArray { void **slot; size_t bytes; bool up, down; };
+
+// ---- The queries of the kept state: mcf_*batch_cost_ranges, _data_ranges and _diagnose, each a device call and a host hook.  One driver
+// runs all of them on both placements (query_on_device, query_on_host, check_query_call); a description says what differs between the
+// queries, the way a placement says what differs between the handles:
+//   Io, io_of        the call's arrays, whichever public struct they came in
+//   Stats, state     a call's statistics, and where the handle keeps the last ones with the query's plan
+//   check            the query's own refusals: after those every call has, before "has not been solved"
+//   arrays           MCF_MEM_HOST: one StagedArray per array of the caller's
+//   footprint        what one instance keeps in LDS: it classes the instances of the LDS tier
+//   kWords, outputs, stats_of      the summary words: how many, the step's outputs with them, what they say
+//   prepare          before the launches; only diagnosis has something to do there
+//   Scratch, on_host the step for one instance with one lane, and the room it may keep between instances
+// The kernels, and the arguments only one placement has, are the placement's (launch_query).
+struct PlainQuery {                     // what a query has unless it says otherwise
+    struct Scratch {};
+    template <class P> static int prepare(typename P::Handle *, const PlacedBatch::QueryPlan &) { return MCF_OK; }
 };
-DataRangeIo data_range_io_of(const mcf_ubatch_data_range_io *io)
-{
-    if (!io) return DataRangeIo{};
-    return DataRangeIo{true, io->memory, io->pairs, io->pair_count, nullptr, nullptr, io->ranged, io->arc_state, io->flow_down, io->flow_up, io->ship_forth, io->ship_back};
-}
-DataRangeIo data_range_io_of(const mcf_rbatch_data_range_io *io)
-{
-    if (!io) return DataRangeIo{};
-    return DataRangeIo{true, io->memory, io->pairs, 0, io->pair_row, io->ship_row, io->ranged, io->arc_state, io->flow_down, io->flow_up, io->ship_forth, io->ship_back};
-}
+
+struct CostRanges : PlainQuery {        // uniform_ranges (ranges_step.hip.h)
+    using Stats = mcf_ubatch_range_stats;
+    using Outputs = mcf::RangeOutputs;
+    struct Io {
+        bool given;
+        int32_t memory;
+        int32_t *ranged;
+        int8_t *arc_state;
+        int64_t *cost_down, *cost_up;
+    };
+    template <class T> static Io io_of(const T *io) { return io ? Io{true, io->memory, io->ranged, io->arc_state, io->cost_down, io->cost_up} : Io{}; }
+    static PlacedBatch::Query<Stats> &state(PlacedBatch *b) { return b->cost_ranges; }
+    template <class P> static int check(const typename P::Handle *, Io *io, const char *what)
+    {
+        if (!io->cost_down != !io->cost_up) return mcf::fail(MCF_ERR_INVALID, "%s: cost_down and cost_up come together or not at all", what);
+        return MCF_OK;
+    }
+    template <class P> static std::array<StagedArray, 4> arrays(const typename P::Handle *b, Io *io)
+    {
+        const size_t count = (size_t)b->d.count, arcs = P::arc_rows(b);
+        return {{{(void **)&io->ranged, 4 * count, false, true},
+                 {(void **)&io->arc_state, arcs, false, true},
+                 {(void **)&io->cost_down, 8 * arcs, false, true},
+                 {(void **)&io->cost_up, 8 * arcs, false, true}}};
+    }
+    static uint32_t footprint(int32_t n, int32_t m) { return mcf::range_layout_of((uint32_t)(m + 2 * n), (uint32_t)n + 1u, (uint32_t)m).bytes; }
+    static constexpr int kWords = 3;
+    static Outputs outputs(const Io &io, int64_t *summary) { return Outputs{io.ranged, io.arc_state, io.cost_down, io.cost_up, summary}; }
+    static void stats_of(const int64_t *words, Stats *st) { st->ranged = words[0]; st->tree_arcs = words[1]; st->cycle_hops = words[2]; }
+    template <class P>
+    static void on_host(const typename P::Handle *, const Io &, const mcf::InstanceView &v, const Outputs &o, int64_t, const BatchSlot &slot, Scratch &)
+    {
+        mcf::uniform_ranges<false>(v, o, slot, nullptr, 0, 1);
+    }
+};
+
 // how many pairs and ship entries a call's arrays hold, where the host can know (the tables of a ragged MCF_MEM_DEVICE call lie on the device)
 struct PairSizes {
     bool known;
     size_t pairs, ships;
+};
+struct DataRanges : PlainQuery {        // uniform_data_ranges (data_ranges_step.hip.h)
+    using Stats = mcf_ubatch_data_range_stats;
+    using Outputs = mcf::DataRangeOutputs;
+    struct Io {                         // the uniform struct's one pair list or the ragged struct's tables, never both
+        bool given;
+        int32_t memory;
+        const int32_t *pairs;
+        int64_t pair_count;                 // the uniform struct's
+        const int64_t *pair_row, *ship_row; // the ragged struct's
+        int32_t *ranged;
+        int8_t *arc_state;
+        int64_t *flow_down, *flow_up, *ship_forth, *ship_back;
+        PairSizes sizes;                    // what check learned (P::check_pairs)
+    };
+    static Io io_of(const mcf_ubatch_data_range_io *io)
+    {
+        if (!io) return Io{};
+        return Io{true, io->memory, io->pairs, io->pair_count, nullptr, nullptr, io->ranged, io->arc_state, io->flow_down, io->flow_up, io->ship_forth, io->ship_back, {}};
+    }
+    static Io io_of(const mcf_rbatch_data_range_io *io)
+    {
+        if (!io) return Io{};
+        return Io{true, io->memory, io->pairs, 0, io->pair_row, io->ship_row, io->ranged, io->arc_state, io->flow_down, io->flow_up, io->ship_forth, io->ship_back, {}};
+    }
+    static PlacedBatch::Query<Stats> &state(PlacedBatch *b) { return b->data_ranges; }
+    template <class P> static int check(const typename P::Handle *b, Io *io, const char *what)
+    {
+        if (!io->flow_down != !io->flow_up) return mcf::fail(MCF_ERR_INVALID, "%s: flow_down and flow_up come together or not at all", what);
+        if (!io->ship_forth != !io->ship_back) return mcf::fail(MCF_ERR_INVALID, "%s: ship_forth and ship_back come together or not at all", what);
+        return P::check_pairs(b, *io, what, &io->sizes);
+    }
+    // the only query with arrays that go up: the pairs and, from a ragged call, their tables.  No pairs: the kernel gets a null list
+    template <class P> static std::array<StagedArray, 9> arrays(const typename P::Handle *b, Io *io)
+    {
+        const size_t count = (size_t)b->d.count, arcs = P::arc_rows(b), graphs = P::template_count(b);
+        if (!io->sizes.pairs) io->pairs = nullptr;
+        return {{{(void **)&io->pairs, 8 * io->sizes.pairs, true, false},
+                 {(void **)&io->pair_row, 8 * (graphs + 1), true, false},
+                 {(void **)&io->ship_row, 8 * (count + 1), true, false},
+                 {(void **)&io->ranged, 4 * count, false, true},
+                 {(void **)&io->arc_state, arcs, false, true},
+                 {(void **)&io->flow_down, 8 * arcs, false, true},
+                 {(void **)&io->flow_up, 8 * arcs, false, true},
+                 {(void **)&io->ship_forth, 8 * io->sizes.ships, false, true},
+                 {(void **)&io->ship_back, 8 * io->sizes.ships, false, true}}};
+    }
+    static uint32_t footprint(int32_t n, int32_t m) { return mcf::data_range_layout_of((uint32_t)m, (uint32_t)n + 1u).bytes; }
+    static constexpr int kWords = 3;
+    static Outputs outputs(const Io &io, int64_t *summary)
+    {
+        return Outputs{io.ranged, io.arc_state, io.flow_down, io.flow_up, io.ship_forth, io.ship_back, summary};
+    }
+    static void stats_of(const int64_t *words, Stats *st) { st->ranged = words[0]; st->walks = words[1]; st->hops = words[2]; }
+    template <class P>
+    static void on_host(const typename P::Handle *b, const Io &io, const mcf::InstanceView &v, const Outputs &o, int64_t i, const BatchSlot &slot, Scratch &)
+    {
+        mcf::uniform_data_ranges<false>(v, o, P::pair_list(b, io, i), slot, nullptr, 0, 1);
+    }
+};
+
+struct Diagnose : PlainQuery {          // uniform_diagnose (diagnose_step.hip.h)
+    using Stats = mcf_ubatch_diagnose_stats;
+    using Outputs = mcf::DiagOutputs;
+    struct Io {
+        bool given;
+        int32_t memory;
+        int32_t *verdict;
+        int64_t *violation;
+        int32_t *set_size;
+        int8_t *side;
+        int64_t *unmet;
+    };
+    template <class T> static Io io_of(const T *io) { return io ? Io{true, io->memory, io->verdict, io->violation, io->set_size, io->side, io->unmet} : Io{}; }
+    static PlacedBatch::Query<Stats> &state(PlacedBatch *b) { return b->diagnose; }
+    template <class P> static int check(const typename P::Handle *, Io *, const char *) { return MCF_OK; }
+    template <class P> static std::array<StagedArray, 5> arrays(const typename P::Handle *b, Io *io)
+    {
+        const size_t count = (size_t)b->d.count, nodes = P::node_rows(b);
+        return {{{(void **)&io->verdict, 4 * count, false, true},
+                 {(void **)&io->violation, 8 * count, false, true},
+                 {(void **)&io->set_size, 4 * count, false, true},
+                 {(void **)&io->side, nodes, false, true},
+                 {(void **)&io->unmet, 8 * nodes, false, true}}};
+    }
+    static uint32_t footprint(int32_t n, int32_t m) { return mcf::diag_layout_of((uint32_t)m, (uint32_t)n + 1u).bytes; }
+    static constexpr int kWords = mcf::kDiagSummaryWords;
+    static Outputs outputs(const Io &io, int64_t *summary) { return Outputs{io.verdict, io.violation, io.set_size, io.side, io.unmet, summary}; }
+    static void stats_of(const int64_t *words, Stats *st)
+    {
+        st->none = words[MCF_DIAG_NONE]; st->feasible = words[MCF_DIAG_FEASIBLE]; st->cut = words[MCF_DIAG_CUT]; st->open = words[MCF_DIAG_OPEN];
+        st->bounds = words[MCF_DIAG_BOUNDS];
+        st->levels = words[MCF_DIAG_BOUNDS + 1]; st->frontier_nodes = words[MCF_DIAG_BOUNDS + 2]; st->inc_entries = words[MCF_DIAG_BOUNDS + 3];
+    }
+    // The global tier's room for unmet, marks and frontiers: per block what the largest instance of that tier needs, 0 when the plan has
+    // no such launch; the buffer only grows.
+    template <class P> static int prepare(typename P::Handle *b, const PlacedBatch::QueryPlan &plan)
+    {
+        b->diag_work_stride = 0;
+        for (const PlacedBatch::QueryLaunch &L : plan.launches) {
+            if (L.in_lds) continue;
+            const LaunchPlan solve = P::plan(b);
+            uint32_t most = 0;
+            for (size_t i = 0; i < (size_t)b->d.count; ++i) {
+                if (class_of(b->lds_max, solve.bytes((int32_t)i)) != kClasses - 1) continue;
+                int32_t n = 0, m = 0;
+                P::sizes(b, i, &n, &m);
+                most = std::max(most, mcf::diag_layout_of(0, (uint32_t)n + 1u).bytes);
+            }
+            b->diag_work_stride = most;
+            const size_t need = (size_t)L.n * (size_t)most;
+            if (b->diag_work_bytes < need) {
+                if (b->d_diag_work) { HIP_TRY(hipFree(b->d_diag_work)); b->d_diag_work = nullptr; b->diag_work_bytes = 0; }
+                HIP_TRY(hipMalloc((void **)&b->d_diag_work, need));
+                b->diag_work_bytes = need;
+            }
+        }
+        return MCF_OK;
+    }
+    struct alignas(16) Word { uint64_t lo, hi; };
+    using Scratch = std::vector<Word>;  // one instance's unmet, marks and frontiers at a time
+    template <class P>
+    static void on_host(const typename P::Handle *, const Io &, const mcf::InstanceView &v, const Outputs &o, int64_t, const BatchSlot &slot, Scratch &room)
+    {
+        const size_t words_needed = mcf::diag_layout_of(0, (uint32_t)v.n + 1u).bytes / sizeof(Word);
+        if (room.size() < words_needed) room.resize(words_needed);
+        mcf::uniform_diagnose<false>(v, o, slot, (unsigned char *)room.data(), 0, 1);
+    }
 };
 
 mcf::UniformOutputs outputs_of(const BatchIo &io)
@@ -1268,32 +1431,26 @@ struct UniformPlacement {
         hipLaunchKernelGGL(uniform_start_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, slots, slab, b->d_inc_start, b->d_inc);
     }
     static constexpr auto finish_kernel = uniform_finish_kernel;
-    static constexpr auto ranges_kernel_in_lds = uniform_ranges_kernel<true>;
     static void launch_validate(const Handle *b, const Problem &p, const mcf::UniformCheck &c, const BatchIo &io)
     {
         hipLaunchKernelGGL(uniform_validate_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, p, c, b->d_inc_start, b->d_inc, io.flows, io.potentials);
     }
-    static void launch_ranges(const Handle *, bool in_lds, unsigned blocks, uint32_t lds, const Problem &p, const mcf::RangeOutputs &o, const BatchSlot *slots,
-                              unsigned char *slab, const int32_t *ids)
+    // a query's kernels, in LDS and in place, and their arguments: go(...) launches one plan entry with them (query_on_device)
+    template <class A, class Go> static int launch_query(CostRanges, const Handle *, const A &a, const Go &go)
     {
-        hipLaunchKernelGGL(in_lds ? ranges_kernel_in_lds : uniform_ranges_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, p, o, slots, slab, ids);
+        return go(uniform_ranges_kernel<true>, uniform_ranges_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids);
     }
-    static constexpr auto data_ranges_kernel_in_lds = uniform_data_ranges_kernel<true>;
-    static void launch_data_ranges(const Handle *, bool in_lds, unsigned blocks, uint32_t lds, const Problem &p, const mcf::DataRangeOutputs &o, const DataRangeIo &io,
-                                   const BatchSlot *slots, unsigned char *slab, const int32_t *ids)
+    template <class A, class Go> static int launch_query(DataRanges, const Handle *, const A &a, const Go &go)
     {
-        hipLaunchKernelGGL(in_lds ? data_ranges_kernel_in_lds : uniform_data_ranges_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, p, o, io.pairs,
-                           io.pair_count, slots, slab, ids);
+        return go(uniform_data_ranges_kernel<true>, uniform_data_ranges_kernel<false>, a.p, a.o, a.io.pairs, a.io.pair_count, a.slots, a.slab, a.ids);
     }
-    static constexpr auto diagnose_kernel_in_lds = uniform_diagnose_kernel<true>;
-    static void launch_diagnose(const Handle *b, bool in_lds, unsigned blocks, uint32_t lds, const Problem &p, const mcf::DiagOutputs &o, const BatchSlot *slots,
-                                unsigned char *slab, const int32_t *ids, unsigned char *work, uint64_t work_stride)
+    template <class A, class Go> static int launch_query(Diagnose, const Handle *b, const A &a, const Go &go)
     {
-        hipLaunchKernelGGL(in_lds ? diagnose_kernel_in_lds : uniform_diagnose_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, p, o, slots, slab, ids,
-                           b->d_inc_start, b->d_inc, work, work_stride);
+        return go(uniform_diagnose_kernel<true>, uniform_diagnose_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids, b->d_inc_start, b->d_inc, b->d_diag_work,
+                  b->diag_work_stride);
     }
     // one list for every instance
-    static int check_pairs(const Handle *b, const DataRangeIo &io, const char *what, PairSizes *sizes)
+    static int check_pairs(const Handle *b, const DataRanges::Io &io, const char *what, PairSizes *sizes)
     {
         if (io.pair_count < 0) return mcf::fail(MCF_ERR_INVALID, "%s: negative pair count", what);
         if (io.pair_count > 0 && !io.pairs) return mcf::fail(MCF_ERR_INVALID, "%s: null pairs", what);
@@ -1301,7 +1458,7 @@ struct UniformPlacement {
         *sizes = PairSizes{true, (size_t)io.pair_count, (size_t)b->d.count * (size_t)io.pair_count};
         return MCF_OK;
     }
-    static mcf::PairList pair_list(const Handle *, const DataRangeIo &io, int64_t i) { return mcf::uniform_pairs(io.pairs, io.pair_count, i); }
+    static mcf::PairList pair_list(const Handle *, const DataRanges::Io &io, int64_t i) { return mcf::uniform_pairs(io.pairs, io.pair_count, i); }
     static void sizes(const Handle *b, size_t, int32_t *n, int32_t *m) { *n = b->d.node_count; *m = b->d.arc_count; }
     static size_t arc_rows(const Handle *b) { return (size_t)b->d.count * (size_t)b->d.arc_count; }
     static size_t node_rows(const Handle *b) { return (size_t)b->d.count * (size_t)b->d.node_count; }
@@ -1373,33 +1530,25 @@ struct RaggedPlacement {
         hipLaunchKernelGGL(ragged_start_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, r, b->d_tmpl, slots, slab);
     }
     static constexpr auto finish_kernel = ragged_finish_kernel;
-    static constexpr auto ranges_kernel_in_lds = ragged_ranges_kernel<true>;
     static void launch_validate(const Handle *b, const Problem &r, const mcf::UniformCheck &c, const BatchIo &io)
     {
         hipLaunchKernelGGL(ragged_validate_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, r, c, io.flows, io.potentials);
     }
-    static void launch_ranges(const Handle *, bool in_lds, unsigned blocks, uint32_t lds, const Problem &r, const mcf::RangeOutputs &o, const BatchSlot *slots,
-                              unsigned char *slab, const int32_t *ids)
+    template <class A, class Go> static int launch_query(CostRanges, const Handle *, const A &a, const Go &go)
     {
-        hipLaunchKernelGGL(in_lds ? ranges_kernel_in_lds : ragged_ranges_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, r, o, slots, slab, ids);
+        return go(ragged_ranges_kernel<true>, ragged_ranges_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids);
     }
-    static constexpr auto data_ranges_kernel_in_lds = ragged_data_ranges_kernel<true>;
-    static void launch_data_ranges(const Handle *, bool in_lds, unsigned blocks, uint32_t lds, const Problem &r, const mcf::DataRangeOutputs &o, const DataRangeIo &io,
-                                   const BatchSlot *slots, unsigned char *slab, const int32_t *ids)
+    template <class A, class Go> static int launch_query(DataRanges, const Handle *, const A &a, const Go &go)
     {
-        hipLaunchKernelGGL(in_lds ? data_ranges_kernel_in_lds : ragged_data_ranges_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, r, o, io.pairs, io.pair_row,
-                           io.ship_row, slots, slab, ids);
+        return go(ragged_data_ranges_kernel<true>, ragged_data_ranges_kernel<false>, a.p, a.o, a.io.pairs, a.io.pair_row, a.io.ship_row, a.slots, a.slab, a.ids);
     }
-    static constexpr auto diagnose_kernel_in_lds = ragged_diagnose_kernel<true>;
-    static void launch_diagnose(const Handle *, bool in_lds, unsigned blocks, uint32_t lds, const Problem &r, const mcf::DiagOutputs &o, const BatchSlot *slots,
-                                unsigned char *slab, const int32_t *ids, unsigned char *work, uint64_t work_stride)
+    template <class A, class Go> static int launch_query(Diagnose, const Handle *b, const A &a, const Go &go)
     {
-        hipLaunchKernelGGL(in_lds ? diagnose_kernel_in_lds : ragged_diagnose_kernel<false>, dim3(blocks), dim3(kBatchThreads), lds, 0, r, o, slots, slab, ids, work,
-                           work_stride);
+        return go(ragged_diagnose_kernel<true>, ragged_diagnose_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids, b->d_diag_work, b->diag_work_stride);
     }
     // one list per graph: pair_row says where each begins, ship_row where each instance's answers do.  Tables in host memory are checked
     // against each other; tables in device memory are the caller's word, as the rows of every call are.
-    static int check_pairs(const Handle *b, const DataRangeIo &io, const char *what, PairSizes *sizes)
+    static int check_pairs(const Handle *b, const DataRanges::Io &io, const char *what, PairSizes *sizes)
     {
         const size_t count = (size_t)b->d.count, G = b->graphs.size();
         if (!io.pair_row != !io.ship_row) return mcf::fail(MCF_ERR_INVALID, "%s: pair_row and ship_row come together or not at all", what);
@@ -1421,7 +1570,7 @@ struct RaggedPlacement {
         *sizes = PairSizes{true, (size_t)io.pair_row[G], (size_t)io.ship_row[count]};
         return MCF_OK;
     }
-    static mcf::PairList pair_list(const Handle *b, const DataRangeIo &io, int64_t i)
+    static mcf::PairList pair_list(const Handle *b, const DataRanges::Io &io, int64_t i)
     {
         return mcf::ragged_pairs(io.pairs, io.pair_row, io.ship_row, b->graph_of[(size_t)i], i);
     }
@@ -1595,9 +1744,28 @@ int state_to_host(PlacedBatch *b, int32_t device, size_t count)          // h_sl
     return MCF_OK;
 }
 
-// The caller's io as the kernels see it: itself for MCF_MEM_DEVICE; for MCF_MEM_HOST every array of *io that is there becomes its staged
-// copy, and what the call reads is uploaded here.  A solve call reads the problem and writes the solution; where it will not write every
-// row (a masked re-solve) the solution goes up too.  A validation call reads both and writes the answers.
+// MCF_MEM_HOST: every array of the table that is there gets its piece of the staging buffer (of `at_least` bytes or more), what the call
+// reads is uploaded and counted by its true length, and the caller's pointer becomes the staged copy's.  stage_down brings back what
+// the call wrote.
+int stage_arrays(PlacedBatch *b, const StagedArray *arrays, size_t n, size_t at_least, Staged *st, int64_t *bytes_up)
+{
+    for (size_t k = 0; k < n; ++k)
+        if (void *const host = *arrays[k].slot) st->add(arrays[k].up ? host : nullptr, arrays[k].down ? host : nullptr, arrays[k].bytes);
+    if (const int rc = reserve_io(b, std::max(st->total, at_least))) return rc;
+    for (const Staged::Piece &pc : st->pieces)
+        if (pc.host_in && pc.bytes) {
+            HIP_TRY(hipMemcpy(b->d_io + pc.offset, pc.host_in, pc.bytes, hipMemcpyHostToDevice));
+            *bytes_up += (int64_t)pc.bytes;
+        }
+    size_t piece = 0;                                                       // the pieces are the arrays that are there, in the table's order
+    for (size_t k = 0; k < n; ++k)
+        if (*arrays[k].slot) *arrays[k].slot = b->d_io + st->pieces[piece++].offset;
+    return MCF_OK;
+}
+
+// The caller's io as the kernels see it: itself for MCF_MEM_DEVICE, staged for MCF_MEM_HOST.  A solve call reads the problem and writes
+// the solution; where it will not write every row (a masked re-solve) the solution goes up too.  A validation call reads both and
+// writes the answers.
 template <class P>
 int stage_up(typename P::Handle *b, BatchIo *io, Staged *st, int64_t *bytes_up)
 {
@@ -1605,8 +1773,7 @@ int stage_up(typename P::Handle *b, BatchIo *io, Staged *st, int64_t *bytes_up)
     const size_t count = (size_t)b->d.count, cap = (size_t)b->d.trace_capacity;
     const RowBytes rows = P::row_bytes(b, *io);
     const bool solution_up = io->check || io->changed, solution_down = !io->check;
-    struct Array { void **slot; size_t bytes; bool up, down; };
-    const Array arrays[] = {{(void **)&io->lower, rows.lower, true, false},
+    const StagedArray arrays[] = {{(void **)&io->lower, rows.lower, true, false},
                             {(void **)&io->upper, rows.upper, true, false},
                             {(void **)&io->cost, rows.cost, true, false},
                             {(void **)&io->supply, rows.supply, true, false},
@@ -1623,19 +1790,7 @@ int stage_up(typename P::Handle *b, BatchIo *io, Staged *st, int64_t *bytes_up)
                             {(void **)&io->first, 4 * count * MCF_VAL_KINDS, false, true},
                             {(void **)&io->objective, 8 * count, false, true},
                             {(void **)&io->dual_cost, 8 * count, false, true}};
-    constexpr int kArrays = (int)(sizeof(arrays) / sizeof(arrays[0]));
-    size_t at[kArrays] = {};
-    for (int k = 0; k < kArrays; ++k)
-        if (void *const host = *arrays[k].slot) at[k] = st->add(arrays[k].up ? host : nullptr, arrays[k].down ? host : nullptr, arrays[k].bytes);
-    if (const int rc = reserve_io(b, st->total)) return rc;
-    for (const Staged::Piece &pc : st->pieces)
-        if (pc.host_in && pc.bytes) {
-            HIP_TRY(hipMemcpy(b->d_io + pc.offset, pc.host_in, pc.bytes, hipMemcpyHostToDevice));
-            *bytes_up += (int64_t)pc.bytes;
-        }
-    for (int k = 0; k < kArrays; ++k)
-        if (*arrays[k].slot) *arrays[k].slot = b->d_io + at[k];
-    return MCF_OK;
+    return stage_arrays(b, arrays, sizeof(arrays) / sizeof(arrays[0]), 0, st, bytes_up);
 }
 int stage_down(PlacedBatch *b, const Staged &st, int64_t *bytes_down)
 {
@@ -1899,38 +2054,26 @@ int validate_on_host(typename P::Handle *b, const BatchIo &io, mcf_ubatch_check_
     return MCF_OK;
 }
 
-// ---- mcf_*batch_cost_ranges / _on_host: uniform_ranges for every instance, on the state the last solve call left; it is only read
-struct RangeIo {
-    bool given;
-    int32_t memory;
-    int32_t *ranged;
-    int8_t *arc_state;
-    int64_t *cost_down, *cost_up;
-};
-template <class Io>
-RangeIo range_io_of(const Io *io)
+// ---- mcf_*batch_cost_ranges, _data_ranges, _diagnose and their _on_host hooks: query Q's step for every instance, on the state the last
+// solve call left; the state is only read.  What every such call refuses before it touches the handle, in this order:
+template <class P, class Q>
+int check_query_call(const typename P::Handle *b, typename Q::Io *io, const char *what, bool host_only)
 {
-    if (!io) return RangeIo{};
-    return RangeIo{true, io->memory, io->ranged, io->arc_state, io->cost_down, io->cost_up};
-}
-
-int check_range_call(const PlacedBatch *b, const RangeIo &io, const char *what, bool host_only)
-{
-    if (!b || !io.given) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
-    if (io.memory != MCF_MEM_HOST && io.memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io.memory);
-    if (host_only && io.memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
-    if (!io.cost_down != !io.cost_up) return mcf::fail(MCF_ERR_INVALID, "%s: cost_down and cost_up come together or not at all", what);
+    if (!b || !io->given) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
+    if (io->memory != MCF_MEM_HOST && io->memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io->memory);
+    if (host_only && io->memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
+    if (const int rc = Q::template check<P>(b, io, what)) return rc;
     if (b->where == PlacedBatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
     return MCF_OK;
 }
 
-// the instances by tier and, in the LDS tier, by the class of what a ranges kernel keeps there (footprint(n, m), never more than the
-// solve's); the table goes up once per handle and plan (again only if the device's LDS limit were another).  An instance is ranged in
-// LDS exactly when it is solved there.
-template <class P, class Footprint>
-int ensure_range_plan(typename P::Handle *b, PlacedBatch::RangePlan &rp, Footprint footprint)
+// the instances by tier and, in the LDS tier, by the class of what query Q keeps there (Q::footprint(n, m), never more than the solve's);
+// the table goes up once per handle and query (again only if the device's LDS limit were another).  An instance is queried in LDS
+// exactly when it is solved there.
+template <class P, class Q>
+int ensure_query_plan(typename P::Handle *b, PlacedBatch::QueryPlan &qp)
 {
-    if (rp.d_ids && rp.lds_max == b->lds_max) return MCF_OK;
+    if (qp.d_ids && qp.lds_max == b->lds_max) return MCF_OK;
     const size_t count = (size_t)b->d.count;
     const LaunchPlan plan = P::plan(b);
     std::vector<int32_t> group[kClasses];
@@ -1938,400 +2081,136 @@ int ensure_range_plan(typename P::Handle *b, PlacedBatch::RangePlan &rp, Footpri
     for (size_t i = 0; i < count; ++i) {
         int32_t n = 0, m = 0;
         P::sizes(b, i, &n, &m);
-        bytes[i] = footprint(n, m);                                         // no more than plan.bytes(i)
+        bytes[i] = Q::footprint(n, m);                                      // no more than plan.bytes(i)
         const bool in_lds = class_of(b->lds_max, plan.bytes((int32_t)i)) != kClasses - 1;
         group[in_lds ? class_of(b->lds_max, bytes[i]) : kClasses - 1].push_back((int32_t)i);
     }
     std::vector<int32_t> ids;
-    rp.launches.clear();
+    qp.launches.clear();
     for (int g = 0; g < kClasses; ++g) {
         if (group[g].empty()) continue;
-        PlacedBatch::RangeLaunch L{(int)ids.size(), (int)group[g].size(), 0, g != kClasses - 1};
+        PlacedBatch::QueryLaunch L{(int)ids.size(), (int)group[g].size(), 0, g != kClasses - 1};
         for (int32_t i : group[g]) {
             ids.push_back(i);
             if (L.in_lds) L.lds = std::max(L.lds, bytes[(size_t)i]);
         }
-        rp.launches.push_back(L);
+        qp.launches.push_back(L);
     }
-    if (!rp.d_ids) HIP_TRY(hipMalloc((void **)&rp.d_ids, count * sizeof(int32_t)));
-    if (!b->d_range_summary) HIP_TRY(hipMalloc((void **)&b->d_range_summary, 3 * sizeof(int64_t)));
-    HIP_TRY(hipMemcpy(rp.d_ids, ids.data(), count * sizeof(int32_t), hipMemcpyHostToDevice));
-    rp.lds_max = b->lds_max;
+    if (!qp.d_ids) HIP_TRY(hipMalloc((void **)&qp.d_ids, count * sizeof(int32_t)));
+    HIP_TRY(hipMemcpy(qp.d_ids, ids.data(), count * sizeof(int32_t), hipMemcpyHostToDevice));
+    qp.lds_max = b->lds_max;
     return MCF_OK;
 }
-inline uint32_t range_footprint(int32_t n, int32_t m) { return mcf::range_layout_of((uint32_t)(m + 2 * n), (uint32_t)n + 1u, (uint32_t)m).bytes; }
-inline uint32_t data_range_footprint(int32_t n, int32_t m) { return mcf::data_range_layout_of((uint32_t)m, (uint32_t)n + 1u).bytes; }
 
+// the problem of a query: the placement's tables where the step runs and the last solve call's supply type (the kept flow belongs to
+// that one); no rows of the caller's
 template <class P>
-int ranges_on_device(typename P::Handle *b, RangeIo io, const char *what)
+typename P::Problem kept_problem(const typename P::Handle *b, bool on_device)
 {
-    if (const int rc = check_range_call(b, io, what, false)) return rc;
-    if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
-    const DeviceGuard guard;
-    if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
-    const size_t count = (size_t)b->d.count;
-    mcf_ubatch_range_stats st{};
-    st.instances = (int64_t)count;
-    if (!count) { b->range_stats = st; return MCF_OK; }
-    if (b->lds_max > (64 << 10))                                            // the opt-in open_device got for the solve's kernels
-        HIP_TRY(hipFuncSetAttribute((const void *)P::ranges_kernel_in_lds, hipFuncAttributeMaxDynamicSharedMemorySize, b->lds_max));
-    if (const int rc = ensure_device_buffers<P>(b)) return rc;
-    const bool first = !b->range_plan.d_ids;
-    if (const int rc = ensure_range_plan<P>(b, b->range_plan, range_footprint)) return rc;
-    if (first) st.bytes_up += (int64_t)(count * sizeof(int32_t));
-    if (const int rc = state_to_device(b, count, &st.bytes_up)) return rc;
-    b->where = PlacedBatch::kOnDevice;                                      // the same state, now there too
-    Staged staged;                                                          // MCF_MEM_HOST: the rows come down through the staging buffer of the solve calls
-    if (io.memory == MCF_MEM_HOST) {
-        const size_t arcs = P::arc_rows(b);
-        size_t at[4] = {};
-        if (io.ranged) at[0] = staged.add(nullptr, io.ranged, 4 * count);
-        if (io.arc_state) at[1] = staged.add(nullptr, io.arc_state, arcs);
-        if (io.cost_down) { at[2] = staged.add(nullptr, io.cost_down, 8 * arcs); at[3] = staged.add(nullptr, io.cost_up, 8 * arcs); }
-        if (const int rc = reserve_io(b, std::max<size_t>(staged.total, 16))) return rc;
-        if (io.ranged) io.ranged = (int32_t *)(b->d_io + at[0]);
-        if (io.arc_state) io.arc_state = (int8_t *)(b->d_io + at[1]);
-        if (io.cost_down) { io.cost_down = (int64_t *)(b->d_io + at[2]); io.cost_up = (int64_t *)(b->d_io + at[3]); }
-    }
-    int64_t words[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpy(b->d_range_summary, words, sizeof(words), hipMemcpyHostToDevice));
-    st.bytes_up += (int64_t)sizeof(words);
-    const mcf::RangeOutputs o{io.ranged, io.arc_state, io.cost_down, io.cost_up, b->d_range_summary};
-    const typename P::Problem p = P::problem(b, BatchIo{}, true);
-    const double t_launch = mcf::now_ns();
-    for (const PlacedBatch::RangeLaunch &L : b->range_plan.launches) {
-        P::launch_ranges(b, L.in_lds, (unsigned)L.n, L.lds, p, o, b->dev.slots, b->dev.slab, b->range_plan.d_ids + L.first);
-        HIP_TRY(hipGetLastError());
-        (L.in_lds ? st.lds_instances : st.global_instances) += L.n;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    st.kernel_ns = mcf::now_ns() - t_launch;
-    HIP_TRY(hipMemcpy(words, b->d_range_summary, sizeof(words), hipMemcpyDeviceToHost));
-    st.bytes_down += (int64_t)sizeof(words);
-    if (const int rc = stage_down(b, staged, &st.bytes_down)) return rc;
-    st.ranged = words[0]; st.tree_arcs = words[1]; st.cycle_hops = words[2];
-    b->range_stats = st;
-    return MCF_OK;
-}
-
-template <class P>
-int ranges_on_host(typename P::Handle *b, const RangeIo &io, const char *what)
-{
-    if (const int rc = check_range_call(b, io, what, true)) return rc;
-    const size_t count = (size_t)b->d.count;
-    b->h_slab.resize(P::slab_bytes(b));
-    b->h_slots.resize(count);
-    if (const int rc = state_to_host(b, b->d.device, count)) return rc;
-    b->where = PlacedBatch::kOnHost;                                        // the same state, now here too
-    mcf_ubatch_range_stats st{};
-    st.instances = (int64_t)count;
-    int64_t words[3] = {0, 0, 0};
-    const mcf::RangeOutputs o{io.ranged, io.arc_state, io.cost_down, io.cost_up, words};
-    const typename P::Problem p = P::problem(b, BatchIo{}, false);
-    const mcf::UniformOutputs none{};
-    const double t_start = mcf::now_ns();
-    for (size_t i = 0; i < count; ++i) {
-        const BatchSlot *tmpl = nullptr;
-        mcf::uniform_ranges<false>(P::view(b, p, none, (int64_t)i, b->h_slab.data(), &tmpl), o, b->h_slots[i], nullptr, 0, 1);
-    }
-    st.kernel_ns = mcf::now_ns() - t_start;
-    st.ranged = words[0]; st.tree_arcs = words[1]; st.cycle_hops = words[2];
-    b->range_stats = st;
-    return MCF_OK;
-}
-
-int get_range_stats(const PlacedBatch *b, mcf_ubatch_range_stats *out)
-{
-    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
-    *out = b->range_stats;
-    return MCF_OK;
-}
-
-// ---- mcf_*batch_data_ranges / _on_host: uniform_data_ranges for every instance, on the state the last solve call left; it is only read
-template <class P>
-int check_data_range_call(const typename P::Handle *b, const DataRangeIo &io, const char *what, bool host_only, PairSizes *sizes)
-{
-    if (!b || !io.given) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
-    if (io.memory != MCF_MEM_HOST && io.memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io.memory);
-    if (host_only && io.memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
-    if (!io.flow_down != !io.flow_up) return mcf::fail(MCF_ERR_INVALID, "%s: flow_down and flow_up come together or not at all", what);
-    if (!io.ship_forth != !io.ship_back) return mcf::fail(MCF_ERR_INVALID, "%s: ship_forth and ship_back come together or not at all", what);
-    if (const int rc = P::check_pairs(b, io, what, sizes)) return rc;
-    if (b->where == PlacedBatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
-    return MCF_OK;
-}
-
-template <class P>
-int data_ranges_on_device(typename P::Handle *b, DataRangeIo io, const char *what)
-{
-    PairSizes sizes{};
-    if (const int rc = check_data_range_call<P>(b, io, what, false, &sizes)) return rc;
-    if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
-    const DeviceGuard guard;
-    if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
-    const size_t count = (size_t)b->d.count;
-    mcf_ubatch_data_range_stats st{};
-    st.instances = (int64_t)count;
-    if (!count) { b->data_range_stats = st; return MCF_OK; }
-    if (b->lds_max > (64 << 10))                                            // the opt-in open_device got for the solve's kernels
-        HIP_TRY(hipFuncSetAttribute((const void *)P::data_ranges_kernel_in_lds, hipFuncAttributeMaxDynamicSharedMemorySize, b->lds_max));
-    if (const int rc = ensure_device_buffers<P>(b)) return rc;
-    const bool first = !b->data_range_plan.d_ids;
-    if (const int rc = ensure_range_plan<P>(b, b->data_range_plan, data_range_footprint)) return rc;
-    if (first) st.bytes_up += (int64_t)(count * sizeof(int32_t));
-    if (const int rc = state_to_device(b, count, &st.bytes_up)) return rc;
-    b->where = PlacedBatch::kOnDevice;                                      // the same state, now there too
-    Staged staged;                                                          // MCF_MEM_HOST: pairs and tables go up, the rows come down, through the staging buffer of the solve calls
-    if (io.memory == MCF_MEM_HOST) {
-        const size_t arcs = P::arc_rows(b), graphs = P::template_count(b);
-        size_t at[9] = {};
-        if (io.pairs && sizes.pairs) at[0] = staged.add(io.pairs, nullptr, 8 * sizes.pairs);
-        if (io.pair_row) { at[1] = staged.add(io.pair_row, nullptr, 8 * (graphs + 1)); at[2] = staged.add(io.ship_row, nullptr, 8 * (count + 1)); }
-        if (io.ranged) at[3] = staged.add(nullptr, io.ranged, 4 * count);
-        if (io.arc_state) at[4] = staged.add(nullptr, io.arc_state, arcs);
-        if (io.flow_down) { at[5] = staged.add(nullptr, io.flow_down, 8 * arcs); at[6] = staged.add(nullptr, io.flow_up, 8 * arcs); }
-        if (io.ship_forth) { at[7] = staged.add(nullptr, io.ship_forth, 8 * sizes.ships); at[8] = staged.add(nullptr, io.ship_back, 8 * sizes.ships); }
-        if (const int rc = reserve_io(b, std::max<size_t>(staged.total, 16))) return rc;
-        for (const Staged::Piece &piece : staged.pieces)
-            if (piece.host_in && piece.bytes) {
-                HIP_TRY(hipMemcpy(b->d_io + piece.offset, piece.host_in, piece.bytes, hipMemcpyHostToDevice));
-                st.bytes_up += (int64_t)piece.bytes;
-            }
-        if (io.pairs && sizes.pairs) io.pairs = (const int32_t *)(b->d_io + at[0]); else io.pairs = nullptr;
-        if (io.pair_row) { io.pair_row = (const int64_t *)(b->d_io + at[1]); io.ship_row = (const int64_t *)(b->d_io + at[2]); }
-        if (io.ranged) io.ranged = (int32_t *)(b->d_io + at[3]);
-        if (io.arc_state) io.arc_state = (int8_t *)(b->d_io + at[4]);
-        if (io.flow_down) { io.flow_down = (int64_t *)(b->d_io + at[5]); io.flow_up = (int64_t *)(b->d_io + at[6]); }
-        if (io.ship_forth) { io.ship_forth = (int64_t *)(b->d_io + at[7]); io.ship_back = (int64_t *)(b->d_io + at[8]); }
-    }
-    int64_t words[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpy(b->d_range_summary, words, sizeof(words), hipMemcpyHostToDevice));
-    st.bytes_up += (int64_t)sizeof(words);
-    const mcf::DataRangeOutputs o{io.ranged, io.arc_state, io.flow_down, io.flow_up, io.ship_forth, io.ship_back, b->d_range_summary};
-    const typename P::Problem p = P::problem(b, BatchIo{}, true);
-    const double t_launch = mcf::now_ns();
-    for (const PlacedBatch::RangeLaunch &L : b->data_range_plan.launches) {
-        P::launch_data_ranges(b, L.in_lds, (unsigned)L.n, L.lds, p, o, io, b->dev.slots, b->dev.slab, b->data_range_plan.d_ids + L.first);
-        HIP_TRY(hipGetLastError());
-        (L.in_lds ? st.lds_instances : st.global_instances) += L.n;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    st.kernel_ns = mcf::now_ns() - t_launch;
-    HIP_TRY(hipMemcpy(words, b->d_range_summary, sizeof(words), hipMemcpyDeviceToHost));
-    st.bytes_down += (int64_t)sizeof(words);
-    if (const int rc = stage_down(b, staged, &st.bytes_down)) return rc;
-    st.ranged = words[0]; st.walks = words[1]; st.hops = words[2];
-    b->data_range_stats = st;
-    return MCF_OK;
-}
-
-template <class P>
-int data_ranges_on_host(typename P::Handle *b, const DataRangeIo &io, const char *what)
-{
-    PairSizes sizes{};
-    if (const int rc = check_data_range_call<P>(b, io, what, true, &sizes)) return rc;
-    const size_t count = (size_t)b->d.count;
-    b->h_slab.resize(P::slab_bytes(b));
-    b->h_slots.resize(count);
-    if (const int rc = state_to_host(b, b->d.device, count)) return rc;
-    b->where = PlacedBatch::kOnHost;                                        // the same state, now here too
-    mcf_ubatch_data_range_stats st{};
-    st.instances = (int64_t)count;
-    int64_t words[3] = {0, 0, 0};
-    const mcf::DataRangeOutputs o{io.ranged, io.arc_state, io.flow_down, io.flow_up, io.ship_forth, io.ship_back, words};
-    const typename P::Problem p = P::problem(b, BatchIo{}, false);
-    const mcf::UniformOutputs none{};
-    const double t_start = mcf::now_ns();
-    for (size_t i = 0; i < count; ++i) {
-        const BatchSlot *tmpl = nullptr;
-        mcf::uniform_data_ranges<false>(P::view(b, p, none, (int64_t)i, b->h_slab.data(), &tmpl), o, P::pair_list(b, io, (int64_t)i), b->h_slots[i], nullptr, 0, 1);
-    }
-    st.kernel_ns = mcf::now_ns() - t_start;
-    st.ranged = words[0]; st.walks = words[1]; st.hops = words[2];
-    b->data_range_stats = st;
-    return MCF_OK;
-}
-
-int get_data_range_stats(const PlacedBatch *b, mcf_ubatch_data_range_stats *out)
-{
-    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
-    *out = b->data_range_stats;
-    return MCF_OK;
-}
-
-// ---- mcf_*batch_diagnose / _on_host: uniform_diagnose for every instance, on the state the last solve call left; it is only read
-struct DiagIo {
-    bool given;
-    int32_t memory;
-    int32_t *verdict;
-    int64_t *violation;
-    int32_t *set_size;
-    int8_t *side;
-    int64_t *unmet;
-};
-template <class Io>
-DiagIo diag_io_of(const Io *io)
-{
-    if (!io) return DiagIo{};
-    return DiagIo{true, io->memory, io->verdict, io->violation, io->set_size, io->side, io->unmet};
-}
-
-int check_diagnose_call(const PlacedBatch *b, const DiagIo &io, const char *what, bool host_only)
-{
-    if (!b || !io.given) return mcf::fail(MCF_ERR_INVALID, "%s: null argument", what);
-    if (io.memory != MCF_MEM_HOST && io.memory != MCF_MEM_DEVICE) return mcf::fail(MCF_ERR_INVALID, "%s: unknown memory kind %d", what, io.memory);
-    if (host_only && io.memory != MCF_MEM_HOST) return mcf::fail(MCF_ERR_INVALID, "%s: the host hooks read and write host memory (MCF_MEM_HOST)", what);
-    if (b->where == PlacedBatch::kNowhere) return mcf::fail(MCF_ERR_STATE, "%s: the batch has not been solved", what);
-    return MCF_OK;
-}
-inline uint32_t diagnose_footprint(int32_t n, int32_t m) { return mcf::diag_layout_of((uint32_t)m, (uint32_t)n + 1u).bytes; }
-void diagnose_stats_of(const int64_t words[mcf::kDiagSummaryWords], mcf_ubatch_diagnose_stats *st)
-{
-    st->none = words[MCF_DIAG_NONE]; st->feasible = words[MCF_DIAG_FEASIBLE]; st->cut = words[MCF_DIAG_CUT]; st->open = words[MCF_DIAG_OPEN];
-    st->bounds = words[MCF_DIAG_BOUNDS];
-    st->levels = words[MCF_DIAG_BOUNDS + 1]; st->frontier_nodes = words[MCF_DIAG_BOUNDS + 2]; st->inc_entries = words[MCF_DIAG_BOUNDS + 3];
-}
-// the room one instance of the global tier needs for unmet, marks and frontiers: the largest such instance's, for every block of that launch
-template <class P>
-uint64_t diagnose_work_stride(const typename P::Handle *b)
-{
-    const LaunchPlan plan = P::plan(const_cast<typename P::Handle *>(b));
-    uint32_t most = 0;
-    for (size_t i = 0; i < (size_t)b->d.count; ++i) {
-        if (class_of(b->lds_max, plan.bytes((int32_t)i)) != kClasses - 1) continue;
-        int32_t n = 0, m = 0;
-        P::sizes(b, i, &n, &m);
-        most = std::max(most, mcf::diag_layout_of(0, (uint32_t)n + 1u).bytes);
-    }
-    return most;
-}
-
-template <class P>
-int diagnose_on_device(typename P::Handle *b, DiagIo io, const char *what)
-{
-    if (const int rc = check_diagnose_call(b, io, what, false)) return rc;
-    if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
-    const DeviceGuard guard;
-    if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
-    const size_t count = (size_t)b->d.count;
-    mcf_ubatch_diagnose_stats st{};
-    st.instances = (int64_t)count;
-    if (!count) { b->diagnose_stats = st; return MCF_OK; }
-    if (b->lds_max > (64 << 10))                                            // the opt-in open_device got for the solve's kernels
-        HIP_TRY(hipFuncSetAttribute((const void *)P::diagnose_kernel_in_lds, hipFuncAttributeMaxDynamicSharedMemorySize, b->lds_max));
-    if (const int rc = ensure_device_buffers<P>(b)) return rc;
-    const bool first = !b->diagnose_plan.d_ids;
-    if (const int rc = ensure_range_plan<P>(b, b->diagnose_plan, diagnose_footprint)) return rc;
-    if (first) st.bytes_up += (int64_t)(count * sizeof(int32_t));
-    if (!b->d_diag_summary) HIP_TRY(hipMalloc((void **)&b->d_diag_summary, mcf::kDiagSummaryWords * sizeof(int64_t)));
-    uint64_t work_stride = 0;
-    for (const PlacedBatch::RangeLaunch &L : b->diagnose_plan.launches) {
-        if (L.in_lds) continue;
-        work_stride = diagnose_work_stride<P>(b);
-        const size_t need = (size_t)L.n * (size_t)work_stride;
-        if (b->diag_work_bytes < need) {
-            if (b->d_diag_work) { HIP_TRY(hipFree(b->d_diag_work)); b->d_diag_work = nullptr; b->diag_work_bytes = 0; }
-            HIP_TRY(hipMalloc((void **)&b->d_diag_work, need));
-            b->diag_work_bytes = need;
-        }
-    }
-    if (const int rc = state_to_device(b, count, &st.bytes_up)) return rc;
-    b->where = PlacedBatch::kOnDevice;                                      // the same state, now there too
-    Staged staged;                                                          // MCF_MEM_HOST: the rows come down through the staging buffer of the solve calls
-    if (io.memory == MCF_MEM_HOST) {
-        const size_t nodes = P::node_rows(b);
-        size_t at[5] = {};
-        if (io.verdict) at[0] = staged.add(nullptr, io.verdict, 4 * count);
-        if (io.violation) at[1] = staged.add(nullptr, io.violation, 8 * count);
-        if (io.set_size) at[2] = staged.add(nullptr, io.set_size, 4 * count);
-        if (io.side) at[3] = staged.add(nullptr, io.side, nodes);
-        if (io.unmet) at[4] = staged.add(nullptr, io.unmet, 8 * nodes);
-        if (const int rc = reserve_io(b, std::max<size_t>(staged.total, 16))) return rc;
-        if (io.verdict) io.verdict = (int32_t *)(b->d_io + at[0]);
-        if (io.violation) io.violation = (int64_t *)(b->d_io + at[1]);
-        if (io.set_size) io.set_size = (int32_t *)(b->d_io + at[2]);
-        if (io.side) io.side = (int8_t *)(b->d_io + at[3]);
-        if (io.unmet) io.unmet = (int64_t *)(b->d_io + at[4]);
-    }
-    int64_t words[mcf::kDiagSummaryWords] = {};
-    HIP_TRY(hipMemcpy(b->d_diag_summary, words, sizeof(words), hipMemcpyHostToDevice));
-    st.bytes_up += (int64_t)sizeof(words);
-    const mcf::DiagOutputs o{io.verdict, io.violation, io.set_size, io.side, io.unmet, b->d_diag_summary};
-    BatchIo kept{};
-    kept.supply_type = b->supply_type;                                      // the last solve call's: the kept flow belongs to that one
-    const typename P::Problem p = P::problem(b, kept, true);
-    const double t_launch = mcf::now_ns();
-    for (const PlacedBatch::RangeLaunch &L : b->diagnose_plan.launches) {
-        P::launch_diagnose(b, L.in_lds, (unsigned)L.n, L.lds, p, o, b->dev.slots, b->dev.slab, b->diagnose_plan.d_ids + L.first, b->d_diag_work, work_stride);
-        HIP_TRY(hipGetLastError());
-        (L.in_lds ? st.lds_instances : st.global_instances) += L.n;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    st.kernel_ns = mcf::now_ns() - t_launch;
-    HIP_TRY(hipMemcpy(words, b->d_diag_summary, sizeof(words), hipMemcpyDeviceToHost));
-    st.bytes_down += (int64_t)sizeof(words);
-    if (const int rc = stage_down(b, staged, &st.bytes_down)) return rc;
-    diagnose_stats_of(words, &st);
-    b->diagnose_stats = st;
-    return MCF_OK;
-}
-
-template <class P>
-int diagnose_on_host(typename P::Handle *b, const DiagIo &io, const char *what)
-{
-    if (const int rc = check_diagnose_call(b, io, what, true)) return rc;
-    const size_t count = (size_t)b->d.count;
-    b->h_slab.resize(P::slab_bytes(b));
-    b->h_slots.resize(count);
-    if (const int rc = state_to_host(b, b->d.device, count)) return rc;
-    b->where = PlacedBatch::kOnHost;                                        // the same state, now here too
-    mcf_ubatch_diagnose_stats st{};
-    st.instances = (int64_t)count;
-    int64_t words[mcf::kDiagSummaryWords] = {};
-    const mcf::DiagOutputs o{io.verdict, io.violation, io.set_size, io.side, io.unmet, words};
     BatchIo kept{};
     kept.supply_type = b->supply_type;
-    const typename P::Problem p = P::problem(b, kept, false);
+    return P::problem(b, kept, on_device);
+}
+
+// what a placement's launch_query names a kernel's arguments from
+template <class P, class Q>
+struct QueryArgs {
+    typename P::Problem p;
+    typename Q::Outputs o;
+    const typename Q::Io &io;
+    const BatchSlot *slots;
+    unsigned char *slab;
+    const int32_t *ids;
+};
+
+template <class P, class Q>
+int query_on_device(typename P::Handle *b, typename Q::Io io, const char *what)
+{
+    if (const int rc = check_query_call<P, Q>(b, &io, what, false)) return rc;
+    if (const int rc = have_device(b->d.device, what)) return rc;          // the handle is as it was
+    const DeviceGuard guard;
+    if (const int rc = open_device(b->d.device, &b->lds_max)) return rc;
+    const size_t count = (size_t)b->d.count;
+    PlacedBatch::Query<typename Q::Stats> &query = Q::state(b);
+    typename Q::Stats st{};
+    st.instances = (int64_t)count;
+    if (!count) { query.stats = st; return MCF_OK; }
+    if (const int rc = ensure_device_buffers<P>(b)) return rc;
+    const bool first = !query.plan.d_ids;
+    if (const int rc = ensure_query_plan<P, Q>(b, query.plan)) return rc;
+    if (first) st.bytes_up += (int64_t)(count * sizeof(int32_t));
+    if (!b->d_query_summary) HIP_TRY(hipMalloc((void **)&b->d_query_summary, kQuerySummaryWords * sizeof(int64_t)));
+    if (const int rc = Q::template prepare<P>(b, query.plan)) return rc;
+    if (const int rc = state_to_device(b, count, &st.bytes_up)) return rc;
+    b->where = PlacedBatch::kOnDevice;                                      // the same state, now there too
+    Staged staged;                                                          // MCF_MEM_HOST: the arrays go through the staging buffer of the solve calls
+    if (io.memory == MCF_MEM_HOST) {
+        const auto arrays = Q::template arrays<P>(b, &io);
+        if (const int rc = stage_arrays(b, arrays.data(), arrays.size(), 16, &staged, &st.bytes_up)) return rc;
+    }
+    int64_t words[Q::kWords] = {};
+    HIP_TRY(hipMemcpy(b->d_query_summary, words, sizeof(words), hipMemcpyHostToDevice));
+    st.bytes_up += (int64_t)sizeof(words);
+    QueryArgs<P, Q> args{kept_problem<P>(b, true), Q::outputs(io, b->d_query_summary), io, b->dev.slots, b->dev.slab, nullptr};
+    bool opted_in = false;
+    const double t_launch = mcf::now_ns();
+    for (const PlacedBatch::QueryLaunch &L : query.plan.launches) {
+        args.ids = query.plan.d_ids + L.first;
+        const int rc = P::launch_query(Q{}, b, args, [&](auto in_lds, auto in_place, const auto &...kernel_args) -> int {
+            if (L.in_lds && !opted_in && b->lds_max > (64 << 10)) {         // the opt-in open_device got for the solve's kernels
+                HIP_TRY(hipFuncSetAttribute((const void *)in_lds, hipFuncAttributeMaxDynamicSharedMemorySize, b->lds_max));
+                opted_in = true;
+            }
+            hipLaunchKernelGGL(L.in_lds ? in_lds : in_place, dim3((unsigned)L.n), dim3(kBatchThreads), L.lds, 0, kernel_args...);
+            HIP_TRY(hipGetLastError());
+            return MCF_OK;
+        });
+        if (rc) return rc;
+        (L.in_lds ? st.lds_instances : st.global_instances) += L.n;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    st.kernel_ns = mcf::now_ns() - t_launch;
+    HIP_TRY(hipMemcpy(words, b->d_query_summary, sizeof(words), hipMemcpyDeviceToHost));
+    st.bytes_down += (int64_t)sizeof(words);
+    if (const int rc = stage_down(b, staged, &st.bytes_down)) return rc;
+    Q::stats_of(words, &st);
+    query.stats = st;                                                       // only a call that succeeded replaces the last one's
+    return MCF_OK;
+}
+
+template <class P, class Q>
+int query_on_host(typename P::Handle *b, typename Q::Io io, const char *what)
+{
+    if (const int rc = check_query_call<P, Q>(b, &io, what, true)) return rc;
+    const size_t count = (size_t)b->d.count;
+    b->h_slab.resize(P::slab_bytes(b));
+    b->h_slots.resize(count);
+    if (const int rc = state_to_host(b, b->d.device, count)) return rc;
+    b->where = PlacedBatch::kOnHost;                                        // the same state, now here too
+    typename Q::Stats st{};
+    st.instances = (int64_t)count;
+    int64_t words[Q::kWords] = {};
+    const typename Q::Outputs o = Q::outputs(io, words);
+    const typename P::Problem p = kept_problem<P>(b, false);
     const mcf::UniformOutputs none{};
-    struct alignas(16) Word { uint64_t lo, hi; };
-    std::vector<Word> room;                                                 // one instance's unmet, marks and frontiers at a time
+    typename Q::Scratch scratch;
     const double t_start = mcf::now_ns();
     for (size_t i = 0; i < count; ++i) {
         const BatchSlot *tmpl = nullptr;
-        const mcf::InstanceView v = P::view(b, p, none, (int64_t)i, b->h_slab.data(), &tmpl);
-        const size_t words_needed = mcf::diag_layout_of(0, (uint32_t)v.n + 1u).bytes / sizeof(Word);
-        if (room.size() < words_needed) room.resize(words_needed);
-        mcf::uniform_diagnose<false>(v, o, b->h_slots[i], (unsigned char *)room.data(), 0, 1);
+        Q::template on_host<P>(b, io, P::view(b, p, none, (int64_t)i, b->h_slab.data(), &tmpl), o, (int64_t)i, b->h_slots[i], scratch);
     }
     st.kernel_ns = mcf::now_ns() - t_start;
-    diagnose_stats_of(words, &st);
-    b->diagnose_stats = st;
+    Q::stats_of(words, &st);
+    Q::state(b).stats = st;
     return MCF_OK;
 }
 
-int get_diagnose_stats(const PlacedBatch *b, mcf_ubatch_diagnose_stats *out)
+// mcf_*batch_get_*stats: the handle's member that holds them -- the statistics themselves, or a query's state with them
+template <class Stats, class Held>
+int get_stats(const PlacedBatch *b, Stats *out, Held PlacedBatch::*member)
 {
     if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
-    *out = b->diagnose_stats;
-    return MCF_OK;
-}
-
-int get_stats(const PlacedBatch *b, mcf_ubatch_stats *out)
-{
-    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
-    *out = b->stats;
-    return MCF_OK;
-}
-int get_start_stats(const PlacedBatch *b, mcf_ubatch_start_stats *out)
-{
-    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
-    *out = b->start_stats;
-    return MCF_OK;
-}
-int get_redata_stats(const PlacedBatch *b, mcf_ubatch_redata_stats *out)
-{
-    if (!b || !out) return mcf::fail(MCF_ERR_INVALID, "null argument");
-    *out = b->redata_stats;
+    *out = b->*member;
     return MCF_OK;
 }
 
@@ -2458,8 +2337,8 @@ int mcf_ubatch_validate_on_host(mcf_ubatch *b, const mcf_ubatch_check_io *io, mc
 {
     return validate_on_host<UniformPlacement>(b, io_of(io), out, "mcf_ubatch_validate_on_host");
 }
-int mcf_ubatch_get_stats(mcf_ubatch *b, mcf_ubatch_stats *out) { return get_stats(b, out); }
-int mcf_ubatch_get_redata_stats(mcf_ubatch *b, mcf_ubatch_redata_stats *out) { return get_redata_stats(b, out); }
+int mcf_ubatch_get_stats(mcf_ubatch *b, mcf_ubatch_stats *out) { return get_stats(b, out, &PlacedBatch::stats); }
+int mcf_ubatch_get_redata_stats(mcf_ubatch *b, mcf_ubatch_redata_stats *out) { return get_stats(b, out, &PlacedBatch::redata_stats); }
 int mcf_ubatch_solve_from(mcf_ubatch *b, const mcf_ubatch_io *io, const mcf_ubatch_basis_io *basis)
 {
     return solve_on_device<UniformPlacement>(b, with_basis(io_of(io), basis), kStart, "mcf_ubatch_solve_from");
@@ -2468,19 +2347,16 @@ int mcf_ubatch_run_from_on_host(mcf_ubatch *b, const mcf_ubatch_io *io, const mc
 {
     return solve_on_host<UniformPlacement>(b, with_basis(io_of(io), basis), kStart, "mcf_ubatch_run_from_on_host");
 }
-int mcf_ubatch_get_start_stats(mcf_ubatch *b, mcf_ubatch_start_stats *out) { return get_start_stats(b, out); }
-int mcf_ubatch_cost_ranges(mcf_ubatch *b, const mcf_ubatch_range_io *io) { return ranges_on_device<UniformPlacement>(b, range_io_of(io), "mcf_ubatch_cost_ranges"); }
-int mcf_ubatch_cost_ranges_on_host(mcf_ubatch *b, const mcf_ubatch_range_io *io) { return ranges_on_host<UniformPlacement>(b, range_io_of(io), "mcf_ubatch_cost_ranges_on_host"); }
-int mcf_ubatch_get_range_stats(mcf_ubatch *b, mcf_ubatch_range_stats *out) { return get_range_stats(b, out); }
-int mcf_ubatch_data_ranges(mcf_ubatch *b, const mcf_ubatch_data_range_io *io) { return data_ranges_on_device<UniformPlacement>(b, data_range_io_of(io), "mcf_ubatch_data_ranges"); }
-int mcf_ubatch_data_ranges_on_host(mcf_ubatch *b, const mcf_ubatch_data_range_io *io)
-{
-    return data_ranges_on_host<UniformPlacement>(b, data_range_io_of(io), "mcf_ubatch_data_ranges_on_host");
-}
-int mcf_ubatch_get_data_range_stats(mcf_ubatch *b, mcf_ubatch_data_range_stats *out) { return get_data_range_stats(b, out); }
-int mcf_ubatch_diagnose(mcf_ubatch *b, const mcf_ubatch_diagnose_io *io) { return diagnose_on_device<UniformPlacement>(b, diag_io_of(io), "mcf_ubatch_diagnose"); }
-int mcf_ubatch_diagnose_on_host(mcf_ubatch *b, const mcf_ubatch_diagnose_io *io) { return diagnose_on_host<UniformPlacement>(b, diag_io_of(io), "mcf_ubatch_diagnose_on_host"); }
-int mcf_ubatch_get_diagnose_stats(mcf_ubatch *b, mcf_ubatch_diagnose_stats *out) { return get_diagnose_stats(b, out); }
+int mcf_ubatch_get_start_stats(mcf_ubatch *b, mcf_ubatch_start_stats *out) { return get_stats(b, out, &PlacedBatch::start_stats); }
+int mcf_ubatch_cost_ranges(mcf_ubatch *b, const mcf_ubatch_range_io *io) { return query_on_device<UniformPlacement, CostRanges>(b, CostRanges::io_of(io), "mcf_ubatch_cost_ranges"); }
+int mcf_ubatch_cost_ranges_on_host(mcf_ubatch *b, const mcf_ubatch_range_io *io) { return query_on_host<UniformPlacement, CostRanges>(b, CostRanges::io_of(io), "mcf_ubatch_cost_ranges_on_host"); }
+int mcf_ubatch_get_range_stats(mcf_ubatch *b, mcf_ubatch_range_stats *out) { return get_stats(b, out, &PlacedBatch::cost_ranges); }
+int mcf_ubatch_data_ranges(mcf_ubatch *b, const mcf_ubatch_data_range_io *io) { return query_on_device<UniformPlacement, DataRanges>(b, DataRanges::io_of(io), "mcf_ubatch_data_ranges"); }
+int mcf_ubatch_data_ranges_on_host(mcf_ubatch *b, const mcf_ubatch_data_range_io *io) { return query_on_host<UniformPlacement, DataRanges>(b, DataRanges::io_of(io), "mcf_ubatch_data_ranges_on_host"); }
+int mcf_ubatch_get_data_range_stats(mcf_ubatch *b, mcf_ubatch_data_range_stats *out) { return get_stats(b, out, &PlacedBatch::data_ranges); }
+int mcf_ubatch_diagnose(mcf_ubatch *b, const mcf_ubatch_diagnose_io *io) { return query_on_device<UniformPlacement, Diagnose>(b, Diagnose::io_of(io), "mcf_ubatch_diagnose"); }
+int mcf_ubatch_diagnose_on_host(mcf_ubatch *b, const mcf_ubatch_diagnose_io *io) { return query_on_host<UniformPlacement, Diagnose>(b, Diagnose::io_of(io), "mcf_ubatch_diagnose_on_host"); }
+int mcf_ubatch_get_diagnose_stats(mcf_ubatch *b, mcf_ubatch_diagnose_stats *out) { return get_stats(b, out, &PlacedBatch::diagnose); }
 
 void mcf_rbatch_destroy(mcf_rbatch *b) { delete b; }
 int mcf_rbatch_solve(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_device<RaggedPlacement>(b, io_of(io), kFresh, "mcf_rbatch_solve"); }
@@ -2497,8 +2373,8 @@ int mcf_rbatch_validate_on_host(mcf_rbatch *b, const mcf_rbatch_check_io *io, mc
 {
     return validate_on_host<RaggedPlacement>(b, io_of(io), out, "mcf_rbatch_validate_on_host");
 }
-int mcf_rbatch_get_stats(mcf_rbatch *b, mcf_ubatch_stats *out) { return get_stats(b, out); }
-int mcf_rbatch_get_redata_stats(mcf_rbatch *b, mcf_ubatch_redata_stats *out) { return get_redata_stats(b, out); }
+int mcf_rbatch_get_stats(mcf_rbatch *b, mcf_ubatch_stats *out) { return get_stats(b, out, &PlacedBatch::stats); }
+int mcf_rbatch_get_redata_stats(mcf_rbatch *b, mcf_ubatch_redata_stats *out) { return get_stats(b, out, &PlacedBatch::redata_stats); }
 int mcf_rbatch_solve_from(mcf_rbatch *b, const mcf_rbatch_io *io, const mcf_rbatch_basis_io *basis)
 {
     return solve_on_device<RaggedPlacement>(b, with_basis(io_of(io), basis), kStart, "mcf_rbatch_solve_from");
@@ -2507,18 +2383,15 @@ int mcf_rbatch_run_from_on_host(mcf_rbatch *b, const mcf_rbatch_io *io, const mc
 {
     return solve_on_host<RaggedPlacement>(b, with_basis(io_of(io), basis), kStart, "mcf_rbatch_run_from_on_host");
 }
-int mcf_rbatch_get_start_stats(mcf_rbatch *b, mcf_ubatch_start_stats *out) { return get_start_stats(b, out); }
-int mcf_rbatch_cost_ranges(mcf_rbatch *b, const mcf_rbatch_range_io *io) { return ranges_on_device<RaggedPlacement>(b, range_io_of(io), "mcf_rbatch_cost_ranges"); }
-int mcf_rbatch_cost_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_range_io *io) { return ranges_on_host<RaggedPlacement>(b, range_io_of(io), "mcf_rbatch_cost_ranges_on_host"); }
-int mcf_rbatch_get_range_stats(mcf_rbatch *b, mcf_ubatch_range_stats *out) { return get_range_stats(b, out); }
-int mcf_rbatch_data_ranges(mcf_rbatch *b, const mcf_rbatch_data_range_io *io) { return data_ranges_on_device<RaggedPlacement>(b, data_range_io_of(io), "mcf_rbatch_data_ranges"); }
-int mcf_rbatch_data_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_data_range_io *io)
-{
-    return data_ranges_on_host<RaggedPlacement>(b, data_range_io_of(io), "mcf_rbatch_data_ranges_on_host");
-}
-int mcf_rbatch_get_data_range_stats(mcf_rbatch *b, mcf_ubatch_data_range_stats *out) { return get_data_range_stats(b, out); }
-int mcf_rbatch_diagnose(mcf_rbatch *b, const mcf_rbatch_diagnose_io *io) { return diagnose_on_device<RaggedPlacement>(b, diag_io_of(io), "mcf_rbatch_diagnose"); }
-int mcf_rbatch_diagnose_on_host(mcf_rbatch *b, const mcf_rbatch_diagnose_io *io) { return diagnose_on_host<RaggedPlacement>(b, diag_io_of(io), "mcf_rbatch_diagnose_on_host"); }
-int mcf_rbatch_get_diagnose_stats(mcf_rbatch *b, mcf_ubatch_diagnose_stats *out) { return get_diagnose_stats(b, out); }
+int mcf_rbatch_get_start_stats(mcf_rbatch *b, mcf_ubatch_start_stats *out) { return get_stats(b, out, &PlacedBatch::start_stats); }
+int mcf_rbatch_cost_ranges(mcf_rbatch *b, const mcf_rbatch_range_io *io) { return query_on_device<RaggedPlacement, CostRanges>(b, CostRanges::io_of(io), "mcf_rbatch_cost_ranges"); }
+int mcf_rbatch_cost_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_range_io *io) { return query_on_host<RaggedPlacement, CostRanges>(b, CostRanges::io_of(io), "mcf_rbatch_cost_ranges_on_host"); }
+int mcf_rbatch_get_range_stats(mcf_rbatch *b, mcf_ubatch_range_stats *out) { return get_stats(b, out, &PlacedBatch::cost_ranges); }
+int mcf_rbatch_data_ranges(mcf_rbatch *b, const mcf_rbatch_data_range_io *io) { return query_on_device<RaggedPlacement, DataRanges>(b, DataRanges::io_of(io), "mcf_rbatch_data_ranges"); }
+int mcf_rbatch_data_ranges_on_host(mcf_rbatch *b, const mcf_rbatch_data_range_io *io) { return query_on_host<RaggedPlacement, DataRanges>(b, DataRanges::io_of(io), "mcf_rbatch_data_ranges_on_host"); }
+int mcf_rbatch_get_data_range_stats(mcf_rbatch *b, mcf_ubatch_data_range_stats *out) { return get_stats(b, out, &PlacedBatch::data_ranges); }
+int mcf_rbatch_diagnose(mcf_rbatch *b, const mcf_rbatch_diagnose_io *io) { return query_on_device<RaggedPlacement, Diagnose>(b, Diagnose::io_of(io), "mcf_rbatch_diagnose"); }
+int mcf_rbatch_diagnose_on_host(mcf_rbatch *b, const mcf_rbatch_diagnose_io *io) { return query_on_host<RaggedPlacement, Diagnose>(b, Diagnose::io_of(io), "mcf_rbatch_diagnose_on_host"); }
+int mcf_rbatch_get_diagnose_stats(mcf_rbatch *b, mcf_ubatch_diagnose_stats *out) { return get_stats(b, out, &PlacedBatch::diagnose); }
 
 }  // extern "C"

@@ -769,36 +769,45 @@ class _PlacedBatch:
             raise ValueError("arc_state: a basis is required (int8, one state per arc)")
         return self._call("run_from_on_host", cost, supply, lower, upper, supply_type, numpy_only=True, arc_state=arc_state)
 
+    def _stats(self, fn, struct) -> dict:
+        st = struct(); L.check(self._fn(fn)(self._h, C.byref(st))); return st.as_dict()
+
     def start_stats(self) -> dict:
         """What the last solve_from() / run_from_on_host() did: primal starts, dual starts, instances cold by rule, fallbacks, dual and
         primal pivots."""
-        st = L.UBatchStartStats(); L.check(self._fn("get_start_stats")(self._h, C.byref(st))); return st.as_dict()
+        return self._stats("get_start_stats", L.UBatchStartStats)
 
     def stats(self) -> dict:
-        st = L.UBatchStats(); L.check(self._fn("get_stats")(self._h, C.byref(st))); return st.as_dict()
+        return self._stats("get_stats", L.UBatchStats)
 
     def resolve_data_stats(self) -> dict:
         """What the last resolve_data() / rerun_data_on_host() did: warm, cold, fallback and untouched instances, dual and primal pivots."""
-        st = L.UBatchRedataStats(); L.check(self._fn("get_redata_stats")(self._h, C.byref(st))); return st.as_dict()
+        return self._stats("get_redata_stats", L.UBatchRedataStats)
+
+    # ---- the queries of the kept state
+    def _like_last(self, tensors):
+        return self._last is not None and _is_tensor(self._last.status) if tensors is None else tensors
+
+    def _query(self, fn, io, fields, skip, sizes, result, tensors):
+        """Fresh rows for every field of `fields` that skip(name, dim) does not leave out, the call, result(rows)"""
+        tensors = self._like_last(tensors)
+        io.memory = L.MEM_DEVICE if tensors else L.MEM_HOST
+        out = {}
+        for name, dtype, dim in fields:
+            if skip(name, dim):
+                continue
+            out[name] = self._empty(sizes[dim], dtype, tensors)
+            setattr(io, name, out[name].data_ptr() if tensors else out[name].ctypes.data)
+        L.check(self._fn(fn)(self._h, C.byref(io)))
+        return result(out)
 
     # ---- cost ranges of the kept basis
     def _ranges(self, out):
         return UniformRanges(**out)
 
     def _cost_ranges(self, fn, tensors, costs):
-        if tensors is None:
-            tensors = self._last is not None and _is_tensor(self._last.status)
-        sizes = self._sizes()
-        io = self._RANGE_IO()
-        io.memory = L.MEM_DEVICE if tensors else L.MEM_HOST
-        out = {}
-        for name, dtype, dim in UniformRanges.FIELDS:
-            if not costs and name in ("cost_down", "cost_up"):
-                continue
-            out[name] = self._empty(sizes[dim], dtype, tensors)
-            setattr(io, name, out[name].data_ptr() if tensors else out[name].ctypes.data)
-        L.check(self._fn(fn)(self._h, C.byref(io)))
-        return self._ranges(out)
+        return self._query(fn, self._RANGE_IO(), UniformRanges.FIELDS, lambda name, dim: not costs and name in ("cost_down", "cost_up"),
+                           self._sizes(), self._ranges, tensors)
 
     def cost_ranges(self, tensors=None, costs=True):
         """Post-optimality cost ranging of the basis every instance's last solve call left, on the device: a UniformRanges /
@@ -813,7 +822,7 @@ class _PlacedBatch:
 
     def range_stats(self) -> dict:
         """What the last cost_ranges() / cost_ranges_on_host() did: instances, ranged ones, tiers, tree arcs ranged, cycle hops, kernel time."""
-        st = L.UBatchRangeStats(); L.check(self._fn("get_range_stats")(self._h, C.byref(st))); return st.as_dict()
+        return self._stats("get_range_stats", L.UBatchRangeStats)
 
     # ---- supply and bound ranges of the kept basis
     def _pair_array(self, pairs, tensors, name="pairs"):
@@ -841,21 +850,13 @@ class _PlacedBatch:
         return np.ascontiguousarray(a, np.int32)
 
     def _data_ranges(self, fn, pairs, tensors, flows):
-        if tensors is None:
-            tensors = self._last is not None and _is_tensor(self._last.status)
+        tensors = self._like_last(tensors)
         io = self._DATA_RANGE_IO()
-        io.memory = L.MEM_DEVICE if tensors else L.MEM_HOST
         keep = []
         ships, ship_rows = self._pairs_into(io, pairs, tensors, keep)           # the shape of the ship rows (None: no pairs)
-        sizes = dict(self._sizes(), p=ships)
-        out = {}
-        for name, dtype, dim in UniformDataRanges.FIELDS:
-            if (not flows and name in ("flow_down", "flow_up")) or (ships is None and dim == "p"):
-                continue
-            out[name] = self._empty(sizes[dim], dtype, tensors)
-            setattr(io, name, out[name].data_ptr() if tensors else out[name].ctypes.data)
-        L.check(self._fn(fn)(self._h, C.byref(io)))
-        return self._data_range_result(out, ship_rows)
+        return self._query(fn, io, UniformDataRanges.FIELDS,
+                           lambda name, dim: (not flows and name in ("flow_down", "flow_up")) or (ships is None and dim == "p"),
+                           dict(self._sizes(), p=ships), lambda out: self._data_range_result(out, ship_rows), tensors)
 
     def data_ranges(self, pairs=None, tensors=None, flows=True):
         """Right-hand-side ranging of the basis every instance's last solve call left, on the device: a UniformDataRanges /
@@ -872,26 +873,14 @@ class _PlacedBatch:
 
     def data_range_stats(self) -> dict:
         """What the last data_ranges() / data_ranges_on_host() did: instances, ranged ones, tiers, walks, hops, kernel time."""
-        st = L.UBatchDataRangeStats(); L.check(self._fn("get_data_range_stats")(self._h, C.byref(st))); return st.as_dict()
+        return self._stats("get_data_range_stats", L.UBatchDataRangeStats)
 
     # ---- why infeasible: a cut from the kept flow
     def _diagnosis(self, out):
         return UniformDiagnosis(**out)
 
     def _diagnose(self, fn, tensors, nodes):
-        if tensors is None:
-            tensors = self._last is not None and _is_tensor(self._last.status)
-        sizes = self._sizes()
-        io = self._DIAGNOSE_IO()
-        io.memory = L.MEM_DEVICE if tensors else L.MEM_HOST
-        out = {}
-        for name, dtype, dim in UniformDiagnosis.FIELDS:
-            if not nodes and dim == "n":
-                continue
-            out[name] = self._empty(sizes[dim], dtype, tensors)
-            setattr(io, name, out[name].data_ptr() if tensors else out[name].ctypes.data)
-        L.check(self._fn(fn)(self._h, C.byref(io)))
-        return self._diagnosis(out)
+        return self._query(fn, self._DIAGNOSE_IO(), UniformDiagnosis.FIELDS, lambda name, dim: not nodes and dim == "n", self._sizes(), self._diagnosis, tensors)
 
     def diagnose(self, tensors=None, nodes=True):
         """Whether the flow every instance's last solve call left satisfies its constraints and, where it does not, a cut that proves the
@@ -907,7 +896,7 @@ class _PlacedBatch:
 
     def diagnose_stats(self) -> dict:
         """What the last diagnose() / diagnose_on_host() did: instances per verdict, tiers, levels, frontier nodes, incidence entries, kernel time."""
-        st = L.UBatchDiagnoseStats(); L.check(self._fn("get_diagnose_stats")(self._h, C.byref(st))); return st.as_dict()
+        return self._stats("get_diagnose_stats", L.UBatchDiagnoseStats)
 
     # ---- validation: the solution's rows where they lie
     SOLUTION_ROWS = (("status", "int32", None), ("total_cost", "int64", None), ("flows", "int64", "arc_count"), ("potentials", "int64", "node_count"))

@@ -16,9 +16,8 @@ import data_ranges_oracle as D
 import wide_graphs as W
 from test_batch_host import RULES
 from test_data_ranges_host import (FIELDS, HOST_RANGES, HOST_REDATA, HOST_SOLVE, assert_same_data_ranges, check_adversarial_batch, check_contract, check_meaning,
-                                   check_not_ranged, check_solves_do_not_see_it, check_three_graphs, check_uniform_families, data_rows, meaning_cases, three_graphs)
-from test_ranges_host import Flat, fuzz_flat, small_case
-from test_redata_host import PADDED_NODES, redata_family
+                                   check_not_ranged, check_solves_do_not_see_it, check_three_graphs, check_uniform_families, data_rows, meaning_cases, three_graphs, two_tiers)
+from test_ranges_host import fuzz_flat, small_case
 from test_uniform_host import ALL_RULES, uniform_of
 
 pytestmark = pytest.mark.gpu
@@ -81,14 +80,7 @@ def test_adversarial_batch_equals_the_hook_and_the_reference_on_the_device(rule)
 # ---- 2: both tiers in one ragged call
 def test_both_tiers_in_one_ragged_call():
     """The 12 x 12 grid, the hub, the big grid and a graph of 9 nodes padded to PADDED_NODES isolated ones: 16 instances in LDS, the rest in place."""
-    flat, graphs, graph_of, pair_lists, _ = three_graphs(O.RULE_BLOCK)
-    t, stype = redata_family()[3]
-    assert stype == O.GEQ
-    small = [O.Problem(PADDED_NODES, p.m, p.src, p.tgt, p.lower, p.upper, p.cost, np.concatenate([p.supply, np.zeros(PADDED_NODES - p.n, np.int64)])) for p in t.variants[:4]]
-    flat = Flat(flat.problems + tuple(small))
-    graphs = graphs + [(PADDED_NODES, t.src, t.tgt)]
-    graph_of = np.concatenate([graph_of, np.full(4, 3, np.int32)]).astype(np.int32)
-    pair_lists = pair_lists + [np.ascontiguousarray(np.concatenate([D.pairs_of((8,), t.n, t.src, t.tgt), [[PADDED_NODES - 1, 0], [PADDED_NODES, 0]]]).astype(np.int32))]
+    flat, graphs, graph_of, pair_lists = two_tiers()
     dev, host = (M.RaggedBatch(graphs, graph_of=graph_of, rule=RULES[O.RULE_BLOCK]) for _ in range(2))
     SOLVE(dev, flat.arrays, O.GEQ)
     HOST_SOLVE(host, flat.arrays, O.GEQ)

@@ -21,7 +21,7 @@ from helpers import validate_solution
 from test_batch_host import ROOT, RULES, fuzz_cases
 from test_batch_resolve_host import cold_reference
 from test_ranges_host import Flat, fuzz_flat, small_case
-from test_redata_host import redata_family
+from test_redata_host import PADDED_NODES, redata_family
 from test_uniform_host import ALL_RULES, TRACE, assert_row_matches_cold, to_numpy, uniform_of
 
 INF = M.RANGE_INF
@@ -154,6 +154,18 @@ def three_graphs(rule):
     ref = {name: np.concatenate([r[name] for r in rows]) for name in FIELDS + ("ranged_arcs",)}
     ref["ship_rows"] = np.concatenate([[0], np.cumsum([len(D.wide_pairs()[g]) for g, t in zip(graphs, tops) for _ in t.variants])])
     return Flat(problems), [(t.n, t.src, t.tgt) for t in tops], np.repeat(np.arange(3), [t.count for t in tops]).astype(np.int32), [D.wide_pairs()[g] for g in graphs], ref
+
+
+def two_tiers():
+    """three_graphs() and a graph of 9 nodes padded to PADDED_NODES isolated ones: (Flat, graphs, graph_of, pair lists per graph).  On the
+    device 16 of the 24 instances are solved in LDS, the rest in place."""
+    flat, graphs, graph_of, pair_lists, _ = three_graphs(O.RULE_BLOCK)
+    t, stype = redata_family()[3]
+    assert stype == O.GEQ
+    small = [O.Problem(PADDED_NODES, p.m, p.src, p.tgt, p.lower, p.upper, p.cost, np.concatenate([p.supply, np.zeros(PADDED_NODES - p.n, np.int64)])) for p in t.variants[:4]]
+    pairs = np.ascontiguousarray(np.concatenate([D.pairs_of((8,), t.n, t.src, t.tgt), [[PADDED_NODES - 1, 0], [PADDED_NODES, 0]]]).astype(np.int32))
+    return (Flat(flat.problems + tuple(small)), graphs + [(PADDED_NODES, t.src, t.tgt)], np.concatenate([graph_of, np.full(4, 3, np.int32)]).astype(np.int32),
+            pair_lists + [pairs])
 
 
 def check_three_graphs(solve, ranges, rule=O.RULE_BLOCK, **kw):

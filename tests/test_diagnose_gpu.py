@@ -16,7 +16,7 @@ import certificate_oracle as K
 import wide_graphs as W
 from test_batch_host import padded_fuzz
 from test_diagnose_host import (FIELDS, HOST_DIAGNOSE, HOST_SOLVE, FlatNodes, V, assert_same_diagnosis, check_contract, check_deep_path, check_edges, check_fuzz,
-                                check_instance, check_one_graph, check_untouched, diag_rows, fuzz_flat, same_counts)
+                                check_instance, check_one_graph, check_three_queries_on_one_handle, check_untouched, diag_rows, fuzz_flat, same_counts)
 from test_ranges_host import small_case
 from test_uniform_host import Topology, to_numpy, uniform_of
 
@@ -226,3 +226,8 @@ def test_host_memory_rows_and_the_state_moving_between_host_and_device():
     st = u.diagnose_stats()
     assert st["bytes_down"] == SUMMARY_BYTES + t.count * (4 + 8 + 4) + t.count * t.n * (1 + 8) and st["bytes_up"] == SUMMARY_BYTES + 4 * t.count, st
     assert V.Cut in diag_rows(want)["verdict"]
+
+
+# ---- 7: the three queries of the kept state on one handle, device calls and hooks in turn
+def test_three_queries_share_one_handle_on_the_device():
+    check_three_queries_on_one_handle(SOLVE, lambda h, a, stype: h.resolve(supply_type=stype, **tensors(a)), True, 3)

@@ -6,6 +6,7 @@ both on the caller's own numbers and neither sharing anything with the code unde
 the checkers from here."""
 import ctypes as C
 import functools
+import itertools
 import os
 import subprocess
 
@@ -18,6 +19,7 @@ from oracle import ns_oracle as O
 
 import certificate_oracle as K
 from test_batch_host import ROOT, RULES, fuzz_cases, fuzz_reference
+from test_data_ranges_host import two_tiers
 from test_ranges_host import Flat, range_rows, small_case
 from test_uniform_host import ALL_RULES, family, to_numpy, uniform_of
 
@@ -455,3 +457,80 @@ def test_the_certificate_oracle_on_cuts_it_must_refuse():
             K.check_cut(p, O.GEQ, side, violation)
     assert K.feasible(p, O.GEQ) is False and K.feasible(problem(3, [(0, 1, 0, 5, 1), (1, 2, 1, None, 1)], [5, 0, -5]), O.GEQ) is True
     assert K.feasible(problem(2, [(0, 1, 3, 2, 1)], [0, 0]), O.GEQ) is None
+
+
+# ---- 7: cost ranges, data ranges and diagnosis share one handle: one driver, one summary buffer, a plan and statistics each
+QUERIES = ("cost_ranges", "data_ranges", "diagnose")
+QUERY_STATS = dict(cost_ranges="range_stats", data_ranges="data_range_stats", diagnose="diagnose_stats")
+QUERY_COUNTS = dict(cost_ranges=("instances", "ranged", "tree_arcs", "cycle_hops"), data_ranges=("instances", "ranged", "walks", "hops"), diagnose=COUNTS)
+QUERY_WORDS = dict(cost_ranges=3, data_ranges=3, diagnose=8)       # summary words: up zeroed and down with every device call
+SLOT_BYTES = 104 + C.sizeof(L.BlockConfig)                          # BatchSlot of csrc/batch_layout.hip.h, which has no padding
+
+
+def query_rows(result):
+    get = lambda a: a if isinstance(a, np.ndarray) else a.cpu().numpy()
+    return {name: get(getattr(result, name)) for name, _, _ in type(result).FIELDS}
+
+
+def check_three_queries_on_one_handle(solve, resolve, device_calls, rounds):
+    """The two-tier ragged batch of test_data_ranges_host.py, solved once per handle, then the three queries in each of their six orders,
+    `rounds` times over.  device_calls: call k of a handle runs on the device (tensors: only the summary words, the query's table of
+    instances and the kept state cross the bus in the library) when k plus the order's number is even, and is the hook otherwise, so
+    that the state moves between every two calls; without it every call is the hook.  Every row and every count must be the hook's on a
+    second handle freshly solved; the table of instances goes up with a query's first device call on the handle and never again,
+    whatever ran before; stats() and a resolve() afterwards are what they are without any query."""
+    flat, graphs, graph_of, pair_lists = two_tiers()
+    a, count = flat.arrays, flat.count
+    fresh = lambda: M.RaggedBatch(graphs, graph_of=graph_of, rule=RULES[O.RULE_BLOCK])
+    hook = lambda h, q: h.data_ranges_on_host(pairs=pair_lists) if q == "data_ranges" else getattr(h, q + "_on_host")()
+    on_device = lambda h, q: h.data_ranges(pairs=pair_lists, tensors=True) if q == "data_ranges" else getattr(h, q)(tensors=True)
+    stats_of = lambda h, q: getattr(h, QUERY_STATS[q])()
+    strip = lambda s: {k: v for k, v in s.items() if not k.endswith("_ns") and not k.startswith("bytes_")}
+    new_cost = dict(a, cost=np.ascontiguousarray(a["cost"] + np.arange(len(a["cost"])) % 3))
+
+    ref = fresh()
+    HOST_SOLVE(ref, a, O.GEQ)
+    want = {q: (query_rows(hook(ref, q)), stats_of(ref, q)) for q in QUERIES}
+    assert want["cost_ranges"][1]["ranged"] >= 20 and want["data_ranges"][1]["walks"] > 0 and want["diagnose"][1]["instances"] == count == 24
+    plain = fresh()                                                         # never queried
+    solve(plain, a, O.GEQ)
+    plain_stats = strip(plain.stats())
+    plain_rows = to_numpy(resolve(plain, new_cost, O.GEQ))
+    plain_after = strip(plain.stats())
+
+    for number, order in enumerate(itertools.permutations(QUERIES)):
+        h = fresh()
+        solve(h, a, O.GEQ)
+        solved = h.stats()
+        state_bytes = solved["workspace_bytes"] + count * SLOT_BYTES
+        state_on_host = not device_calls
+        table_is_up = set()
+        for k, q in enumerate(order * rounds):
+            what = (order, k, q)
+            if device_calls and (k + number) % 2 == 0:
+                rows, st = query_rows(on_device(h, q)), stats_of(h, q)
+                assert st["lds_instances"] == 16 and st["global_instances"] == 8, (what, st)
+                up = 8 * QUERY_WORDS[q] + (0 if q in table_is_up else 4 * count) + (state_bytes if state_on_host else 0)
+                assert st["bytes_up"] == up and st["bytes_down"] == 8 * QUERY_WORDS[q], (what, st, up)
+                table_is_up.add(q)
+                state_on_host = False
+            else:
+                rows, st = query_rows(hook(h, q)), stats_of(h, q)
+                assert st["lds_instances"] == st["global_instances"] == st["bytes_up"] == st["bytes_down"] == 0, (what, st)
+                state_on_host = True
+            for name, row in want[q][0].items():
+                assert rows[name].dtype == row.dtype and np.array_equal(rows[name], row), (what, name)
+            assert all(st[f] == want[q][1][f] for f in QUERY_COUNTS[q]), (what, st, want[q][1])
+            for other in QUERIES:                                           # a call replaces its own query's statistics and no other's
+                if other not in order[:k + 1]:
+                    assert stats_of(h, other)["instances"] == 0, (what, other)
+        assert h.stats() == solved and strip(solved) == plain_stats, order
+        assert not any(h.resolve_data_stats().values()) and not any(h.start_stats().values()), order
+        rows = to_numpy(resolve(h, new_cost, O.GEQ))
+        for name in plain_rows:
+            assert np.array_equal(rows[name], plain_rows[name]), (order, name)
+        assert strip(h.stats()) == plain_after, order
+
+
+def test_three_queries_share_one_handle_on_the_host():
+    check_three_queries_on_one_handle(HOST_SOLVE, lambda h, a, stype: h.rerun_on_host(supply_type=stype, **a), False, 2)

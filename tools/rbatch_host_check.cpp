@@ -1,10 +1,12 @@
 // rbatch_host_check.cpp -- the host side of the placed batches as a stand-alone program, so that it can be built together with the
 // library's host sources under -fsanitize=address,undefined and run on a CPU ("Ragged batch").  It runs the ragged entry
-// points (mcf_rbatch_create, _run_on_host, _rerun_on_host, _validate_on_host) on its input, exports the first solve's basis
-// (_cost_ranges_on_host), asks the same basis' supply and bound ranges (_data_ranges_on_host, pairs included), diagnoses the same state
-// (_diagnose_on_host, on a ragged and a uniform handle, verdict counts printed) and starts a second handle from it (_run_from_on_host: the same data must give the first solve's status and
-// total cost; the second costs run for the sanitizer's sake), then the instances of the input's first graph through the uniform entry
-// points (mcf_ubatch_*), which share the drivers, and compares every row of the two.  Needs no GPU and is not loaded into Python.
+// points (mcf_rbatch_create, _run_on_host, _rerun_on_host, _validate_on_host) on its input, exports the first solve's basis with its
+// cost ranges (_cost_ranges_on_host), asks the same basis' supply and bound ranges (_data_ranges_on_host, pairs included), diagnoses the
+// same state (_diagnose_on_host, verdict counts printed) and starts a second handle from it (_run_from_on_host: the same data must give
+// the first solve's status and total cost; the second costs run for the sanitizer's sake), then the instances of the input's first graph
+// through the uniform entry points (mcf_ubatch_*), which share the drivers -- the solves, the validations and all three queries of the
+// kept state (cost ranges, data ranges with graph 0's pair list, diagnosis) -- and compares every row of the two.  Needs no GPU and is
+// not loaded into Python.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -I../include \
 //         rbatch_host_check.cpp ../mincostflow_amd/csrc/{batch.hip,ns_core.cpp,ns_host.cpp,engine.hip,validate.hip,problems.cpp,util.cpp,exchange.cpp} \
@@ -138,17 +140,18 @@ int main(int argc, char **argv)
             CHECK(mcf_rbatch_validate_on_host(b, &c, &summary));
             invalid_total += summary.invalid;
             const Answers r_first = r;
-            // the basis as far as the caller's arcs go, exactly sized like the outputs
+            // the basis as far as the caller's arcs go and its cost ranges, exactly sized like the outputs
             std::vector<int8_t> arc_state(lower.size());
             std::vector<int32_t> ranged((size_t)count);
+            std::vector<int64_t> cost_down(lower.size()), cost_up(lower.size());
             mcf_rbatch_range_io rio{};
-            rio.memory = MCF_MEM_HOST; rio.ranged = ranged.data(); rio.arc_state = arc_state.data();
+            rio.memory = MCF_MEM_HOST; rio.ranged = ranged.data(); rio.arc_state = arc_state.data(); rio.cost_down = cost_down.data(); rio.cost_up = cost_up.data();
             CHECK(mcf_rbatch_cost_ranges_on_host(b, &rio));
+            // the supply and bound ranges of the same basis: per graph the two ends of every third arc, its first and last node both
+            // ways round, a pair (0, 0) and one with an id out of range; pairs, tables and every output exactly sized
+            std::vector<int32_t> pairs;
+            std::vector<int64_t> pair_row{0}, ship_row{0}, flow_down(lower.size()), flow_up(lower.size()), ship_forth, ship_back;
             {
-                // the supply and bound ranges of the same basis: per graph the two ends of every third arc, its first and last node both
-                // ways round, a pair (0, 0) and one with an id out of range; pairs, tables and every output exactly sized
-                std::vector<int32_t> pairs;
-                std::vector<int64_t> pair_row{0}, ship_row{0};
                 for (int g = 0; g < G; ++g) {
                     const int32_t n = node_count[(size_t)g];
                     for (int64_t e = arc_start[(size_t)g]; e < arc_start[(size_t)g + 1]; e += 3) { pairs.push_back(source[(size_t)e]); pairs.push_back(target[(size_t)e]); }
@@ -161,7 +164,7 @@ int main(int argc, char **argv)
                 }
                 std::vector<int8_t> data_state(lower.size());
                 std::vector<int32_t> data_ranged((size_t)count);
-                std::vector<int64_t> flow_down(lower.size()), flow_up(lower.size()), ship_forth((size_t)ship_row.back()), ship_back((size_t)ship_row.back());
+                ship_forth.resize((size_t)ship_row.back()); ship_back.resize((size_t)ship_row.back());
                 mcf_rbatch_data_range_io dio{};
                 dio.memory = MCF_MEM_HOST; dio.pairs = pairs.data(); dio.pair_row = pair_row.data(); dio.ship_row = ship_row.data();
                 dio.ranged = data_ranged.data(); dio.arc_state = data_state.data(); dio.flow_down = flow_down.data(); dio.flow_up = flow_up.data();
@@ -283,6 +286,33 @@ int main(int argc, char **argv)
                     return 1;
                 }
                 for (int32_t v : ug.verdict) ++uniform_verdicts[v];
+            }
+            {
+                // the cost ranges, and the data ranges with graph 0's pair list, of the same basis: exactly sized, every row the ragged handle's
+                const size_t pairs0 = (size_t)pair_row[1];
+                std::vector<int32_t> u_ranged(sel.size()), u_data_ranged(sel.size());
+                std::vector<int8_t> u_state(u_lower.size()), u_data_state(u_lower.size());
+                std::vector<int64_t> u_down(u_lower.size()), u_up(u_lower.size()), u_flow_down(u_lower.size()), u_flow_up(u_lower.size()),
+                    u_forth(sel.size() * pairs0), u_back(sel.size() * pairs0);
+                mcf_ubatch_range_io urio{};
+                urio.memory = MCF_MEM_HOST; urio.ranged = u_ranged.data(); urio.arc_state = u_state.data(); urio.cost_down = u_down.data(); urio.cost_up = u_up.data();
+                CHECK(mcf_ubatch_cost_ranges_on_host(ub, &urio));
+                mcf_ubatch_data_range_io udio{};
+                udio.memory = MCF_MEM_HOST; udio.pairs = pairs.data(); udio.pair_count = (int64_t)pairs0;
+                udio.ranged = u_data_ranged.data(); udio.arc_state = u_data_state.data(); udio.flow_down = u_flow_down.data(); udio.flow_up = u_flow_up.data();
+                udio.ship_forth = u_forth.data(); udio.ship_back = u_back.data();
+                CHECK(mcf_ubatch_data_ranges_on_host(ub, &udio));
+                if (u_ranged != dense(ranged, one, 1, 1, sel) || u_state != dense(arc_state, arc_row, 1, m0, sel) || u_down != dense(cost_down, arc_row, 1, m0, sel) ||
+                    u_up != dense(cost_up, arc_row, 1, m0, sel)) {
+                    fprintf(stderr, "the uniform batch's cost ranges differ from the ragged batch's\n");
+                    return 1;
+                }
+                if (u_data_ranged != u_ranged || u_data_state != u_state || u_flow_down != dense(flow_down, arc_row, 1, m0, sel) ||
+                    u_flow_up != dense(flow_up, arc_row, 1, m0, sel) || u_forth != dense(ship_forth, ship_row, 1, (int64_t)pairs0, sel) ||
+                    u_back != dense(ship_back, ship_row, 1, (int64_t)pairs0, sel)) {
+                    fprintf(stderr, "the uniform batch's data ranges differ from the ragged batch's\n");
+                    return 1;
+                }
             }
             uio.cost = u_cost2.data(); uio.changed = u_changed.data();
             CHECK(mcf_ubatch_rerun_on_host(ub, &uio));
