@@ -1230,6 +1230,72 @@ MCF_API int mcf_rbatch_diagnose(mcf_rbatch *b, const mcf_rbatch_diagnose_io *io)
 MCF_API int mcf_rbatch_diagnose_on_host(mcf_rbatch *b, const mcf_rbatch_diagnose_io *io);
 MCF_API int mcf_rbatch_get_diagnose_stats(mcf_rbatch *b, mcf_ubatch_diagnose_stats *out);
 
+/* ---- Unbounded or not (DESIGN.md 3.14 "Unbounded or not: a negative cycle or labels from the kept data"): a certificate either way,
+ * read on the device from the costs and capacities every instance's last solve call left in its workspace.  The status word mirrors the
+ * reference (a negative cycle of uncapacitated arcs is answered MCF_OPTIMAL with flows of 2^62 - 1 and a total cost that wraps), so this
+ * call answers the question itself, on the caller's arcs, an arc being uncapacitated where upper = MCF_INF_CAP (csrc/rays_step.hip.h):
+ *   MCF_RAY_CYCLE    there is a directed cycle of uncapacitated arcs of total cost < 0: on_cycle[] marks the arcs of ONE simple such
+ *                    cycle (a self loop is one of length 1; of parallel arcs one is marked), cycle_cost < 0 is their cost and
+ *                    cycle_length >= 1 their number.  If the instance is feasible at all its objective is unbounded below, and
+ *                    whatever the status says its cost and flows are no optimum.  label[] is 0.
+ *   MCF_RAY_BOUNDED  there is none, and label[] proves it: label[target] <= label[source] + cost on every uncapacitated arc, which
+ *                    summed round any cycle of them gives a cost >= 0.  on_cycle all 0, cycle_cost 0, cycle_length 0.
+ *   MCF_RAY_BOUNDS   some arc has upper < lower: the workspace was never set up.  Zero rows.
+ *   MCF_RAY_NONE     no solve call has set this instance's workspace up.  Zero rows.
+ * Every other ending of the last solve call (no entering arc, Unbounded, a limit) gets the real answer: the call reads costs and
+ * capacities only, never the flow or the basis, so it also answers after a re-solve of either kind from the data that left.
+ * A level-synchronous Bellman-Ford from all-zero labels, one wave per instance: with k nodes that have an uncapacitated arc coming in,
+ * at most k + 1 rounds of two barriers and one sweep over the nodes each -- a bounded instance with costs >= 0 takes one, a long
+ * negative cycle takes all of them.  An instance is queried in LDS exactly when it is solved there (16 bytes per arc of the caller's
+ * and 29 per node, below the solve's footprint); the others read their workspace in place with labels, marks and frontiers in the
+ * handle's buffer that mcf_*batch_diagnose uses.  Contract as mcf_*batch_diagnose's: null stream, returns synchronised; the call reads
+ * the kept state and changes none of it; MCF_ERR_STATE before a solve of either kind; MCF_ERR_NO_DEVICE without a GPU leaves the handle
+ * as it was; MCF_ERR_INVALID for a null argument or an unknown memory kind.  With MCF_MEM_DEVICE only the summary words cross the bus
+ * in a call (a table of one int32 per instance goes up once per handle, with the first call).  Without the rows the verdict, cycle_cost
+ * and cycle_length are computed all the same. */
+#define MCF_RAY_NONE 0
+#define MCF_RAY_BOUNDED 1
+#define MCF_RAY_CYCLE 2
+#define MCF_RAY_BOUNDS 3
+typedef struct mcf_ubatch_rays_io {
+    int32_t memory;               /* MCF_MEM_HOST / MCF_MEM_DEVICE: where every pointer below points */
+    int32_t reserved;
+    /* results, any may be NULL */
+    int32_t *verdict;             /* [count] MCF_RAY_* */
+    int64_t *cycle_cost;          /* [count] */
+    int32_t *cycle_length;        /* [count] arcs on the cycle */
+    int8_t *on_cycle;             /* [count * arc_count] 1 = on the cycle */
+    int64_t *label;               /* [count * node_count] */
+} mcf_ubatch_rays_io;
+typedef struct mcf_rbatch_rays_io {                    /* the same with flat rows: instance i's arcs at [arc_row[i], arc_row[i + 1]), nodes alike */
+    int32_t memory;
+    int32_t reserved;
+    int32_t *verdict;             /* [count] */
+    int64_t *cycle_cost;          /* [count] */
+    int32_t *cycle_length;        /* [count] */
+    int8_t *on_cycle;             /* [arc_row[count]] */
+    int64_t *label;               /* [node_row[count]] */
+} mcf_rbatch_rays_io;
+typedef struct mcf_ubatch_rays_stats {     /* of the last mcf_*batch_rays / _on_host (all zero before one) */
+    int64_t instances;
+    int64_t none, bounded, cycle, bounds;               /* of `instances`, by verdict */
+    int64_t lds_instances;        /* of `instances`, by the tier they are solved in; 0 and 0 from the host hook */
+    int64_t global_instances;
+    int64_t rounds;               /* rounds of all instances: two barriers and one sweep over the nodes each */
+    int64_t frontier_nodes;       /* nodes of all frontiers; the first of an instance holds every node */
+    int64_t inc_entries;          /* incidence entries read, pushing from the frontiers and pulling at the marked nodes */
+    int64_t cycle_arcs;           /* the sum of cycle_length */
+    double kernel_ns;             /* round the launches, synchronised */
+    int64_t bytes_up, bytes_down; /* MCF_MEM_DEVICE: the summary words; MCF_MEM_HOST adds the arrays */
+} mcf_ubatch_rays_stats;
+MCF_API int mcf_ubatch_rays(mcf_ubatch *b, const mcf_ubatch_rays_io *io);
+/* TEST HOOK: the same step (uniform_rays, csrc/rays_step.hip.h) with one lane on the CPU.  io->memory must be MCF_MEM_HOST. */
+MCF_API int mcf_ubatch_rays_on_host(mcf_ubatch *b, const mcf_ubatch_rays_io *io);
+MCF_API int mcf_ubatch_get_rays_stats(mcf_ubatch *b, mcf_ubatch_rays_stats *out);
+MCF_API int mcf_rbatch_rays(mcf_rbatch *b, const mcf_rbatch_rays_io *io);
+MCF_API int mcf_rbatch_rays_on_host(mcf_rbatch *b, const mcf_rbatch_rays_io *io);
+MCF_API int mcf_rbatch_get_rays_stats(mcf_rbatch *b, mcf_ubatch_rays_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

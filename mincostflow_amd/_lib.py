@@ -303,6 +303,29 @@ class UBatchDiagnoseStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+RAY_NONE, RAY_BOUNDED, RAY_CYCLE, RAY_BOUNDS = range(4)                    # MCF_RAY_*
+
+
+class UBatchRaysIo(C.Structure):
+    """mcf_ubatch_rays_io"""
+    _fields_ = [("memory", C.c_int32), ("reserved", C.c_int32)] + [(name, C.c_void_p) for name in ("verdict", "cycle_cost", "cycle_length", "on_cycle", "label")]
+
+
+class RBatchRaysIo(C.Structure):
+    """mcf_rbatch_rays_io"""
+    _fields_ = UBatchRaysIo._fields_
+
+
+class UBatchRaysStats(C.Structure):
+    """mcf_ubatch_rays_stats"""
+    _fields_ = [(name, C.c_int64) for name in ("instances", "none", "bounded", "cycle", "bounds", "lds_instances", "global_instances", "rounds",
+                                               "frontier_nodes", "inc_entries", "cycle_arcs")] + \
+               [("kernel_ns", C.c_double), ("bytes_up", C.c_int64), ("bytes_down", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class ProblemStruct(C.Structure):
     _fields_ = [("node_count", C.c_int32), ("arc_count", C.c_int32), ("source", C.POINTER(C.c_int32)),
                 ("target", C.POINTER(C.c_int32)), ("lower", C.POINTER(C.c_int64)), ("upper", C.POINTER(C.c_int64)),
@@ -493,6 +516,12 @@ SIGNATURES = {
     "mcf_rbatch_diagnose": (C.c_int, [C.c_void_p, _P(RBatchDiagnoseIo)]),
     "mcf_rbatch_diagnose_on_host": (C.c_int, [C.c_void_p, _P(RBatchDiagnoseIo)]),
     "mcf_rbatch_get_diagnose_stats": (C.c_int, [C.c_void_p, _P(UBatchDiagnoseStats)]),
+    "mcf_ubatch_rays": (C.c_int, [C.c_void_p, _P(UBatchRaysIo)]),
+    "mcf_ubatch_rays_on_host": (C.c_int, [C.c_void_p, _P(UBatchRaysIo)]),
+    "mcf_ubatch_get_rays_stats": (C.c_int, [C.c_void_p, _P(UBatchRaysStats)]),
+    "mcf_rbatch_rays": (C.c_int, [C.c_void_p, _P(RBatchRaysIo)]),
+    "mcf_rbatch_rays_on_host": (C.c_int, [C.c_void_p, _P(RBatchRaysIo)]),
+    "mcf_rbatch_get_rays_stats": (C.c_int, [C.c_void_p, _P(UBatchRaysStats)]),
     "mcf_problem_free": (None, [_P(ProblemStruct)]),
     "mcf_gen_netgen_like": (C.c_int, [_P(ProblemStruct), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64]),

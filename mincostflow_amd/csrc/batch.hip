@@ -18,6 +18,8 @@
 //     data_ranges_step.hip.h on the same state, the same way; every walk gathers into registers, so they need no atomics.
 //   * why an instance is infeasible (mcf_ubatch_diagnose, mcf_rbatch_diagnose): the diagnose kernels run diagnose_step.hip.h on the same
 //     state, the same way; marks and frontiers lie in LDS or, for the global tier, in a buffer of the handle's.
+//   * unbounded or not (mcf_ubatch_rays, mcf_rbatch_rays): the rays kernels run rays_step.hip.h on the costs and capacities of the same
+//     state, the same way; labels, marks and frontiers lie in LDS or, for the global tier, in the same buffer of the handle's.
 //   * solves that start from a basis the caller supplies (mcf_ubatch_solve_from, mcf_rbatch_solve_from): the start kernels run
 //     uniform_begin_from in place of the set-up launch; rounds and settle launch are those of a re-solve with new data.
 // Device code does no bounds checks: mcf_batch_add validates every end point (core_create), and every index the kernel follows after
@@ -36,6 +38,7 @@
 #include "diagnose_step.hip.h"
 #include "ns_core.h"
 #include "ranges_step.hip.h"
+#include "rays_step.hip.h"
 #include "uniform_step.hip.h"
 
 namespace {
@@ -315,6 +318,30 @@ __global__ __launch_bounds__(kBatchThreads) void ragged_diagnose_kernel(mcf::Rag
     const int64_t i = (int64_t)ids[blockIdx.x];
     mcf::uniform_diagnose<kLds>(mcf::ragged_view(r, nullptr, i, slab, nullptr), o, slots[i], kLds ? lds : work + (uint64_t)blockIdx.x * work_stride, (int)threadIdx.x,
                                 kBatchThreads);
+}
+
+// mcf_*batch_rays: the same launch shape on rays_step.hip.h.  kLds: dynamic LDS holds cost and upper of the caller's arcs, the two label
+// arrays, preds, frontiers and marks (at least rays_layout_of(m, n + 1).bytes); otherwise block k works in work + k * work_stride, which
+// the host sized for the largest instance of the global tier, and reads cost and upper in the workspace.
+template <bool kLds>
+__global__ __launch_bounds__(kBatchThreads) void uniform_rays_kernel(mcf::UniformProblem p, mcf::RaysOutputs o, const BatchSlot *slots, unsigned char *slab,
+                                                                     const int32_t *ids, const int32_t *inc_start, const int32_t *inc, unsigned char *work,
+                                                                     uint64_t work_stride)
+{
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int64_t i = (int64_t)ids[blockIdx.x];
+    mcf::InstanceView v = mcf::uniform_view(p, nullptr, i, slab);
+    v.inc_start = inc_start; v.inc = inc;
+    mcf::uniform_rays<kLds>(v, o, slots[i], kLds ? lds : work + (uint64_t)blockIdx.x * work_stride, (int)threadIdx.x, kBatchThreads);
+}
+template <bool kLds>
+__global__ __launch_bounds__(kBatchThreads) void ragged_rays_kernel(mcf::RaggedProblem r, mcf::RaysOutputs o, const BatchSlot *slots, unsigned char *slab,
+                                                                    const int32_t *ids, unsigned char *work, uint64_t work_stride)
+{
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int64_t i = (int64_t)ids[blockIdx.x];
+    mcf::uniform_rays<kLds>(mcf::ragged_view(r, nullptr, i, slab, nullptr), o, slots[i], kLds ? lds : work + (uint64_t)blockIdx.x * work_stride, (int)threadIdx.x,
+                            kBatchThreads);
 }
 
 struct Instance {
@@ -1051,7 +1078,7 @@ struct PlacedBatch {
     int64_t *d_summary = nullptr;       // validation: invalid instances, the lowest invalid index.  Allocated last: it says the tables are up
     unsigned char *d_io = nullptr;      // MCF_MEM_HOST: the caller's arrays on their way up and down
     size_t d_io_bytes = 0;
-    // The queries of the kept state (cost ranges, data ranges, diagnosis): each has its own plan -- the instances by tier and by the class
+    // The queries of the kept state (cost ranges, data ranges, diagnosis, rays): each has its own plan -- the instances by tier and by the class
     // of ITS footprint, planned for the lds_max it names, the id table up once -- and the statistics of its last call that succeeded.
     struct QueryLaunch { int first, n; uint32_t lds; bool in_lds; };
     struct QueryPlan {
@@ -1069,9 +1096,10 @@ struct PlacedBatch {
     Query<mcf_ubatch_range_stats> cost_ranges;
     Query<mcf_ubatch_data_range_stats> data_ranges;
     Query<mcf_ubatch_diagnose_stats> diagnose;
+    Query<mcf_ubatch_rays_stats> rays;
     int64_t *d_query_summary = nullptr; // kQuerySummaryWords, whichever query runs; allocated with the first device call of any of them
-    // diagnosis, global tier: marks and frontiers, diag_work_stride bytes per instance of that tier in launch order (the last call's
-    // stride; allocated with the first call that has such instances)
+    // diagnosis and rays, global tier: the working arrays of whichever runs, diag_work_stride bytes per instance of that tier in launch
+    // order (the last call's stride; allocated with the first call that has such instances, grown where a later one needs more)
     unsigned char *d_diag_work = nullptr;
     size_t diag_work_bytes = 0;
     uint64_t diag_work_stride = 0;
@@ -1084,7 +1112,7 @@ struct PlacedBatch {
             if (p) (void)hipFree(p);
     }
 };
-constexpr int kQuerySummaryWords = mcf::kDiagSummaryWords > 3 ? mcf::kDiagSummaryWords : 3;    // the most any query has
+constexpr int kQuerySummaryWords = std::max({mcf::kDiagSummaryWords, mcf::kRaysSummaryWords, 3});    // the most any query has
 
 }  // namespace
 
@@ -1188,7 +1216,7 @@ BatchIo io_of(const mcf_rbatch_check_io *io) { return check_io(io); }
 // pointer, its true length, whether the call reads it and whether it writes it.
 struct StagedArray { void **slot; size_t bytes; bool up, down; };
 
-// ---- The queries of the kept state: mcf_*batch_cost_ranges, _data_ranges and _diagnose, each a device call and a host hook.  One driver
+// ---- The queries of the kept state: mcf_*batch_cost_ranges, _data_ranges, _diagnose and _rays, each a device call and a host hook.  One driver
 // runs all of them on both placements (query_on_device, query_on_host, check_query_call); a description says what differs between the
 // queries, the way a placement says what differs between the handles:
 //   Io, io_of        the call's arrays, whichever public struct they came in
@@ -1197,7 +1225,7 @@ struct StagedArray { void **slot; size_t bytes; bool up, down; };
 //   arrays           MCF_MEM_HOST: one StagedArray per array of the caller's
 //   footprint        what one instance keeps in LDS: it classes the instances of the LDS tier
 //   kWords, outputs, stats_of      the summary words: how many, the step's outputs with them, what they say
-//   prepare          before the launches; only diagnosis has something to do there
+//   prepare          before the launches; diagnosis and rays size the global tier's working buffer there
 //   Scratch, on_host the step for one instance with one lane, and the room it may keep between instances
 // The kernels, and the arguments only one placement has, are the placement's (launch_query).
 struct PlainQuery {                     // what a query has unless it says otherwise
@@ -1306,6 +1334,33 @@ struct DataRanges : PlainQuery {        // uniform_data_ranges (data_ranges_step
     }
 };
 
+// The global tier's room for the working arrays of a diagnosis or a rays call: per block what the largest instance of that tier needs
+// (bytes_of(n + 1)), 0 when the plan has no such launch; the buffer is the handle's one and only grows.
+template <class P, class Bytes>
+int prepare_work(typename P::Handle *b, const PlacedBatch::QueryPlan &plan, const Bytes &bytes_of)
+{
+    b->diag_work_stride = 0;
+    for (const PlacedBatch::QueryLaunch &L : plan.launches) {
+        if (L.in_lds) continue;
+        const LaunchPlan solve = P::plan(b);
+        uint32_t most = 0;
+        for (size_t i = 0; i < (size_t)b->d.count; ++i) {
+            if (class_of(b->lds_max, solve.bytes((int32_t)i)) != kClasses - 1) continue;
+            int32_t n = 0, m = 0;
+            P::sizes(b, i, &n, &m);
+            most = std::max(most, (uint32_t)bytes_of((uint32_t)n + 1u));
+        }
+        b->diag_work_stride = most;
+        const size_t need = (size_t)L.n * (size_t)most;
+        if (b->diag_work_bytes < need) {
+            if (b->d_diag_work) { HIP_TRY(hipFree(b->d_diag_work)); b->d_diag_work = nullptr; b->diag_work_bytes = 0; }
+            HIP_TRY(hipMalloc((void **)&b->d_diag_work, need));
+            b->diag_work_bytes = need;
+        }
+    }
+    return MCF_OK;
+}
+
 struct Diagnose : PlainQuery {          // uniform_diagnose (diagnose_step.hip.h)
     using Stats = mcf_ubatch_diagnose_stats;
     using Outputs = mcf::DiagOutputs;
@@ -1339,30 +1394,9 @@ struct Diagnose : PlainQuery {          // uniform_diagnose (diagnose_step.hip.h
         st->bounds = words[MCF_DIAG_BOUNDS];
         st->levels = words[MCF_DIAG_BOUNDS + 1]; st->frontier_nodes = words[MCF_DIAG_BOUNDS + 2]; st->inc_entries = words[MCF_DIAG_BOUNDS + 3];
     }
-    // The global tier's room for unmet, marks and frontiers: per block what the largest instance of that tier needs, 0 when the plan has
-    // no such launch; the buffer only grows.
     template <class P> static int prepare(typename P::Handle *b, const PlacedBatch::QueryPlan &plan)
     {
-        b->diag_work_stride = 0;
-        for (const PlacedBatch::QueryLaunch &L : plan.launches) {
-            if (L.in_lds) continue;
-            const LaunchPlan solve = P::plan(b);
-            uint32_t most = 0;
-            for (size_t i = 0; i < (size_t)b->d.count; ++i) {
-                if (class_of(b->lds_max, solve.bytes((int32_t)i)) != kClasses - 1) continue;
-                int32_t n = 0, m = 0;
-                P::sizes(b, i, &n, &m);
-                most = std::max(most, mcf::diag_layout_of(0, (uint32_t)n + 1u).bytes);
-            }
-            b->diag_work_stride = most;
-            const size_t need = (size_t)L.n * (size_t)most;
-            if (b->diag_work_bytes < need) {
-                if (b->d_diag_work) { HIP_TRY(hipFree(b->d_diag_work)); b->d_diag_work = nullptr; b->diag_work_bytes = 0; }
-                HIP_TRY(hipMalloc((void **)&b->d_diag_work, need));
-                b->diag_work_bytes = need;
-            }
-        }
-        return MCF_OK;
+        return prepare_work<P>(b, plan, [](uint32_t N) { return mcf::diag_layout_of(0, N).bytes; });
     }
     struct alignas(16) Word { uint64_t lo, hi; };
     using Scratch = std::vector<Word>;  // one instance's unmet, marks and frontiers at a time
@@ -1372,6 +1406,53 @@ struct Diagnose : PlainQuery {          // uniform_diagnose (diagnose_step.hip.h
         const size_t words_needed = mcf::diag_layout_of(0, (uint32_t)v.n + 1u).bytes / sizeof(Word);
         if (room.size() < words_needed) room.resize(words_needed);
         mcf::uniform_diagnose<false>(v, o, slot, (unsigned char *)room.data(), 0, 1);
+    }
+};
+
+struct Rays : PlainQuery {              // uniform_rays (rays_step.hip.h)
+    using Stats = mcf_ubatch_rays_stats;
+    using Outputs = mcf::RaysOutputs;
+    struct Io {
+        bool given;
+        int32_t memory;
+        int32_t *verdict;
+        int64_t *cycle_cost;
+        int32_t *cycle_length;
+        int8_t *on_cycle;
+        int64_t *label;
+    };
+    template <class T> static Io io_of(const T *io) { return io ? Io{true, io->memory, io->verdict, io->cycle_cost, io->cycle_length, io->on_cycle, io->label} : Io{}; }
+    static PlacedBatch::Query<Stats> &state(PlacedBatch *b) { return b->rays; }
+    template <class P> static int check(const typename P::Handle *, Io *, const char *) { return MCF_OK; }
+    template <class P> static std::array<StagedArray, 5> arrays(const typename P::Handle *b, Io *io)
+    {
+        const size_t count = (size_t)b->d.count, arcs = P::arc_rows(b), nodes = P::node_rows(b);
+        return {{{(void **)&io->verdict, 4 * count, false, true},
+                 {(void **)&io->cycle_cost, 8 * count, false, true},
+                 {(void **)&io->cycle_length, 4 * count, false, true},
+                 {(void **)&io->on_cycle, arcs, false, true},
+                 {(void **)&io->label, 8 * nodes, false, true}}};
+    }
+    static uint32_t footprint(int32_t n, int32_t m) { return mcf::rays_layout_of((uint32_t)m, (uint32_t)n + 1u).bytes; }
+    static constexpr int kWords = mcf::kRaysSummaryWords;
+    static Outputs outputs(const Io &io, int64_t *summary) { return Outputs{io.verdict, io.cycle_cost, io.cycle_length, io.on_cycle, io.label, summary}; }
+    static void stats_of(const int64_t *words, Stats *st)
+    {
+        st->none = words[MCF_RAY_NONE]; st->bounded = words[MCF_RAY_BOUNDED]; st->cycle = words[MCF_RAY_CYCLE]; st->bounds = words[MCF_RAY_BOUNDS];
+        st->rounds = words[MCF_RAY_BOUNDS + 1]; st->frontier_nodes = words[MCF_RAY_BOUNDS + 2]; st->inc_entries = words[MCF_RAY_BOUNDS + 3];
+        st->cycle_arcs = words[MCF_RAY_BOUNDS + 4];
+    }
+    template <class P> static int prepare(typename P::Handle *b, const PlacedBatch::QueryPlan &plan)
+    {
+        return prepare_work<P>(b, plan, [](uint32_t N) { return mcf::rays_layout_of(0, N).bytes; });
+    }
+    using Scratch = Diagnose::Scratch;  // one instance's labels, preds, marks and frontiers at a time
+    template <class P>
+    static void on_host(const typename P::Handle *, const Io &, const mcf::InstanceView &v, const Outputs &o, int64_t, const BatchSlot &slot, Scratch &room)
+    {
+        const size_t words_needed = mcf::rays_layout_of(0, (uint32_t)v.n + 1u).bytes / sizeof(Diagnose::Word);
+        if (room.size() < words_needed) room.resize(words_needed);
+        mcf::uniform_rays<false>(v, o, slot, (unsigned char *)room.data(), 0, 1);
     }
 };
 
@@ -1448,6 +1529,10 @@ struct UniformPlacement {
     {
         return go(uniform_diagnose_kernel<true>, uniform_diagnose_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids, b->d_inc_start, b->d_inc, b->d_diag_work,
                   b->diag_work_stride);
+    }
+    template <class A, class Go> static int launch_query(Rays, const Handle *b, const A &a, const Go &go)
+    {
+        return go(uniform_rays_kernel<true>, uniform_rays_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids, b->d_inc_start, b->d_inc, b->d_diag_work, b->diag_work_stride);
     }
     // one list for every instance
     static int check_pairs(const Handle *b, const DataRanges::Io &io, const char *what, PairSizes *sizes)
@@ -1545,6 +1630,10 @@ struct RaggedPlacement {
     template <class A, class Go> static int launch_query(Diagnose, const Handle *b, const A &a, const Go &go)
     {
         return go(ragged_diagnose_kernel<true>, ragged_diagnose_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids, b->d_diag_work, b->diag_work_stride);
+    }
+    template <class A, class Go> static int launch_query(Rays, const Handle *b, const A &a, const Go &go)
+    {
+        return go(ragged_rays_kernel<true>, ragged_rays_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids, b->d_diag_work, b->diag_work_stride);
     }
     // one list per graph: pair_row says where each begins, ship_row where each instance's answers do.  Tables in host memory are checked
     // against each other; tables in device memory are the caller's word, as the rows of every call are.
@@ -2054,7 +2143,7 @@ int validate_on_host(typename P::Handle *b, const BatchIo &io, mcf_ubatch_check_
     return MCF_OK;
 }
 
-// ---- mcf_*batch_cost_ranges, _data_ranges, _diagnose and their _on_host hooks: query Q's step for every instance, on the state the last
+// ---- mcf_*batch_cost_ranges, _data_ranges, _diagnose, _rays and their _on_host hooks: query Q's step for every instance, on the state the last
 // solve call left; the state is only read.  What every such call refuses before it touches the handle, in this order:
 template <class P, class Q>
 int check_query_call(const typename P::Handle *b, typename Q::Io *io, const char *what, bool host_only)
@@ -2357,6 +2446,9 @@ int mcf_ubatch_get_data_range_stats(mcf_ubatch *b, mcf_ubatch_data_range_stats *
 int mcf_ubatch_diagnose(mcf_ubatch *b, const mcf_ubatch_diagnose_io *io) { return query_on_device<UniformPlacement, Diagnose>(b, Diagnose::io_of(io), "mcf_ubatch_diagnose"); }
 int mcf_ubatch_diagnose_on_host(mcf_ubatch *b, const mcf_ubatch_diagnose_io *io) { return query_on_host<UniformPlacement, Diagnose>(b, Diagnose::io_of(io), "mcf_ubatch_diagnose_on_host"); }
 int mcf_ubatch_get_diagnose_stats(mcf_ubatch *b, mcf_ubatch_diagnose_stats *out) { return get_stats(b, out, &PlacedBatch::diagnose); }
+int mcf_ubatch_rays(mcf_ubatch *b, const mcf_ubatch_rays_io *io) { return query_on_device<UniformPlacement, Rays>(b, Rays::io_of(io), "mcf_ubatch_rays"); }
+int mcf_ubatch_rays_on_host(mcf_ubatch *b, const mcf_ubatch_rays_io *io) { return query_on_host<UniformPlacement, Rays>(b, Rays::io_of(io), "mcf_ubatch_rays_on_host"); }
+int mcf_ubatch_get_rays_stats(mcf_ubatch *b, mcf_ubatch_rays_stats *out) { return get_stats(b, out, &PlacedBatch::rays); }
 
 void mcf_rbatch_destroy(mcf_rbatch *b) { delete b; }
 int mcf_rbatch_solve(mcf_rbatch *b, const mcf_rbatch_io *io) { return solve_on_device<RaggedPlacement>(b, io_of(io), kFresh, "mcf_rbatch_solve"); }
@@ -2393,5 +2485,8 @@ int mcf_rbatch_get_data_range_stats(mcf_rbatch *b, mcf_ubatch_data_range_stats *
 int mcf_rbatch_diagnose(mcf_rbatch *b, const mcf_rbatch_diagnose_io *io) { return query_on_device<RaggedPlacement, Diagnose>(b, Diagnose::io_of(io), "mcf_rbatch_diagnose"); }
 int mcf_rbatch_diagnose_on_host(mcf_rbatch *b, const mcf_rbatch_diagnose_io *io) { return query_on_host<RaggedPlacement, Diagnose>(b, Diagnose::io_of(io), "mcf_rbatch_diagnose_on_host"); }
 int mcf_rbatch_get_diagnose_stats(mcf_rbatch *b, mcf_ubatch_diagnose_stats *out) { return get_stats(b, out, &PlacedBatch::diagnose); }
+int mcf_rbatch_rays(mcf_rbatch *b, const mcf_rbatch_rays_io *io) { return query_on_device<RaggedPlacement, Rays>(b, Rays::io_of(io), "mcf_rbatch_rays"); }
+int mcf_rbatch_rays_on_host(mcf_rbatch *b, const mcf_rbatch_rays_io *io) { return query_on_host<RaggedPlacement, Rays>(b, Rays::io_of(io), "mcf_rbatch_rays_on_host"); }
+int mcf_rbatch_get_rays_stats(mcf_rbatch *b, mcf_ubatch_rays_stats *out) { return get_stats(b, out, &PlacedBatch::rays); }
 
 }  // extern "C"

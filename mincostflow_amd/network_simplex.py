@@ -36,6 +36,10 @@ class Verdict:                        # MCF_DIAG_* of include/mcf_hip.h: what di
     NoVerdict, Feasible, Cut, Open, Bounds = L.DIAG_NONE, L.DIAG_FEASIBLE, L.DIAG_CUT, L.DIAG_OPEN, L.DIAG_BOUNDS
 
 
+class Ray:                            # MCF_RAY_* of include/mcf_hip.h: what rays() says of an instance
+    NoVerdict, Bounded, Cycle, Bounds = L.RAY_NONE, L.RAY_BOUNDED, L.RAY_CYCLE, L.RAY_BOUNDS
+
+
 def _vector_width_abi(v: int) -> int:
     """Python side: 0 = not hardware accelerated, 2 / 4 / 8 = Vector<long>.Count (the oracle's convention).  C ABI: MCF_VECTOR_NONE = -1, 0 = default (4)."""
     if v not in (0, 2, 4, 8):
@@ -602,6 +606,38 @@ class RaggedDiagnosis(UniformDiagnosis):
         return tuple(None if a is None else a[lo:hi] for a in (self.side, self.unmet))
 
 
+class UniformRays:
+    """What UniformBatch.rays returns: one row per instance, numpy arrays or tensors.  verdict[i] is a Ray.  Cycle: the instance holds a
+    directed cycle of uncapacitated arcs (upper = INF_CAP) of total cost < 0 -- on_cycle[i] marks the arcs of one simple such cycle,
+    cycle_cost[i] < 0 is their cost, cycle_length[i] their number -- so if it is feasible at all its objective is unbounded below, and
+    whatever status says its cost and flows are no optimum.  Bounded: there is none, and label[i] proves it: label[target] <=
+    label[source] + cost on every uncapacitated arc.  Bounds: an upper bound below its lower bound.  NoVerdict: never solved.  Rows that
+    a verdict does not fill are zero.  on_cycle and label are None where they were not asked for."""
+    __slots__ = ("verdict", "cycle_cost", "cycle_length", "on_cycle", "label")
+    FIELDS = (("verdict", "int32", ""), ("cycle_cost", "int64", ""), ("cycle_length", "int32", ""), ("on_cycle", "int8", "m"), ("label", "int64", "n"))
+
+    def __init__(self, **arrays):
+        for name, _, _ in self.FIELDS:
+            setattr(self, name, arrays.get(name))
+
+
+class RaggedRays(UniformRays):
+    """What RaggedBatch.rays returns: UniformRays' fields with the per-arc and per-node rows FLAT -- instance i's arcs are
+    [arc_rows[i], arc_rows[i + 1]), its nodes [node_rows[i], node_rows[i + 1]); arcs(i) returns on_cycle and nodes(i) label of
+    instance i as views."""
+    __slots__ = ("arc_rows", "node_rows")
+
+    def __init__(self, arc_rows, node_rows, **arrays):
+        super().__init__(**arrays)
+        self.arc_rows, self.node_rows = arc_rows, node_rows
+
+    def arcs(self, i: int):
+        return None if self.on_cycle is None else self.on_cycle[int(self.arc_rows[i]):int(self.arc_rows[i + 1])]
+
+    def nodes(self, i: int):
+        return None if self.label is None else self.label[int(self.node_rows[i]):int(self.node_rows[i + 1])]
+
+
 class _PlacedBatch:
     """What UniformBatch and RaggedBatch share: the checks of every array of a call, the calls and their results.  A subclass has the
     constructor (which sets _h, _last = None, count, device, record_trace) and says what differs:
@@ -610,6 +646,7 @@ class _PlacedBatch:
       _RANGE_IO          the ctypes struct of a cost-ranges call; _ranges(out) makes its result
       _BASIS_IO          the ctypes struct that carries a given basis into solve_from()
       _DIAGNOSE_IO       the ctypes struct of a diagnose call; _diagnosis(out) makes its result
+      _RAYS_IO           the ctypes struct of a rays call; _rays_result(out) makes its result
       _RESULT            the result class; _result(out) makes one
       _sizes()           the shapes of the outputs by UniformResult.FIELDS' dimension key
       _stride(...)       the expected shape of the array of a given name, its contiguity, and the stride it is passed with"""
@@ -898,6 +935,31 @@ class _PlacedBatch:
         """What the last diagnose() / diagnose_on_host() did: instances per verdict, tiers, levels, frontier nodes, incidence entries, kernel time."""
         return self._stats("get_diagnose_stats", L.UBatchDiagnoseStats)
 
+    # ---- unbounded or not: a negative cycle or labels from the kept data
+    def _rays_result(self, out):
+        return UniformRays(**out)
+
+    def _rays(self, fn, tensors, arcs, labels):
+        return self._query(fn, self._RAYS_IO(), UniformRays.FIELDS, lambda name, dim: (not arcs and dim == "m") or (not labels and dim == "n"), self._sizes(),
+                           self._rays_result, tensors)
+
+    def rays(self, tensors=None, arcs=True, labels=True):
+        """Whether every instance's objective is bounded below, from the costs and capacities its last solve call left, on the device: a
+        UniformRays / RaggedRays with a negative cycle of uncapacitated arcs where it is not and node labels that prove there is none
+        where it is.  The solver mirrors the reference, which answers such a cycle Optimal with a cost that wraps: this is the guard.
+        tensors: True = tensors on the handle's device (nothing that scales with the batch crosses the bus), False = numpy arrays, None =
+        like the last result.  arcs=False leaves on_cycle out, labels=False label (the verdict, cycle_cost and cycle_length come all the
+        same).  The kept state is read, never changed: solve calls, range calls, diagnose() and this one mix in any order."""
+        return self._rays("rays", tensors, arcs, labels)
+
+    def rays_on_host(self, arcs=True, labels=True):
+        """Test hook: rays() with one lane on the CPU.  numpy only."""
+        return self._rays("rays_on_host", False, arcs, labels)
+
+    def ray_stats(self) -> dict:
+        """What the last rays() / rays_on_host() did: instances per verdict, tiers, rounds, frontier nodes, incidence entries, cycle arcs, kernel time."""
+        return self._stats("get_rays_stats", L.UBatchRaysStats)
+
     # ---- validation: the solution's rows where they lie
     SOLUTION_ROWS = (("status", "int32", None), ("total_cost", "int64", None), ("flows", "int64", "arc_count"), ("potentials", "int64", "node_count"))
 
@@ -964,6 +1026,7 @@ class UniformBatch(_PlacedBatch):
 
     _DATA_RANGE_IO = L.UBatchDataRangeIo
     _DIAGNOSE_IO = L.UBatchDiagnoseIo
+    _RAYS_IO = L.UBatchRaysIo
 
     def _pairs_into(self, io, pairs, tensors, keep):
         """one list for every instance: ship rows [count, k]"""
@@ -1050,6 +1113,10 @@ class RaggedBatch(_PlacedBatch):
 
     _DATA_RANGE_IO = L.RBatchDataRangeIo
     _DIAGNOSE_IO = L.RBatchDiagnoseIo
+    _RAYS_IO = L.RBatchRaysIo
+
+    def _rays_result(self, out):
+        return RaggedRays(self.arc_rows, self.node_rows, **out)
 
     def _diagnosis(self, out):
         return RaggedDiagnosis(self.node_rows, **out)

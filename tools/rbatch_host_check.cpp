@@ -2,10 +2,11 @@
 // library's host sources under -fsanitize=address,undefined and run on a CPU ("Ragged batch").  It runs the ragged entry
 // points (mcf_rbatch_create, _run_on_host, _rerun_on_host, _validate_on_host) on its input, exports the first solve's basis with its
 // cost ranges (_cost_ranges_on_host), asks the same basis' supply and bound ranges (_data_ranges_on_host, pairs included), diagnoses the
-// same state (_diagnose_on_host, verdict counts printed) and starts a second handle from it (_run_from_on_host: the same data must give
+// same state (_diagnose_on_host, verdict counts printed), asks whether it is unbounded (_rays_on_host with and without the rows, every
+// cycle summed and every row of labels checked, verdict counts printed) and starts a second handle from it (_run_from_on_host: the same data must give
 // the first solve's status and total cost; the second costs run for the sanitizer's sake), then the instances of the input's first graph
 // through the uniform entry points (mcf_ubatch_*), which share the drivers -- the solves, the validations and all three queries of the
-// kept state (cost ranges, data ranges with graph 0's pair list, diagnosis) -- and compares every row of the two.  Needs no GPU and is
+// kept state (cost ranges, data ranges with graph 0's pair list, diagnosis, rays) -- and compares every row of the two.  Needs no GPU and is
 // not loaded into Python.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -I../include \
@@ -51,6 +52,14 @@ struct Diagnosis {
     std::vector<int64_t> violation, unmet;
     std::vector<int8_t> side;
     Diagnosis(size_t count, size_t nodes) : verdict(count), set_size(count), violation(count), unmet(nodes), side(nodes) {}
+};
+
+// what a rays call wrote, exactly sized
+struct Rays {
+    std::vector<int32_t> verdict, cycle_length;
+    std::vector<int64_t> cycle_cost, label;
+    std::vector<int8_t> on_cycle;
+    Rays(size_t count, size_t arcs, size_t nodes) : verdict(count), cycle_length(count), cycle_cost(count), label(nodes), on_cycle(arcs) {}
 };
 
 // what a solve call and a validation call wrote
@@ -113,6 +122,7 @@ int main(int argc, char **argv)
 
     int64_t pivots_total = 0, invalid_total = 0, started = 0, data_ranged_total = 0, data_walks = 0;
     int64_t verdicts[MCF_DIAG_BOUNDS + 1] = {}, uniform_verdicts[MCF_DIAG_BOUNDS + 1] = {}, diag_levels = 0;
+    int64_t ray_verdicts[MCF_RAY_BOUNDS + 1] = {}, uniform_ray_verdicts[MCF_RAY_BOUNDS + 1] = {}, ray_rounds = 0;
     for (int32_t rule : {MCF_RULE_BLOCK_SEARCH, MCF_RULE_BEST_ELIGIBLE, MCF_RULE_FIRST_ELIGIBLE})
         for (int32_t stype : {MCF_SUPPLY_GEQ, MCF_SUPPLY_LEQ}) {
             mcf_rbatch_desc d{};
@@ -221,6 +231,43 @@ int main(int argc, char **argv)
                 CHECK(mcf_rbatch_diagnose_on_host(b, &gio));
                 if (dg.verdict != with_rows) { fprintf(stderr, "another verdict without the node rows\n"); return 1; }
             }
+            // unbounded or not, from the same kept state: every output exactly sized; a cycle's marks sum to its cost and count to its
+            // length, a bounded instance's labels hold on every uncapacitated arc
+            Rays ry((size_t)count, lower.size(), supply.size());
+            {
+                mcf_rbatch_rays_io yio{};
+                yio.memory = MCF_MEM_HOST; yio.verdict = ry.verdict.data(); yio.cycle_cost = ry.cycle_cost.data(); yio.cycle_length = ry.cycle_length.data();
+                yio.on_cycle = ry.on_cycle.data(); yio.label = ry.label.data();
+                CHECK(mcf_rbatch_rays_on_host(b, &yio));
+                mcf_ubatch_rays_stats ys{};
+                CHECK(mcf_rbatch_get_rays_stats(b, &ys));
+                ray_rounds += ys.rounds;
+                for (int i = 0; i < count; ++i) {
+                    const int32_t v = ry.verdict[(size_t)i];
+                    if (v < MCF_RAY_NONE || v > MCF_RAY_BOUNDS) { fprintf(stderr, "instance %d: ray verdict %d\n", i, v); return 1; }
+                    ++ray_verdicts[v];
+                    const size_t g = (size_t)graph_of[(size_t)i];
+                    int64_t sum = 0, length = 0;
+                    bool holds = true;
+                    for (int64_t e = 0; e < arc_start[g + 1] - arc_start[g]; ++e) {
+                        const size_t at = (size_t)(arc_row[(size_t)i] + e);
+                        if (ry.on_cycle[at]) { sum += cost[at]; ++length; }
+                        const int64_t *const label = ry.label.data() + node_row[(size_t)i];
+                        if (upper[at] == MCF_INF_CAP) holds = holds && label[target[(size_t)(arc_start[g] + e)]] <= label[source[(size_t)(arc_start[g] + e)]] + cost[at];
+                    }
+                    if (sum != ry.cycle_cost[(size_t)i] || length != ry.cycle_length[(size_t)i] || (v == MCF_RAY_CYCLE) != (sum < 0) || (v == MCF_RAY_BOUNDED && !holds)) {
+                        fprintf(stderr, "instance %d: ray verdict %d, cycle cost %lld over %lld arcs, labels %s\n", i, v, (long long)sum, (long long)length, holds ? "hold" : "broken");
+                        return 1;
+                    }
+                }
+                yio.on_cycle = nullptr; yio.label = nullptr;              // without the rows the rounds still run
+                const Rays with_rows = ry;
+                CHECK(mcf_rbatch_rays_on_host(b, &yio));
+                if (ry.verdict != with_rows.verdict || ry.cycle_cost != with_rows.cycle_cost || ry.cycle_length != with_rows.cycle_length) {
+                    fprintf(stderr, "another ray verdict without the rows\n");
+                    return 1;
+                }
+            }
             {
                 mcf_rbatch *from = nullptr;
                 CHECK(mcf_rbatch_create(&from, &d));
@@ -288,6 +335,19 @@ int main(int argc, char **argv)
                 for (int32_t v : ug.verdict) ++uniform_verdicts[v];
             }
             {
+                Rays uy(sel.size(), u_lower.size(), u_supply.size());
+                mcf_ubatch_rays_io yio{};
+                yio.memory = MCF_MEM_HOST; yio.verdict = uy.verdict.data(); yio.cycle_cost = uy.cycle_cost.data(); yio.cycle_length = uy.cycle_length.data();
+                yio.on_cycle = uy.on_cycle.data(); yio.label = uy.label.data();
+                CHECK(mcf_ubatch_rays_on_host(ub, &yio));
+                if (uy.verdict != dense(ry.verdict, one, 1, 1, sel) || uy.cycle_cost != dense(ry.cycle_cost, one, 1, 1, sel) || uy.cycle_length != dense(ry.cycle_length, one, 1, 1, sel) ||
+                    uy.on_cycle != dense(ry.on_cycle, arc_row, 1, m0, sel) || uy.label != dense(ry.label, node_row, 1, n0, sel)) {
+                    fprintf(stderr, "the uniform batch's rays differ from the ragged batch's\n");
+                    return 1;
+                }
+                for (int32_t v : uy.verdict) ++uniform_ray_verdicts[v];
+            }
+            {
                 // the cost ranges, and the data ranges with graph 0's pair list, of the same basis: exactly sized, every row the ragged handle's
                 const size_t pairs0 = (size_t)pair_row[1];
                 std::vector<int32_t> u_ranged(sel.size()), u_data_ranged(sel.size());
@@ -332,5 +392,9 @@ int main(int argc, char **argv)
            (long long)verdicts[MCF_DIAG_NONE], (long long)verdicts[MCF_DIAG_FEASIBLE], (long long)verdicts[MCF_DIAG_CUT], (long long)verdicts[MCF_DIAG_OPEN],
            (long long)verdicts[MCF_DIAG_BOUNDS], (long long)diag_levels, (long long)uniform_verdicts[MCF_DIAG_NONE], (long long)uniform_verdicts[MCF_DIAG_FEASIBLE],
            (long long)uniform_verdicts[MCF_DIAG_CUT], (long long)uniform_verdicts[MCF_DIAG_OPEN], (long long)uniform_verdicts[MCF_DIAG_BOUNDS]);
+    printf("rays over all handles: ragged none %lld, bounded %lld, cycle %lld, by bounds %lld (%lld rounds); uniform none %lld, bounded %lld, cycle %lld, by bounds %lld\n",
+           (long long)ray_verdicts[MCF_RAY_NONE], (long long)ray_verdicts[MCF_RAY_BOUNDED], (long long)ray_verdicts[MCF_RAY_CYCLE], (long long)ray_verdicts[MCF_RAY_BOUNDS],
+           (long long)ray_rounds, (long long)uniform_ray_verdicts[MCF_RAY_NONE], (long long)uniform_ray_verdicts[MCF_RAY_BOUNDED], (long long)uniform_ray_verdicts[MCF_RAY_CYCLE],
+           (long long)uniform_ray_verdicts[MCF_RAY_BOUNDS]);
     return 0;
 }
