@@ -11,17 +11,22 @@
 //     instances again: from the basis they ended with where that ended Optimal (new cost[] up, batch_reprice on the device, changing part
 //     down), from the start basis otherwise.
 //   * re-solves with new supplies and bounds (mcf_ubatch_resolve_data, mcf_rbatch_resolve_data): batch_dual_kernel runs the dual pivots of
-//     batch_step.hip.h in front of the primal ones, between a re-data launch and a settle launch (uniform_step.hip.h).
-//   * cost ranges of the kept basis (mcf_ubatch_cost_ranges, mcf_rbatch_cost_ranges): the ranges kernels run ranges_step.hip.h on the
-//     workspaces as the last solve call left them, and write nothing there.
-//   * supply and bound ranges of the kept basis (mcf_ubatch_data_ranges, mcf_rbatch_data_ranges): the data-ranges kernels run
-//     data_ranges_step.hip.h on the same state, the same way; every walk gathers into registers, so they need no atomics.
-//   * why an instance is infeasible (mcf_ubatch_diagnose, mcf_rbatch_diagnose): the diagnose kernels run diagnose_step.hip.h on the same
-//     state, the same way; marks and frontiers lie in LDS or, for the global tier, in a buffer of the handle's.
-//   * unbounded or not (mcf_ubatch_rays, mcf_rbatch_rays): the rays kernels run rays_step.hip.h on the costs and capacities of the same
-//     state, the same way; labels, marks and frontiers lie in LDS or, for the global tier, in the same buffer of the handle's.
-//   * solves that start from a basis the caller supplies (mcf_ubatch_solve_from, mcf_rbatch_solve_from): the start kernels run
-//     uniform_begin_from in place of the set-up launch; rounds and settle launch are those of a re-solve with new data.
+//     batch_step.hip.h in front of the primal ones, between a re-data launch and a settle launch (step_kernel on uniform_redata and
+//     uniform_redata_settle, uniform_step.hip.h).
+//   * the placed batches (mcf_ubatch_*, mcf_rbatch_*): problem data in and results out where they are.  Their kernels are stated once
+//     over the kind of problem -- step_kernel<Problem, Step>, finish_kernel<Problem>, validate_kernel<Problem>, query_kernel<Problem,
+//     Query, kLds> -- as their host side is stated once over a placement; view_of (uniform_step.hip.h) is what tells a UniformProblem
+//     from a RaggedProblem.
+//   * cost ranges of the kept basis (mcf_ubatch_cost_ranges, mcf_rbatch_cost_ranges): query_kernel<.., CostRanges, ..> runs
+//     ranges_step.hip.h on the workspaces as the last solve call left them, and writes nothing there.
+//   * supply and bound ranges of the kept basis (mcf_ubatch_data_ranges, mcf_rbatch_data_ranges): query_kernel<.., DataRanges, ..> runs
+//     data_ranges_step.hip.h on the same state, the same way; every walk gathers into registers, so it needs no atomics.
+//   * why an instance is infeasible (mcf_ubatch_diagnose, mcf_rbatch_diagnose): query_kernel<.., Diagnose, ..> runs diagnose_step.hip.h on
+//     the same state, the same way; marks and frontiers lie in LDS or, for the global tier, in a buffer of the handle's.
+//   * unbounded or not (mcf_ubatch_rays, mcf_rbatch_rays): query_kernel<.., Rays, ..> runs rays_step.hip.h on the costs and capacities of
+//     the same state, the same way; labels, marks and frontiers lie in LDS or, for the global tier, in the same buffer of the handle's.
+//   * solves that start from a basis the caller supplies (mcf_ubatch_solve_from, mcf_rbatch_solve_from): step_kernel<.., uniform_begin_from>
+//     is the set-up launch; rounds and settle launch are those of a re-solve with new data.
 // Device code does no bounds checks: mcf_batch_add validates every end point (core_create), and every index the kernel follows after
 // that was written by start_basis or by the pivot itself.
 #include <hip/hip_runtime.h>
@@ -148,200 +153,65 @@ __global__ __launch_bounds__(kStageThreads) void stage_kernel(const BatchSlot *s
     for (uint32_t i = threadIdx.x; i < count; i += kStageThreads) dst[i] = src[i];
 }
 
-// The uniform batch (mcf_ubatch_*): the steps of uniform_step.hip.h, one workgroup of one wave per instance like batch_kernel -- the
-// start basis numbers the artificial arcs by a wave-wide prefix count, and all three combine their lanes by wave reductions.  Block i
-// serves instance i and leaves at once where `changed` (a re-solve's mask) says so.  They work on the workspace in device memory; the
-// caller's arrays are read and written as base + i * stride, consecutive lanes on consecutive arcs or nodes.  Each forms the placed
-// view of its instance (uniform_view) and hands it to the step.
-__global__ __launch_bounds__(kBatchThreads) void uniform_begin_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
-{
-    const int64_t i = (int64_t)blockIdx.x;
-    mcf::uniform_begin(mcf::uniform_view(p, nullptr, i, slab), *tmpl, slots[i], (int)threadIdx.x, kBatchThreads);
-}
-__global__ __launch_bounds__(kBatchThreads) void uniform_recost_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
-{
-    const int64_t i = (int64_t)blockIdx.x;
-    if (p.changed && !p.changed[i]) return;
-    mcf::uniform_recost(mcf::uniform_view(p, nullptr, i, slab), *tmpl, slots[i], (int)threadIdx.x, kBatchThreads);
-}
-__global__ __launch_bounds__(kBatchThreads) void uniform_redata_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
+// The placed batches (mcf_ubatch_*, mcf_rbatch_*): the steps of uniform_step.hip.h and of the query headers, each kernel stated once over
+// the kind of problem.  view_of forms the placed view of an instance from either kind: a UniformProblem places by strides (the caller's
+// arrays as base + i * stride, the workspace at i * stride), a RaggedProblem by the handle's tables in device memory (the instance's graph
+// record, its rows and its workspace at running sums, its graph's slot template); every table entry a block reads is the same for all its
+// lanes.  One workgroup of one wave per instance, like batch_kernel: the start basis numbers the artificial arcs by a wave-wide prefix
+// count, and every step combines its lanes by wave reductions.  Consecutive lanes work on consecutive arcs or nodes.
+//
+// step_kernel: the set-up launch of a solve (uniform_begin, _recost, _redata, _begin_from) and the settle launch (uniform_redata_settle).
+// Block i serves instance i, on its workspace in device memory, with its graph's slot template, and leaves at once where `changed` (a
+// re-solve's mask) says so.  A fresh solve and a solve from a given basis have no mask: solve_on_device clears it for a call that is no
+// re-solve, check_call refuses one beside a basis, so for uniform_begin and uniform_begin_from the test never holds.
+using Step = void (*)(const mcf::InstanceView &, const BatchSlot &, BatchSlot &, int, int);
+template <class Problem, Step kStep>
+__global__ __launch_bounds__(kBatchThreads) void step_kernel(Problem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
 {
     const int64_t i = (int64_t)blockIdx.x;
     if (p.changed && !p.changed[i]) return;
-    mcf::uniform_redata(mcf::uniform_view(p, nullptr, i, slab), *tmpl, slots[i], (int)threadIdx.x, kBatchThreads);
+    int32_t t;
+    const mcf::InstanceView v = mcf::view_of(p, nullptr, i, slab, &t);
+    kStep(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
 }
-// mcf_ubatch_solve_from: the view as the re-data kernel forms it, with the handle's incidence lists (the validation's) for the walk
-__global__ __launch_bounds__(kBatchThreads) void uniform_start_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab,
-                                                                      const int32_t *inc_start, const int32_t *inc)
-{
-    const int64_t i = (int64_t)blockIdx.x;
-    mcf::InstanceView v = mcf::uniform_view(p, nullptr, i, slab);
-    v.inc_start = inc_start; v.inc = inc;
-    mcf::uniform_begin_from(v, *tmpl, slots[i], (int)threadIdx.x, kBatchThreads);
-}
-__global__ __launch_bounds__(kBatchThreads) void uniform_settle_kernel(mcf::UniformProblem p, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
+// the finish launch: the status and the output rows of every instance the call ran
+template <class Problem>
+__global__ __launch_bounds__(kBatchThreads) void finish_kernel(Problem p, mcf::UniformOutputs o, const BatchSlot *slots, unsigned char *slab, const int32_t *traces)
 {
     const int64_t i = (int64_t)blockIdx.x;
     if (p.changed && !p.changed[i]) return;
-    mcf::uniform_redata_settle(mcf::uniform_view(p, nullptr, i, slab), *tmpl, slots[i], (int)threadIdx.x, kBatchThreads);
+    mcf::uniform_finish(mcf::view_of(p, &o, i, slab, nullptr), o, slots[i], traces, (int)threadIdx.x, kBatchThreads);
 }
-__global__ __launch_bounds__(kBatchThreads) void uniform_finish_kernel(mcf::UniformProblem p, mcf::UniformOutputs o, const BatchSlot *slots, unsigned char *slab,
-                                                                       const int32_t *traces)
-{
-    const int64_t i = (int64_t)blockIdx.x;
-    if (p.changed && !p.changed[i]) return;
-    mcf::uniform_finish(mcf::uniform_view(p, &o, i, slab), o, slots[i], traces, (int)threadIdx.x, kBatchThreads);
-}
-// mcf_ubatch_validate: block i checks instance i's rows.  One wave for the same reason: every combine is a wave reduction.  It touches
+// mcf_*batch_validate: block i checks instance i's rows.  One wave for the same reason: every combine is a wave reduction.  It touches
 // neither slab nor slots; the only words instances share are the two of the summary, and only invalid instances write them.
-__global__ __launch_bounds__(kBatchThreads) void uniform_validate_kernel(mcf::UniformProblem p, mcf::UniformCheck c, const int32_t *inc_start, const int32_t *inc,
-                                                                         const int64_t *flows, const int64_t *potentials)
+template <class Problem>
+__global__ __launch_bounds__(kBatchThreads) void validate_kernel(Problem p, mcf::UniformCheck c, const int64_t *flows, const int64_t *potentials)
 {
-    mcf::uniform_validate(mcf::uniform_check_view(p, inc_start, inc, flows, potentials, (int64_t)blockIdx.x), c, (int)threadIdx.x, kBatchThreads);
+    mcf::uniform_validate(mcf::check_view_of(p, flows, potentials, (int64_t)blockIdx.x), c, (int)threadIdx.x, kBatchThreads);
 }
 
-// The ragged batch (mcf_rbatch_*): the same four steps on the same launch shape -- block i = instance i, one wave -- with the view
-// formed from the handle's tables in device memory (ragged_view): the instance's graph record, its rows and its workspace at running
-// sums, its graph's slot template.  Every table entry a block reads is the same for all its lanes.
-__global__ __launch_bounds__(kBatchThreads) void ragged_begin_kernel(mcf::RaggedProblem r, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
-{
-    const int64_t i = (int64_t)blockIdx.x;
-    int32_t t;
-    const mcf::InstanceView v = mcf::ragged_view(r, nullptr, i, slab, &t);
-    mcf::uniform_begin(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
-}
-__global__ __launch_bounds__(kBatchThreads) void ragged_recost_kernel(mcf::RaggedProblem r, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
-{
-    const int64_t i = (int64_t)blockIdx.x;
-    if (r.changed && !r.changed[i]) return;
-    int32_t t;
-    const mcf::InstanceView v = mcf::ragged_view(r, nullptr, i, slab, &t);
-    mcf::uniform_recost(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
-}
-__global__ __launch_bounds__(kBatchThreads) void ragged_redata_kernel(mcf::RaggedProblem r, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
-{
-    const int64_t i = (int64_t)blockIdx.x;
-    if (r.changed && !r.changed[i]) return;
-    int32_t t;
-    const mcf::InstanceView v = mcf::ragged_view(r, nullptr, i, slab, &t);
-    mcf::uniform_redata(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
-}
-__global__ __launch_bounds__(kBatchThreads) void ragged_start_kernel(mcf::RaggedProblem r, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
-{
-    const int64_t i = (int64_t)blockIdx.x;
-    int32_t t;
-    const mcf::InstanceView v = mcf::ragged_view(r, nullptr, i, slab, &t);
-    mcf::uniform_begin_from(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
-}
-__global__ __launch_bounds__(kBatchThreads) void ragged_settle_kernel(mcf::RaggedProblem r, const BatchSlot *tmpl, BatchSlot *slots, unsigned char *slab)
-{
-    const int64_t i = (int64_t)blockIdx.x;
-    if (r.changed && !r.changed[i]) return;
-    int32_t t;
-    const mcf::InstanceView v = mcf::ragged_view(r, nullptr, i, slab, &t);
-    mcf::uniform_redata_settle(v, tmpl[t], slots[i], (int)threadIdx.x, kBatchThreads);
-}
-__global__ __launch_bounds__(kBatchThreads) void ragged_finish_kernel(mcf::RaggedProblem r, mcf::UniformOutputs o, const BatchSlot *slots, unsigned char *slab,
-                                                                      const int32_t *traces)
-{
-    const int64_t i = (int64_t)blockIdx.x;
-    if (r.changed && !r.changed[i]) return;
-    mcf::uniform_finish(mcf::ragged_view(r, &o, i, slab, nullptr), o, slots[i], traces, (int)threadIdx.x, kBatchThreads);
-}
-__global__ __launch_bounds__(kBatchThreads) void ragged_validate_kernel(mcf::RaggedProblem r, mcf::UniformCheck c, const int64_t *flows, const int64_t *potentials)
-{
-    mcf::uniform_validate(mcf::ragged_check_view(r, flows, potentials, (int64_t)blockIdx.x), c, (int)threadIdx.x, kBatchThreads);
-}
-
-// mcf_*batch_cost_ranges: block k serves instance ids[k] (the handle's table of the instances by tier and footprint class, up once per
-// handle).  One wave, like every kernel here: the minima of one instance meet in its own rows or its own LDS, and the barriers between
-// the passes are the workgroup's.  kLds: dynamic LDS holds what the step reads and the two accumulators (the host launches with at least
-// range_layout_of(m + 2n, n + 1, m).bytes); otherwise the walks run on the workspace and the minima are taken in the caller's rows.
-template <bool kLds>
-__global__ __launch_bounds__(kBatchThreads) void uniform_ranges_kernel(mcf::UniformProblem p, mcf::RangeOutputs o, const BatchSlot *slots, unsigned char *slab,
-                                                                       const int32_t *ids)
+// The queries of the kept state (mcf_*batch_cost_ranges, _data_ranges, _diagnose, _rays): Query is one of the descriptions below (CostRanges,
+// DataRanges, Diagnose, Rays), whose step<kLds> runs its header's step.  Block k serves instance ids[k] (the handle's table of the
+// instances by tier and footprint class, up once per handle and query).  One wave, like every kernel here: what the lanes of one
+// instance share meets in its own rows, its own LDS or its own part of the work buffer, and the barriers between the passes are the
+// workgroup's.  kLds: dynamic LDS holds what the step reads and its working arrays (the host launches with at least Query::footprint(n, m)
+// bytes of it):
+//   cost ranges   what the walks read and the two accumulators; otherwise the walks run on the workspace, the minima in the caller's rows;
+//   data ranges   what a hop reads and the room arrays, written before the one barrier and read after it; otherwise the walks follow the
+//                 workspace in place.  The walks gather into registers and the answers go straight to the caller's rows;
+//   diagnosis     flow and upper of the caller's arcs, unmet, marks and frontiers;
+//   rays          cost and upper of the caller's arcs, the two label arrays, preds, frontiers and marks.
+// Otherwise diagnosis and rays read the workspace, and block k keeps its working arrays in work + k * work_stride, which the host sized
+// for the largest instance of the global tier (prepare_work); the two range queries keep none and get a stride of 0.  pairs: the data
+// ranges' pair lists, one for all or one per graph (pairs_of); empty for the other queries.
+template <class Problem, class Query, bool kLds>
+__global__ __launch_bounds__(kBatchThreads) void query_kernel(Problem p, typename Query::Outputs o, mcf::PairArgs pairs, const BatchSlot *slots, unsigned char *slab,
+                                                              const int32_t *ids, unsigned char *work, uint64_t work_stride)
 {
     extern __shared__ __align__(16) unsigned char lds[];
     const int64_t i = (int64_t)ids[blockIdx.x];
-    mcf::uniform_ranges<kLds>(mcf::uniform_view(p, nullptr, i, slab), o, slots[i], lds, (int)threadIdx.x, kBatchThreads);
-}
-template <bool kLds>
-__global__ __launch_bounds__(kBatchThreads) void ragged_ranges_kernel(mcf::RaggedProblem r, mcf::RangeOutputs o, const BatchSlot *slots, unsigned char *slab,
-                                                                      const int32_t *ids)
-{
-    extern __shared__ __align__(16) unsigned char lds[];
-    const int64_t i = (int64_t)ids[blockIdx.x];
-    mcf::uniform_ranges<kLds>(mcf::ragged_view(r, nullptr, i, slab, nullptr), o, slots[i], lds, (int)threadIdx.x, kBatchThreads);
-}
-
-// mcf_*batch_data_ranges: the same launch shape on data_ranges_step.hip.h.  Nothing of an instance is shared between lanes but the room
-// arrays of the LDS tier, written before the one barrier and read after it; the walks gather into registers and the answers go straight
-// to the caller's rows.  kLds: dynamic LDS holds what a hop reads (at least data_range_layout_of(m, n + 1).bytes); otherwise the walks
-// follow the workspace in place.  The pairs: one list for all (uniform), one per graph by the caller's tables (ragged).
-template <bool kLds>
-__global__ __launch_bounds__(kBatchThreads) void uniform_data_ranges_kernel(mcf::UniformProblem p, mcf::DataRangeOutputs o, const int32_t *pairs, int64_t pair_count,
-                                                                            const BatchSlot *slots, unsigned char *slab, const int32_t *ids)
-{
-    extern __shared__ __align__(16) unsigned char lds[];
-    const int64_t i = (int64_t)ids[blockIdx.x];
-    mcf::uniform_data_ranges<kLds>(mcf::uniform_view(p, nullptr, i, slab), o, mcf::uniform_pairs(pairs, pair_count, i), slots[i], lds, (int)threadIdx.x, kBatchThreads);
-}
-template <bool kLds>
-__global__ __launch_bounds__(kBatchThreads) void ragged_data_ranges_kernel(mcf::RaggedProblem r, mcf::DataRangeOutputs o, const int32_t *pairs, const int64_t *pair_row,
-                                                                           const int64_t *ship_row, const BatchSlot *slots, unsigned char *slab, const int32_t *ids)
-{
-    extern __shared__ __align__(16) unsigned char lds[];
-    const int64_t i = (int64_t)ids[blockIdx.x];
-    mcf::uniform_data_ranges<kLds>(mcf::ragged_view(r, nullptr, i, slab, nullptr), o, mcf::ragged_pairs(pairs, pair_row, ship_row, r.graph_of[i], i), slots[i], lds,
-                                   (int)threadIdx.x, kBatchThreads);
-}
-
-// mcf_*batch_diagnose: the same launch shape on diagnose_step.hip.h.  kLds: dynamic LDS holds flow and upper of the caller's arcs, unmet,
-// marks and frontiers (at least diag_layout_of(m, n + 1).bytes); otherwise block k works in work + k * work_stride, which the host sized
-// for the largest instance of the global tier, and reads flow and upper in the workspace.
-template <bool kLds>
-__global__ __launch_bounds__(kBatchThreads) void uniform_diagnose_kernel(mcf::UniformProblem p, mcf::DiagOutputs o, const BatchSlot *slots, unsigned char *slab,
-                                                                         const int32_t *ids, const int32_t *inc_start, const int32_t *inc, unsigned char *work,
-                                                                         uint64_t work_stride)
-{
-    extern __shared__ __align__(16) unsigned char lds[];
-    const int64_t i = (int64_t)ids[blockIdx.x];
-    mcf::InstanceView v = mcf::uniform_view(p, nullptr, i, slab);
-    v.inc_start = inc_start; v.inc = inc;
-    mcf::uniform_diagnose<kLds>(v, o, slots[i], kLds ? lds : work + (uint64_t)blockIdx.x * work_stride, (int)threadIdx.x, kBatchThreads);
-}
-template <bool kLds>
-__global__ __launch_bounds__(kBatchThreads) void ragged_diagnose_kernel(mcf::RaggedProblem r, mcf::DiagOutputs o, const BatchSlot *slots, unsigned char *slab,
-                                                                        const int32_t *ids, unsigned char *work, uint64_t work_stride)
-{
-    extern __shared__ __align__(16) unsigned char lds[];
-    const int64_t i = (int64_t)ids[blockIdx.x];
-    mcf::uniform_diagnose<kLds>(mcf::ragged_view(r, nullptr, i, slab, nullptr), o, slots[i], kLds ? lds : work + (uint64_t)blockIdx.x * work_stride, (int)threadIdx.x,
-                                kBatchThreads);
-}
-
-// mcf_*batch_rays: the same launch shape on rays_step.hip.h.  kLds: dynamic LDS holds cost and upper of the caller's arcs, the two label
-// arrays, preds, frontiers and marks (at least rays_layout_of(m, n + 1).bytes); otherwise block k works in work + k * work_stride, which
-// the host sized for the largest instance of the global tier, and reads cost and upper in the workspace.
-template <bool kLds>
-__global__ __launch_bounds__(kBatchThreads) void uniform_rays_kernel(mcf::UniformProblem p, mcf::RaysOutputs o, const BatchSlot *slots, unsigned char *slab,
-                                                                     const int32_t *ids, const int32_t *inc_start, const int32_t *inc, unsigned char *work,
-                                                                     uint64_t work_stride)
-{
-    extern __shared__ __align__(16) unsigned char lds[];
-    const int64_t i = (int64_t)ids[blockIdx.x];
-    mcf::InstanceView v = mcf::uniform_view(p, nullptr, i, slab);
-    v.inc_start = inc_start; v.inc = inc;
-    mcf::uniform_rays<kLds>(v, o, slots[i], kLds ? lds : work + (uint64_t)blockIdx.x * work_stride, (int)threadIdx.x, kBatchThreads);
-}
-template <bool kLds>
-__global__ __launch_bounds__(kBatchThreads) void ragged_rays_kernel(mcf::RaggedProblem r, mcf::RaysOutputs o, const BatchSlot *slots, unsigned char *slab,
-                                                                    const int32_t *ids, unsigned char *work, uint64_t work_stride)
-{
-    extern __shared__ __align__(16) unsigned char lds[];
-    const int64_t i = (int64_t)ids[blockIdx.x];
-    mcf::uniform_rays<kLds>(mcf::ragged_view(r, nullptr, i, slab, nullptr), o, slots[i], kLds ? lds : work + (uint64_t)blockIdx.x * work_stride, (int)threadIdx.x,
-                            kBatchThreads);
+    Query::template step<kLds>(mcf::view_of(p, nullptr, i, slab, nullptr), o, mcf::pairs_of(p, pairs, i), slots[i], kLds ? lds : work + (uint64_t)blockIdx.x * work_stride,
+                               (int)threadIdx.x, kBatchThreads);
 }
 
 struct Instance {
@@ -1060,8 +930,9 @@ int mcf_batch_get_stats(mcf_batch *b, mcf_batch_stats *out)
 // ================================================================================================
 // mcf_ubatch_* and mcf_rbatch_*: problem data in and results out where they are ("Uniform batch", "Ragged batch").
 // One handle body (PlacedBatch) and one set of drivers for both.  What differs between one topology at a fixed stride and a set of
-// graphs at running sums -- sizes, tables, how a problem value and a view are formed, which kernels -- is a placement:
-// UniformPlacement and RaggedPlacement, static members of the same names, chosen at compile time by the entry points.
+// graphs at running sums -- sizes, tables, how a problem value is formed, the rules only one has -- is a placement: UniformPlacement
+// and RaggedPlacement, static members of the same names, chosen at compile time by the entry points.  The kernels and the host loops
+// take the placement's Problem and form their views from it (view_of, check_view_of, pairs_of).
 // ================================================================================================
 namespace {
 
@@ -1122,7 +993,7 @@ struct mcf_ubatch : PlacedBatch {
     std::vector<int32_t> inc_start, inc; // per node its arcs, arc << 1 | (the node is the target): what mcf_ubatch_validate walks
     BatchSlot tmpl{};                   // everything of a slot that the topology and the descriptor decide (configure_slot), filled once
     uint32_t stride = 0;                // bytes between workspaces
-    const int32_t *d_source = nullptr, *d_target = nullptr, *d_inc_start = nullptr, *d_inc = nullptr;     // into d_tables
+    mcf::UniformProblem dt{};           // the pointers into d_tables: source, target, inc_start, inc
 };
 
 struct mcf_rbatch : PlacedBatch {
@@ -1225,12 +1096,13 @@ struct StagedArray { void **slot; size_t bytes; bool up, down; };
 //   arrays           MCF_MEM_HOST: one StagedArray per array of the caller's
 //   footprint        what one instance keeps in LDS: it classes the instances of the LDS tier
 //   kWords, outputs, stats_of      the summary words: how many, the step's outputs with them, what they say
-//   prepare          before the launches; diagnosis and rays size the global tier's working buffer there
-//   Scratch, on_host the step for one instance with one lane, and the room it may keep between instances
-// The kernels, and the arguments only one placement has, are the placement's (launch_query).
+//   room             the working arrays of an instance of N nodes (the root among them) that is not served in LDS, in bytes: the global tier's buffer has
+//                    as much per block (prepare_work), the host hook as much for the instance at hand
+//   pairs            the call's pair lists, for pairs_of
+//   step<kLds>       the step of the query's header for one instance: what query_kernel runs with 64 lanes and query_on_host with one
 struct PlainQuery {                     // what a query has unless it says otherwise
-    struct Scratch {};
-    template <class P> static int prepare(typename P::Handle *, const PlacedBatch::QueryPlan &) { return MCF_OK; }
+    static uint32_t room(uint32_t) { return 0; }
+    template <class Io> static mcf::PairArgs pairs(const Io &) { return mcf::PairArgs{}; }
 };
 
 struct CostRanges : PlainQuery {        // uniform_ranges (ranges_step.hip.h)
@@ -1262,10 +1134,10 @@ struct CostRanges : PlainQuery {        // uniform_ranges (ranges_step.hip.h)
     static constexpr int kWords = 3;
     static Outputs outputs(const Io &io, int64_t *summary) { return Outputs{io.ranged, io.arc_state, io.cost_down, io.cost_up, summary}; }
     static void stats_of(const int64_t *words, Stats *st) { st->ranged = words[0]; st->tree_arcs = words[1]; st->cycle_hops = words[2]; }
-    template <class P>
-    static void on_host(const typename P::Handle *, const Io &, const mcf::InstanceView &v, const Outputs &o, int64_t, const BatchSlot &slot, Scratch &)
+    template <bool kLds>
+    MCF_HD static void step(const mcf::InstanceView &v, const Outputs &o, const mcf::PairList &, const BatchSlot &slot, unsigned char *room, int lane, int lanes)
     {
-        mcf::uniform_ranges<false>(v, o, slot, nullptr, 0, 1);
+        mcf::uniform_ranges<kLds>(v, o, slot, room, lane, lanes);
     }
 };
 
@@ -1327,39 +1199,13 @@ struct DataRanges : PlainQuery {        // uniform_data_ranges (data_ranges_step
         return Outputs{io.ranged, io.arc_state, io.flow_down, io.flow_up, io.ship_forth, io.ship_back, summary};
     }
     static void stats_of(const int64_t *words, Stats *st) { st->ranged = words[0]; st->walks = words[1]; st->hops = words[2]; }
-    template <class P>
-    static void on_host(const typename P::Handle *b, const Io &io, const mcf::InstanceView &v, const Outputs &o, int64_t i, const BatchSlot &slot, Scratch &)
+    static mcf::PairArgs pairs(const Io &io) { return mcf::PairArgs{io.pairs, io.pair_count, io.pair_row, io.ship_row}; }
+    template <bool kLds>
+    MCF_HD static void step(const mcf::InstanceView &v, const Outputs &o, const mcf::PairList &q, const BatchSlot &slot, unsigned char *room, int lane, int lanes)
     {
-        mcf::uniform_data_ranges<false>(v, o, P::pair_list(b, io, i), slot, nullptr, 0, 1);
+        mcf::uniform_data_ranges<kLds>(v, o, q, slot, room, lane, lanes);
     }
 };
-
-// The global tier's room for the working arrays of a diagnosis or a rays call: per block what the largest instance of that tier needs
-// (bytes_of(n + 1)), 0 when the plan has no such launch; the buffer is the handle's one and only grows.
-template <class P, class Bytes>
-int prepare_work(typename P::Handle *b, const PlacedBatch::QueryPlan &plan, const Bytes &bytes_of)
-{
-    b->diag_work_stride = 0;
-    for (const PlacedBatch::QueryLaunch &L : plan.launches) {
-        if (L.in_lds) continue;
-        const LaunchPlan solve = P::plan(b);
-        uint32_t most = 0;
-        for (size_t i = 0; i < (size_t)b->d.count; ++i) {
-            if (class_of(b->lds_max, solve.bytes((int32_t)i)) != kClasses - 1) continue;
-            int32_t n = 0, m = 0;
-            P::sizes(b, i, &n, &m);
-            most = std::max(most, (uint32_t)bytes_of((uint32_t)n + 1u));
-        }
-        b->diag_work_stride = most;
-        const size_t need = (size_t)L.n * (size_t)most;
-        if (b->diag_work_bytes < need) {
-            if (b->d_diag_work) { HIP_TRY(hipFree(b->d_diag_work)); b->d_diag_work = nullptr; b->diag_work_bytes = 0; }
-            HIP_TRY(hipMalloc((void **)&b->d_diag_work, need));
-            b->diag_work_bytes = need;
-        }
-    }
-    return MCF_OK;
-}
 
 struct Diagnose : PlainQuery {          // uniform_diagnose (diagnose_step.hip.h)
     using Stats = mcf_ubatch_diagnose_stats;
@@ -1394,18 +1240,11 @@ struct Diagnose : PlainQuery {          // uniform_diagnose (diagnose_step.hip.h
         st->bounds = words[MCF_DIAG_BOUNDS];
         st->levels = words[MCF_DIAG_BOUNDS + 1]; st->frontier_nodes = words[MCF_DIAG_BOUNDS + 2]; st->inc_entries = words[MCF_DIAG_BOUNDS + 3];
     }
-    template <class P> static int prepare(typename P::Handle *b, const PlacedBatch::QueryPlan &plan)
+    static uint32_t room(uint32_t N) { return mcf::diag_layout_of(0, N).bytes; }        // unmet, marks and frontiers
+    template <bool kLds>
+    MCF_HD static void step(const mcf::InstanceView &v, const Outputs &o, const mcf::PairList &, const BatchSlot &slot, unsigned char *room, int lane, int lanes)
     {
-        return prepare_work<P>(b, plan, [](uint32_t N) { return mcf::diag_layout_of(0, N).bytes; });
-    }
-    struct alignas(16) Word { uint64_t lo, hi; };
-    using Scratch = std::vector<Word>;  // one instance's unmet, marks and frontiers at a time
-    template <class P>
-    static void on_host(const typename P::Handle *, const Io &, const mcf::InstanceView &v, const Outputs &o, int64_t, const BatchSlot &slot, Scratch &room)
-    {
-        const size_t words_needed = mcf::diag_layout_of(0, (uint32_t)v.n + 1u).bytes / sizeof(Word);
-        if (room.size() < words_needed) room.resize(words_needed);
-        mcf::uniform_diagnose<false>(v, o, slot, (unsigned char *)room.data(), 0, 1);
+        mcf::uniform_diagnose<kLds>(v, o, slot, room, lane, lanes);
     }
 };
 
@@ -1442,17 +1281,11 @@ struct Rays : PlainQuery {              // uniform_rays (rays_step.hip.h)
         st->rounds = words[MCF_RAY_BOUNDS + 1]; st->frontier_nodes = words[MCF_RAY_BOUNDS + 2]; st->inc_entries = words[MCF_RAY_BOUNDS + 3];
         st->cycle_arcs = words[MCF_RAY_BOUNDS + 4];
     }
-    template <class P> static int prepare(typename P::Handle *b, const PlacedBatch::QueryPlan &plan)
+    static uint32_t room(uint32_t N) { return mcf::rays_layout_of(0, N).bytes; }        // labels, preds, marks and frontiers
+    template <bool kLds>
+    MCF_HD static void step(const mcf::InstanceView &v, const Outputs &o, const mcf::PairList &, const BatchSlot &slot, unsigned char *room, int lane, int lanes)
     {
-        return prepare_work<P>(b, plan, [](uint32_t N) { return mcf::rays_layout_of(0, N).bytes; });
-    }
-    using Scratch = Diagnose::Scratch;  // one instance's labels, preds, marks and frontiers at a time
-    template <class P>
-    static void on_host(const typename P::Handle *, const Io &, const mcf::InstanceView &v, const Outputs &o, int64_t, const BatchSlot &slot, Scratch &room)
-    {
-        const size_t words_needed = mcf::rays_layout_of(0, (uint32_t)v.n + 1u).bytes / sizeof(Diagnose::Word);
-        if (room.size() < words_needed) room.resize(words_needed);
-        mcf::uniform_rays<false>(v, o, slot, (unsigned char *)room.data(), 0, 1);
+        mcf::uniform_rays<kLds>(v, o, slot, room, lane, lanes);
     }
 };
 
@@ -1503,37 +1336,6 @@ int upload_image(PlacedBatch *b, TablePart *parts, size_t part_count)
 struct UniformPlacement {
     using Handle = mcf_ubatch;
     using Problem = mcf::UniformProblem;
-    static constexpr auto begin_kernel = uniform_begin_kernel;
-    static constexpr auto recost_kernel = uniform_recost_kernel;
-    static constexpr auto redata_kernel = uniform_redata_kernel;
-    static constexpr auto settle_kernel = uniform_settle_kernel;
-    static void launch_start(const Handle *b, const Problem &p, BatchSlot *slots, unsigned char *slab)
-    {
-        hipLaunchKernelGGL(uniform_start_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, slots, slab, b->d_inc_start, b->d_inc);
-    }
-    static constexpr auto finish_kernel = uniform_finish_kernel;
-    static void launch_validate(const Handle *b, const Problem &p, const mcf::UniformCheck &c, const BatchIo &io)
-    {
-        hipLaunchKernelGGL(uniform_validate_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, p, c, b->d_inc_start, b->d_inc, io.flows, io.potentials);
-    }
-    // a query's kernels, in LDS and in place, and their arguments: go(...) launches one plan entry with them (query_on_device)
-    template <class A, class Go> static int launch_query(CostRanges, const Handle *, const A &a, const Go &go)
-    {
-        return go(uniform_ranges_kernel<true>, uniform_ranges_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids);
-    }
-    template <class A, class Go> static int launch_query(DataRanges, const Handle *, const A &a, const Go &go)
-    {
-        return go(uniform_data_ranges_kernel<true>, uniform_data_ranges_kernel<false>, a.p, a.o, a.io.pairs, a.io.pair_count, a.slots, a.slab, a.ids);
-    }
-    template <class A, class Go> static int launch_query(Diagnose, const Handle *b, const A &a, const Go &go)
-    {
-        return go(uniform_diagnose_kernel<true>, uniform_diagnose_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids, b->d_inc_start, b->d_inc, b->d_diag_work,
-                  b->diag_work_stride);
-    }
-    template <class A, class Go> static int launch_query(Rays, const Handle *b, const A &a, const Go &go)
-    {
-        return go(uniform_rays_kernel<true>, uniform_rays_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids, b->d_inc_start, b->d_inc, b->d_diag_work, b->diag_work_stride);
-    }
     // one list for every instance
     static int check_pairs(const Handle *b, const DataRanges::Io &io, const char *what, PairSizes *sizes)
     {
@@ -1543,7 +1345,6 @@ struct UniformPlacement {
         *sizes = PairSizes{true, (size_t)io.pair_count, (size_t)b->d.count * (size_t)io.pair_count};
         return MCF_OK;
     }
-    static mcf::PairList pair_list(const Handle *, const DataRanges::Io &io, int64_t i) { return mcf::uniform_pairs(io.pairs, io.pair_count, i); }
     static void sizes(const Handle *b, size_t, int32_t *n, int32_t *m) { *n = b->d.node_count; *m = b->d.arc_count; }
     static size_t arc_rows(const Handle *b) { return (size_t)b->d.count * (size_t)b->d.arc_count; }
     static size_t node_rows(const Handle *b) { return (size_t)b->d.count * (size_t)b->d.node_count; }
@@ -1572,16 +1373,18 @@ struct UniformPlacement {
                              {b->inc.data(), b->inc.size() * sizeof(int32_t), 0}};
         if (const int rc = upload_image(b, parts, 4)) return rc;
         const unsigned char *const base = b->d_tables;
-        b->d_source = (const int32_t *)(base + parts[0].at); b->d_target = (const int32_t *)(base + parts[1].at);
-        b->d_inc_start = (const int32_t *)(base + parts[2].at); b->d_inc = (const int32_t *)(base + parts[3].at);
+        Problem &p = b->dt;
+        p = Problem{};
+        p.source = (const int32_t *)(base + parts[0].at); p.target = (const int32_t *)(base + parts[1].at);
+        p.inc_start = (const int32_t *)(base + parts[2].at); p.inc = (const int32_t *)(base + parts[3].at);
         return MCF_OK;
     }
-    // the problem where the steps run: the topology in device memory or the host's, with the rows of io
+    // the problem where the steps run: the topology and its lists in device memory or the host's, with the rows of io
     static Problem problem(const Handle *b, const BatchIo &io, bool on_device)
     {
-        Problem p{};
+        Problem p = b->dt;
+        if (!on_device) { p.source = b->source.data(); p.target = b->target.data(); p.inc_start = b->inc_start.data(); p.inc = b->inc.data(); }
         p.n = b->d.node_count; p.m = b->d.arc_count; p.supply_type = io.supply_type; p.trace_cap = b->d.trace_capacity;
-        p.source = on_device ? b->d_source : b->source.data(); p.target = on_device ? b->d_target : b->target.data();
         p.lower = io.lower; p.upper = io.upper; p.cost = io.cost; p.supply = io.supply;
         p.lower_stride = io.lower_stride; p.upper_stride = io.upper_stride; p.cost_stride = io.cost_stride; p.supply_stride = io.supply_stride;
         p.stride = b->stride;
@@ -1589,52 +1392,12 @@ struct UniformPlacement {
         p.start_state = io.start_state; p.start_stride = io.start_stride;
         return p;
     }
-    static mcf::InstanceView view(const Handle *b, const Problem &p, const mcf::UniformOutputs &o, int64_t i, unsigned char *slab, const BatchSlot **tmpl)
-    {
-        *tmpl = &b->tmpl;
-        mcf::InstanceView v = mcf::uniform_view(p, &o, i, slab);
-        v.inc_start = b->inc_start.data(); v.inc = b->inc.data();             // the host's lists: uniform_begin_from walks them
-        return v;
-    }
-    static mcf::InstanceView check_view(const Handle *b, const Problem &p, const BatchIo &io, int64_t i)
-    {
-        return mcf::uniform_check_view(p, b->inc_start.data(), b->inc.data(), io.flows, io.potentials, i);
-    }
 };
 
 // ---- a set of graphs, instance i's rows and workspace at running sums: tables say where, one slot template per graph
 struct RaggedPlacement {
     using Handle = mcf_rbatch;
     using Problem = mcf::RaggedProblem;
-    static constexpr auto begin_kernel = ragged_begin_kernel;
-    static constexpr auto recost_kernel = ragged_recost_kernel;
-    static constexpr auto redata_kernel = ragged_redata_kernel;
-    static constexpr auto settle_kernel = ragged_settle_kernel;
-    static void launch_start(const Handle *b, const Problem &r, BatchSlot *slots, unsigned char *slab)
-    {
-        hipLaunchKernelGGL(ragged_start_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, r, b->d_tmpl, slots, slab);
-    }
-    static constexpr auto finish_kernel = ragged_finish_kernel;
-    static void launch_validate(const Handle *b, const Problem &r, const mcf::UniformCheck &c, const BatchIo &io)
-    {
-        hipLaunchKernelGGL(ragged_validate_kernel, dim3((unsigned)b->d.count), dim3(kBatchThreads), 0, 0, r, c, io.flows, io.potentials);
-    }
-    template <class A, class Go> static int launch_query(CostRanges, const Handle *, const A &a, const Go &go)
-    {
-        return go(ragged_ranges_kernel<true>, ragged_ranges_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids);
-    }
-    template <class A, class Go> static int launch_query(DataRanges, const Handle *, const A &a, const Go &go)
-    {
-        return go(ragged_data_ranges_kernel<true>, ragged_data_ranges_kernel<false>, a.p, a.o, a.io.pairs, a.io.pair_row, a.io.ship_row, a.slots, a.slab, a.ids);
-    }
-    template <class A, class Go> static int launch_query(Diagnose, const Handle *b, const A &a, const Go &go)
-    {
-        return go(ragged_diagnose_kernel<true>, ragged_diagnose_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids, b->d_diag_work, b->diag_work_stride);
-    }
-    template <class A, class Go> static int launch_query(Rays, const Handle *b, const A &a, const Go &go)
-    {
-        return go(ragged_rays_kernel<true>, ragged_rays_kernel<false>, a.p, a.o, a.slots, a.slab, a.ids, b->d_diag_work, b->diag_work_stride);
-    }
     // one list per graph: pair_row says where each begins, ship_row where each instance's answers do.  Tables in host memory are checked
     // against each other; tables in device memory are the caller's word, as the rows of every call are.
     static int check_pairs(const Handle *b, const DataRanges::Io &io, const char *what, PairSizes *sizes)
@@ -1658,10 +1421,6 @@ struct RaggedPlacement {
         if (io.ship_forth && io.ship_row[count] == 0 && io.pair_row[G] == 0) return mcf::fail(MCF_ERR_INVALID, "%s: ship rows without pairs", what);
         *sizes = PairSizes{true, (size_t)io.pair_row[G], (size_t)io.ship_row[count]};
         return MCF_OK;
-    }
-    static mcf::PairList pair_list(const Handle *b, const DataRanges::Io &io, int64_t i)
-    {
-        return mcf::ragged_pairs(io.pairs, io.pair_row, io.ship_row, b->graph_of[(size_t)i], i);
     }
     static void sizes(const Handle *b, size_t i, int32_t *n, int32_t *m) { const mcf::RaggedGraph &g = b->graphs[(size_t)b->graph_of[i]]; *n = g.n; *m = g.m; }
     static size_t arc_rows(const Handle *b) { return (size_t)b->arc_row[(size_t)b->d.count]; }
@@ -1721,14 +1480,6 @@ struct RaggedPlacement {
         r.start_state = io.start_state;
         return r;
     }
-    static mcf::InstanceView view(const Handle *b, const Problem &r, const mcf::UniformOutputs &o, int64_t i, unsigned char *slab, const BatchSlot **tmpl)
-    {
-        int32_t t = 0;
-        const mcf::InstanceView v = mcf::ragged_view(r, &o, i, slab, &t);
-        *tmpl = &b->tmpl[(size_t)t];
-        return v;
-    }
-    static mcf::InstanceView check_view(const Handle *, const Problem &r, const BatchIo &io, int64_t i) { return mcf::ragged_check_view(r, io.flows, io.potentials, i); }
 };
 
 // what every call refuses before it touches the handle.  Solve calls take MCF_SUPPLY_GEQ / _LEQ, validation calls MCF_SUPPLY_EQ too
@@ -1972,12 +1723,11 @@ int solve_on_device(typename P::Handle *b, BatchIo io, Call call, const char *wh
     const double t_begin = mcf::now_ns();
     HIP_TRY(hipMemcpy(b->d_tmpl, P::templates(b), P::template_count(b) * sizeof(BatchSlot), hipMemcpyHostToDevice));
     b->stats.bytes_up += (int64_t)(P::template_count(b) * sizeof(BatchSlot));
-    if (call == kStart) {
-        P::launch_start(b, p, dev.slots, dev.slab);
-    } else {
-        const auto begin_kernel = call == kFresh ? P::begin_kernel : call == kRecost ? P::recost_kernel : P::redata_kernel;
-        hipLaunchKernelGGL(begin_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
-    }
+    const auto begin_kernel = call == kFresh    ? step_kernel<typename P::Problem, mcf::uniform_begin>
+                              : call == kRecost ? step_kernel<typename P::Problem, mcf::uniform_recost>
+                              : call == kRedata ? step_kernel<typename P::Problem, mcf::uniform_redata>
+                                                : step_kernel<typename P::Problem, mcf::uniform_begin_from>;
+    hipLaunchKernelGGL(begin_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
     HIP_TRY(hipGetLastError());
     b->where = PlacedBatch::kOnDevice;
     b->supply_type = io.supply_type;
@@ -1999,7 +1749,7 @@ int solve_on_device(typename P::Handle *b, BatchIo io, Call call, const char *wh
         for (int32_t i : run) redata.ran(slots[(size_t)i]);
     if (!attempts.empty()) {
         // the warm attempts are judged where they lie; the ones that did not stand have been set up again and run like a fresh solve's
-        hipLaunchKernelGGL(P::settle_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
+        hipLaunchKernelGGL((step_kernel<typename P::Problem, mcf::uniform_redata_settle>), dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, b->d_tmpl, dev.slots, dev.slab);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(slots.data(), dev.slots, count * sizeof(BatchSlot), hipMemcpyDeviceToHost));
         b->stats.bytes_down += (int64_t)(count * sizeof(BatchSlot));
@@ -2018,7 +1768,7 @@ int solve_on_device(typename P::Handle *b, BatchIo io, Call call, const char *wh
     b->stats.kernel_ns = t.kernel_ns;
 
     const double t_finish = mcf::now_ns();
-    hipLaunchKernelGGL(P::finish_kernel, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, outputs_of(io), dev.slots, dev.slab, dev.traces);
+    hipLaunchKernelGGL(finish_kernel<typename P::Problem>, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, p, outputs_of(io), dev.slots, dev.slab, dev.traces);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     b->stats.finish_ns = mcf::now_ns() - t_finish;
@@ -2066,19 +1816,20 @@ int solve_on_host(typename P::Handle *b, BatchIo io, Call call, const char *what
     for (size_t i = 0; i < count; ++i) {
         BatchSlot &slot = b->h_slots[i];
         if (io.changed && !io.changed[i]) { redata.begun(slot, false); continue; }
-        const BatchSlot *tmpl = nullptr;
-        const mcf::InstanceView v = P::view(b, p, o, (int64_t)i, b->h_slab.data(), &tmpl);
-        if (call == kFresh) mcf::uniform_begin(v, *tmpl, slot, 0, 1);
-        else if (call == kRecost) mcf::uniform_recost(v, *tmpl, slot, 0, 1);
-        else if (call == kRedata) mcf::uniform_redata(v, *tmpl, slot, 0, 1);
-        else mcf::uniform_begin_from(v, *tmpl, slot, 0, 1);
+        int32_t t = 0;
+        const mcf::InstanceView v = mcf::view_of(p, &o, (int64_t)i, b->h_slab.data(), &t);
+        const BatchSlot &tmpl = P::templates(b)[t];
+        if (call == kFresh) mcf::uniform_begin(v, tmpl, slot, 0, 1);
+        else if (call == kRecost) mcf::uniform_recost(v, tmpl, slot, 0, 1);
+        else if (call == kRedata) mcf::uniform_redata(v, tmpl, slot, 0, 1);
+        else mcf::uniform_begin_from(v, tmpl, slot, 0, 1);
         redata.begun(slot, true);
         const bool ran = slot.run == mcf::kBatchRunning || slot.run == mcf::kBatchDual;
         if (ran) {
             run_slot_on_host(slot, v.home, b->h_traces.data());
             redata.ran(slot);
             if (slot.reprice == 2) {                                        // a warm attempt: judged, and run again cold where it did not stand
-                mcf::uniform_redata_settle(v, *tmpl, slot, 0, 1);
+                mcf::uniform_redata_settle(v, tmpl, slot, 0, 1);
                 if (slot.run == mcf::kBatchRunning) {
                     redata.st.fallback_instances++;
                     run_slot_on_host(slot, v.home, b->h_traces.data());
@@ -2116,7 +1867,8 @@ int validate_on_device(typename P::Handle *b, BatchIo io, mcf_ubatch_check_summa
     HIP_TRY(hipMemcpy(b->d_summary, words, sizeof(words), hipMemcpyHostToDevice));
     out->bytes_up += (int64_t)sizeof(words);
     const double t_launch = mcf::now_ns();
-    P::launch_validate(b, P::problem(b, io, true), check_of(io, b->d_summary), io);
+    hipLaunchKernelGGL(validate_kernel<typename P::Problem>, dim3((unsigned)count), dim3(kBatchThreads), 0, 0, P::problem(b, io, true), check_of(io, b->d_summary), io.flows,
+                       io.potentials);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     out->kernel_ns = mcf::now_ns() - t_launch;
@@ -2137,7 +1889,7 @@ int validate_on_host(typename P::Handle *b, const BatchIo &io, mcf_ubatch_check_
     const typename P::Problem p = P::problem(b, io, false);
     const mcf::UniformCheck c = check_of(io, words);
     const double t_start = mcf::now_ns();
-    for (int64_t i = 0; i < (int64_t)b->d.count; ++i) mcf::uniform_validate(P::check_view(b, p, io, i), c, 0, 1);
+    for (int64_t i = 0; i < (int64_t)b->d.count; ++i) mcf::uniform_validate(mcf::check_view_of(p, io.flows, io.potentials, i), c, 0, 1);
     out->kernel_ns = mcf::now_ns() - t_start;
     summary_of(words, (int64_t)b->d.count, out);
     return MCF_OK;
@@ -2191,6 +1943,33 @@ int ensure_query_plan(typename P::Handle *b, PlacedBatch::QueryPlan &qp)
     return MCF_OK;
 }
 
+// The global tier's room for the working arrays of a diagnosis or a rays call: per block what the largest instance of that tier needs
+// (Q::room(n + 1)), 0 when the plan has no such launch or the query keeps no such arrays; the buffer is the handle's one and only grows.
+template <class P, class Q>
+int prepare_work(typename P::Handle *b, const PlacedBatch::QueryPlan &plan)
+{
+    b->diag_work_stride = 0;
+    for (const PlacedBatch::QueryLaunch &L : plan.launches) {
+        if (L.in_lds) continue;
+        const LaunchPlan solve = P::plan(b);
+        uint32_t most = 0;
+        for (size_t i = 0; i < (size_t)b->d.count; ++i) {
+            if (class_of(b->lds_max, solve.bytes((int32_t)i)) != kClasses - 1) continue;
+            int32_t n = 0, m = 0;
+            P::sizes(b, i, &n, &m);
+            most = std::max(most, Q::room((uint32_t)n + 1u));
+        }
+        b->diag_work_stride = most;
+        const size_t need = (size_t)L.n * (size_t)most;
+        if (b->diag_work_bytes < need) {
+            if (b->d_diag_work) { HIP_TRY(hipFree(b->d_diag_work)); b->d_diag_work = nullptr; b->diag_work_bytes = 0; }
+            HIP_TRY(hipMalloc((void **)&b->d_diag_work, need));
+            b->diag_work_bytes = need;
+        }
+    }
+    return MCF_OK;
+}
+
 // the problem of a query: the placement's tables where the step runs and the last solve call's supply type (the kept flow belongs to
 // that one); no rows of the caller's
 template <class P>
@@ -2200,17 +1979,6 @@ typename P::Problem kept_problem(const typename P::Handle *b, bool on_device)
     kept.supply_type = b->supply_type;
     return P::problem(b, kept, on_device);
 }
-
-// what a placement's launch_query names a kernel's arguments from
-template <class P, class Q>
-struct QueryArgs {
-    typename P::Problem p;
-    typename Q::Outputs o;
-    const typename Q::Io &io;
-    const BatchSlot *slots;
-    unsigned char *slab;
-    const int32_t *ids;
-};
 
 template <class P, class Q>
 int query_on_device(typename P::Handle *b, typename Q::Io io, const char *what)
@@ -2229,7 +1997,7 @@ int query_on_device(typename P::Handle *b, typename Q::Io io, const char *what)
     if (const int rc = ensure_query_plan<P, Q>(b, query.plan)) return rc;
     if (first) st.bytes_up += (int64_t)(count * sizeof(int32_t));
     if (!b->d_query_summary) HIP_TRY(hipMalloc((void **)&b->d_query_summary, kQuerySummaryWords * sizeof(int64_t)));
-    if (const int rc = Q::template prepare<P>(b, query.plan)) return rc;
+    if (const int rc = prepare_work<P, Q>(b, query.plan)) return rc;
     if (const int rc = state_to_device(b, count, &st.bytes_up)) return rc;
     b->where = PlacedBatch::kOnDevice;                                      // the same state, now there too
     Staged staged;                                                          // MCF_MEM_HOST: the arrays go through the staging buffer of the solve calls
@@ -2240,21 +2008,21 @@ int query_on_device(typename P::Handle *b, typename Q::Io io, const char *what)
     int64_t words[Q::kWords] = {};
     HIP_TRY(hipMemcpy(b->d_query_summary, words, sizeof(words), hipMemcpyHostToDevice));
     st.bytes_up += (int64_t)sizeof(words);
-    QueryArgs<P, Q> args{kept_problem<P>(b, true), Q::outputs(io, b->d_query_summary), io, b->dev.slots, b->dev.slab, nullptr};
+    const typename P::Problem p = kept_problem<P>(b, true);
+    const typename Q::Outputs o = Q::outputs(io, b->d_query_summary);
+    const mcf::PairArgs pairs = Q::pairs(io);
+    const auto in_lds = query_kernel<typename P::Problem, Q, true>, in_place = query_kernel<typename P::Problem, Q, false>;
+    unsigned char *const work = b->diag_work_stride ? b->d_diag_work : nullptr;        // a stride of 0: no block works there in this call
     bool opted_in = false;
     const double t_launch = mcf::now_ns();
     for (const PlacedBatch::QueryLaunch &L : query.plan.launches) {
-        args.ids = query.plan.d_ids + L.first;
-        const int rc = P::launch_query(Q{}, b, args, [&](auto in_lds, auto in_place, const auto &...kernel_args) -> int {
-            if (L.in_lds && !opted_in && b->lds_max > (64 << 10)) {         // the opt-in open_device got for the solve's kernels
-                HIP_TRY(hipFuncSetAttribute((const void *)in_lds, hipFuncAttributeMaxDynamicSharedMemorySize, b->lds_max));
-                opted_in = true;
-            }
-            hipLaunchKernelGGL(L.in_lds ? in_lds : in_place, dim3((unsigned)L.n), dim3(kBatchThreads), L.lds, 0, kernel_args...);
-            HIP_TRY(hipGetLastError());
-            return MCF_OK;
-        });
-        if (rc) return rc;
+        if (L.in_lds && !opted_in && b->lds_max > (64 << 10)) {             // the opt-in open_device got for the solve's kernels
+            HIP_TRY(hipFuncSetAttribute((const void *)in_lds, hipFuncAttributeMaxDynamicSharedMemorySize, b->lds_max));
+            opted_in = true;
+        }
+        hipLaunchKernelGGL(L.in_lds ? in_lds : in_place, dim3((unsigned)L.n), dim3(kBatchThreads), L.lds, 0, p, o, pairs, b->dev.slots, b->dev.slab,
+                           query.plan.d_ids + L.first, work, b->diag_work_stride);
+        HIP_TRY(hipGetLastError());
         (L.in_lds ? st.lds_instances : st.global_instances) += L.n;
     }
     HIP_TRY(hipDeviceSynchronize());
@@ -2281,12 +2049,15 @@ int query_on_host(typename P::Handle *b, typename Q::Io io, const char *what)
     int64_t words[Q::kWords] = {};
     const typename Q::Outputs o = Q::outputs(io, words);
     const typename P::Problem p = kept_problem<P>(b, false);
-    const mcf::UniformOutputs none{};
-    typename Q::Scratch scratch;
+    const mcf::PairArgs pairs = Q::pairs(io);
+    struct alignas(16) Word { uint64_t lo, hi; };
+    std::vector<Word> room;                                                 // one instance's working arrays at a time (Q::room), as the layouts align them
     const double t_start = mcf::now_ns();
     for (size_t i = 0; i < count; ++i) {
-        const BatchSlot *tmpl = nullptr;
-        Q::template on_host<P>(b, io, P::view(b, p, none, (int64_t)i, b->h_slab.data(), &tmpl), o, (int64_t)i, b->h_slots[i], scratch);
+        const mcf::InstanceView v = mcf::view_of(p, nullptr, (int64_t)i, b->h_slab.data(), nullptr);
+        const size_t words_needed = Q::room((uint32_t)v.n + 1u) / sizeof(Word);
+        if (room.size() < words_needed) room.resize(words_needed);
+        Q::template step<false>(v, o, mcf::pairs_of(p, pairs, (int64_t)i), b->h_slots[i], (unsigned char *)room.data(), 0, 1);
     }
     st.kernel_ns = mcf::now_ns() - t_start;
     Q::stats_of(words, &st);

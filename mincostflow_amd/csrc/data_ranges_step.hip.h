@@ -172,11 +172,19 @@ struct PairList {
     const int32_t *pairs;              // [count][2]
     int64_t count, ship_row;
 };
-MCF_HD inline PairList uniform_pairs(const int32_t *pairs, int64_t pair_count, int64_t i) { return PairList{pairs, pairs ? pair_count : 0, i * pair_count}; }
-MCF_HD inline PairList ragged_pairs(const int32_t *pairs, const int64_t *pair_row, const int64_t *ship_row, int32_t graph, int64_t i)
+// what a call says of its pairs: one list for every instance (uniform: pairs, pair_count) or one per graph by the caller's tables
+// (ragged: pairs, pair_row[graphs + 1], ship_row[count + 1]); each kind of problem reads its own members
+struct PairArgs {
+    const int32_t *pairs;
+    int64_t pair_count;
+    const int64_t *pair_row, *ship_row;
+};
+MCF_HD inline PairList pairs_of(const UniformProblem &, const PairArgs &a, int64_t i) { return PairList{a.pairs, a.pairs ? a.pair_count : 0, i * a.pair_count}; }
+MCF_HD inline PairList pairs_of(const RaggedProblem &r, const PairArgs &a, int64_t i)
 {
-    if (!pairs || !pair_row || !ship_row) return PairList{nullptr, 0, 0};
-    return PairList{pairs + 2 * pair_row[graph], pair_row[graph + 1] - pair_row[graph], ship_row[i]};
+    if (!a.pairs || !a.pair_row || !a.ship_row) return PairList{nullptr, 0, 0};
+    const int32_t graph = r.graph_of[i];
+    return PairList{a.pairs + 2 * a.pair_row[graph], a.pair_row[graph + 1] - a.pair_row[graph], a.ship_row[i]};
 }
 
 MCF_HD inline void data_range_summary_add(int64_t *summary, const DataRangeCount &c)

@@ -15,7 +15,8 @@
 // whether those pointers are device or host memory, nor how the rows were found: they work on an InstanceView, the instance PLACED.
 // Two ways lead to a view.  uniform_view: one topology, rows at base + instance * stride (stride 0 = one array for all), workspaces at a
 // fixed stride (mcf_ubatch_*).  ragged_view: a set of graphs, every instance names its own, rows and workspaces at running sums kept in
-// per-handle tables (mcf_rbatch_*, DESIGN.md 3.14 "Ragged batch").
+// per-handle tables (mcf_rbatch_*, DESIGN.md 3.14 "Ragged batch").  Code that serves both names neither: view_of and check_view_of
+// take the problem of either kind.
 // Nothing here depends on the order in which lanes add: the supply shift and the total cost are integer sums (they wrap, they commute),
 // so one lane and 64 lanes give the same bits, and both give ns_core.cpp's.
 #pragma once
@@ -31,6 +32,7 @@ namespace mcf {
 struct UniformProblem {
     int32_t n, m, supply_type, trace_cap;
     const int32_t *source, *target;                      // [m], validated by mcf_ubatch_create
+    const int32_t *inc_start, *inc;                      // its incidence lists [n + 1], [2m]
     const int64_t *lower, *upper, *cost, *supply;        // null: 0 / uncapacitated / 0 / 0
     int64_t lower_stride, upper_stride, cost_stride, supply_stride;     // elements between instances, 0 = shared
     uint64_t stride;                                     // bytes between workspaces: layout_of(m + 2n, n + 1).bytes
@@ -129,7 +131,7 @@ MCF_HD inline InstanceView uniform_view(const UniformProblem &p, const UniformOu
 {
     InstanceView v{};
     v.i = i; v.n = p.n; v.m = p.m; v.supply_type = p.supply_type; v.trace_cap = p.trace_cap;
-    v.source = p.source; v.target = p.target;
+    v.source = p.source; v.target = p.target; v.inc_start = p.inc_start; v.inc = p.inc;
     v.lower = uniform_row(p.lower, p.lower_stride, i); v.upper = uniform_row(p.upper, p.upper_stride, i);
     v.cost = uniform_row(p.cost, p.cost_stride, i); v.supply = uniform_row(p.supply, p.supply_stride, i);
     v.arc_row = i * (int64_t)p.m; v.node_row = i * (int64_t)p.n;
@@ -142,10 +144,9 @@ MCF_HD inline InstanceView uniform_view(const UniformProblem &p, const UniformOu
     }
     return v;
 }
-MCF_HD inline InstanceView uniform_check_view(const UniformProblem &p, const int32_t *inc_start, const int32_t *inc, const int64_t *flows, const int64_t *potentials, int64_t i)
+MCF_HD inline InstanceView uniform_check_view(const UniformProblem &p, const int64_t *flows, const int64_t *potentials, int64_t i)
 {
     InstanceView v = uniform_view(p, nullptr, i, nullptr);
-    v.inc_start = inc_start; v.inc = inc;
     v.check_flows = flows + i * (int64_t)p.m; v.check_potentials = potentials + i * (int64_t)p.n;
     return v;
 }
@@ -176,6 +177,15 @@ MCF_HD inline InstanceView ragged_check_view(const RaggedProblem &r, const int64
     v.check_flows = flows + r.arc_row[i]; v.check_potentials = potentials + r.node_row[i];
     return v;
 }
+// one way from a problem of either kind to a view.  *tmpl = the index of the instance's slot template: a uniform handle holds one
+MCF_HD inline InstanceView view_of(const UniformProblem &p, const UniformOutputs *o, int64_t i, unsigned char *slab, int32_t *tmpl)
+{
+    if (tmpl) *tmpl = 0;
+    return uniform_view(p, o, i, slab);
+}
+MCF_HD inline InstanceView view_of(const RaggedProblem &r, const UniformOutputs *o, int64_t i, unsigned char *slab, int32_t *tmpl) { return ragged_view(r, o, i, slab, tmpl); }
+MCF_HD inline InstanceView check_view_of(const UniformProblem &p, const int64_t *flows, const int64_t *potentials, int64_t i) { return uniform_check_view(p, flows, potentials, i); }
+MCF_HD inline InstanceView check_view_of(const RaggedProblem &r, const int64_t *flows, const int64_t *potentials, int64_t i) { return ragged_check_view(r, flows, potentials, i); }
 MCF_HD inline int64_t uniform_upper(const int64_t *upper, int e) { return !upper || upper[e] == MCF_INF_CAP ? kInf : upper[e]; }       // core_set_problem
 MCF_HD inline int64_t uniform_art_cost(const int64_t *cost, int n, int m, int lane, int lanes)     // art_cost_of
 {

@@ -69,9 +69,10 @@ def test_padded_instances_in_the_global_tier():
         assert st["global_instances"] == flat.count == 12 and st["lds_instances"] == 0 and same_counts(st, host.ray_stats()), (st, host.ray_stats())
         assert st["bytes_down"] == SUMMARY_BYTES, st
 
-    h, d = check_padded(SOLVE, RAYS, stats_check)
+    h, d, u, st = check_padded(SOLVE, RAYS, stats_check)
     assert d.label.is_cuda
     assert_same_rays(d, want, "padded")
+    assert st["global_instances"] == len(u) == 3 and st["lds_instances"] == 0 and st["bytes_down"] == SUMMARY_BYTES, st       # the uniform handle
 
 
 # ---- 3: a frontier wider than a wave: the ballot prefix is carried across strides

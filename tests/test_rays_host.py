@@ -22,7 +22,7 @@ from adversarial import random_problem
 from test_batch_host import LDS_LIMITS, PADDED_NODES, ROOT, footprint_of
 from test_diagnose_host import FlatNodes, diag_rows, problem
 from test_ranges_host import small_case
-from test_uniform_host import Topology, on_topology, to_numpy, uniform_of
+from test_uniform_host import Topology, on_topology, stride_of, to_numpy, uniform_of
 
 Ray = M.Ray
 FIELDS = ("verdict", "cycle_cost", "cycle_length", "on_cycle", "label")
@@ -423,7 +423,22 @@ def padded_family():
     return tuple(out)
 
 
+@functools.lru_cache(maxsize=None)
+def padded_topology():
+    """Three variants of ray_topology() padded the same way, for one uniform handle in the global tier: the first with a negative cycle,
+    the first without and the one that is infeasible by its bounds."""
+    t = ray_topology()
+    cyclic = [k != BY_BOUNDS and R.has_negative_cycle(p) for k, p in enumerate(t.variants)]
+    keep = (cyclic.index(True), min(k for k in range(t.count) if not cyclic[k] and k != BY_BOUNDS), BY_BOUNDS)
+    variants = [O.Problem(PADDED_NODES, p.m, p.src, p.tgt, p.lower, p.upper, p.cost, np.concatenate([p.supply, np.zeros(PADDED_NODES - p.n, np.int64)]))
+                for p in (t.variants[k] for k in keep)]
+    padded = Topology(PADDED_NODES, t.src, t.tgt, variants, [False] * len(variants))
+    assert stride_of(padded) > max(LDS_LIMITS)              # a uniform handle is one class: its stride decides the tier
+    return padded
+
+
 def check_padded(solve, rays, stats_check):
+    """-> the ragged handle and its answers; the uniform handle and the statistics of its call"""
     flat = FlatNodes(padded_family())
     h = flat.handle()
     solve(h, flat.arrays, O.GEQ)
@@ -431,7 +446,16 @@ def check_padded(solve, rays, stats_check):
     rows = check_answers(flat.problems, flat, d, h.ray_stats(), "padded")
     assert {Ray.Cycle, Ray.Bounded} == set(rows["verdict"])
     stats_check(h.ray_stats())
-    return h, d
+    # one uniform handle of the same tier: bit for bit what the same handle's hook says of the same state
+    t = padded_topology()
+    u = uniform_of(t, O.RULE_BLOCK)
+    solve(u, t.arrays(), O.GEQ)
+    du = rays(u)
+    st = u.ray_stats()
+    assert list(ray_rows(du)["verdict"]) == [Ray.Cycle, Ray.Bounded, Ray.Bounds] and ray_rows(du)["label"].shape == (t.count, PADDED_NODES)
+    assert_same_rays(du, HOST_RAYS(u), "padded, uniform")
+    assert st["instances"] == t.count and same_counts(st, u.ray_stats()), (st, u.ray_stats())
+    return h, d, u, st
 
 
 def test_padded_instances_on_the_host():
